@@ -1,15 +1,24 @@
 #!/usr/bin/env python3
 """bench.py - IQ Msamples/s through the 4096-point Welch PSD on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]                 (N > 1: spawns its own N ranks)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]     (N > 1: spawns its own N ranks)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set up, ramp, warm up, time the K steps, write --dump-outputs, print
+the line (headline keys + the `roofline` of the timed launches).  --full adds everything else: the prefix parity against
+the CPU oracle, the HBM read probe, at N = 1 the extra keys and sub-objects listed below and the `cpu_baseline*` keys
+(--no-extras / --no-cpu-baseline still drop those two groups from a --full run).
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step as DIR/<name>.npy (float32):
+N = 1 `psd` [4096]; C4 `sweep_db` [8, 3584] (the gathered wideband rows); c5 `rows` [64, 16384], `noise_floor` [64],
+`channel_power` [64, channels]; c2 `psd` [4096].  The inputs are seeded synthetic IQ: the same arguments give the
+same inputs on every run.
 
 A step = one pass of the hot path over one batch of synthetic IQ that is already resident in HBM.
 
 N = 1  workload "C2" (the configuration BASELINE.json's metric is quoted on): one 2^28-sample complex64
        stream (2 GiB), Hann, nperseg = nfft = 4096, 50 % overlap, detrend constant, density scaling
        (the welch() call of ofdm_cr_tools.py:342): welch4096ws kernel + the cross-workgroup finalize.
-       Extra keys on the same line: `host_visible_ms_per_step` (the same step through the host-output entry point:
+       Extra keys on the same line (--full): `host_visible_ms_per_step` (the same step through the host-output entry point:
        launch to PSD in host memory, SURVEY 8d's end point), `sweep_c4` (the N > 1 workload run on this one GPU, so
        that the N-GPU speed-up is a plain division), `sweep_c4_ref` (the same sweep through the call the reference's
        block actually makes, spectrum_sweeper.py:263: flattop, nperseg = 1024 zero-padded to 4096, step 512),
@@ -25,7 +34,7 @@ N = 1  workload "C2" (the configuration BASELINE.json's metric is quoted on): on
 N > 1  --workload c5: BASELINE config 5 over the ranks (64 channel streams, stream c on rank c mod N, PSD rows + decision
        stage per rank, one all-gather of rows + noise floors + channel powers: BatchScanPlan.scan_sharded); --workload c2: the
        2^28-sample stream cut into one contiguous run of segments per rank (sweep.welch_long_stream: one all-gather of raw
-       sums).  Both STRONG scaling, each with `ranks_seen`, a prefix parity number and a `scaling_base` naming the N = 1 key
+       sums).  Both STRONG scaling, each with `ranks_seen`, a prefix parity number (--full) and a `scaling_base` naming the N = 1 key
        to divide by.  Default (the driver's line):
 N > 1  workload "C4" (BASELINE config 4 = the north star's 8-segment sweep), STRONG scaling: a FIXED sweep of
        8 RF segments x 2^27 samples, segment i on rank i mod N, the same Welch parameters + fftshift + 256-bin
@@ -275,6 +284,23 @@ def timed_steps(torch, dist, dev, step, fence, steps, multi):
     return float(wall.item()), [float(v) for v in per.cpu()]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, float32 (float64 kept as it is), 64 MiB at most in all."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, 'detach') else np.asarray(a)
+        out[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, 'outputs of %d bytes exceed the %d-byte dump limit' % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -291,10 +317,17 @@ def main():
                          'c2 = the 2^28-sample stream cut into one run of segments per rank (sweep.welch_long_stream: one '
                          'all-gather of raw sums)')
     ap.add_argument('--scan-log2-samples', type=int, default=22, help='samples per channel stream of --workload c5')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: prefix parity against the CPU oracle, HBM read probe, (N = 1) the extra keys '
+                         'and sub-objects and the CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the timed path computed in its last step as DIR/<name>.npy (float32)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the cpu_baseline* keys')
     ap.add_argument('--no-extras', action='store_true',
-                    help='N = 1: skip the sweep_c4, csd_c3, scan_c5, host-visible and h2d_inclusive keys')
+                    help='--full, N = 1: skip the sweep_c4, csd_c3, scan_c5, host-visible and h2d_inclusive keys')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))                 # before anything in this process touches the GPU
 
@@ -374,10 +407,11 @@ def main():
         return windows.get_window('flattop', n)
 
     # ---------------------------------------------------------------- the 8-segment sweep (C4) ----------
-    def sweep_bench(steps, warmup, ref_call=False):
+    def sweep_bench(steps, warmup, ref_call=False, headline=False):
         """ref_call: the call spectrum_sweeper's stitcher actually makes (spectrum_sweeper.py:263: flattop, nperseg =
         fft_len / 4 zero-padded to fft_len, SciPy's default 50 % overlap of nperseg) instead of the Hann nperseg = 4096 form
-        BASELINE's metric is quoted on - four transforms per 2048 new samples: VALU-bound by construction."""
+        BASELINE's metric is quoted on - four transforms per 2048 new samples: VALU-bound by construction.
+        headline: this is the line's own timed path (N > 1), so --dump-outputs writes its gathered rows."""
         S = 1 << args.sweep_log2_samples
         trim = 256
         nbins = NFFT - 2 * trim
@@ -413,9 +447,11 @@ def main():
         ctx.set_timing(False)
         wide = pipe.wideband(last[0])
         assert int(wide.numel()) == SWEEP_SEGMENTS * nbins and bool(torch.isfinite(wide).all())
+        if headline and args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {'sweep_db': wide.reshape(SWEEP_SEGMENTS, nbins)})
         # parity of this rank's first segment on a prefix, against the oracle (outside the timed region)
         err = None
-        if rank == 0:
+        if rank == 0 and args.full:
             from oracle import ref_cpu as R
             pre = seg[0][:1 << 20].cpu().numpy().view(np.complex64).reshape(-1)
             if ref_call:
@@ -634,8 +670,10 @@ def main():
         ctx.set_timing(False)
         rows, noise, power = got[0]
         assert tuple(rows.shape) == (nch, N) and bool(torch.isfinite(rows).all()) and bool((noise > 0).all())
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {'rows': rows, 'noise_floor': noise, 'channel_power': power})
         err = None
-        if rank == 0:      # channel 0 (this rank's first stream), prefix of 2^20 samples, against the oracle
+        if rank == 0 and args.full:      # channel 0 (this rank's first stream), prefix of 2^20 samples, against the oracle
             from oracle import ref_cpu as R
             m = min(S, 1 << 20)
             pre = iq[:m].cpu().numpy().view(np.complex64).reshape(-1)
@@ -687,8 +725,10 @@ def main():
         ctx.set_timing(False)
         psd, nseg_total = got[0]
         assert nseg_total == plan.nseg(n) and bool(torch.isfinite(psd).all()) and int(psd.numel()) == NFFT
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {'psd': psd})
         err = None
-        if rank == 0:
+        if rank == 0 and args.full:
             from oracle import ref_cpu as R
             pre = iq[:1 << 20].cpu().numpy().view(np.complex64).reshape(-1)
             _, ref = R.welch_np(pre, fs=1.0, nperseg=NFFT, nfft=NFFT)
@@ -824,7 +864,7 @@ def main():
             }
     elif multi:
         seen = ranks_seen()
-        sw, S = sweep_bench(args.steps, args.warmup)
+        sw, S = sweep_bench(args.steps, args.warmup, headline=True)
         if rank == 0:
             kavg = sw['kernel_avg_ms']
             achieved = 8.0 * S / (kavg * 1e-3) / 1e9 if kavg else 0.0
@@ -874,19 +914,14 @@ def main():
         ctx.set_timing(False)
         psd = out[count[0] & 1]
         assert bool(torch.isfinite(psd).all())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {'psd': psd})
         med = statistics.median(per)
         kavg_ms = kern_ms / max(launches, 1)
         achieved = 8.0 * n / (kavg_ms * 1e-3) / 1e9
         # HBM bytes per launch: NOT measured by this run (PMC counters need rocprofv3 around the process) - the
         # figure of the builder's last profile of the same kernel, labelled as such
         traffic, traffic_source = profile_traffic('C2', 8 * n)
-        # sanity / parity on a prefix, outside the timed region
-        from oracle import ref_cpu as R
-        pre = iq[:1 << 20].cpu().numpy().view(np.complex64).reshape(-1)
-        chk = ctx.welch_plan(NFFT, window=hann, fs=1.0)
-        _, ref = R.welch_np(pre, fs=1.0, nperseg=NFFT, nfft=NFFT)
-        err = float(np.max(np.abs(chk.exec(pre) - ref) / ref))
-        probe_ms = ctx.stream_read_probe(iq.data_ptr(), n * 8, 5)
         result = {
             'metric': 'IQ Msamples/s Welch-PSD (4096-pt, 50% ovlp)',
             'value': n / (med * 1e-3) / 1e6, 'unit': 'Msamples/s', 'n_gpus': 1, 'steps': args.steps,
@@ -903,12 +938,20 @@ def main():
                          'kernel_note': 'one launch per step: the pilot of the constant detrend is formed in this kernel\'s '
                                         'prologue (round 5), so kernel_avg_ms covers it; finalize_wide_kernel is in ms_per_step',
                          'kernel_avg_ms': kavg_ms, 'launches': int(launches),
-                         'algorithmic_bytes_per_launch': 8 * n,
-                         'read_probe_GBps': 8.0 * n / (probe_ms * 1e-3) / 1e9},
-            'parity_prefix_max_rel_err': err,
+                         'algorithmic_bytes_per_launch': 8 * n},
             'device': ctx.device_name(),
+            'cpu_baseline': None,
         }
-        if not args.no_extras:
+        if args.full:
+            # sanity / parity on a prefix, outside the timed region
+            from oracle import ref_cpu as R
+            pre = iq[:1 << 20].cpu().numpy().view(np.complex64).reshape(-1)
+            chk = ctx.welch_plan(NFFT, window=hann, fs=1.0)
+            _, ref = R.welch_np(pre, fs=1.0, nperseg=NFFT, nfft=NFFT)
+            result['parity_prefix_max_rel_err'] = float(np.max(np.abs(chk.exec(pre) - ref) / ref))
+            probe_ms = ctx.stream_read_probe(iq.data_ptr(), n * 8, 5)
+            result['roofline']['read_probe_GBps'] = 8.0 * n / (probe_ms * 1e-3) / 1e9
+        if args.full and not args.no_extras:
             # SURVEY 8d ends the metric at "PSD available on host": the same step through the host-output entry point
             # (oth_welch_exec with a device source: kernels + 16 KiB D2H + stream synchronisation inside the call)
             # (the prefix parity check above ran on the CPU for a few hundred ms: the device has dropped to its idle clock
@@ -971,12 +1014,10 @@ def main():
             for nf in (32768, 65536):
                 result['welch_%d' % nf] = big_welch_bench(nf, max(5, args.steps // 10), max(2, args.warmup // 10))
                 torch.cuda.empty_cache()
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             result['cpu_baseline'], result['cpu_baseline_parallel'] = cpu_baseline(NFFT)
             result['cpu_baseline_c5'] = cpu_baseline_c5()
             result['cpu_baseline_c1'] = cpu_baseline_c1()
-        else:
-            result['cpu_baseline'] = None
     if multi:
         dist.barrier()
         dist.destroy_process_group()

@@ -11,6 +11,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'ofdm_tools_hip.h')
 
 
+def product_lib(path):
+    """The built library through plain ctypes, torch imported first - _hip.load()'s rule of one HIP runtime per process:
+    a library loaded before torch pulls the system runtime in next to torch's, and on a GPU machine the GPU tests later
+    in the same pytest process then find no device."""
+    import torch  # noqa: F401
+    return ctypes.CDLL(path)
+
+
 def declared_symbols():
     src = open(HEADER).read()
     src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
@@ -30,7 +38,7 @@ def test_library_exports_every_declared_symbol():
     from ofdm_tools import _hip
     if not os.path.exists(_hip.LIB_PATH):
         pytest.skip('library not built yet (run __graft_entry__.build())')
-    lib = ctypes.CDLL(_hip.LIB_PATH)
+    lib = product_lib(_hip.LIB_PATH)
     missing = [n for n in declared_symbols() if not hasattr(lib, n)]
     assert not missing, missing
 
@@ -78,7 +86,7 @@ def test_exception_barrier_at_the_abi(tmp_path):
     assert probe.oth_probe_throw(3) in (-4, -6)             # a real over-sized std::vector, not a staged throw
     if not os.path.exists(_hip.LIB_PATH):
         pytest.skip('library not built yet')
-    lib = ctypes.CDLL(_hip.LIB_PATH)
+    lib = product_lib(_hip.LIB_PATH)
     lib.oth_strerror.restype = ctypes.c_char_p
     assert b'internal' in lib.oth_strerror(-6)
     # the product library exports exactly what the header declares: no undeclared diagnostic hooks

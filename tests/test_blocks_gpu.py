@@ -997,7 +997,7 @@ def test_bench_gpus_2_spawns_its_own_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env['BENCH_REHEARSE'] = '1'
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2',
-                        '--sweep-log2-samples', '22', '--ramp-ms', '20'], env=env, capture_output=True, timeout=600)
+                        '--sweep-log2-samples', '22', '--ramp-ms', '20', '--full'], env=env, capture_output=True, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -1105,7 +1105,7 @@ def test_bench_gpus_4_rehearsal_two_segments_per_rank(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env['BENCH_REHEARSE'] = '1'
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '4', '--steps', '4', '--warmup', '1',
-                        '--sweep-log2-samples', '20', '--ramp-ms', '10'], env=env, capture_output=True, timeout=600)
+                        '--sweep-log2-samples', '20', '--ramp-ms', '10', '--full'], env=env, capture_output=True, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -1130,7 +1130,7 @@ def test_bench_workloads_c5_and_c2_over_ranks_rehearsal(workload, ranks):
     env['BENCH_REHEARSE'] = '1'
     size = ['--scan-log2-samples', '18'] if workload == 'c5' else ['--log2-samples', '23']
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(ranks), '--workload', workload, '--steps', '4',
-                        '--warmup', '1', '--ramp-ms', '10'] + size, env=env, capture_output=True, timeout=600)
+                        '--warmup', '1', '--ramp-ms', '10', '--full'] + size, env=env, capture_output=True, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -1144,6 +1144,40 @@ def test_bench_workloads_c5_and_c2_over_ranks_rehearsal(workload, ranks):
     else:
         assert r['config']['parallelism'] == 'time-shard-per-gpu x%d' % ranks and '--gpus 1' in r['scaling_base']
         assert 'kernel=welch4096:ws' in r['roofline']['kernel']
+
+
+def test_bench_plain_run_dumps_the_timed_psd(ctx, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line only (no sub-objects, no CPU baseline, no
+    parity), `steps` = K, and --dump-outputs writes the PSD of the last timed step - checked here against the oracle on the
+    same seeded device input."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+    log2 = 22
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--ramp-ms', '10', '--log2-samples', str(log2), '--dump-outputs', str(tmp_path / 'out')],
+                       env=env, capture_output=True, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r['steps'] == 3 and r['ms_per_step'] > 0 and r['value'] > 0 and r['unit'] == 'Msamples/s'
+    assert r['higher_is_better'] is True and r['dtype'] == 'f32' and r['cpu_baseline'] is None
+    assert not {'sweep_c4', 'csd_c3', 'scan_c5', 'host_visible_ms_per_step', 'parity_prefix_max_rel_err'} & set(r)
+    assert sorted(os.listdir(str(tmp_path / 'out'))) == ['psd.npy']
+    psd = np.load(str(tmp_path / 'out' / 'psd.npy'))
+    assert psd.dtype == np.float32 and psd.shape == (bench.NFFT,)
+    n = 1 << log2
+    iq = torch.empty((n, 2), dtype=torch.float32, device='cuda:0')
+    ctx.synth_iq(iq.data_ptr(), n, 1002, bench.TONES, bench.DC)
+    ctx.sync()
+    x = iq.cpu().numpy().view(np.complex64).reshape(-1)
+    _, ref = R.welch_np(x, fs=1.0, nperseg=bench.NFFT, nfft=bench.NFFT)
+    assert relerr(psd, ref) < RTOL
 
 
 def test_full_size_config1_sensor_v2(ctx):
