@@ -151,7 +151,8 @@ struct oth_chain {
     float *d_out = nullptr;            // rows handed back by the host-output forms
     size_t out_cap = 0;
     // asynchronous work() form (oth_chain_push_async): pinned input ring + pinned latest-row ring.  A slot is
-    // reused kRing pushes later; the push waits only if the GPU is still that far behind.
+    // reused kRing tickets later; before it is written again the push waits for the event of the slot's last push that
+    // enqueued work - however many dropped tickets lie in between - which costs nothing once the GPU has caught up.
     static constexpr int kRing = 4;
     void *h_in[kRing] = {nullptr, nullptr, nullptr, nullptr};
     size_t h_in_cap[kRing] = {0, 0, 0, 0};
@@ -163,8 +164,16 @@ struct oth_chain {
     AnyTables any;                     // any.sh.kind != ANY_NONE: the chain's length runs through fft_any.hip
     // round 6: what a work()-sized push costs
     uint64_t ops = 0;                  // stream operations (asynchronous copies + kernel launches) the last push enqueued
-    bool noop[kRing] = {false, false, false, false};      // the slot's push enqueued nothing (every vector dropped): ready at once
-    bool leftover_stale = false;       // the partial vector in d_buf was not copied (it is not a kept one): never emit it
+    bool noop[kRing] = {false, false, false, false};      // the slot's ticket enqueued nothing (every vector dropped): ready at
+                                                          // once; ev[slot] still belongs to the slot's last real push
+    // A partial vector whose samples came (in part) from pushes chain_push_dropped skipped: d_buf holds its first
+    // tail_from samples, h_tail its samples [tail_from, leftover) - copied on the host, no stream operation.  The next
+    // push that enqueues work uploads them first; set_keep_one_in_n may make the vector a kept one meanwhile.
+    bool leftover_stale = false;
+    size_t tail_from = 0;
+    float2 *h_tail = nullptr;          // nfft samples, pinned
+    hipEvent_t tail_ev = nullptr;      // recorded behind push / push_dev's upload from h_tail
+    bool tail_ev_live = false;         // ... which a dropped push waits for before it rewrites h_tail
 };
 
 namespace {
@@ -2356,6 +2365,8 @@ int oth_chain_create(oth_ctx *c, int nfft, const float *window, int fftshift, in
     if (e == hipSuccess) e = hipMalloc(&h->d_iir, sizeof(float) * nfft);
     if (e == hipSuccess) e = hipMalloc(&h->d_peak, sizeof(float) * nfft);
     if (e == hipSuccess) e = hipMalloc(&h->d_peak_init, sizeof(int));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&h->h_tail, sizeof(float2) * nfft, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->tail_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipMemcpyAsync(h->d_win, w.data(), sizeof(float) * nfft, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->d_iir, 0, sizeof(float) * nfft, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->d_peak, 0, sizeof(float) * nfft, c->stream);
@@ -2387,6 +2398,8 @@ int oth_chain_destroy(oth_chain *h) {
     if (h->d_partial) hipFree(h->d_partial);
     if (h->d_tail) hipFree(h->d_tail);
     if (h->d_out) hipFree(h->d_out);
+    if (h->h_tail) hipHostFree(h->h_tail);
+    if (h->tail_ev) hipEventDestroy(h->tail_ev);
     any_tables_free(h->any);
     for (int i = 0; i < oth_chain::kRing; ++i) {
         if (h->h_in[i]) hipHostFree(h->h_in[i]);
@@ -2403,8 +2416,9 @@ int oth_chain_set_keep_one_in_n(oth_chain *h, int n) {
     CtxGuard guard_(h ? h->ctx : nullptr);
     if (!h) return fail(nullptr, OTH_ERR_INVALID, "chain is NULL");
     if (n < 1) return fail(h->ctx, OTH_ERR_INVALID, "keep_one_in_n must be >= 1");
-    h->keep_n = h->count = n;   // keep_one_in_n::set_n restarts the count (a partial vector whose samples were skipped as
-                                // dropped stays unemitted: chain_feed's leftover_stale)
+    h->keep_n = h->count = n;   // keep_one_in_n::set_n restarts the count in front of the vector that is still incomplete;
+                                // a partial one whose samples were skipped as dropped is kept if the new count says so (its
+                                // samples wait in h_tail for the next push that enqueues work)
     return OTH_OK;
     OTH_CATCH((h ? h->ctx : nullptr))
 }
@@ -2451,6 +2465,7 @@ int oth_chain_reset(oth_chain *h) {
     h->peak_flag_set = false;
     h->leftover = 0;
     h->leftover_stale = false;
+    h->tail_from = 0;
     h->count = h->keep_n;
     return OTH_OK;
     OTH_CATCH((h ? h->ctx : nullptr))
@@ -2617,6 +2632,7 @@ static int chain_feed(oth_chain *h, const float2 *src, size_t nsamples, float *r
                       uint64_t *nrows_out) {
     oth_ctx *c = h->ctx;
     const int N = h->nfft;
+    if (h->leftover_stale) return fail(c, OTH_ERR_STATE, "chain: host-only samples of the partial vector were not uploaded");
     int rc = ensure(c, &h->d_buf, &h->buf_cap, sizeof(float2) * (size_t)N);
     if (rc) return rc;
     bool head = false;           // a vector completed in d_buf
@@ -2638,10 +2654,9 @@ static int chain_feed(oth_chain *h, const float2 *src, size_t nsamples, float *r
     long long k_head = 0;
     if (head) {
         if (--h->count == 0) {
-            k_head = h->leftover_stale ? 0 : 1;      // (stale: its first samples were never copied - see chain_push_dropped)
+            k_head = 1;
             h->count = h->keep_n;
         }
-        h->leftover_stale = false;
     }
     long long k_body = 0, first = h->count - 1;
     if (nvec > first) k_body = 1 + (nvec - 1 - first) / h->keep_n;
@@ -2662,10 +2677,35 @@ static int chain_feed(oth_chain *h, const float2 *src, size_t nsamples, float *r
         HIPCHK(c, hipMemcpyAsync(h->d_buf, src + used, keep * sizeof(float2), hipMemcpyDeviceToDevice, c->stream));
         h->ops += 1;
         h->leftover = keep;
-        h->leftover_stale = false;
     }
     if (nrows_out) *nrows_out = (uint64_t)(k_head + k_body);
     return OTH_OK;
+}
+
+// push / push_dev after asynchronous pushes that skipped part of the current vector: its host-only samples go up first,
+// straight from the pinned h_tail; an event behind the copy lets a later dropped push wait for it before rewriting h_tail
+// (push_dev stays asynchronous).
+static int chain_upload_tail(oth_chain *h) {
+    if (!h->leftover_stale) return OTH_OK;
+    oth_ctx *c = h->ctx;
+    int rc = ensure(c, &h->d_buf, &h->buf_cap, sizeof(float2) * (size_t)h->nfft);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(h->d_buf + h->tail_from, h->h_tail + h->tail_from,
+                             (h->leftover - h->tail_from) * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(h->tail_ev, c->stream));
+    h->tail_ev_live = true;
+    h->ops += 1;
+    h->leftover_stale = false;
+    return OTH_OK;
+}
+
+// h_tail may be rewritten once the device has read the last upload from it; false on an error (the push then takes the
+// path that enqueues work, which reports it)
+static bool chain_tail_writable(oth_chain *h) {
+    if (!h->tail_ev_live) return true;
+    if (hipEventSynchronize(h->tail_ev) != hipSuccess) return false;
+    h->tail_ev_live = false;
+    return true;
 }
 
 int oth_chain_push_dev(oth_chain *h, const void *iq_dev, size_t nsamples, float *rows_out_dev, size_t rows_capacity,
@@ -2679,6 +2719,8 @@ int oth_chain_push_dev(oth_chain *h, const void *iq_dev, size_t nsamples, float 
     if (!nsamples) return OTH_OK;
     if (use_device(c)) return OTH_ERR_HIP;
     h->ops = 0;
+    int rc = chain_upload_tail(h);
+    if (rc) return rc;
     return chain_feed(h, (const float2 *)iq_dev, nsamples, rows_out_dev, rows_out_dev ? rows_capacity : 0, nrows_out);
     OTH_CATCH((h ? h->ctx : nullptr))
 }
@@ -2697,6 +2739,7 @@ int oth_chain_push(oth_chain *h, const void *iq, size_t nsamples, int src_is_dev
     const float2 *src = (const float2 *)iq;
     int rc;
     h->ops = 0;
+    if ((rc = chain_upload_tail(h))) return rc;
     if (!src_is_device) {
         if ((rc = ensure(c, &h->d_stage, &h->stage_cap, nsamples * sizeof(float2)))) return rc;
         HIPCHK(c, hipMemcpyAsync(h->d_stage, iq, nsamples * sizeof(float2), hipMemcpyHostToDevice, c->stream));
@@ -2721,37 +2764,38 @@ int oth_chain_push(oth_chain *h, const void *iq, size_t nsamples, int src_is_dev
 // leaves behind is not one either.  Then nothing needs to reach the device - only the stream position moves on.  This is the
 // common case of a sensor with a low sens_per_sec: spectrum_sensor_v2.py:86-87 keeps one vector in int(Sf / N / sens_per_sec)
 // (97 of 98 at 1 MS/s, 1024 points, 10 PSDs per second), and GNU Radio's work() chunks hold 4-32 of them.
+// The samples such a push adds to a partial vector are kept on the host (h_tail, a plain memcpy): if the vector turns into a
+// kept one later (set_keep_one_in_n), the push that continues it uploads them.
 // -> true and the state advanced, or false and nothing touched.
-static bool chain_push_dropped(oth_chain *h, size_t nsamples) {
+static bool chain_push_dropped(oth_chain *h, const float2 *src, size_t nsamples) {
     const size_t N = (size_t)h->nfft;
     size_t L = h->leftover, rest = nsamples;
     long long count = h->count;
-    bool stale = h->leftover_stale;
     if (L) {
         const size_t take = rest < N - L ? rest : N - L;
-        L += take;
-        rest -= take;
-        if (L == N) {
-            if (--count == 0) {
-                if (!stale) return false;      // the head vector is a kept one
-                count = h->keep_n;
-            }
-            L = 0;
-            stale = false;
-        } else {
-            if (count == 1 && !stale) return false;      // still inside a vector that will be kept: its samples are needed
-            h->leftover = L;
-            h->leftover_stale = true;      // (a dropped vector's samples: d_buf is not written)
+        if (count == 1) return false;      // the vector in progress is a kept one: its samples are needed
+        if (L + take < N) {                // it stays partial: keep the new samples on the host
+            if (!chain_tail_writable(h)) return false;
+            if (!h->leftover_stale) h->tail_from = L;
+            memcpy(h->h_tail + L, src, take * sizeof(float2));
+            h->leftover = L + take;
+            h->leftover_stale = true;
             return true;
         }
+        --count;                           // it completes and is dropped
+        src += take;
+        rest -= take;
     }
     const long long nvec = (long long)(rest / N);
     if (nvec > count - 1) return false;      // a vector of the body is kept
     count -= nvec;
     const size_t keep = rest - (size_t)nvec * N;
     if (keep && count == 1) return false;      // the vector that begins here will be kept
+    if (keep && !chain_tail_writable(h)) return false;
+    if (keep) memcpy(h->h_tail, src + (size_t)nvec * N, keep * sizeof(float2));
     h->leftover = keep;
     h->leftover_stale = keep != 0;
+    h->tail_from = 0;
     h->count = (int)count;
     return true;
 }
@@ -2771,8 +2815,8 @@ int oth_chain_push_async(oth_chain *h, const void *iq_host, size_t nsamples, uin
     const uint64_t ticket = h->next_ticket;
     const int slot = (int)(ticket % oth_chain::kRing);
     h->ops = 0;
-    if (nsamples && chain_push_dropped(h, nsamples)) {      // nothing to compute: no copy, no launch, no event
-        h->noop[slot] = true;
+    if (nsamples && chain_push_dropped(h, (const float2 *)iq_host, nsamples)) {      // nothing to compute: no copy, no launch,
+        h->noop[slot] = true;                                                          // no event
         h->ticket_of[slot] = ticket;
         h->nrows_of[slot] = 0;
         h->next_ticket = ticket + 1;
@@ -2783,37 +2827,55 @@ int oth_chain_push_async(oth_chain *h, const void *iq_host, size_t nsamples, uin
     if (!h->ev[slot]) {
         HIPCHK(c, hipEventCreateWithFlags(&h->ev[slot], hipEventDisableTiming));
         HIPCHK(c, hipHostMalloc((void **)&h->h_row[slot], sizeof(float) * N, hipHostMallocDefault));
-    } else if (h->ticket_of[slot] && !h->noop[slot]) {
-        HIPCHK(c, hipEventSynchronize(h->ev[slot]));      // only when the GPU is kRing pushes behind
+    } else {
+        // h_in[slot] / h_row[slot] belong to the slot's last real push - kRing tickets ago, or more when dropped tickets
+        // (noop) came in between - until its event completes; waits only when the GPU is still that far behind
+        HIPCHK(c, hipEventSynchronize(h->ev[slot]));
     }
     h->noop[slot] = false;
-    const size_t bytes = nsamples * sizeof(float2);
+    // host-only samples of the partial vector (skipped by dropped pushes) go up in front of the new ones
+    const size_t tail = nsamples && h->leftover_stale ? h->leftover - h->tail_from : 0;
+    const size_t bytes = nsamples * sizeof(float2), tail_bytes = tail * sizeof(float2);
     const bool pinned_src = bytes > kPinnedStageMax && host_ptr_is_pinned(iq_host);
     const bool direct = bytes > kPinnedStageMax && !pinned_src;      // the runtime stages pageable memory itself
     const bool wait_copy = pinned_src && bytes > kPinnedRingMax;
-    if (!direct && !wait_copy && h->h_in_cap[slot] < bytes) {
+    const size_t in_bytes = (direct || wait_copy ? 0 : bytes) + tail_bytes;
+    if (h->h_in_cap[slot] < in_bytes) {
         if (h->h_in[slot]) HIPCHK(c, hipHostFree(h->h_in[slot]));
         h->h_in[slot] = nullptr;
         h->h_in_cap[slot] = 0;
-        const size_t cap = bytes + bytes / 2 + 4096;
+        const size_t cap = in_bytes + in_bytes / 2 + 4096;
         HIPCHK(c, hipHostMalloc(&h->h_in[slot], cap, hipHostMallocDefault));
         h->h_in_cap[slot] = cap;
     }
     int rc;
     uint64_t nrows = 0;
     if (nsamples) {
-        if ((rc = ensure(c, &h->d_stage, &h->stage_cap, bytes))) return rc;
+        if ((rc = ensure(c, &h->d_stage, &h->stage_cap, tail_bytes + bytes))) return rc;
+        char *pin = (char *)h->h_in[slot];
+        if (tail) memcpy(pin, h->h_tail + h->tail_from, tail_bytes);
         if (wait_copy) {
-            if ((rc = copy_in_and_wait(c, h->d_stage, iq_host, bytes))) return rc;
+            if ((rc = copy_in_and_wait(c, h->d_stage + tail, iq_host, bytes))) return rc;
         } else if (direct) {      // the runtime's staged copy returns once the caller's buffer has been read
-            HIPCHK(c, hipMemcpyAsync(h->d_stage, iq_host, bytes, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(h->d_stage + tail, iq_host, bytes, hipMemcpyHostToDevice, c->stream));
         } else {
-            memcpy(h->h_in[slot], iq_host, bytes);      // the scheduler's buffer dies when work() returns
-            HIPCHK(c, hipMemcpyAsync(h->d_stage, h->h_in[slot], bytes, hipMemcpyHostToDevice, c->stream));
+            memcpy(pin + tail_bytes, iq_host, bytes);      // the scheduler's buffer dies when work() returns
         }
-        h->ops += 1;
+        if (in_bytes) HIPCHK(c, hipMemcpyAsync(h->d_stage, pin, in_bytes, hipMemcpyHostToDevice, c->stream));
+        h->ops += (direct || wait_copy) && tail ? 2 : 1;
+        const size_t leftover0 = h->leftover;
+        const int count0 = h->count;
+        if (tail) {      // d_buf keeps the vector's first tail_from samples; the rest comes from d_stage
+            h->leftover = h->tail_from;
+            h->leftover_stale = false;
+        }
         // the latest row goes from the closing kernel straight into the slot's pinned row (device-visible host memory)
-        if ((rc = chain_feed(h, h->d_stage, nsamples, h->h_row[slot], 1, &nrows))) return rc;
+        if ((rc = chain_feed(h, h->d_stage, tail + nsamples, h->h_row[slot], 1, &nrows))) {
+            h->leftover = leftover0;      // the stream position stays where it was: h_tail still holds the samples
+            h->leftover_stale = tail != 0;
+            h->count = count0;
+            return rc;
+        }
     }
     HIPCHK(c, hipEventRecord(h->ev[slot], c->stream));
     h->ticket_of[slot] = ticket;

@@ -17,6 +17,7 @@ EPI_MAG, EPI_MAG2, EPI_MAG2_OVER_N2 = 0, 1, 2
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_TUNED = 0, 1, 2
 SCHED_CONTIGUOUS, SCHED_INTERLEAVED, SCHED_DYNAMIC = 0, 1, 2
 HOSTWAIT_POLL, HOSTWAIT_SYNC = 0, 1
+OUT_RING = 4      # oth_plan::kOutRing: launch (ticket) t of a plan delivers into output slot t % OUT_RING
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('OFDM_TOOLS_HIP_LIB',
@@ -365,6 +366,8 @@ class Context(object):
 class WelchPlan(object):
     def __init__(self, ctx, nfft, nperseg, noverlap, window, detrend, scaling, fs, fftshift, trim_bins, db, kernel):
         self.ctx = ctx
+        # exec_async() tickets not collected yet, and the last one issued; poll() / wait() may run on other threads
+        self._tickets, self._last_ticket, self._tickets_lock = set(), 0, threading.Lock()
         nperseg = int(nfft if nperseg is None else nperseg)
         noverlap = int(nperseg // 2 if noverlap is None else noverlap)
         self.nfft, self.nperseg, self.noverlap = int(nfft), nperseg, noverlap
@@ -452,8 +455,26 @@ class WelchPlan(object):
         else:
             rc = self.ctx.lib.oth_welch_exec_async(self.h, C.c_void_p(x), int(nsamples), 1, C.byref(t))
         self.ctx.check(rc, 'oth_welch_exec_async')
-        self.outstanding = getattr(self, 'outstanding', 0) + 1      # tickets not collected yet (Context.cached_plan keeps such a plan)
+        with self._tickets_lock:
+            self._tickets.add(int(t.value))
+            self._last_ticket = int(t.value)
         return int(t.value)
+
+    @property
+    def outstanding(self):
+        """exec_async() tickets not collected yet (Context.cached_plan never closes a plan that owes one)."""
+        with self._tickets_lock:
+            return len(self._tickets)
+
+    def next_ticket_slot_free(self):
+        """True when the next exec_async() ticket - the one after the last, on a plan that serves exec_async() only -
+        delivers into an output slot that holds no uncollected ticket, i.e. it overwrites nothing anybody still waits for."""
+        with self._tickets_lock:
+            return self._last_ticket + 1 - OUT_RING not in self._tickets
+
+    def _collected(self, ticket):
+        with self._tickets_lock:
+            self._tickets.discard(int(ticket))
 
     def poll(self, ticket):
         """-> None while the GPU is still working, else the float32 PSD (last_nseg is set)."""
@@ -463,7 +484,7 @@ class WelchPlan(object):
                        'oth_welch_poll')
         if not ready.value:
             return None
-        self.outstanding = max(0, getattr(self, 'outstanding', 0) - 1)
+        self._collected(ticket)
         self.last_nseg = n.value
         return out
 
@@ -473,7 +494,7 @@ class WelchPlan(object):
         try:
             self.ctx.check(self.ctx.lib.oth_welch_wait(self.h, int(ticket), _fptr(out), C.byref(n)), 'oth_welch_wait')
         finally:
-            self.outstanding = max(0, getattr(self, 'outstanding', 0) - 1)
+            self._collected(ticket)
         self.last_nseg = n.value
         return out
 

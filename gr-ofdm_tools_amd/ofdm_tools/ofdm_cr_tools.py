@@ -8,6 +8,7 @@ bookkeeping.  The FFTs, the Welch averaging, the moving average and the channel
 sums run in HIP kernels; nothing here falls back to NumPy/SciPy for them.
 """
 import math
+import threading
 
 import numpy as np
 
@@ -30,13 +31,31 @@ def _welch_plan(ctx, nfft, window_name, Sf, npts=None, use='exec'):
     """The reference's `sg.welch(x, Sf, window, nperseg=nfft, nfft=nfft)` + fftshift (ofdm_cr_tools.py:214,322,342).
     SciPy shortens nperseg to the input length when the vector is shorter than nfft ("nperseg = N is greater than input
     length", one zero-padded segment) - which fast_spectrum_scan(n_fft=0) always hits, its nFFT being the next power of
-    two above len(vct_sample) (ofdm_cr_tools.py:474-475)."""
+    two above len(vct_sample) (ofdm_cr_tools.py:474-475).  -> (cache key, factory) with use='async', else the plan."""
     nperseg = nfft if npts is None else min(int(nfft), int(npts))
-    # `use`: the ticket callers (SpectrumScan: exec_async / poll from work()) keep plans of their own - a plan's output ring
-    # holds the last four launches, and blocking helper calls on a shared plan could push an uncollected ticket out of it
-    return ctx.cached_plan(('welch', use, nfft, nperseg, window_name, float(Sf)),
-                 lambda: ctx.welch_plan(nfft, nperseg=nperseg, window=windows.get_window(window_name, nperseg), fs=float(Sf),
-                                        fftshift=True))
+    key = ('welch', use, nfft, nperseg, window_name, float(Sf))
+    make = lambda: ctx.welch_plan(nfft, nperseg=nperseg, window=windows.get_window(window_name, nperseg), fs=float(Sf),
+                                  fftshift=True)
+    # `use`: the ticket callers (SpectrumScan: exec_async / poll from work()) do not share plans with the blocking helpers,
+    # whose calls could push an uncollected ticket out of a plan's output ring; among themselves they share a pool
+    # (_exec_async_pooled)
+    return (key, make) if use == 'async' else ctx.cached_plan(key, make)
+
+
+def _exec_async_pooled(ctx, key, make, vector):
+    """exec_async() on the first plan of the shape's pool (cache keys key + (0,), key + (1,), ...) whose next ticket lands
+    in an output-ring slot no uncollected ticket holds (WelchPlan.next_ticket_slot_free: the library keeps launch t in
+    slot t % 4, so a plan owing fewer than four tickets can still be unsafe when they are collected out of order); a new
+    plan joins the pool when none is free.  Several scans of one shape in flight - SpectrumScans of several blocks on the
+    default context, collected in any order - then never lose a ticket to each other, and Context.cached_plan keeps every
+    plan that still owes one.  Pool plans serve exec_async() only.  -> (plan, ticket)."""
+    with ctx.__dict__.setdefault('_async_pool_lock', threading.Lock()):      # one free slot cannot go to two threads
+        i = 0
+        while True:
+            plan = ctx.cached_plan(key + (i,), make)
+            if plan.next_ticket_slot_free():
+                return plan, plan.exec_async(vector)
+            i += 1
 
 
 def frange(x, y, jump):
@@ -85,8 +104,8 @@ def _plain_channel_sums(psd, Fr, Sf, bb_freqs, srch_bins, ctx):
 
 def _enqueue_welch(vector, nFFT, Sf, ctx):
     """src_power_welch's PSD (flattop, nperseg = nfft, ofdm_cr_tools.py:213-216) as a ticket: -> (plan, ticket, post)."""
-    plan = _welch_plan(ctx, nFFT, 'flattop', Sf, len(vector), use='async')
-    return plan, plan.exec_async(vector), None
+    plan, ticket = _exec_async_pooled(ctx, *_welch_plan(ctx, nFFT, 'flattop', Sf, len(vector), use='async'), vector=vector)
+    return plan, ticket, None
 
 
 def _enqueue_fft(vector, nFFT, Sf, ctx):
@@ -95,10 +114,11 @@ def _enqueue_fft(vector, nFFT, Sf, ctx):
     total = len(vector)                   # the reference windows ALL len(vector) samples, then np.fft.fft(., nFFT) keeps the first nFFT
     vector = vector[:nFFT]
     npts = len(vector)
-    plan = ctx.cached_plan(('fft', nFFT, total, npts),
-                 lambda: ctx.welch_plan(nFFT, nperseg=npts, noverlap=0, window=windows.flattop(total)[:nFFT],
-                                        detrend=_hip.DETREND_NONE, scaling=_hip.SCALE_RAW, fftshift=True))
-    return plan, plan.exec_async(vector), (lambda psd: psd / np.float32(nFFT))
+    plan, ticket = _exec_async_pooled(
+        ctx, ('fft', nFFT, total, npts),
+        lambda: ctx.welch_plan(nFFT, nperseg=npts, noverlap=0, window=windows.flattop(total)[:nFFT],
+                               detrend=_hip.DETREND_NONE, scaling=_hip.SCALE_RAW, fftshift=True), vector)
+    return plan, ticket, (lambda psd: psd / np.float32(nFFT))
 
 
 def src_power_welch(vector, npts, nFFT, Fr, Sf, bb_freqs, srch_bins, ctx=None):

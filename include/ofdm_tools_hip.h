@@ -286,6 +286,10 @@ int oth_csd_scale_dev(oth_plan *plan, const float *sums_dev, uint64_t nseg_total
  * multichannel_scanner.py:78-86.  The chain keeps GNU Radio's stream state
  * between calls: leftover samples of a partial vector, the keep_one_in_n
  * counter, the IIR memory and the peak-hold vector.  nfft: any length (TRANSFORM LENGTHS above).
+ * oth_chain_set_keep_one_in_n is GNU Radio 3.7's keep_one_in_n::set_n (d_n = d_count = n): the count restarts in
+ * front of the vector that is still incomplete.  That vector is kept if the new count says so even when
+ * oth_chain_push_async skipped its first samples as dropped: such samples wait in host memory (a plain copy, no
+ * stream operation) and go to the device with the next push that enqueues work.
  */
 int oth_chain_create(oth_ctx *ctx, int nfft, const float *window, int fftshift, int epilogue,
                      int keep_one_in_n, oth_chain **out);

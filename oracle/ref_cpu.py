@@ -478,12 +478,42 @@ def gr_decimation(sample_rate, fft_len, rate):
     return max(1, int(_py2div(_py2div(sample_rate, fft_len), rate)))
 
 
-def gr_kept_vectors(x, fft_len, n):
+def gr_kept_indices(nvec, fft_len, n, schedule=None):
+    """Indices of the vectors keep_one_in_n(n) passes out of the first `nvec`
+    of stream_to_vector(fft_len), with ``set_n`` calls in mid-stream.
+
+    GNU Radio 3.7's keep_one_in_n::general_work counts down once per complete
+    vector and keeps the vector that brings ``d_count`` to 0 (then
+    ``d_count = d_n``); ``set_n(n)`` sets ``d_n = d_count = n``.  `schedule`
+    is a list of ``(sample_position, n)``: a call made once the stream has
+    delivered `sample_position` samples acts before the first vector that is
+    still incomplete there - a vector ending exactly at that position has
+    already been counted.  Calls at one position apply in list order."""
+    changes = sorted(schedule or (), key=lambda c: c[0])
+    d_n = d_count = int(n)
+    j = 0
+    kept = []
+    for v in range(int(nvec)):
+        end = (v + 1) * fft_len
+        while j < len(changes) and changes[j][0] < end:
+            d_n = d_count = int(changes[j][1])
+            j += 1
+        d_count -= 1
+        if d_count <= 0:
+            kept.append(v)
+            d_count = d_n
+    return kept
+
+
+def gr_kept_vectors(x, fft_len, n, schedule=None):
     """stream_to_vector(fft_len) then keep_one_in_n(n): the LAST of every n
-    vectors (indices n-1, 2n-1, ...)."""
+    vectors (indices n-1, 2n-1, ...); with a `schedule` of set_n calls, the
+    vectors gr_kept_indices selects."""
     nvec = len(x) // fft_len
     v = np.asarray(x[:nvec * fft_len]).reshape(nvec, fft_len)
-    return v[n - 1::n]
+    if schedule is None:
+        return v[n - 1::n]
+    return v[gr_kept_indices(nvec, fft_len, n, schedule)]
 
 
 def gr_fft_vcc(vecs, window=None, shift=True):
@@ -496,10 +526,10 @@ def gr_fft_vcc(vecs, window=None, shift=True):
     return np.fft.fftshift(X, axes=1) if shift else X
 
 
-def chain_sensor_v2(x, fft_len, decim=1):
+def chain_sensor_v2(x, fft_len, decim=1, schedule=None):
     """spectrum_sensor_v2.py:85-93,116 (= multichannel_scanner.py:78-86,100):
     rectangular window, shifted FFT, |.|^2, x 1/N^2, per kept vector."""
-    X = gr_fft_vcc(gr_kept_vectors(x, fft_len, decim), None, True)
+    X = gr_fft_vcc(gr_kept_vectors(x, fft_len, decim, schedule), None, True)
     return (X.real ** 2 + X.imag ** 2) * (1.0 / float(fft_len ** 2))
 
 
@@ -515,19 +545,19 @@ def chain_sensor_v2_mean_c64(x, fft_len):
     return np.fft.fftshift(p.mean(axis=0, dtype=np.float64))
 
 
-def chain_psd_logger(x, fft_len, decim=1):
+def chain_psd_logger(x, fft_len, decim=1, schedule=None):
     """psd_logger.py:43-56,85: Blackman-Harris FFT (no shift), magnitude,
     running peak.  The first vector initialises the peak."""
-    X = gr_fft_vcc(gr_kept_vectors(x, fft_len, decim), gr_blackmanharris(fft_len), False)
+    X = gr_fft_vcc(gr_kept_vectors(x, fft_len, decim, schedule), gr_blackmanharris(fft_len), False)
     mag = np.abs(X)
     return mag, np.maximum.accumulate(mag, axis=0)
 
 
-def chain_local_worker(x, fft_len, sample_rate, average, decim=1):
+def chain_local_worker(x, fft_len, sample_rate, average, decim=1, schedule=None):
     """local_worker.py:58-71,79: BH-windowed shifted FFT, |.|^2,
     single_pole_iir_filter_ff(average) (y = a x + (1-a) y_prev, y_-1 = 0),
     nlog10_ff(10, N, -10log10(N) - 10log10(Sf))."""
-    X = gr_fft_vcc(gr_kept_vectors(x, fft_len, decim), gr_blackmanharris(fft_len), True)
+    X = gr_fft_vcc(gr_kept_vectors(x, fft_len, decim, schedule), gr_blackmanharris(fft_len), True)
     p = X.real ** 2 + X.imag ** 2
     k = -10 * math.log10(fft_len) - 10 * math.log10(sample_rate)
     y = np.zeros(fft_len)

@@ -1311,21 +1311,28 @@ def test_work_sized_pushes_cost_at_most_three_stream_operations(ctx):
     assert len(rows) == len(ref) == 3
     check_single_rows(np.array(rows), ref)
     assert ops.count(0) >= len(ops) - 3 * 3, (len(ops), ops.count(0))      # only the pushes that touch a kept vector do anything
-    # set_keep_one_in_n in mid-stream keeps the vector grid (a partial vector whose samples were skipped is not emitted)
+    # set_keep_one_in_n in mid-stream, row by row against GNU Radio's keep_one_in_n::set_n (d_n = d_count = n in front of
+    # the vector still incomplete at the call; tests/test_chain_async_gpu.py has the other push forms and cases)
     ch = ctx.chain(N, None, True, _hip_epi(), 7)
-    got = []
+    schedule = [(4900, 2)]
+    ref = R.chain_sensor_v2(x[:20 * N], N, 7, schedule)
+    kept = R.gr_kept_indices(20, N, 7, schedule)
+    got, want = [], []
     for pos in range(0, 20 * N, 700):
         if pos == 4900:
             ch.set_keep_one_in_n(2)
-        t = ch.push_async(x[pos:min(pos + 700, 20 * N)])
+        end = min(pos + 700, 20 * N)
+        t = ch.push_async(x[pos:end])
+        done = [i for i, v in enumerate(kept) if pos < (v + 1) * N <= end]      # (700 < N: one vector at most)
+        assert ch.ticket_rows(t) == len(done), pos
         row, k = ch.wait(t)
+        assert k == len(done), pos
         if k:
             got.append(row.copy())
+            want.append(ref[done[-1]])
     ch.close()
-    allrows = R.chain_sensor_v2(x[:20 * N], N)
-    assert 5 <= len(got) <= 8
-    for r in got:      # every emitted row is a vector of the N-aligned grid
-        assert min(float(np.max(np.abs(r - a) / a.max())) for a in allrows) < 1e-5
+    assert len(got) == len(kept) == 8
+    check_single_rows(np.array(got), np.array(want))
 
 
 def _hip_epi():

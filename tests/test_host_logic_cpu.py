@@ -1,10 +1,12 @@
 """CPU tests of the host logic around the HIP path: wire format, decision stage, block API
 surface, and the multi-rank sweep sharding over gloo (world_size 2, and 8 for BASELINE config 4's own shape)."""
+import ctypes as C
 import inspect
 import os
 import struct
 import subprocess
 import sys
+import threading
 
 import numpy as np
 import pytest
@@ -423,6 +425,170 @@ class _Rx(object):
 
     def set_center_freq(self, f, chan):
         self.tuned.append(f)
+
+
+class _RingLib(object):
+    """The part of the C ABI that WelchPlan's tickets use, with the library's output ring: launch t of a plan delivers
+    into slot t % 4 (oth_plan::kOutRing), and collecting a ticket whose slot a later launch took is OTH_ERR_STATE.  The
+    PSD a ticket returns is the first sample of the vector it was enqueued with.  The real Context / WelchPlan code runs
+    on top of it."""
+
+    def __init__(self):
+        self.plans, self.closed, self.lock = {}, set(), threading.Lock()
+
+    def oth_welch_plan(self, ctx, nfft, nperseg, noverlap, w, detrend, scaling, fs, shift, trim, out):
+        with self.lock:
+            h = len(self.plans) + 1
+            self.plans[h] = {'next': 1, 'ring': {}, 'nfft': nfft}
+        out._obj.value = h
+        return 0
+
+    def oth_plan_out_len(self, h, n):
+        n._obj.value = self.plans[h.value]['nfft']
+        return 0
+
+    def oth_plan_destroy(self, h):
+        self.closed.add(h.value)
+
+    def oth_last_error(self, h):
+        return b'ticket unknown or overwritten'
+
+    def oth_welch_exec_async(self, h, x, nsamples, is_dev, t):
+        p = self.plans[h.value]
+        with self.lock:
+            ticket = p['next']
+            p['next'] += 1
+            p['ring'][ticket % 4] = (ticket, C.cast(x, C.POINTER(C.c_float))[0])
+        t._obj.value = ticket
+        return 0
+
+    def _collect(self, h, ticket, out):
+        p = self.plans[h.value]
+        held, value = p['ring'].get(ticket % 4, (0, 0.0))
+        if held != ticket:
+            return -5
+        for i in range(p['nfft']):
+            out[i] = value
+        return 0
+
+    def oth_welch_poll(self, h, ticket, out, n, ready):
+        rc = self._collect(h, ticket, out)
+        ready._obj.value = 1 if rc == 0 else 0
+        return rc
+
+    def oth_welch_wait(self, h, ticket, out, n):
+        return self._collect(h, ticket, out)
+
+
+def _ring_ctx():
+    from ofdm_tools import _hip
+    ctx = object.__new__(_hip.Context)        # the real cached_plan (LRU) and welch_plan, on _RingLib
+    ctx.lib, ctx.h, ctx.device, ctx.stream = _RingLib(), C.c_void_p(1), 0, None
+    ctx._plans_lock = threading.Lock()
+    return ctx
+
+
+def _pool_plans(ctx):
+    return [p for k, p in ctx._plans.items() if k[0] != 'other']
+
+
+def test_async_scans_of_one_shape_get_a_plan_pool_without_gpu():
+    """SpectrumScan's enqueue helpers (oth_welch_exec_async tickets): ten scans of one shape in flight never share a plan
+    beyond its four-launch output ring - the pool grows to three plans (4 + 4 + 2 tickets) and every ticket collects its
+    own vector; once they are collected the first plan serves again; the blocking helpers keep a plan of their own; the
+    LRU of Context.cached_plan never closes a plan that still owes a ticket, and does close it afterwards."""
+    from ofdm_tools import ofdm_cr_tools as T
+    vecs = [np.full(8192, i + 1, np.complex64) for i in range(10)]
+    for enqueue in (T._enqueue_welch, T._enqueue_fft):
+        ctx = _ring_ctx()
+        got = [enqueue(v, 1024, 1000000, ctx)[:2] for v in vecs]
+        made = _pool_plans(ctx)
+        assert len(made) == 3
+        assert [sum(p is q for p, _ in got) for q in made] == [4, 4, 2]
+        # LRU pressure while all ten are in flight: 70 other shapes past the limit of 64
+        for i in range(70):
+            ctx.cached_plan(('other', i), lambda: ctx.welch_plan(64))
+        assert not any(p.h.value in ctx.lib.closed for p in made)
+        for i in reversed(range(10)):
+            plan, ticket = got[i]
+            assert plan.wait(ticket)[0] == i + 1
+        assert all(p.outstanding == 0 for p in made)
+        plan, ticket = enqueue(vecs[3], 1024, 1000000, ctx)[:2]
+        assert plan is made[0] and len(_pool_plans(ctx)) == 3 and plan.wait(ticket)[0] == 4
+        for i in range(70, 140):                   # nothing owed any more: the pool's plans age out like any other
+            ctx.cached_plan(('other', i), lambda: ctx.welch_plan(64))
+        assert all(p.h is None for p in made)
+    # the blocking helpers' plan is not one of the pool's
+    ctx = _ring_ctx()
+    blocking = T._welch_plan(ctx, 1024, 'flattop', 1000000, 8192)
+    pooled, _, _ = T._enqueue_welch(vecs[0], 1024, 1000000, ctx)
+    assert blocking is not pooled and len(ctx._plans) == 2
+
+
+def test_async_scan_pool_with_out_of_order_collects_without_gpu():
+    """Scans collected out of order: four in flight on one plan, the last three collected, one more enqueued - that
+    launch would take the first scan's ring slot, so it goes to another plan and the first scan still collects its own
+    result.  Then a seeded random interleaving of enqueues and collects (wait or poll, any order, up to 12 in flight) on
+    one shape: every scan gets its own vector, and no plan ever owes a ticket whose slot its next launch would take."""
+    from ofdm_tools import ofdm_cr_tools as T
+    for enqueue in (T._enqueue_welch, T._enqueue_fft):
+        ctx = _ring_ctx()
+        vec = lambda v: np.full(8192, v, np.complex64)      # noqa: E731
+        first = [enqueue(vec(i + 1), 1024, 1000000, ctx)[:2] for i in range(4)]
+        for plan, t in first[1:]:
+            plan.wait(t)
+        plan5, t5 = enqueue(vec(5), 1024, 1000000, ctx)[:2]
+        assert plan5 is not first[0][0]
+        assert first[0][0].wait(first[0][1])[0] == 1 and plan5.wait(t5)[0] == 5
+        plan6, t6 = enqueue(vec(6), 1024, 1000000, ctx)[:2]
+        assert plan6 is first[0][0] and plan6.wait(t6)[0] == 6      # its next slot is free again
+        rng = np.random.default_rng(11)
+        pending, value = [], 100
+        for _ in range(600):
+            if pending and (len(pending) >= 12 or rng.random() < 0.45):
+                plan, t, v = pending.pop(int(rng.integers(len(pending))))
+                psd = plan.wait(t) if rng.random() < 0.5 else plan.poll(t)
+                assert psd is not None and psd[0] == v
+            else:
+                value += 1
+                plan, t = enqueue(vec(value), 1024, 1000000, ctx)[:2]
+                pending.append((plan, t, value))
+        for plan, t, v in pending:
+            assert plan.wait(t)[0] == v
+        assert all(p.outstanding == 0 for p in _pool_plans(ctx))
+        assert len(_pool_plans(ctx)) <= 12
+
+
+def test_async_scan_pool_shared_by_threads_without_gpu():
+    """Block threads enqueue and collect on one shape at once: the per-plan ticket bookkeeping is updated under a lock,
+    so no scan loses its result and every plan ends owing nothing."""
+    from ofdm_tools import ofdm_cr_tools as T
+    ctx = _ring_ctx()
+    errors = []
+
+    def worker(k):
+        try:
+            held = []
+            for j in range(300):
+                v = float(k * 1000 + j + 1)
+                held.append(T._enqueue_welch(np.full(8192, v, np.complex64), 1024, 1000000, ctx)[:2] + (v,))
+                if len(held) > 2 or j % 7 == 0:
+                    plan, t, want = held.pop(0 if j % 2 else -1)
+                    if plan.wait(t)[0] != want:
+                        errors.append((k, j))
+            for plan, t, want in held:
+                if plan.wait(t)[0] != want:
+                    errors.append((k, 'end'))
+        except Exception as e:      # noqa: BLE001 - report anything from the worker thread
+            errors.append(repr(e))
+
+    ts = [threading.Thread(target=worker, args=(k,)) for k in range(6)]
+    for th in ts:
+        th.start()
+    for th in ts:
+        th.join()
+    assert not errors, errors[:5]
+    assert all(p.outstanding == 0 for p in _pool_plans(ctx))
 
 
 def test_spectrum_sweeper_stitcher_thread_start_stop_without_gpu():

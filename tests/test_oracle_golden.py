@@ -89,6 +89,48 @@ def test_keep_one_in_n_takes_last_of_group():
     assert R.gr_decimation(1000000, 1024, 10) == 97  # int(1000000/1024/10) with py2 int division
 
 
+def test_keep_one_in_n_without_a_schedule_is_unchanged():
+    """An empty set_n schedule selects exactly the vectors of the plain rule (v[n-1::n]), and the chains return the same
+    arrays bit for bit with and without it."""
+    for nvec, N, n in ((10, 4, 3), (23, 8, 5), (7, 4, 1), (3, 4, 7), (0, 4, 2), (41, 16, 100)):
+        x = (np.arange(nvec * N + 3) * (1 + 1j)).astype(np.complex64)
+        plain = R.gr_kept_vectors(x, N, n)
+        assert R.gr_kept_indices(nvec, N, n) == list(range(n - 1, nvec, n))
+        assert R.gr_kept_indices(nvec, N, n, []) == list(range(n - 1, nvec, n))
+        assert np.array_equal(R.gr_kept_vectors(x, N, n, []), plain)
+    x = R.synth_iq(64 * 20 + 9, 5)
+    assert np.array_equal(R.chain_sensor_v2(x, 64, 3, []), R.chain_sensor_v2(x, 64, 3))
+    for a, b in zip(R.chain_psd_logger(x, 64, 3, []), R.chain_psd_logger(x, 64, 3)):
+        assert np.array_equal(a, b)
+    for a, b in zip(R.chain_local_worker(x, 64, 1e6, 0.3, 3, []), R.chain_local_worker(x, 64, 1e6, 0.3, 3)):
+        assert np.array_equal(a, b)
+
+
+@pytest.mark.parametrize('schedule, want', [
+    ([], [2, 5, 8]),
+    ([(12, 2)], [2, 4, 6, 8]),                     # on the boundary of vectors 2 / 3: vector 2 was counted with n = 3
+    ([(13, 2)], [2, 4, 6, 8]),                     # inside vector 3: restarts the count in front of it
+    ([(11, 2)], [3, 5, 7, 9]),                     # inside vector 2, which n = 3 would have kept: it is not now
+    ([(5, 1)], [1, 2, 3, 4, 5, 6, 7, 8, 9]),       # set_n(1) while vector 1 (a dropped one under n = 3) is partial
+    ([(8, 1)], [2, 3, 4, 5, 6, 7, 8, 9]),          # set_n(1) right after vector 1 completed: vector 1 stays dropped
+    ([(5, 1), (7, 4)], [4, 8]),                    # two changes inside one vector: the later one holds
+    ([(6, 4), (6, 1)], [1, 2, 3, 4, 5, 6, 7, 8, 9]),   # two at one position: in call order
+    ([(0, 2)], [1, 3, 5, 7, 9]),                   # before the first sample
+    ([(40, 1)], [2, 5, 8]),                        # after the last complete vector
+    ([(26, 2), (5, 4)], [4, 7, 9]),                # unsorted: applied in stream order (n = 4 at 5, n = 2 at 26)
+])
+def test_keep_one_in_n_set_n_schedule_hand_worked(schedule, want):
+    """GNU Radio 3.7 keep_one_in_n with set_n in mid-stream, 4-sample vectors, n = 3, ten vectors (sample positions
+    0..40): d_count goes down once per complete vector, the vector that takes it to 0 is kept, set_n(m) sets
+    d_n = d_count = m in front of the first vector still incomplete at the call's position."""
+    x = np.arange(10 * 4 + 2).astype(np.complex64)
+    assert R.gr_kept_indices(10, 4, 3, schedule) == want
+    v = R.gr_kept_vectors(x, 4, 3, schedule)
+    assert v.shape == (len(want), 4) and np.array_equal(v[:, 0].real, 4 * np.array(want, float))
+    rows = R.chain_sensor_v2(x, 4, 3, schedule)
+    assert np.allclose(rows, R.chain_sensor_v2(x[np.add.outer(4 * np.array(want), np.arange(4)).ravel()], 4))
+
+
 def test_src_power_cases(golden):
     g = golden('src_power_cases.npz')
     for i in range(int(g['n'])):
