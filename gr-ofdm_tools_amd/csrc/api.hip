@@ -123,6 +123,19 @@ struct oth_plan {
     // first caller's row before it was copied out (advisor, round 5).
     std::mutex exec_mu;
     int hostwait = 0;                  // 0 poll the completion word (default), 1 hipStreamSynchronize (oth_plan_set_hostwait)
+    // average = OTH_AVERAGE_MEDIAN (oth_plan_set_average): the rows producer writes one raw |X|^2 row per segment into
+    // d_rows ([stream][segment][nfft], grown on demand: ensure() drains the stream before it frees, so a queued ticket
+    // never reads a freed buffer), median.hip selects into d_med, finalize_kernel scales by scale / bias
+    int average = OTH_AVERAGE_MEAN;
+    float *d_rows = nullptr;
+    size_t rows_cap = 0;
+    float *d_med = nullptr;            // [nstreams][nfft] medians, natural bin order
+    size_t med_cap = 0;
+    unsigned *d_msel = nullptr;        // radix-select scratch (median_scratch_words)
+    size_t msel_cap = 0;
+    AnyTables rows_any;                // the any-length tables of a power-of-two plan's rows (p->any serves the others)
+    long long bias_nseg = 0;           // _median_bias(bias_nseg) = bias, cached
+    double bias = 1.0;
 };
 
 struct oth_chain {
@@ -1344,6 +1357,108 @@ int finalize_and_rearm(oth_ctx *c, FinalizeArgs &f, int nstreams) {
     return OTH_OK;
 }
 
+// ---- median average (OTH_AVERAGE_MEDIAN) --------------------------------------------------------------------------------
+// scipy.signal._spectral_helper's _median_bias(n): 1 + sum_{i=1}^{(n-1)//2} (1 / (2 i + 1) - 1 / (2 i)), in double
+double median_bias(long long n) {
+    double b = 1.0;
+    for (long long i = 1; i <= (n - 1) / 2; ++i) b += 1.0 / (double)(2 * i + 1) - 1.0 / (double)(2 * i);
+    return b;
+}
+
+int refuse_median(oth_plan *p, const char *what) {
+    return fail(p->ctx, OTH_ERR_UNSUPPORTED, std::string(what) + " is not available with OTH_AVERAGE_MEDIAN: a median is not a "
+                "sum of partials (the median runs through oth_welch_exec, _exec_async and _exec_dev)");
+}
+
+// Rows producer: nseg raw |X|^2 rows per stream, [stream][segment][nfft] in natural bin order, into p->d_rows.  256 ... 4096
+// points with nperseg = nfft: the chain build of seg_kernel (segfft.hip launch_seg_rows); every other shape: any_run's rows.
+int median_rows(oth_plan *p, const float2 *x, int nstreams, size_t stride, long long nseg, const char **route) {
+    oth_ctx *c = p->ctx;
+    const int N = p->nfft;
+    const size_t need = sizeof(float) * (size_t)nstreams * (size_t)nseg * (size_t)N;
+    if (int rc = ensure(c, &p->d_rows, &p->rows_cap, need)) {
+        if (rc != OTH_ERR_NOMEM) return rc;
+        return fail(c, rc, "per-segment rows workspace of " + std::to_string(need) +
+                               " bytes (nstreams x nseg x nfft x 4 B) could not be allocated (" + c->err + ")");
+    }
+    const bool det = p->detrend != OTH_DETREND_NONE;
+    if (seg_supported(N) && p->nperseg == N) {
+        SegArgs a{};
+        a.x = x;
+        a.stream_stride = stride;
+        a.nstreams = nstreams;
+        a.win = p->d_win;
+        a.tw = p->d_tw;
+        a.first = 0;
+        a.step = p->step;
+        a.nseg = nseg;
+        a.detrend = det ? 1 : 0;
+        a.chain = 1;
+        a.acc_mode = 3;      // rows only
+        a.rows = p->d_rows;
+        a.store_from = 0;
+        a.epilogue = OTH_EPI_MAG2;
+        a.scale = 1.0f;
+        // interleaved chunks, as the chain's fused launch
+        const long long teams_max = (long long)c->cu_count * seg_rows_teams_per_cu(N);
+        a.chunk = nseg >= 16 * teams_max ? 8 : (nseg >= 4 * teams_max ? 4 : 2);
+        const long long nchunks = (nseg + a.chunk - 1) / a.chunk;
+        a.wg_per_stream = (int)std::max(1LL, std::min(teams_max, nchunks));
+        a.sched = 1;
+        a.tail_chunk = a.chunk;
+        a.nbig = nseg / a.chunk;
+        HIPCHK(c, launch_seg_rows(N, a, c->stream));
+        *route = "seg";
+        return OTH_OK;
+    }
+    AnyTables *t = &p->any;
+    if (t->sh.kind == ANY_NONE) {      // power-of-two plans: tables of their own (any_describe: "direct" up to 16384)
+        t = &p->rows_any;
+        if (t->sh.kind == ANY_NONE)
+            if (int rc = any_tables_init(c, N, t)) return rc;
+    }
+    for (int st = 0; st < nstreams; ++st)
+        if (int rc = any_run(c, *t, x + (size_t)st * stride, nullptr, 0, p->step, p->nperseg, p->d_win, det, nseg, nullptr, 0,
+                             p->d_rows + (size_t)st * nseg * N, OTH_EPI_MAG2, 1.0f, 0))
+            return rc;
+    *route = kAnyKindName[t->sh.kind];
+    return OTH_OK;
+}
+
+// rows + radix select: the medians of every bin of every stream land in p->d_med ([stream][nfft], unscaled)
+int median_run(oth_plan *p, const float2 *x, size_t nsamples, int nstreams, size_t stride, long long *nseg_out) {
+    oth_ctx *c = p->ctx;
+    long long nseg = 0;
+    if (segments(p, nsamples, &nseg) != OTH_OK) return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
+    if (nseg >= (1LL << 31)) return fail(c, OTH_ERR_UNSUPPORTED, "median average: more than 2^31 segments per stream");
+    const int N = p->nfft;
+    int rc = ensure(c, &p->d_med, &p->med_cap, sizeof(float) * (size_t)nstreams * N);
+    if (!rc) rc = ensure(c, &p->d_msel, &p->msel_cap, sizeof(unsigned) * median_scratch_words(N, nstreams));
+    if (rc) return rc;
+    MedianArgs m{};
+    m.nseg = nseg;
+    m.nfft = N;
+    m.nstreams = nstreams;
+    m.seg_per_wg = median_seg_per_wg(nseg, N, nstreams, c->cu_count);
+    median_bind_scratch(m, p->d_msel);
+    m.med = p->d_med;
+    const char *route = "";
+    {
+        Timed tm(c);      // rows producer + selection
+        if ((rc = median_rows(p, x, nstreams, stride, nseg, &route))) return rc;
+        m.rows = reinterpret_cast<const unsigned *>(p->d_rows);
+        HIPCHK(c, launch_median_select(m, c->stream));
+    }
+    p->last_recipe = std::string("kernel=median rows=") + route + " nfft=" + std::to_string(N) + " nseg=" + std::to_string(nseg) +
+                     " nstreams=" + std::to_string(nstreams) + " select=radix8x4 seg_per_wg=" + std::to_string(m.seg_per_wg);
+    if (p->bias_nseg != nseg) {
+        p->bias = median_bias(nseg);
+        p->bias_nseg = nseg;
+    }
+    *nseg_out = nseg;
+    return OTH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1728,6 +1843,10 @@ int oth_plan_destroy(oth_plan *p) {
     if (p->d_sum) hipFree(p->d_sum);
     if (p->d_stream) hipFree(p->d_stream);
     any_tables_free(p->any);
+    any_tables_free(p->rows_any);
+    if (p->d_rows) hipFree(p->d_rows);
+    if (p->d_med) hipFree(p->d_med);
+    if (p->d_msel) hipFree(p->d_msel);
     for (int i = 0; i < 4; ++i) {
         if (p->h_ring[i]) hipHostFree(p->h_ring[i]);
         if (p->h_ring_ev[i]) hipEventDestroy(p->h_ring_ev[i]);
@@ -1814,6 +1933,54 @@ int oth_plan_out_len(oth_plan *p, int *n) {
     OTH_CATCH((p ? p->ctx : nullptr))
 }
 
+int oth_plan_set_average(oth_plan *p, int mode) {
+    OTH_TRY
+    CtxGuard guard_(p ? p->ctx : nullptr);
+    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    if (mode != OTH_AVERAGE_MEAN && mode != OTH_AVERAGE_MEDIAN) return fail(p->ctx, OTH_ERR_INVALID, "unknown average mode");
+    if (p->nseg_total || p->carry)
+        return fail(p->ctx, OTH_ERR_STATE, "an accumulation is in progress (oth_welch_finalize or oth_welch_reset first)");
+    p->average = mode;
+    return OTH_OK;
+    OTH_CATCH((p ? p->ctx : nullptr))
+}
+
+int oth_welch_segments_dev(oth_plan *p, const void *iq_dev, size_t nsamples, float *rows_dev, uint64_t capacity_rows,
+                           uint64_t *nseg_out) {
+    OTH_TRY
+    CtxGuard guard_(p ? p->ctx : nullptr);
+    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    oth_ctx *c = p->ctx;
+    if (!iq_dev || !rows_dev) return fail(c, OTH_ERR_INVALID, "bad argument");
+    long long nseg = 0;
+    if (segments(p, nsamples, &nseg) != OTH_OK) return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
+    if ((uint64_t)nseg > capacity_rows)
+        return fail(c, OTH_ERR_INVALID, "capacity_rows " + std::to_string(capacity_rows) + " < nseg " + std::to_string(nseg));
+    if (use_device(c)) return OTH_ERR_HIP;
+    const char *route = "";
+    if (int rc = median_rows(p, (const float2 *)iq_dev, 1, nsamples, nseg, &route)) return rc;
+    // the plan's scaling, fftshift, trim and dB per row: finalize_kernel with one "stream" per segment (grid.y <= 65535)
+    const int nout = p->nfft - 2 * p->trim;
+    for (long long s0 = 0; s0 < nseg; s0 += 65535) {
+        const long long nb = std::min(65535LL, nseg - s0);
+        FinalizeArgs f{};
+        f.partial = p->d_rows + (size_t)s0 * p->nfft;
+        f.out0 = rows_dev + (size_t)s0 * nout;
+        f.scale = p->scale;
+        f.W = 1;
+        f.nfft = p->nfft;
+        f.nch = 1;
+        f.fftshift = p->fftshift;
+        f.trim = p->trim;
+        f.db = p->db;
+        f.nout = nout;
+        HIPCHK(c, launch_finalize(f, (int)nb, c->stream));
+    }
+    if (nseg_out) *nseg_out = (uint64_t)nseg;
+    return OTH_OK;
+    OTH_CATCH((p ? p->ctx : nullptr))
+}
+
 // averaging launch + finalize into psd_out (device memory, or a pinned host row when host_seq is given: the finalize
 // launch then also publishes seq_value there once the row is complete)
 static int welch_exec_dev_impl(oth_plan *p, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride,
@@ -1824,13 +1991,21 @@ static int welch_exec_dev_impl(oth_plan *p, const void *iq_dev, size_t nsamples,
     if (use_device(c)) return OTH_ERR_HIP;
     long long nseg = 0;
     int W = 0, layout = 0;
-    int rc = run_average(p, (const float2 *)iq_dev, nullptr, nsamples, nstreams, stream_stride, &nseg, &W, &layout);
-    if (rc) return rc;
     FinalizeArgs f{};
-    f.partial = p->d_partial;
-    f.scratch = p->d_reduce;
+    if (p->average == OTH_AVERAGE_MEDIAN) {
+        // one row of medians per stream: finalize_kernel applies scale / bias, fftshift, trim and dB
+        if (int rc = median_run(p, (const float2 *)iq_dev, nsamples, nstreams, stream_stride, &nseg)) return rc;
+        f.partial = p->d_med;
+        f.scale = p->scale / p->bias;
+        W = 1;
+    } else {
+        int rc = run_average(p, (const float2 *)iq_dev, nullptr, nsamples, nstreams, stream_stride, &nseg, &W, &layout);
+        if (rc) return rc;
+        f.partial = p->d_partial;
+        f.scratch = p->d_reduce;
+        f.scale = p->scale / (double)nseg;
+    }
     f.out0 = psd_out_dev;
-    f.scale = p->scale / (double)nseg;
     f.W = W;
     f.nfft = p->nfft;
     f.nch = 1;
@@ -2079,6 +2254,7 @@ int oth_welch_partial_dev(oth_plan *p, const void *iq_dev, size_t nsamples, floa
     OTH_TRY
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_welch_partial_dev");
     oth_ctx *c = p->ctx;
     if (!iq_dev || !sum_out_dev) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (use_device(c)) return OTH_ERR_HIP;
@@ -2107,6 +2283,7 @@ int oth_welch_scale_dev(oth_plan *p, const float *sum_dev, uint64_t nseg_total, 
     OTH_TRY
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_welch_scale_dev");
     oth_ctx *c = p->ctx;
     if (!sum_dev || !psd_out_dev || !nseg_total) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (use_device(c)) return OTH_ERR_HIP;
@@ -2133,6 +2310,7 @@ int oth_welch_accumulate(oth_plan *p, const void *iq_host, size_t nsamples) {
     OTH_TRY
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_welch_accumulate");
     oth_ctx *c = p->ctx;
     if (!iq_host && nsamples) return fail(c, OTH_ERR_INVALID, "iq is NULL");
     if (!nsamples) return OTH_OK;
@@ -2214,6 +2392,7 @@ int oth_welch_finalize(oth_plan *p, float *psd_out, uint64_t *nseg_out) {
     OTH_TRY
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_welch_finalize");
     oth_ctx *c = p->ctx;
     if (!psd_out) return fail(c, OTH_ERR_INVALID, "psd_out is NULL");
     if (!p->nseg_total) return fail(c, OTH_ERR_STATE, "no complete segment accumulated yet");
@@ -2265,6 +2444,7 @@ int oth_csd_exec_dev(oth_plan *p, const void *x_dev, const void *y_dev, size_t n
     OTH_TRY
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_csd_exec_dev");
     oth_ctx *c = p->ctx;
     if (!x_dev || !y_dev) return fail(c, OTH_ERR_INVALID, "x/y is NULL");
     if (p->db) return fail(c, OTH_ERR_UNSUPPORTED, "dB output is not defined for the cross spectrum");
@@ -2280,6 +2460,7 @@ int oth_csd_partial_dev(oth_plan *p, const void *x_dev, const void *y_dev, size_
     OTH_TRY
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_csd_partial_dev");
     oth_ctx *c = p->ctx;
     if (!x_dev || !y_dev || !sums_out_dev) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (nsamples < (size_t)p->nperseg) return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
@@ -2295,6 +2476,7 @@ int oth_csd_scale_dev(oth_plan *p, const float *sums_dev, uint64_t nseg_total, f
     OTH_TRY
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_csd_scale_dev");
     oth_ctx *c = p->ctx;
     if (!sums_dev || !nseg_total) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (use_device(c)) return OTH_ERR_HIP;
@@ -2309,6 +2491,7 @@ int oth_csd_exec(oth_plan *p, const void *x, const void *y, size_t nsamples, int
     OTH_TRY
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_csd_exec");
     oth_ctx *c = p->ctx;
     if (!x || !y) return fail(c, OTH_ERR_INVALID, "x/y is NULL");
     if (p->db) return fail(c, OTH_ERR_UNSUPPORTED, "dB output is not defined for the cross spectrum");

@@ -350,4 +350,30 @@ hipError_t launch_tl_mean(const float2 *x, long long first, long long seg_step, 
 hipError_t launch_tl_k1(int L, const TlArgs &a, hipStream_t s);
 hipError_t launch_tl_k2(int L, const TlArgs &a, int W, hipStream_t s);
 
+// ---- median over segments (scipy.signal.welch average='median') ------------------------------------------------------
+// segfft.hip: one raw |X|^2 row per segment, [stream][segment][nfft] in natural bin order, nperseg = nfft 256 ... 4096;
+// a.detrend: each segment's own mean comes off (time domain, before the transform).  SegArgs as the chain's (chain = 1).
+int seg_rows_teams_per_cu(int nfft);
+hipError_t launch_seg_rows(int nfft, const SegArgs &a, hipStream_t s);
+
+// median.hip: exact order statistics of nseg rows per bin by a radix select over the float bit patterns (8-bit digits
+// from the top, four passes; integer counts only, so the result does not depend on the schedule).
+struct MedianArgs {
+    const unsigned *rows;   // [nstreams][nseg][nfft] bit patterns of non-negative floats (|X|^2)
+    long long nseg;
+    long long seg_per_wg;   // segments of one histogram workgroup (grid.y chunks per tile)
+    int nfft;
+    int nstreams;
+    unsigned *counts;       // [nstreams][nfft][256] digit counts of the pass, all zero between passes
+    unsigned *state;        // [nstreams][nfft][2]: key prefix fixed so far, rank left inside it
+    unsigned *above;        // [nstreams][nfft]: smallest key above the final 24-bit bucket (last pass)
+    unsigned *nanflag;      // [nstreams][nfft]: 1 when a segment value of the bin is NaN
+    float *med;             // [nstreams][nfft] the median (mean of the two middle values for even nseg)
+};
+constexpr int kMedianTile = 64;                 // bins per histogram workgroup
+size_t median_scratch_words(int nfft, int nstreams);      // counts + state + above + nanflag
+void median_bind_scratch(MedianArgs &a, unsigned *scratch);
+long long median_seg_per_wg(long long nseg, int nfft, int nstreams, int cu_count);
+hipError_t launch_median_select(const MedianArgs &a, hipStream_t s);
+
 }  // namespace oth

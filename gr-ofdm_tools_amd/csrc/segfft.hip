@@ -999,6 +999,30 @@ hipError_t launch_seg_padded(int nfft, int nperseg, const SegArgs &a, int kind, 
     return nperseg * 4 == nfft ? launch_pad<8, 4>(a, kind, s) : launch_pad<8, 8>(a, kind, s);
 }
 
+// Rows of the median average (api.hip median_rows): the chain build (CHAIN, whole-segment loads, SegArgs.acc_mode 3,
+// epilogue |X|^2 x 1) with an overlapped step; with a.detrend each segment's own mean comes off before the window - a build
+// of its own (DETREND and CHAIN), no pilot.
+template <int R> hipError_t launch_rows_r(const SegArgs &a, hipStream_t s) {
+    if (!a.detrend) return launch_one<R, LOAD_FULL, false, true, OTH_CHAIN_WPS>(a, s);
+    const dim3 grid((a.wg_per_stream + Geo<R>::TPB - 1) / Geo<R>::TPB, a.nstreams);
+    constexpr size_t lds = seg_lds_bytes<R, true>();
+    hipLaunchKernelGGL((seg_kernel<R, LOAD_FULL, true, true, OTH_CHAIN_WPS>), grid, dim3(Geo<R>::BLOCK), lds, s, a);
+    return hipGetLastError();
+}
+
+int seg_rows_teams_per_cu(int nfft) { return seg_teams_per_cu(nfft, 2, false); }
+
+hipError_t launch_seg_rows(int nfft, const SegArgs &a, hipStream_t s) {
+    switch (nfft) {
+        case 256: return launch_rows_r<1>(a, s);
+        case 512: return launch_rows_r<2>(a, s);
+        case 1024: return launch_rows_r<4>(a, s);
+        case 2048: return launch_rows_r<8>(a, s);
+        case 4096: return launch_rows_r<16>(a, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_seg(int nfft, const SegArgs &a, int kind, bool wps4, hipStream_t s) {
     switch (nfft) {
         case 256: return launch_r<1>(a, kind, wps4, s);

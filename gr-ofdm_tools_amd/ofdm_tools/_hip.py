@@ -17,6 +17,7 @@ EPI_MAG, EPI_MAG2, EPI_MAG2_OVER_N2 = 0, 1, 2
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_TUNED = 0, 1, 2
 SCHED_CONTIGUOUS, SCHED_INTERLEAVED, SCHED_DYNAMIC = 0, 1, 2
 HOSTWAIT_POLL, HOSTWAIT_SYNC = 0, 1
+AVERAGE_MEAN, AVERAGE_MEDIAN = 0, 1      # oth_plan_set_average: scipy.signal.welch average='mean' / 'median'
 OUT_RING = 4      # oth_plan::kOutRing: launch (ticket) t of a plan delivers into output slot t % OUT_RING
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -68,6 +69,8 @@ SIGNATURES = {
     'oth_plan_set_schedule': (C.c_int, [_p, C.c_int]),
     'oth_plan_out_len': (C.c_int, [_p, C.POINTER(C.c_int)]),
     'oth_plan_set_hostwait': (C.c_int, [_p, C.c_int]),
+    'oth_plan_set_average': (C.c_int, [_p, C.c_int]),
+    'oth_welch_segments_dev': (C.c_int, [_p, _p, C.c_size_t, _p, C.c_uint64, _u64p]),
     'oth_plan_set_tuning': (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int, C.c_int]),
     'oth_welch_exec': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _u64p]),
     'oth_welch_exec_async': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _u64p]),
@@ -280,9 +283,13 @@ class Context(object):
 
     # -- factories ------------------------------------------------------------
     def welch_plan(self, nfft, nperseg=None, noverlap=None, window=None, detrend=DETREND_CONSTANT,
-                   scaling=SCALE_DENSITY, fs=1.0, fftshift=False, trim_bins=0, db=False, kernel=KERNEL_AUTO):
-        return WelchPlan(self, nfft, nperseg, noverlap, window, detrend, scaling, fs, fftshift, trim_bins, db,
-                         kernel)
+                   scaling=SCALE_DENSITY, fs=1.0, fftshift=False, trim_bins=0, db=False, kernel=KERNEL_AUTO,
+                   average='mean'):
+        """average: 'mean' (default), 'median' (scipy.signal.welch average='median') or AVERAGE_MEAN / AVERAGE_MEDIAN."""
+        plan = WelchPlan(self, nfft, nperseg, noverlap, window, detrend, scaling, fs, fftshift, trim_bins, db, kernel)
+        if average_code(average) != AVERAGE_MEAN:
+            plan.set_average(average)
+        return plan
 
     def chain(self, nfft, window=None, fftshift=True, epilogue=EPI_MAG2, keep_one_in_n=1):
         return Chain(self, nfft, window, fftshift, epilogue, keep_one_in_n)
@@ -363,6 +370,18 @@ class Context(object):
         return out
 
 
+def average_code(average):
+    """'mean' / 'median' / AVERAGE_* -> AVERAGE_*; anything else is a ValueError."""
+    codes = {'mean': AVERAGE_MEAN, 'median': AVERAGE_MEDIAN}
+    if isinstance(average, str):
+        if average not in codes:
+            raise ValueError("average must be 'mean' or 'median', not %r" % (average,))
+        return codes[average]
+    if average not in (AVERAGE_MEAN, AVERAGE_MEDIAN):
+        raise ValueError('unknown average code %r' % (average,))
+    return int(average)
+
+
 class WelchPlan(object):
     def __init__(self, ctx, nfft, nperseg, noverlap, window, detrend, scaling, fs, fftshift, trim_bins, db, kernel):
         self.ctx = ctx
@@ -420,6 +439,41 @@ class WelchPlan(object):
 
     def nseg(self, nsamples):
         return (nsamples - self.noverlap) // self.step if nsamples >= self.nperseg else 0
+
+    average = AVERAGE_MEAN      # (class default: plans start with the mean)
+
+    def set_average(self, average):
+        """'mean' / 'median' (or AVERAGE_*): how exec / exec_async / exec_dev average the segments' periodograms.  The
+        median refuses the partial / scale / accumulate / csd calls (HipError OTH_ERR_UNSUPPORTED)."""
+        code = average_code(average)
+        self.ctx.check(self.ctx.lib.oth_plan_set_average(self.h, code), 'oth_plan_set_average')
+        self.average = code
+
+    def segments(self, x):
+        """x: host complex64 array -> float32 [nseg, out_len]: one periodogram row per segment with the plan's scaling,
+        fftshift, trim and dB (scipy.signal.spectrogram(mode='psd', return_onesided=False) with the axes swapped)."""
+        x = _c64(x)
+        nseg = self.nseg(len(x))
+        if nseg < 1:
+            raise ValueError('input shorter than nperseg')
+        xd = self.ctx.alloc(x.nbytes)
+        try:
+            rows = self.ctx.alloc(4 * nseg * self.out_len)
+            try:
+                self.ctx.h2d(xd, x)
+                self.segments_dev(xd, len(x), rows, nseg)
+                return self.ctx.d2h(rows, (nseg, self.out_len), np.float32)      # (stream-ordered, then synchronised)
+            finally:
+                self.ctx.free(rows)
+        finally:
+            self.ctx.free(xd)
+
+    def segments_dev(self, dptr, nsamples, rows_dptr, capacity):
+        """Asynchronous: device in, device out [nseg][out_len] float32 (capacity >= nseg rows).  -> nseg"""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_welch_segments_dev(self.h, C.c_void_p(dptr), int(nsamples), C.c_void_p(rows_dptr),
+                                                           int(capacity), C.byref(n)), 'oth_welch_segments_dev')
+        return n.value
 
     def last_recipe(self):
         """Diagnostics: 'kernel=... form=... pilot=... sched=... chunk=... W=...' of the last averaging launch."""

@@ -27,15 +27,18 @@ def _py2div(a, b):
     return a / b
 
 
-def _welch_plan(ctx, nfft, window_name, Sf, npts=None, use='exec'):
+def _welch_plan(ctx, nfft, window_name, Sf, npts=None, use='exec', average='mean'):
     """The reference's `sg.welch(x, Sf, window, nperseg=nfft, nfft=nfft)` + fftshift (ofdm_cr_tools.py:214,322,342).
     SciPy shortens nperseg to the input length when the vector is shorter than nfft ("nperseg = N is greater than input
     length", one zero-padded segment) - which fast_spectrum_scan(n_fft=0) always hits, its nFFT being the next power of
-    two above len(vct_sample) (ofdm_cr_tools.py:474-475).  -> (cache key, factory) with use='async', else the plan."""
+    two above len(vct_sample) (ofdm_cr_tools.py:474-475).  average: 'mean' (the reference's call) or 'median'
+    (sg.welch(..., average='median')).  -> (cache key, factory) with use='async', else the plan."""
     nperseg = nfft if npts is None else min(int(nfft), int(npts))
-    key = ('welch', use, nfft, nperseg, window_name, float(Sf))
+    code = _hip.average_code(average)
+    key = ('welch', use, nfft, nperseg, window_name, float(Sf), code)
+    extra = {} if code == _hip.AVERAGE_MEAN else {'average': code}
     make = lambda: ctx.welch_plan(nfft, nperseg=nperseg, window=windows.get_window(window_name, nperseg), fs=float(Sf),
-                                  fftshift=True)
+                                  fftshift=True, **extra)
     # `use`: the ticket callers (SpectrumScan: exec_async / poll from work()) do not share plans with the blocking helpers,
     # whose calls could push an uncollected ticket out of a plan's output ring; among themselves they share a pool
     # (_exec_async_pooled)
@@ -102,9 +105,10 @@ def _plain_channel_sums(psd, Fr, Sf, bb_freqs, srch_bins, ctx):
     return [float(v) for v in ctx.channel_power(psd, 1.0, lo, hi)]
 
 
-def _enqueue_welch(vector, nFFT, Sf, ctx):
+def _enqueue_welch(vector, nFFT, Sf, ctx, average='mean'):
     """src_power_welch's PSD (flattop, nperseg = nfft, ofdm_cr_tools.py:213-216) as a ticket: -> (plan, ticket, post)."""
-    plan, ticket = _exec_async_pooled(ctx, *_welch_plan(ctx, nFFT, 'flattop', Sf, len(vector), use='async'), vector=vector)
+    plan, ticket = _exec_async_pooled(ctx, *_welch_plan(ctx, nFFT, 'flattop', Sf, len(vector), use='async', average=average),
+                                      vector=vector)
     return plan, ticket, None
 
 
@@ -121,10 +125,10 @@ def _enqueue_fft(vector, nFFT, Sf, ctx):
     return plan, ticket, (lambda psd: psd / np.float32(nFFT))
 
 
-def src_power_welch(vector, npts, nFFT, Fr, Sf, bb_freqs, srch_bins, ctx=None):
-    """ofdm_cr_tools.py:213-230."""
+def src_power_welch(vector, npts, nFFT, Fr, Sf, bb_freqs, srch_bins, ctx=None, average='mean'):
+    """ofdm_cr_tools.py:213-230 (average='median': the same with sg.welch(..., average='median'))."""
     ctx = ctx or _hip.default_context()
-    plan, ticket, _ = _enqueue_welch(vector, nFFT, Sf, ctx)
+    plan, ticket, _ = _enqueue_welch(vector, nFFT, Sf, ctx, average)
     psd = plan.wait(ticket)
     axis = np.fft.fftshift(np.fft.fftfreq(nFFT, 1.0 / Sf))
     return psd, axis, _plain_channel_sums(psd, Fr, Sf, bb_freqs, srch_bins, ctx)
@@ -197,18 +201,18 @@ def fac(data, length, ctx=None):
     return (ctx or _hip.default_context()).fac(data, length)
 
 
-def welch_plot_dB(data, Sf, fc, nfft, ctx=None):
+def welch_plot_dB(data, Sf, fc, nfft, ctx=None, average='mean'):
     """ofdm_cr_tools.py:321-326 (default Hann window, 50 % overlap)."""
     ctx = ctx or _hip.default_context()
-    psd = _welch_plan(ctx, nfft, 'hann', Sf, len(data)).exec(data)
+    psd = _welch_plan(ctx, nfft, 'hann', Sf, len(data), average=average).exec(data)
     axis = np.fft.fftshift(np.fft.fftfreq(nfft, 1.0 / Sf))
     return [item + fc for item in axis], [10 * math.log10(item + 1e-20) for item in psd]
 
 
-def welch_power_estimate(vector, nFFT, Sf, ctx=None):
+def welch_power_estimate(vector, nFFT, Sf, ctx=None, average='mean'):
     """ofdm_cr_tools.py:341-345."""
     ctx = ctx or _hip.default_context()
-    return float(np.sum(_welch_plan(ctx, nFFT, 'hann', Sf, len(vector)).exec(vector), dtype=np.float64))
+    return float(np.sum(_welch_plan(ctx, nFFT, 'hann', Sf, len(vector), average=average).exec(vector), dtype=np.float64))
 
 
 class SpectrumScan(object):

@@ -144,7 +144,11 @@ def ctx_then_torch(ctx):
 def welch_long_stream(plan, local_dptr, local_first_sample, nsamples_total, device, rank, world, group=None):
     """Welch PSD of one stream of nsamples_total samples spread over the ranks in time order.  This rank's HBM
     buffer at local_dptr starts at stream sample local_first_sample and must cover its run + halo
-    (time_shard()).  -> (psd float32 tensor [plan.out_len] on `device`, nseg_total), identical on every rank."""
+    (time_shard()).  -> (psd float32 tensor [plan.out_len] on `device`, nseg_total), identical on every rank.  A median plan
+    is refused (ValueError): a median is not a sum of per-rank partials."""
+    from . import _hip
+    if getattr(plan, 'average', _hip.AVERAGE_MEAN) != _hip.AVERAGE_MEAN:
+        raise ValueError("welch_long_stream sums per-rank partials; a plan with average='median' cannot be time-sharded")
     def partial(first, n, out):
         torch_then_ctx(plan.ctx, device)     # torch.zeros(out) has landed
         nseg = plan.partial_dev(local_dptr + 8 * (first - local_first_sample), n, out.data_ptr())

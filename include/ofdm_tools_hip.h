@@ -190,7 +190,8 @@ int oth_iq_power(oth_ctx *ctx, const void *iq_dev, size_t nsamples, double *mean
  *   ofdm_cr_tools.py:342  (same)                                  welch_power_estimate
  *   spectrum_sweeper.py:263 (flattop, nperseg=nfft/4 zero-padded) _src_power
  * followed by the fftshift / excess-bin trim / 10*log10 of
- * spectrum_sweeper.py:265-276.  Two-sided, mean over segments.
+ * spectrum_sweeper.py:265-276.  Two-sided, mean over segments (the default; oth_plan_set_average below selects
+ * scipy.signal.welch's average='median').
  *
  * window: nperseg host floats (NULL = rectangular).  trim_bins bins are dropped
  * from each end AFTER the optional fftshift (np.fft.fftshift: bin k to (k + nfft / 2) mod nfft, odd nfft included);
@@ -221,6 +222,27 @@ int oth_plan_set_hostwait(oth_plan *plan, int mode);
  * (0 = default).  The OTH_W4096_VARIANT / _SCHED / _CHUNK / _TAIL environment variables give the initial values
  * and are read once, in oth_welch_plan(). */
 int oth_plan_set_tuning(oth_plan *plan, const char *variant, int sched, int chunk, int tail_chunk);
+
+/* MEDIAN AVERAGE and PER-SEGMENT ROWS.  Additions inside ABI 6 (OTH_ABI_VERSION stays 6): a caller probes for them by the
+ * symbols oth_plan_set_average / oth_welch_segments_dev.
+ * oth_plan_set_average(MEDIAN): oth_welch_exec, oth_welch_exec_async / _poll / _wait and oth_welch_exec_dev (one median
+ * per stream) return scipy.signal.welch(..., average='median'): per bin the median over segments of |X|^2 (numpy's: the
+ * mean of the two middle values for an even count; NaN where a segment value is NaN), divided by SciPy's
+ * _median_bias(nseg) = 1 + sum_{i=1}^{(nseg-1)//2} (1/(2i+1) - 1/(2i)), then the plan's scaling, fftshift, trim and dB.
+ * The selection is exact (a radix select over the float bit patterns with integer counts, bit-identical under every
+ * schedule); nseg_out is unchanged.  The rows take a device workspace of nstreams x nseg x nfft x 4 bytes, grown on demand
+ * (OTH_ERR_NOMEM with the size when it cannot be had).  Refused with OTH_ERR_UNSUPPORTED under MEDIAN (a median is not a
+ * sum of partials): oth_welch_partial_dev / _scale_dev (and so the time-sharded multi-GPU form), oth_welch_accumulate /
+ * _finalize, every oth_csd_* call.  oth_plan_set_average during an unfinished accumulation: OTH_ERR_STATE. */
+#define OTH_AVERAGE_MEAN   0   /* default */
+#define OTH_AVERAGE_MEDIAN 1
+int oth_plan_set_average(oth_plan *plan, int mode);
+/* One row per segment, [nseg][out_len] floats at rows_dev, each with the plan's scaling, fftshift, trim and dB:
+ * scipy.signal.spectrogram(..., mode='psd', return_onesided=False) with the axes swapped (segmentation, window, zero padding
+ * and the per-segment constant detrend as the plan's).  Device in, device out, asynchronous; either average mode.
+ * OTH_ERR_INVALID when capacity_rows < nseg. */
+int oth_welch_segments_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, float *rows_dev, uint64_t capacity_rows,
+                           uint64_t *nseg_out);
 
 /* one-shot: nsamples complex64 -> psd_out[nfft - 2*trim] (host).  Blocking: returns when the PSD is in psd_out.  The
  * last launch writes the row and a completion word into pinned host memory and the call polls that word (no interrupt
