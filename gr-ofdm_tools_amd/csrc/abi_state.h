@@ -1,0 +1,416 @@
+// Private header of the host files of the C ABI (abi_*.hip): the context, plan and chain state, the helpers every entry
+// point uses, and the functions one host file calls in another.  The library exports the oth_* entry points only
+// (abi_exports.map); everything declared here stays inside it.
+#pragma once
+#include "../../include/ofdm_tools_hip.h"
+#include "oth_internal.h"
+#include "abi_barrier.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <new>
+#include <string>
+#include <vector>
+
+using namespace oth;
+
+struct oth_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    int cu_count = 256;
+    std::string err;
+    std::string name;
+    bool timing = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
+    double total_ms = 0.0;
+    uint64_t launches = 0;
+    std::map<int, float2 *> twiddles;
+    float *sink = nullptr;
+    double *acc4 = nullptr;
+    unsigned *queue = nullptr;         // 64 chunk tickets for the dynamic segment schedule
+    unsigned *done_count = nullptr;    // arrival counter of a finalize launch that signals a polling host (FinalizeArgs)
+    std::recursive_mutex mu;           // every entry point that takes this context (or a plan / chain of it) holds it
+    bool queue_clean = false;          // all zero on the stream's timeline (finalize_kernel re-zeroes what a launch used)
+    int queue_used = 0;                // counters the last averaging launch drew from
+    unsigned char *scratch = nullptr;  // device scratch of the small ops (channel power, decision stage, xcorr): grown on
+    size_t scratch_cap = 0;            // demand, never freed per call
+    // channel slice bounds of the decision stage (oth_scan_decide_dev*): a scanner passes the same lo / hi on every
+    // call, so they live on the device and are uploaded again only when their contents change - through a pinned
+    // staging buffer, so that the upload is a real asynchronous copy (from pageable memory hipMemcpyAsync may hold the
+    // host until the stream has drained, which would make the "asynchronous" entry points wait for the PSD kernels)
+    std::vector<int> bounds_host;      // lo[nch] then hi[nch], as last uploaded
+    int *d_bounds = nullptr;
+    int *h_bounds = nullptr;           // pinned
+    size_t bounds_cap = 0;             // ints
+    hipEvent_t bounds_ev = nullptr;    // behind the last upload: the pinned words may be rewritten after it
+};
+
+// Device tables and scratch of the any-length route (fft_any.hip) of one plan / chain
+struct AnyTables {
+    AnyShape sh{};                     // kind ANY_NONE: not in use
+    const float2 *tw = nullptr;        // W_L^k, L entries (the context's table cache owns it)
+    float2 *chirp = nullptr;           // Bluestein c[n] = exp(-i pi n^2 / nfft), nfft entries
+    float2 *midtab = nullptr;          // Bluestein FFT_M(conj c) / M, M entries by natural index
+    float2 *ws = nullptr;              // workspace [channel][segment of the chunk][L]
+    size_t ws_cap = 0;
+    float4 *mean = nullptr;            // [channel][segment of the chunk] hi / lo means
+    size_t mean_cap = 0;
+};
+
+struct oth_plan {
+    oth_ctx *ctx = nullptr;
+    int nfft = 0, nperseg = 0, noverlap = 0, step = 0, detrend = 0, scaling = 0, fftshift = 0, trim = 0;
+    int db = 0, kernel = OTH_KERNEL_AUTO, sched = OTH_SCHED_DYNAMIC;
+    double fs = 1.0, scale = 1.0;      // scale applies to the MEAN over segments
+    float *d_win = nullptr;
+    const float2 *d_tw = nullptr;
+    float4 *d_fd = nullptr;            // window spectrum for the frequency-domain detrend (welch4096ws), or nullptr
+    float4 *d_fd1x = nullptr;          // the same for welch16k1x_half_kernel (16384 points, spectrum confined to |k| < 16)
+    float2 *d_pilot = nullptr;         // per-stream pilots of the frequency-domain detrend (WelchArgs.pilot)
+    size_t pilot_cap = 0;
+    bool fast_detrend = false;         // OTH_DETREND_CONSTANT_FAST: the builds without the pilot (WelchArgs.pilot)
+    bool rect_window = false;          // every window value is 1 (window == NULL or boxcar): builds without the multiply
+    float *d_partial = nullptr;
+    size_t partial_cap = 0;
+    int last_W = 0;
+    float *d_reduce = nullptr;         // stage-1 output of the two-stage partial-sum reduction
+    size_t reduce_cap = 0;
+    float *d_out = nullptr;            // [4][nfft] + pxy extra
+    size_t out_cap = 0;
+    // Host-output ring of oth_welch_exec / _exec_async (round 5).  The finalize launch writes the PSD straight into a
+    // pinned, device-visible row (no copy-engine hop) and then a completion word next to it (FinalizeArgs.host_seq);
+    // the host polls that word instead of sleeping in hipStreamSynchronize.  A slot is reused kOutRing launches later.
+    static constexpr int kOutRing = 4;
+    float *h_out = nullptr;            // pinned [kOutRing][nfft]
+    unsigned *h_seq = nullptr;         // pinned [kOutRing]: low 32 bits of the ticket whose row is complete
+    uint64_t out_ticket[kOutRing] = {0, 0, 0, 0};
+    uint64_t out_nseg[kOutRing] = {0, 0, 0, 0};
+    uint64_t next_out_ticket = 1;
+    bool pilot_launch = false;         // A/B + parity: the pilot from pilot_mean_kernel also where the kernel could form it
+    std::string last_recipe;           // recipe_text() of the last averaging launch (oth__debug_last_recipe)
+    float2 *d_stage = nullptr;         // host-input staging (x then y)
+    size_t stage_cap = 0;
+    // streaming state
+    float *d_sum = nullptr;            // raw sum |X|^2, natural order
+    float *d_wpm = nullptr;            // 65536-point plans on welch32k.hip: w[n] + w[n + 32768], then w[n] - w[n + 32768] (n < 32768)
+    uint64_t nseg_total = 0;
+    size_t carry = 0;                  // samples kept at the front of d_stream
+    float2 *d_stream = nullptr;
+    size_t stream_cap = 0;
+    // launch tuning (A/B tools and the parity suite): the OTH_W4096_* environment variables are read ONCE, when
+    // the plan is created; oth_plan_set_tuning() changes them afterwards.  0 / -1 / empty = library default.
+    std::string tune_variant;
+    int tune_sched = -1, tune_chunk = 0, tune_tail = 0;
+    // pinned staging ring of the streaming form (oth_welch_accumulate): the caller's buffer is copied here, the
+    // H2D copy and the kernels are enqueued, and the call returns without waiting for the GPU
+    void *h_ring[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t h_ring_cap[4] = {0, 0, 0, 0};
+    hipEvent_t h_ring_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    unsigned h_ring_next = 0;
+    AnyTables any;                     // any.sh.kind != ANY_NONE: the plan's length runs through fft_any.hip
+    // Blocking oth_welch_exec calls on one plan run one at a time (enqueue + collect under this mutex; the CONTEXT lock is
+    // free while they wait): with the 4-slot output ring a fifth concurrent caller's launch would otherwise rewrite the
+    // first caller's row before it was copied out (advisor, round 5).
+    std::mutex exec_mu;
+    int hostwait = 0;                  // 0 poll the completion word (default), 1 hipStreamSynchronize (oth_plan_set_hostwait)
+    // average = OTH_AVERAGE_MEDIAN (oth_plan_set_average): the rows producer writes one raw |X|^2 row per segment into
+    // d_rows ([stream][segment][nfft], grown on demand: ensure() drains the stream before it frees, so a queued ticket
+    // never reads a freed buffer), median.hip selects into d_med, finalize_kernel scales by scale / bias
+    int average = OTH_AVERAGE_MEAN;
+    float *d_rows = nullptr;
+    size_t rows_cap = 0;
+    float *d_med = nullptr;            // [nstreams][nfft] medians, natural bin order
+    size_t med_cap = 0;
+    unsigned *d_msel = nullptr;        // radix-select scratch (median_scratch_words)
+    size_t msel_cap = 0;
+    AnyTables rows_any;                // the any-length tables of a power-of-two plan's rows (p->any serves the others)
+    long long bias_nseg = 0;           // _median_bias(bias_nseg) = bias, cached
+    double bias = 1.0;
+};
+
+struct oth_chain {
+    oth_ctx *ctx = nullptr;
+    int nfft = 0, fftshift = 0, epilogue = 0, keep_n = 1, count = 1;
+    float *d_win = nullptr;
+    const float2 *d_tw = nullptr;
+    float2 *d_buf = nullptr;           // leftover + new samples
+    size_t buf_cap = 0;
+    size_t leftover = 0;               // samples at the front of d_buf
+    float *d_rows = nullptr;
+    size_t rows_cap = 0;
+    int do_iir = 0, do_peak = 0;
+    float alpha = 0.f, kdb = 0.f;
+    float *d_iir = nullptr, *d_peak = nullptr;
+    int *d_peak_init = nullptr;
+    float2 *d_stage = nullptr;         // host input lands here (H2D), then feeds the kernels
+    size_t stage_cap = 0;
+    float *d_partial = nullptr;        // per-team accumulator rows of the fused kernel
+    size_t partial_cap = 0;
+    float *d_tail = nullptr;           // group rows of the two-launch cross-team reduction
+    size_t tail_cap = 0;
+    bool peak_flag_set = false;        // d_peak_init is 1 on the stream's timeline
+    bool rect = false;                 // the window is all ones (fft_vcc's `()`): the 8192 / 16384 chain skips the multiply
+    int kernel = OTH_KERNEL_AUTO;      // OTH_KERNEL_GENERIC forces the coverage kernels (parity tests)
+    float *d_out = nullptr;            // rows handed back by the host-output forms
+    size_t out_cap = 0;
+    // asynchronous work() form (oth_chain_push_async): pinned input ring + pinned latest-row ring.  A slot is
+    // reused kRing tickets later; before it is written again the push waits for the event of the slot's last push that
+    // enqueued work - however many dropped tickets lie in between - which costs nothing once the GPU has caught up.
+    static constexpr int kRing = 4;
+    void *h_in[kRing] = {nullptr, nullptr, nullptr, nullptr};
+    size_t h_in_cap[kRing] = {0, 0, 0, 0};
+    float *h_row[kRing] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[kRing] = {nullptr, nullptr, nullptr, nullptr};      // recorded behind the D2H of the slot's row
+    uint64_t ticket_of[kRing] = {0, 0, 0, 0};
+    uint64_t nrows_of[kRing] = {0, 0, 0, 0};
+    uint64_t next_ticket = 1;
+    AnyTables any;                     // any.sh.kind != ANY_NONE: the chain's length runs through fft_any.hip
+    // round 6: what a work()-sized push costs
+    uint64_t ops = 0;                  // stream operations (asynchronous copies + kernel launches) the last push enqueued
+    bool noop[kRing] = {false, false, false, false};      // the slot's ticket enqueued nothing (every vector dropped): ready at
+                                                          // once; ev[slot] still belongs to the slot's last real push
+    // A partial vector whose samples came (in part) from pushes chain_push_dropped skipped: d_buf holds its first
+    // tail_from samples, h_tail its samples [tail_from, leftover) - copied on the host, no stream operation.  The next
+    // push that enqueues work uploads them first; set_keep_one_in_n may make the vector a kept one meanwhile.
+    bool leftover_stale = false;
+    size_t tail_from = 0;
+    float2 *h_tail = nullptr;          // nfft samples, pinned
+    hipEvent_t tail_ev = nullptr;      // recorded behind push / push_dev's upload from h_tail
+    bool tail_ev_live = false;         // ... which a dropped push waits for before it rewrites h_tail
+};
+
+namespace oth {
+// host chunks up to this size go through the pinned staging rings (work()-sized buffers: the copy is trivial and the
+// call returns at once); larger ones use the runtime's staged copy from pageable memory directly
+constexpr size_t kPinnedStageMax = 1u << 20;
+// a PINNED / registered source above this size is not copied into the ring (that would pin as much again): its DMA is
+// enqueued directly and the call waits for that one copy - the only case in which a push waits for the stream
+constexpr size_t kPinnedRingMax = 64u << 20;
+
+// A host buffer the runtime can DMA from directly (hipHostMalloc / hipHostRegister'd, e.g. a torch pinned tensor or a
+// registered scheduler buffer): hipMemcpyAsync from it returns before the bytes are read, so the "input valid only
+// during the call" contract of work() needs a copy that has finished when the call returns.  Pageable memory is
+// staged by the runtime before hipMemcpyAsync returns.
+bool host_ptr_is_pinned(const void *p);
+
+int fail(oth_ctx *c, int code, const std::string &msg);
+
+// Serialises the entry points per context: GNU Radio runs each block's work() on its own thread and the
+// blocks of one process share the default context (scratch buffers, ticket counters, timing events).
+struct CtxGuard {
+    oth_ctx *c;
+    explicit CtxGuard(oth_ctx *ctx) : c(ctx) {
+        if (c) c->mu.lock();
+    }
+    ~CtxGuard() {
+        if (c) c->mu.unlock();
+    }
+    CtxGuard(const CtxGuard &) = delete;
+    CtxGuard &operator=(const CtxGuard &) = delete;
+};
+
+#define HIPCHK(c, expr)                                                                                 \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess)                                                                           \
+            return fail((c), OTH_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));           \
+    } while (0)
+
+// The exception barrier of the C ABI (include/ofdm_tools_hip.h: "nothing throws or aborts").  Every extern "C" body
+// sits between OTH_TRY and OTH_CATCH(context): a std::bad_alloc (std::vector / std::string growth), a
+// std::system_error (the context's recursive mutex) or anything else a C++ runtime call may raise becomes an error
+// code + last-error text instead of std::terminate() inside the host's ctypes call.  The handlers themselves must not
+// throw: the text is stored through fail_nothrow().
+int fail_nothrow(oth_ctx *c, int code, const char *what) noexcept;
+
+// OTH_TRY / OTH_CATCH(context): csrc/abi_barrier.h (shared with the host-only probe the CPU suite builds)
+
+int use_device(oth_ctx *c);
+
+// H2D copy of a caller's host buffer that must be consumed before the call returns, without a ring slot
+int copy_in_and_wait(oth_ctx *c, void *dst, const void *src, size_t bytes);
+
+int get_twiddles(oth_ctx *c, int nfft, const float2 **out);
+
+template <typename P> int ensure(oth_ctx *c, P **ptr, size_t *cap, size_t need_bytes) {
+    if (*cap >= need_bytes && *ptr) return OTH_OK;
+    if (*ptr) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipFree(*ptr));
+        *ptr = nullptr;
+        *cap = 0;
+    }
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, need_bytes);
+    if (e != hipSuccess) return fail(c, OTH_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    *ptr = reinterpret_cast<P *>(p);
+    *cap = need_bytes;
+    return OTH_OK;
+}
+
+// grow while keeping the first keep_bytes
+template <typename P> int ensure_keep(oth_ctx *c, P **ptr, size_t *cap, size_t need_bytes, size_t keep_bytes) {
+    if (*cap >= need_bytes && *ptr) return OTH_OK;
+    void *p = nullptr;
+    const size_t newcap = need_bytes + need_bytes / 4;
+    hipError_t e = hipMalloc(&p, newcap);
+    if (e != hipSuccess) return fail(c, OTH_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    if (*ptr) {
+        if (keep_bytes) HIPCHK(c, hipMemcpyAsync(p, *ptr, keep_bytes, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipFree(*ptr));
+    }
+    *ptr = reinterpret_cast<P *>(p);
+    *cap = newcap;
+    return OTH_OK;
+}
+
+// A pinned host buffer of at least `bytes` (the staging rings): a short one is freed and replaced by one half as large
+// again (+ 4 KiB), so that a caller whose chunks grow slowly does not reallocate on every call.
+int grow_pinned(oth_ctx *c, void **buf, size_t *cap, size_t bytes);
+
+struct Timed {
+    oth_ctx *c;
+    hipEvent_t a = nullptr, b = nullptr;
+    explicit Timed(oth_ctx *ctx) : c(ctx) {
+        if (!c->timing) return;
+        if (c->events.size() >= 8192) {   // fold what we have
+            hipStreamSynchronize(c->stream);
+            for (auto &ev : c->events) {
+                float ms = 0.f;
+                if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) c->total_ms += ms;
+                c->free_events.push_back(ev);
+            }
+            c->events.clear();
+        }
+        if (!c->free_events.empty()) {
+            a = c->free_events.back().first;
+            b = c->free_events.back().second;
+            c->free_events.pop_back();
+        } else if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
+            a = b = nullptr;
+            return;
+        }
+        hipEventRecord(a, c->stream);
+    }
+    ~Timed() {
+        if (!a) return;
+        hipEventRecord(b, c->stream);
+        c->events.emplace_back(a, b);
+        c->launches++;
+    }
+};
+
+// The interleaved schedule of a rows / chain launch of segfft.hip or welch16k.hip over a.nseg segments, for at most
+// teams_max resident teams: segments per chunk 8 once every team gets two chunks (+2-4 % over 4), fewer for short
+// launches so that more teams take part; chunk c goes to team c mod wg_per_stream.
+inline void interleaved_chunks(SegArgs &a, long long teams_max) {
+    a.chunk = a.nseg >= 16 * teams_max ? 8 : (a.nseg >= 4 * teams_max ? 4 : 2);
+    const long long nchunks = (a.nseg + a.chunk - 1) / a.chunk;
+    a.wg_per_stream = (int)std::max(1LL, std::min(teams_max, nchunks));
+    a.sched = 1;
+    a.tail_chunk = a.chunk;
+    a.nbig = a.nseg / a.chunk;
+}
+
+// ---- abi_route.hip: which kernel build runs a launch ---------------------------------------------------------------------
+// Build variants of the welch4096 kernel; OTH_W4096_VARIANT=<tag> selects one (experiments only).
+struct W4096Variant {
+    const char *tag;
+    hipError_t (*launch)(const WelchArgs &, hipStream_t);
+    int (*blocks_per_cu)();
+    int chunk;      // default segments per chunk of the dynamic schedule (same-box A/B, tools/archive/ab_variants.py)
+    int rows;       // rows of partial sums each workgroup writes
+    bool fd;        // detrends in the frequency domain: needs WelchArgs.fd (a window with a confined spectrum)
+    bool inline_pilot = false;      // forms the pilot of the constant detrend in its own prologue (WelchArgs.pilot_inline)
+};
+bool w4096_variant_known(const char *tag);      // a tag of abi_route.hip's table of builds (oth_plan_set_tuning)
+
+enum RecipeKernel {
+    RK_GENERIC = 0,      // welch_generic_kernel (coverage Stockham kernel; also the two-channel coverage path)
+    RK_W4096,            // welch4096[ws]_kernel: the build in `variant`
+    RK_CSD4096,          // csd4096_kernel (one role)
+    RK_CSD4096WS,        // csd4096ws_kernel (role-split pairs)
+    RK_W16K,             // welch16k_kernel<., F> (4 x 4096 / 2 x 4096)
+    RK_W16K1X,           // welch16k1x_pipe_kernel / welch16k1x_kernel (one exchange, no overlap)
+    RK_W16K1X_HALF,      // welch16k1x_half_kernel (one exchange, 50 % overlap)
+    RK_SEG,              // seg_kernel<R, ...>
+    RK_SEGWS,            // segws_kernel<R, DET>
+    RK_SEGPAD,           // seg_kernel<R, ..., NA> zero-padded
+    RK_ANY,              // any_fft_kernel launches (fft_any.hip): lengths the kernels above do not take
+};
+extern const char *const kAnyKindName[];      // AnyKind -> name
+
+// what resolve_recipe() needs to know of a plan (oth_plan holds the same fields; the debug entry builds one by hand)
+struct PlanShape {
+    int nfft = 0, nperseg = 0, step = 0;
+    bool detrend = false, fast_detrend = false;
+    bool fd_ok = false;          // a window-spectrum table exists for this size (oth_plan::d_fd)
+    bool fd1x_ok = false;        // ... and the one for welch16k1x_half (spectrum confined to |k| < 16)
+    bool rect_window = false;
+    int kernel = OTH_KERNEL_AUTO, sched = OTH_SCHED_DYNAMIC;
+    bool pilot_launch = false;
+    std::string tune_variant;
+    int tune_sched = -1, tune_chunk = 0, tune_tail = 0;
+    AnyShape any{};              // kind != ANY_NONE: the any-length route
+};
+
+// resident workgroups (teams) per CU of a tuned build: the runtime asks the occupancy calculator (needs a device), the
+// debug entry uses abi_route.hip's table_bpc - what the calculator returns on MI355X for the shipped builds
+// (tests/test_hip_parity.py::test_recipe_occupancy_table_matches_the_runtime compares the two on the GPU)
+struct OccupancyKey {
+    RecipeKernel kern;
+    const char *variant;      // RK_W4096
+    int nfft, nperseg, seg_kind;
+    bool seg_wps4;
+    bool half_ws;             // RK_W16K1X_HALF at 8192 points: the role-split build (one 1024-thread workgroup per CU)
+};
+int runtime_bpc(const OccupancyKey &k);
+
+struct LaunchRecipe {
+    RecipeKernel kern = RK_GENERIC;
+    const W4096Variant *variant = nullptr;      // RK_W4096
+    bool csd = false;
+    int form = 0;                // constant detrend: 0 none, 1 before the window (time domain), 2 after the transform (needs the table)
+    int pilot = 0;               // 0 none (no detrend, or OTH_DETREND_CONSTANT_FAST), 1 pilot_mean_kernel in front, 2 in the kernel's prologue
+    bool use_fd1x = false;       // the table handed to the kernel is d_fd1x
+    int seg_kind = 0, seg_det = 0;
+    bool seg_wps4 = false;
+    bool x1_window = false, x1_plain = false;      // RK_W16K1X: windowed build / the un-pipelined loop
+    bool half_ws = false;                          // RK_W16K1X_HALF, 8192 points: welch8kws_kernel
+    int bpc = 0;                 // resident workgroups (teams) per CU (0: generic grid rule)
+    int W = 1, rows = 1, nch = 1, layout = 0;
+    int sched = 0, chunk = 1, tail_chunk = 1;
+    long long nbig = 0, nseg_run = 0;
+    bool tickets = false;        // draws chunk tickets from the context's queue
+    bool two_runs = false;       // "ws2": the stream cut into two runs of segments
+    int any_kind = 0;            // RK_ANY: AnyKind
+    bool any_r16 = false;        // ... on fft_tl.hip's register radix-16 kernels (32768 / 65536 points)
+    bool any_onewg = false;      // ... 32768 points, one channel, full segments: welch32k.hip (the segment never leaves the CU)
+};
+
+// -> OTH_OK, or OTH_ERR_UNSUPPORTED with *why set (OTH_KERNEL_TUNED on a plan no tuned kernel covers)
+int resolve_recipe(const PlanShape &p, bool csd, long long nseg, int nstreams, int cu_count, int (*bpc_of)(const OccupancyKey &),
+                   LaunchRecipe *out, const char **why);
+std::string recipe_text(const LaunchRecipe &r, int nfft);
+PlanShape shape_of(const oth_plan *p);
+
+// ---- abi_any.hip: the any-length host driver (fft_any.hip, fft_tl.hip, welch32k.hip) --------------------------------------
+void any_tables_free(AnyTables &t);
+int any_tables_init(oth_ctx *c, int nfft, AnyTables *t);
+int any_partial_rows(const AnyShape &sh, long long nseg, int cu_count);
+int any_run(oth_ctx *c, AnyTables &t, const float2 *x, const float2 *y, long long first, long long seg_step, int nperseg,
+            const float *win, bool detrend, long long nseg, float *partial, int W, float *rows, int epilogue, float scale,
+            int fftshift, bool coverage_only = false);
+// points of scratch any_fft_nat() needs behind the data
+inline size_t any_fft_nat_scratch(const AnyShape &sh) { return 2 * (size_t)sh.L; }
+int any_fft_nat(oth_ctx *c, const AnyTables &t, float2 *data, float2 *scratch);
+void host_fft_pow2(std::vector<double> &re, std::vector<double> &im);
+}  // namespace oth

@@ -1,5 +1,5 @@
 // Host-only probe of the ABI's exception barrier (csrc/abi_barrier.h), built on the fly by
-// tests/test_abi_cpu.py::test_exception_barrier_at_the_abi with g++ - NOT part of libofdmtools_hip.so.
+// tests/test_abi_cpu.py::test_exception_barrier_of_the_abi_host_files with g++ - NOT part of libofdmtools_hip.so.
 //   g++ -std=c++17 -shared -fPIC -I../../include barrier_probe.cpp -o barrier_probe.so
 // oth_probe_throw(kind): 0 std::bad_alloc, 1 std::runtime_error, 2 a non-std exception, 3 a real over-sized std::vector,
 // anything else returns OTH_OK; oth_probe_last_error(): the text the barrier stored.

@@ -14,7 +14,7 @@
 //                  workgroup's segments; partial rows in [k1][k2] order (finalize layout 6).
 //   two channels   (oth_csd_exec / coherence): K1 per channel on blockIdx.z, K2<CSD> transforms row k1 of x and of y back
 //                  to back and adds |X|^2, |Y|^2, conj(X) Y: partial rows [W][4][L].
-// The workspace holds a chunk of segments (any_run, api.hip) small enough to stay in the Infinity Cache between the two.
+// The workspace holds a chunk of segments (any_run, abi_any.hip) small enough to stay in the Infinity Cache between the two.
 #include "fft4096.hip.h"
 #include "oth_internal.h"
 

@@ -59,7 +59,7 @@ __device__ __forceinline__ int unshifted(int ks, int n) {
 // barrier collects the waves where more than wave 0 stores (ALL_WAVES), and thread 0 arrives on the device counter.
 // Whoever arrives last has, through that counter, every other block's fence before it: it re-arms the counter for the
 // next launch and publishes the sequence value with a system-scope release store.  The host (oth_welch_exec / _poll /
-// _wait in api.hip) reads the word with acquire semantics and then the rows.
+// _wait in abi_welch.hip) reads the word with acquire semantics and then the rows.
 template <bool ALL_WAVES>
 __device__ __forceinline__ void finalize_signal(const FinalizeArgs &a) {
     if (!a.host_seq) return;      // launch-uniform

@@ -999,7 +999,7 @@ hipError_t launch_seg_padded(int nfft, int nperseg, const SegArgs &a, int kind, 
     return nperseg * 4 == nfft ? launch_pad<8, 4>(a, kind, s) : launch_pad<8, 8>(a, kind, s);
 }
 
-// Rows of the median average (api.hip median_rows): the chain build (CHAIN, whole-segment loads, SegArgs.acc_mode 3,
+// Rows of the median average (abi_welch.hip median_rows): the chain build (CHAIN, whole-segment loads, SegArgs.acc_mode 3,
 // epilogue |X|^2 x 1) with an overlapped step; with a.detrend each segment's own mean comes off before the window - a build
 // of its own (DETREND and CHAIN), no pilot.
 template <int R> hipError_t launch_rows_r(const SegArgs &a, hipStream_t s) {

@@ -786,7 +786,7 @@ template <int NW = 16> constexpr size_t x1h_lds_bytes() {
 
 // NW = 8: the same at 8192 points (round 5; two workgroups per CU).  The bins |k| < 16 the detrend corrects are then
 // register k2 = 0 of lanes 0 and 32 (k1 = 0, q = 0 of k0 = 2 k0' and 2 k0' + 1) and register k2 = 15 of lanes 31 and 63
-// (k1 = 7, q = 3) of each wave (window_spectrum_table_1x in api.hip).
+// (k1 = 7, q = 3) of each wave (window_spectrum_table_1x in abi_welch.hip).
 template <int NW, int DET, bool PILOT = false>
 __global__ __launch_bounds__(64 * NW, 4) void welch16k1x_half_kernel(WelchArgs p) {
     static_assert(DET == 2 || !PILOT, "the pilot belongs to the detrend");

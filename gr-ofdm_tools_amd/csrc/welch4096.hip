@@ -38,7 +38,7 @@
 #include "fft_lds.hip.h"
 #include "oth_internal.h"
 
-// Build-time switches (the Makefile compiles this file once per shipped build; api.hip picks one):
+// Build-time switches (the Makefile compiles this file once per shipped build; abi_route.hip picks one):
 //   OTH_W4096_TAG       suffix of the exported launcher
 #ifndef OTH_W4096_TAG
 #define OTH_W4096_TAG dpp

@@ -397,7 +397,7 @@ int oth_fac(oth_ctx *ctx, const void *data, size_t n, int L, float *out);
 
 /* ---- diagnostics (ABI 5) ------------------------------------------------------------------------------------------
  * Which kernel build, detrend form, pilot, schedule, chunk sizes, grid and partial-row layout a launch takes is decided by
- * pure host logic (csrc/api.hip resolve_recipe) and can be read back as text:
+ * pure host logic (csrc/abi_route.hip resolve_recipe) and can be read back as text:
  *   "kernel=welch4096:ws nfft=4096 form=freq pilot=inline sched=dynamic chunk=20 tail=5 nbig=6297 bpc=2 W=512 rows=1 nch=1 layout=1"
  * oth__debug_recipe needs NO device: window_class 0 = all ones, 1 = confined spectrum (periodic cosine-sum windows),
  * 2 = wide (no detrend table), 3 = confined to 256 nfft / 4096 bins only; runtime_occupancy 0 = resident workgroups per CU

@@ -1,5 +1,5 @@
 """Enumeration of the launch-recipe table through oth__debug_recipe (test infrastructure; no GPU: the choice of kernel
-build, detrend form, pilot, schedule, chunk sizes and grid is pure host logic in csrc/api.hip resolve_recipe()).
+build, detrend form, pilot, schedule, chunk sizes and grid is pure host logic in csrc/abi_route.hip resolve_recipe()).
 
   python tests/recipes.py --write     regenerate tests/golden/recipes_small.txt and recipes_full.sha256 after an
                                       INTENDED routing change (review the diff of the small table)
