@@ -12,21 +12,9 @@ namespace {
 constexpr long long kFdMinSegments = 8;
 
 const W4096Variant kVariants[] = {
-    {"dpp", launch_welch_tuned4096_dpp, tuned4096_blocks_per_cu_dpp, 8, 1, false},            // any step
-    {"pipe", launch_welch_tuned4096_pipe, tuned4096_blocks_per_cu_pipe, 16, 1, false},        // step 2048 (50 % overlap)
-    {"ws", launch_welch_tuned4096_ws, tuned4096_blocks_per_cu_ws, 20, 1, true, true},     // step 2048, confined window spectrum
-#ifdef OTH_EXPERIMENTS
-    {"ws2", launch_welch_tuned4096_ws2, tuned4096_blocks_per_cu_ws2, 20, 2, true},  // the same in one 1024-thread workgroup per CU (A/B, +7 %)
-    {"diag", launch_welch_tuned4096_diag, tuned4096_blocks_per_cu_diag, 16, 1, false},      // stamped build (tools/archive/diag_stamps.py)
-    {"exp1", launch_welch_tuned4096_exp1, tuned4096_blocks_per_cu_exp1, 16, 1, false},
-    {"exp2", launch_welch_tuned4096_exp2, tuned4096_blocks_per_cu_exp2, 16, 1, false},
-    {"exp3", launch_welch_tuned4096_exp3, tuned4096_blocks_per_cu_exp3, 16, 1, false},
-    {"exp4", launch_welch_tuned4096_exp4, tuned4096_blocks_per_cu_exp4, 16, 1, false},
-    {"wsx1", launch_welch_tuned4096_wsx1, tuned4096_blocks_per_cu_wsx1, 32, 1, true, true},
-    {"wsx2", launch_welch_tuned4096_wsx2, tuned4096_blocks_per_cu_wsx2, 32, 1, true, true},
-    {"wsx3", launch_welch_tuned4096_wsx3, tuned4096_blocks_per_cu_wsx3, 32, 1, true, true},
-    {"wsx4", launch_welch_tuned4096_wsx4, tuned4096_blocks_per_cu_wsx4, 32, 1, true, true},
-#endif
+    {"dpp", launch_welch_tuned4096_dpp, tuned4096_blocks_per_cu_dpp, 8, false},          // any step
+    {"pipe", launch_welch_tuned4096_pipe, tuned4096_blocks_per_cu_pipe, 16, false},      // step 2048 (50 % overlap)
+    {"ws", launch_welch_tuned4096_ws, tuned4096_blocks_per_cu_ws, 20, true, true},       // step 2048, confined window spectrum
 };
 // the three shipped builds are looked up by tag, never by position: the table is edited between rounds
 const W4096Variant *variant_by_tag(const char *tag) {
@@ -124,7 +112,6 @@ int resolve_recipe(const PlanShape &p, bool csd, long long nseg, int nstreams, i
         r.form = p.detrend ? 1 : 0;
         r.W = r.any_onewg ? welch32k_rows(nseg, cu_count, p.any.L == 65536) : any_partial_rows(p.any, nseg, cu_count);
         r.layout = r.any_onewg ? (p.any.L == 65536 ? 8 : 7) : (p.any.kind == ANY_TWOLEVEL ? 6 : 0);
-        r.nseg_run = nseg;
         *out = r;
         return OTH_OK;
     }
@@ -154,9 +141,6 @@ int resolve_recipe(const PlanShape &p, bool csd, long long nseg, int nstreams, i
         r.kern = RK_W4096;
         const bool fd_ok = (!p.detrend || fd) && nseg < (1LL << 30);      // ws: 32-bit segment indices
         r.variant = w4096_variant(p.nperseg == 4096 ? p.step : 0, fd_ok, tv);
-        // "ws2" cuts the stream into two equal runs of segments: an odd count (or a single segment) stays on "ws"
-        if (!strcmp(r.variant->tag, "ws2") && (nseg < 2 || (nseg & 1))) r.variant = variant_by_tag("ws");
-        r.two_runs = !strcmp(r.variant->tag, "ws2");
     } else if (want_tuned && big_size && (p.nperseg == p.nfft || p.nperseg * 4 == p.nfft)) {      // (nfft / 4: the sweeper's zero padding)
         r.kern = RK_W16K;
         if (p.nperseg == p.nfft && tv != "16k4") {
@@ -209,8 +193,6 @@ int resolve_recipe(const PlanShape &p, bool csd, long long nseg, int nstreams, i
         r.x1_plain = tv == "16kplain";
     }
     // ---- grid: exactly the resident workgroups (one wave of workgroups, no tail round); generic: by LDS footprint
-    r.rows = r.kern == RK_W4096 ? r.variant->rows : 1;
-    r.nseg_run = r.two_runs ? nseg / 2 : nseg;      // segments the schedule of one run covers
     if (r.kern == RK_GENERIC) {
         r.W = generic_wg_for(cu_count, p.nfft, nseg, nstreams);
     } else {
@@ -218,7 +200,7 @@ int resolve_recipe(const PlanShape &p, bool csd, long long nseg, int nstreams, i
         r.bpc = bpc_of(key);
         if (r.bpc < 1) r.bpc = 1;
         const long long w = ((long long)cu_count * r.bpc + nstreams - 1) / nstreams;
-        r.W = (int)(w > r.nseg_run ? r.nseg_run : (w < 1 ? 1 : w));
+        r.W = (int)(w > nseg ? nseg : (w < 1 ? 1 : w));
     }
     r.layout = (r.kern == RK_W4096 || r.kern == RK_CSD4096 || r.kern == RK_CSD4096WS) ? 1
                : (r.kern == RK_W16K1X || r.kern == RK_W16K1X_HALF) ? (p.nfft == 16384 ? 4 : 5)
@@ -226,7 +208,7 @@ int resolve_recipe(const PlanShape &p, bool csd, long long nseg, int nstreams, i
     // ---- schedule and chunks (tuned kernels only; the coverage kernel walks contiguous runs)
     if (r.kern != RK_GENERIC) {
         const bool auto_sched = p.tune_sched < 0 && p.sched == OTH_SCHED_DYNAMIC;      // "the library's choice"
-        const long long per_team = r.nseg_run / (r.W > 0 ? r.W : 1);
+        const long long per_team = nseg / (r.W > 0 ? r.W : 1);
         const bool is_seg = r.kern == RK_SEG || r.kern == RK_SEGPAD || r.kern == RK_SEGWS;
         const bool big = r.kern == RK_W16K || r.kern == RK_W16K1X || r.kern == RK_W16K1X_HALF;
         r.sched = p.tune_sched >= 0 ? p.tune_sched : p.sched;
@@ -283,7 +265,7 @@ int resolve_recipe(const PlanShape &p, bool csd, long long nseg, int nstreams, i
         if (r.kern == RK_W16K1X && chunk < 2) chunk = 2;
         r.chunk = chunk;
         r.tail_chunk = chunk;
-        r.nbig = r.nseg_run / chunk;
+        r.nbig = nseg / chunk;
         if (r.sched == OTH_SCHED_DYNAMIC) {
             if (nstreams > 64) {
                 r.sched = OTH_SCHED_INTERLEAVED;      // the context holds 64 ticket words
@@ -294,7 +276,7 @@ int resolve_recipe(const PlanShape &p, bool csd, long long nseg, int nstreams, i
                 if (r.tail_chunk < 1) r.tail_chunk = 1;
                 if (r.kern == RK_W16K1X && r.tail_chunk < 2) r.tail_chunk = 2;
                 const long long tail_segs = (long long)r.W * chunk / 2;
-                r.nbig = r.nseg_run > tail_segs ? (r.nseg_run - tail_segs) / chunk : 0;
+                r.nbig = nseg > tail_segs ? (nseg - tail_segs) / chunk : 0;
             }
         }
     }
@@ -314,8 +296,9 @@ std::string recipe_text(const LaunchRecipe &r, int nfft) {
     if (r.kern == RK_W16K1X) k += std::string(r.x1_plain || r.x1_window ? ":plain" : ":pipe") + (r.x1_window ? ":window" : "");
     if (r.kern == RK_W16K1X_HALF && r.half_ws) k += ":ws";
     if (r.kern == RK_ANY) k += r.any_onewg ? std::string(":onewg") : std::string(":") + kAnyKindName[r.any_kind] + (r.any_r16 ? ":r16" : "");
-    snprintf(buf, sizeof buf, "kernel=%s nfft=%d form=%s pilot=%s sched=%s chunk=%d tail=%d nbig=%lld bpc=%d W=%d rows=%d nch=%d layout=%d",
-             k.c_str(), nfft, kForm[r.form], kPilot[r.pilot], kSched[r.sched], r.chunk, r.tail_chunk, r.nbig, r.bpc, r.W, r.rows,
+    // rows=1: every kernel leaves one partial row per workgroup; the field stays because the text is compared byte for byte
+    snprintf(buf, sizeof buf, "kernel=%s nfft=%d form=%s pilot=%s sched=%s chunk=%d tail=%d nbig=%lld bpc=%d W=%d rows=1 nch=%d layout=%d",
+             k.c_str(), nfft, kForm[r.form], kPilot[r.pilot], kSched[r.sched], r.chunk, r.tail_chunk, r.nbig, r.bpc, r.W,
              r.nch, r.layout);
     return buf;
 }

@@ -79,7 +79,6 @@ struct oth_plan {
     bool rect_window = false;          // every window value is 1 (window == NULL or boxcar): builds without the multiply
     float *d_partial = nullptr;
     size_t partial_cap = 0;
-    int last_W = 0;
     float *d_reduce = nullptr;         // stage-1 output of the two-stage partial-sum reduction
     size_t reduce_cap = 0;
     float *d_out = nullptr;            // [4][nfft] + pxy extra
@@ -327,7 +326,6 @@ struct W4096Variant {
     hipError_t (*launch)(const WelchArgs &, hipStream_t);
     int (*blocks_per_cu)();
     int chunk;      // default segments per chunk of the dynamic schedule (same-box A/B, tools/archive/ab_variants.py)
-    int rows;       // rows of partial sums each workgroup writes
     bool fd;        // detrends in the frequency domain: needs WelchArgs.fd (a window with a confined spectrum)
     bool inline_pilot = false;      // forms the pilot of the constant detrend in its own prologue (WelchArgs.pilot_inline)
 };
@@ -386,11 +384,10 @@ struct LaunchRecipe {
     bool x1_window = false, x1_plain = false;      // RK_W16K1X: windowed build / the un-pipelined loop
     bool half_ws = false;                          // RK_W16K1X_HALF, 8192 points: welch8kws_kernel
     int bpc = 0;                 // resident workgroups (teams) per CU (0: generic grid rule)
-    int W = 1, rows = 1, nch = 1, layout = 0;
+    int W = 1, nch = 1, layout = 0;
     int sched = 0, chunk = 1, tail_chunk = 1;
-    long long nbig = 0, nseg_run = 0;
+    long long nbig = 0;
     bool tickets = false;        // draws chunk tickets from the context's queue
-    bool two_runs = false;       // "ws2": the stream cut into two runs of segments
     int any_kind = 0;            // RK_ANY: AnyKind
     bool any_r16 = false;        // ... on fft_tl.hip's register radix-16 kernels (32768 / 65536 points)
     bool any_onewg = false;      // ... 32768 points, one channel, full segments: welch32k.hip (the segment never leaves the CU)

@@ -121,12 +121,9 @@ int run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
     if (int rrc = resolve_recipe(shape_of(p), csd, nseg, nstreams, c->cu_count, runtime_bpc, &r, &why))
         return fail(c, rrc, why);
     p->last_recipe = recipe_text(r, p->nfft);
-    // + 1 KiB per row of stamp space behind the sums (only the diagnostic kernel builds write it)
-    int rc = ensure(c, &p->d_partial, &p->partial_cap,
-                    sizeof(float) * (size_t)nstreams * r.W * r.rows * r.nch * p->nfft + 2048 * (size_t)nstreams * r.W * r.rows);      // (+ 2 KiB per row: the phase stamps of the diagnostic builds)
-    p->last_W = r.W * r.rows * nstreams;
+    int rc = ensure(c, &p->d_partial, &p->partial_cap, sizeof(float) * (size_t)nstreams * r.W * r.nch * p->nfft);
     {
-        const int groups = std::max(kReduceGroups, finalize_row_groups(p->nfft, r.W * r.rows, r.nch));
+        const int groups = std::max(kReduceGroups, finalize_row_groups(p->nfft, r.W, r.nch));
         if (!rc) rc = ensure(c, &p->d_reduce, &p->reduce_cap, sizeof(float) * (size_t)nstreams * groups * r.nch * p->nfft);
     }
     if (rc) return rc;
@@ -200,8 +197,7 @@ int run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
         a.win = p->d_win;
         a.tw = p->d_tw;
         a.partial = p->d_partial;
-        a.nseg = r.nseg_run;
-        if (r.two_runs) a.y = x + (size_t)r.nseg_run * 2048;      // run B starts nseg / 2 segments in (its first half-block is run A's last)
+        a.nseg = nseg;
         a.stream_stride = stride;
         a.nperseg = p->nperseg;
         a.step = p->step;
@@ -230,7 +226,7 @@ int run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
         }
     }
     *nseg_out = nseg;
-    *W_out = r.W * r.rows;
+    *W_out = r.W;
     *layout_out = r.layout;
     return OTH_OK;
 }
@@ -1116,52 +1112,6 @@ int oth_csd_exec(oth_plan *p, const void *x, const void *y, size_t nsamples, int
     return OTH_OK;
     OTH_CATCH((p ? p->ctx : nullptr))
 }
-
-#ifdef OTH_EXPERIMENTS      // the three readers below serve the stamped / diagnostic kernel builds: `make EXP=1` only
-// Not part of the ABI (not in the header): raw bytes behind the partial sums (diagnostic kernel builds).
-int oth__debug_tail(oth_plan *p, void *out, size_t nbytes, int *nwg) {
-    OTH_TRY
-    CtxGuard guard_(p ? p->ctx : nullptr);
-    if (!p || !out || !nwg) return OTH_ERR_INVALID;
-    oth_ctx *c = p->ctx;
-    if (nbytes > 1024 * (size_t)p->last_W) return OTH_ERR_INVALID;
-    HIPCHK(c, hipMemcpyAsync(out, p->d_partial + (size_t)p->last_W * p->nfft, nbytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *nwg = p->last_W;
-    return OTH_OK;
-    OTH_CATCH((p ? p->ctx : nullptr))
-}
-
-// Not part of the ABI (not in the header): reads the per-workgroup stamps of the diagnostic kernel build.
-int oth__debug_stamps(oth_plan *p, unsigned long long *out, int max_wg, int *nwg) {
-    OTH_TRY
-    CtxGuard guard_(p ? p->ctx : nullptr);
-    if (!p || !out || !nwg) return OTH_ERR_INVALID;
-    oth_ctx *c = p->ctx;
-    const int n = p->last_W < max_wg ? p->last_W : max_wg;
-    if (n != p->last_W) return OTH_ERR_INVALID;      // records [n][4] then phases [n][4 waves][12]
-    HIPCHK(c, hipMemcpyAsync(out, p->d_partial + (size_t)p->last_W * p->nfft, (32 + 384) * (size_t)n,
-                             hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *nwg = n;
-    return OTH_OK;
-    OTH_CATCH((p ? p->ctx : nullptr))
-}
-
-// Not part of the ABI: raw bytes of the plan's partial-sum buffer from a float offset on (diagnostic builds' stamps).
-int oth__debug_partial_raw(oth_plan *p, size_t float_offset, void *out, size_t nbytes) {
-    OTH_TRY
-    CtxGuard guard_(p ? p->ctx : nullptr);
-    if (!p || !out) return OTH_ERR_INVALID;
-    oth_ctx *c = p->ctx;
-    if (float_offset * sizeof(float) + nbytes > p->partial_cap) return OTH_ERR_INVALID;
-    HIPCHK(c, hipMemcpyAsync(out, p->d_partial + float_offset, nbytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return OTH_OK;
-    OTH_CATCH((p ? p->ctx : nullptr))
-}
-
-#endif      // OTH_EXPERIMENTS
 
 // recipe of the plan's last averaging launch ("" before the first)
 int oth__debug_last_recipe(oth_plan *p, char *buf, size_t buflen) {

@@ -19,37 +19,15 @@
 // through 32 ds_bpermute_b32 and chose Re / Im per lane half with 32 v_cndmask.)  Every thread carries 32
 // accumulators (the one-role csd4096 kernel: 64, which held it at three waves per SIMD with no room to keep the
 // overlapped halves or to prefetch): both streams are read once, the halves stay in registers, the next halves are
-// prefetched, four waves per SIMD.  The fifteen pass-2 twiddles come from a 2 KiB LDS table, read as eight
-// ds_read_b128 between the two butterfly layers of pass 2 (round 2 multiplied them out of two seeds: 52 VALU per step).
+// prefetched, four waves per SIMD.  The fifteen pass-2 twiddles are multiplied out of two seeds per step (52 VALU).
+// tried: the fifteen kept in registers (no room beside 32 accumulators at 128 VGPRs), and read from a 2 KiB LDS table
+// between the butterfly layers of pass 2 (0.3126 against 0.3111 ms, 0.3495 against 0.3486 ms: no gain, NOTES 4.1c).
 //
 // The two pairs run the same chunk schedule (Px draws the tickets, Py reads them), so x_s and y_s are always in
 // the same step.  Frequency-domain detrend as in welch4096ws.hip (needs WelchArgs.fd).
 #include <mutex>
 #include <type_traits>
 #include "fft4096.hip.h"
-
-#ifndef OTH_CSDWS_TW
-#define OTH_CSDWS_TW 0      // pass-2 twiddles: 0 multiplied out of two seeds per step, 1 kept in registers, 2 LDS table (A/B: no gain)
-#endif
-// wave priorities: producer latency sections / butterflies, consumer latency sections / butterflies / swap + accumulate
-#ifndef OTH_CSDWS_PAL
-#define OTH_CSDWS_PAL 2
-#endif
-#ifndef OTH_CSDWS_PAC
-#define OTH_CSDWS_PAC 0
-#endif
-#ifndef OTH_CSDWS_PBL
-#define OTH_CSDWS_PBL 2
-#endif
-#ifndef OTH_CSDWS_PBC
-#define OTH_CSDWS_PBC 1
-#endif
-#ifndef OTH_CSDWS_PBA
-#define OTH_CSDWS_PBA 2
-#endif
-#ifndef OTH_CSDWS_SWAP
-#define OTH_CSDWS_SWAP 1    // 1: spectra traded with v_permlane32_swap_b32, 0: ds_bpermute_b32 (round 2)
-#endif
 
 namespace oth {
 namespace {
@@ -59,35 +37,18 @@ constexpr int CS_RED = 32;                 // float2 per pair: per image the fou
 constexpr int CS_CTRL = 16;                // ints per pair: item kind per image [0..1], next-chunk ticket [4] (pair 0)
 constexpr size_t CS_PAIR_BYTES = (2 * LDS_X + CS_RED) * sizeof(float2) + CS_CTRL * sizeof(int);
 constexpr size_t CS_FW_BYTES = 256 * sizeof(float4);      // window-spectrum entries of the detrend, one per t
-constexpr size_t CS_TW_BYTES = 8 * 16 * sizeof(float4);   // pass-2 twiddles [k1 / 2][c]: (W256^(k1 c), W256^((k1 + 1) c))
-constexpr size_t CS_LDS_BYTES = 2 * CS_PAIR_BYTES + CS_FW_BYTES + CS_TW_BYTES;
+constexpr size_t CS_LDS_BYTES = 2 * CS_PAIR_BYTES + CS_FW_BYTES;
 static_assert((2 * CS_PAIR_BYTES) % 16 == 0, "the detrend table is read as float4");
 
 enum { CS_STOP = 0, CS_DATA = 1, CS_BUBBLE = 2 };
 
-// -DOTH_CSDWS_DIAG=1 (tools/archive/csd_phases.py): per-wave cycle counts of the phases of a step, accumulated in scalar
-// registers and written behind the partial sums (1 KiB per workgroup: 16 waves x 8 counters)
-#ifndef OTH_CSDWS_DIAG
-#define OTH_CSDWS_DIAG 0
-#endif
-#if OTH_CSDWS_DIAG
-#define CS_STAMP(i)                                                 \
-    {                                                               \
-        const unsigned long long n_ = __builtin_amdgcn_s_memtime(); \
-        phase[i] += n_ - last_;                                     \
-        last_ = n_;                                                 \
-    }
-#else
-#define CS_STAMP(i)
-#endif
+// wave priorities: producer latency sections / butterflies, consumer latency sections / butterflies / swap + accumulate
+// (profiles/r05_ab_c3_priorities.txt: every other assignment was slower, by 0.1-4 %)
+constexpr int CS_PAL = 2, CS_PAC = 0, CS_PBL = 2, CS_PBC = 1, CS_PBA = 2;
 
 template <bool DETREND, bool PILOT = false>
 __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
     static_assert(DETREND || !PILOT, "the pilot belongs to the detrend");
-#if OTH_CSDWS_DIAG
-    unsigned long long phase[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long last_ = __builtin_amdgcn_s_memtime();
-#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const bool producer = tid < 512;
@@ -147,9 +108,7 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
         };
         auto step_end = [&](int item) {
             if (t == 0) ctrl[it & 1] = item;
-            CS_STAMP(2);      // pass 1 + twiddles + exchange-1 writes issued
             lds_barrier();
-            CS_STAMP(3);      // barrier (includes the LDS writes landing)
             ++it;
         };
         auto item = [&](auto first_, auto mode_, int s, int nsb, bool publish) {
@@ -157,13 +116,8 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
             constexpr int MODE = decltype(mode_)::value;
             const int q = it & 1;
             float2 *lx = img + q * LDS_X;
-            __builtin_amdgcn_s_setprio(OTH_CSDWS_PAL);
+            __builtin_amdgcn_s_setprio(CS_PAL);
             float2 v[16];
-#if OTH_CSDWS_DIAG
-            CS_STAMP(0);      // loop / chunk bookkeeping
-            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-            CS_STAMP(1);      // wait for the prefetched half
-#endif
             float2 sumf = make_float2(0.f, 0.f), sum = make_float2(0.f, 0.f);
             if (FIRST) {
 #pragma unroll
@@ -204,9 +158,9 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
                 if ((t & 63) == 63) red[q * 8 + wave] = cadd(sum, other);
                 prev_new = sum;
             }
-            __builtin_amdgcn_s_setprio(OTH_CSDWS_PAC);
+            __builtin_amdgcn_s_setprio(CS_PAC);
             dft16(v);
-            __builtin_amdgcn_s_setprio(OTH_CSDWS_PAL);
+            __builtin_amdgcn_s_setprio(CS_PAL);
             scatter_pow16<RS>(v, lx + w1, b1, b4);
             step_end(CS_DATA);
         };
@@ -284,67 +238,29 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
         float2 *red = img + 2 * LDS_X;
         // W256^c, W256^(4c): the fifteen pass-2 twiddles are multiplied out per item (32 accumulators leave no room
         // for the thirty registers the headline kernel's consumer spends on them)
-#if OTH_CSDWS_TW == 1
-        float2 tw2[16];
-#pragma unroll
-        for (int k = 1; k < 16; ++k) tw2[k] = p.tw[16 * lo * k];
-#elif OTH_CSDWS_TW == 0
         const float2 c1 = p.tw[16 * lo], c4 = p.tw[64 * lo];
-#else
-        // table of the fifteen W256^(k1 c): entry [k1 / 2][c] holds k1 even and odd side by side, so that the sixteen
-        // lanes that differ in c read 256 contiguous bytes per ds_read_b128 (no bank conflict)
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        float4 *twl = reinterpret_cast<float4 *>(smem + 2 * CS_PAIR_BYTES + CS_FW_BYTES);
-        if (cidx < 128) {
-            const int j = cidx >> 4, c = cidx & 15;
-            const float2 e = p.tw[16 * c * (2 * j)], o = p.tw[16 * c * (2 * j + 1)];
-            twl[j * 16 + c] = make_float4(e.x, e.y, o.x, o.y);      // visible to all behind the first step's barrier
-        }
-        const unsigned tw_addr = (unsigned)(unsigned long long)(twl + lo);
-        f4 tq[4];      // k1 = 0..7, read between the butterfly layers of pass 2; k1 = 8..15 follow when these are used up
-#endif
         // The detrend's window-spectrum entries and the segment mean are fetched from LDS where they are used: held in
         // registers across the step they pushed the allocation past 128 VGPRs, and the one spilled register came
         // back through scratch memory behind an s_waitcnt vmcnt(0) in every step (42 % of the consumers' time).
         float4 *fwl = reinterpret_cast<float4 *>(smem + 2 * CS_PAIR_BYTES);
         if (DETREND && pair == 0) fwl[t] = p.fd[t];      // lanes l and l + 32 (same t) are in one wave: ordered
-#if OTH_CSDWS_SWAP
         float axx[8], ayy[8], are[8], aim[8];      // lanes 0..31: bins k2 = j, lanes 32..63: bins k2 = j + 8
 #pragma unroll
         for (int k = 0; k < 8; ++k) axx[k] = ayy[k] = are[k] = aim[k] = 0.f;
-#else
-        float acs[16], acx[16];       // own power |X|^2 (or |Y|^2); cross term Re (pair 0) or Im (pair 1) of conj(X) Y
-#pragma unroll
-        for (int k = 0; k < 16; ++k) acs[k] = acx[k] = 0.f;
-#endif
         float2 v[16];
         int it = 0;
 
         // barrier A of step `it`, then what the producer left in image it & 1: item word, sums, pass 2
         auto next_item = [&]() -> int {
-            __builtin_amdgcn_s_setprio(OTH_CSDWS_PBL);
-            CS_STAMP(4);      // exchange + accumulation (loop tail)
+            __builtin_amdgcn_s_setprio(CS_PBL);
             lds_barrier();
-            CS_STAMP(0);      // barrier
             const int q = it & 1;
             const float2 *lq = img + q * LDS_X;
             const int kind = __builtin_amdgcn_readfirstlane(ctrl0[q]);      // both streams run the same schedule
-#if OTH_CSDWS_TW == 2
-            dft16_from_lds<17>(v, lq + r1, [] { __builtin_amdgcn_s_setprio(OTH_CSDWS_PBC); }, [&] {
-#define CS_TW_READ(j) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(tq[j]) : "v"(tw_addr), "n"(256 * (j)))
-                CS_TW_READ(0); CS_TW_READ(1); CS_TW_READ(2); CS_TW_READ(3);
-#undef CS_TW_READ
-            });
-#else
-            dft16_from_lds<17>(v, lq + r1, [] { __builtin_amdgcn_s_setprio(OTH_CSDWS_PBC); });
-#endif
-            CS_STAMP(1);      // exchange-1 reads + pass 2
+            dft16_from_lds<17>(v, lq + r1, [] { __builtin_amdgcn_s_setprio(CS_PBC); });
             ++it;
             return kind;
         };
-#if !OTH_CSDWS_SWAP
-        const int partner = ((tid & 63) ^ 32) << 2;      // ds_bpermute address of the lane that holds the other stream's bin
-#endif
         if (PILOT && p.pilot_inline) lds_barrier();      // the producers' pilot barrier
         int item = next_item();
         for (;;) {
@@ -352,35 +268,8 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
             if (item == CS_STOP) break;
             const int q = (it & 1) ^ 1;   // the image whose pass 2 sits in v
             float2 *lx = img + q * LDS_X;
-            __builtin_amdgcn_s_setprio(OTH_CSDWS_PBL);
-#if OTH_CSDWS_TW == 1
-            lx[w2] = v[r16(0)];
-#pragma unroll
-            for (int k1 = 1; k1 < 16; ++k1) lx[w2 + k1 * 17] = cmul(v[r16(k1)], tw2[k1]);
-#elif OTH_CSDWS_TW == 0
+            __builtin_amdgcn_s_setprio(CS_PBL);
             scatter_pow16<17>(v, lx + w2, c1, c4);
-#else
-            // the first half of the table went out between the butterfly layers of pass 2: long since back.  The second
-            // half reuses its registers (all sixteen at once cost 15-26 spilled registers at the 128-VGPR cap).
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tq[0]), "+v"(tq[1]), "+v"(tq[2]), "+v"(tq[3]));
-            lx[w2] = v[r16(0)];
-#pragma unroll
-            for (int k1 = 1; k1 < 8; ++k1) {
-                const f4 e = tq[k1 >> 1];
-                lx[w2 + k1 * 17] = cmul(v[r16(k1)], (k1 & 1) ? make_float2(e.z, e.w) : make_float2(e.x, e.y));
-            }
-            f4 tr[4];
-#define CS_TW_READ(j) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(tr[j]) : "v"(tw_addr), "n"(256 * (4 + (j))))
-            CS_TW_READ(0); CS_TW_READ(1); CS_TW_READ(2); CS_TW_READ(3);
-#undef CS_TW_READ
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tr[0]), "+v"(tr[1]), "+v"(tr[2]), "+v"(tr[3]));
-#pragma unroll
-            for (int k1 = 8; k1 < 16; ++k1) {
-                const f4 e = tr[(k1 - 8) >> 1];
-                lx[w2 + k1 * 17] = cmul(v[r16(k1)], (k1 & 1) ? make_float2(e.z, e.w) : make_float2(e.x, e.y));
-            }
-#endif
-            CS_STAMP(2);      // pass-2 twiddles + exchange-2 writes issued
             wave_lds_sync();
             float4 fw = make_float4(0.f, 0.f, 0.f, 0.f);
             float2 h0 = make_float2(0.f, 0.f), h1 = h0, h2 = h0, h3 = h0;
@@ -388,8 +277,7 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
                 fw = fwl[t];
                 h0 = red[q * 8], h1 = red[q * 8 + 1], h2 = red[q * 8 + 2], h3 = red[q * 8 + 3];
             }
-            dft16_from_lds<1>(v, lx + r2, [] { __builtin_amdgcn_s_setprio(OTH_CSDWS_PBC); });
-            CS_STAMP(3);      // exchange-2 reads + pass 3
+            dft16_from_lds<1>(v, lx + r2, [] { __builtin_amdgcn_s_setprio(CS_PBC); });
             if (DETREND) {
                 const float2 tot = cadd(cadd(h0, h1), cadd(h2, h3));
                 const float2 mean = make_float2(tot.x * (1.0f / 4096.0f), tot.y * (1.0f / 4096.0f));
@@ -398,8 +286,7 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
                 v[r16(15)] = make_float2(v[r16(15)].x - (mean.x * fw.z - mean.y * fw.w),
                                          v[r16(15)].y - (mean.x * fw.w + mean.y * fw.z));
             }
-            __builtin_amdgcn_s_setprio(OTH_CSDWS_PBA);
-#if OTH_CSDWS_SWAP
+            __builtin_amdgcn_s_setprio(CS_PBA);
             // v_permlane32_swap_b32 a, b swaps a's lanes 32..63 with b's lanes 0..31.  With a = bin j and b = bin j + 8
             // (x-stream values in lanes 0..31, y-stream values in lanes 32..63 of both): a' = X[j] | X[j + 8],
             // b' = Y[j] | Y[j + 8] - lane l holds bin j of both streams, lane l + 32 bin j + 8.
@@ -416,33 +303,10 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
                 are[j] = fmaf(X.x, Y.x, fmaf(X.y, Y.y, are[j]));
                 aim[j] = fmaf(X.x, Y.y, fmaf(-X.y, Y.x, aim[j]));
             }
-#else
-            // conj(X) Y with own = this lane's bin, o = the partner lane's:  x lanes  Re = Xr Yr + Xi Yi = own.x o.x + own.y o.y
-            //                                                                y lanes  Im = Xr Yi - Xi Yr = own.y o.x - own.x o.y
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float2 o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float2 m = v[r16(4 * g + j)];
-                    o[j].x = __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(m.x)));
-                    o[j].y = __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(m.y)));
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int k2 = 4 * g + j;
-                    const float2 m = v[r16(k2)];
-                    const float u = pair ? m.y : m.x, w = pair ? -m.x : m.y;
-                    acx[k2] = fmaf(u, o[j].x, fmaf(w, o[j].y, acx[k2]));
-                    acs[k2] = fmaf(m.x, m.x, fmaf(m.y, m.y, acs[k2]));
-                }
-            }
-#endif
             item = next_item();
         }
         // channels xx, yy, re, im; bin k0 + 16 k1 + 256 k2 at t + 256 k2 (finalize_kernel layout 1)
         float *dst = p.partial + ((size_t)stream * W + wg) * 4 * 4096;
-#if OTH_CSDWS_SWAP
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int o = 256 * (pair ? j + 8 : j) + t;
@@ -451,22 +315,7 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
             dst[8192 + o] = are[j];
             dst[12288 + o] = aim[j];
         }
-#else
-#pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2) {
-            dst[(pair ? 4096 : 0) + 256 * k2 + t] = acs[k2];
-            dst[(pair ? 12288 : 8192) + 256 * k2 + t] = acx[k2];
-        }
-#endif
     }
-#if OTH_CSDWS_DIAG
-    if ((tid & 63) == 0) {
-        unsigned long long *st = reinterpret_cast<unsigned long long *>(p.partial + (size_t)p.nstreams * W * 4 * 4096) +
-                                 ((size_t)stream * W + wg) * 128 + (tid >> 6) * 8;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) st[i] = phase[i];
-    }
-#endif
 }
 
 }  // namespace

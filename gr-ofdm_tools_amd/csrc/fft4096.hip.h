@@ -37,7 +37,7 @@ constexpr float T1 = 0.41421356237309503f;   // tan(pi/8)
 // W16^1 u = cos(pi/8) (x + t y, y - t x), W16^3 u = cos(pi/8) (t x + y, t y - x), t = tan(pi/8), and so on;
 // inside one 4-point butterfly the two odd inputs share their scale, so the scale rides on the fused
 // multiply-adds that replace the butterfly's additions.  144 operations per 16-point DFT instead of 160
-// (64 + 16 + 20 + 22 + 22 against 64 + 16 + 24 + 28 + 28).  `OTH_DFT16_PLAIN` restores the multiply-then-add form.
+// (64 + 16 + 20 + 22 + 22 against 64 + 16 + 24 + 28 + 28).  dft16<true> is the multiply-then-add form.
 __device__ __forceinline__ void dft4_tail(float2 t0, float2 t1, float2 p1, float2 p3, float S, float2 &a0, float2 &a1,
                                           float2 &a2, float2 &a3) {
     const float2 q = cadd(p1, p3), r = csub(p1, p3);
@@ -46,15 +46,10 @@ __device__ __forceinline__ void dft4_tail(float2 t0, float2 t1, float2 p1, float
     a1 = make_float2(fmaf(S, r.y, t1.x), fmaf(-S, r.x, t1.y));       // t1 + (-i) S r
     a3 = make_float2(fmaf(-S, r.y, t1.x), fmaf(S, r.x, t1.y));
 }
-#ifdef OTH_DFT16_PLAIN
-constexpr bool kDft16Plain = true;
-#else
-constexpr bool kDft16Plain = false;
-#endif
 // PLAIN: multiply-then-add (160 operations; every inner twiddle product rounded on its own) - the periodogram-chain
 // builds take it, their single rows are compared bin by bin and the chain is HBM-bound; the Welch averages take the
 // folded form
-template <bool PLAIN = kDft16Plain>
+template <bool PLAIN = false>
 __device__ __forceinline__ void dft16_layer2(float2 (&v)[16]) {
   if constexpr (PLAIN) {
     v[5] = mul_w1(v[5]);
@@ -100,7 +95,7 @@ __device__ __forceinline__ void dft16_layer2(float2 (&v)[16]) {
 }
 
 // Forward 16-point DFT in place: in v[a], a = 0..15; out y[k] at v[r16(k)].
-template <bool PLAIN = kDft16Plain>
+template <bool PLAIN = false>
 __device__ __forceinline__ void dft16(float2 (&v)[16]) {
 #pragma unroll
     for (int a0 = 0; a0 < 4; ++a0) dft4<false>(v[a0], v[a0 + 4], v[a0 + 8], v[a0 + 12]);
@@ -109,7 +104,7 @@ __device__ __forceinline__ void dft16(float2 (&v)[16]) {
 
 // 8-point DFT, natural order in and out; the sqrt(1/2) of W8^1 and W8^3 rides on the last layer's additions
 // (PLAIN: multiplied out first, as dft16_layer2<true>)
-template <bool PLAIN = kDft16Plain>
+template <bool PLAIN = false>
 __device__ __forceinline__ void dft8(float2 (&v)[8]) {
     dft4<false>(v[0], v[2], v[4], v[6]);
     dft4<false>(v[1], v[3], v[5], v[7]);
@@ -148,14 +143,6 @@ __device__ __forceinline__ void dft8(float2 (&v)[8]) {
 // (a twiddle table, say) have the second layer to hide behind and do not disturb the counted waits above them.
 template <int STRIDE, class F, class M>
 __device__ __forceinline__ void dft16_from_lds(float2 (&v)[16], const float2 *base, F issued, M mid) {
-#ifdef OTH_PLAIN_LDS_READS      // A/B switch: compiler-scheduled reads
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v[i] = base[STRIDE * i];
-    issued();
-    mid();
-    dft16(v);
-    return;
-#endif
     const unsigned addr = (unsigned)(unsigned long long)base;      // LDS byte address = low half of the flat address
     double r[16];
 #define OTH_LDS_READ(i) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(r[i]) : "v"(addr), "n"(8 * STRIDE * (i)))
@@ -321,13 +308,8 @@ __device__ __forceinline__ float wave_total_lane63(float v) {
     // keep their value.  Through __builtin_amdgcn_update_dpp(0, ...) + add the compiler emits v_mov 0, v_mov_dpp, v_add
     // per step (the builtin's semantics give the other rows 0 first): 8 VALU instructions more per complex sum.  The
     // s_nop covers the VALU-write -> DPP-read hazard, which the compiler does not see inside the asm.
-#ifdef OTH_WAVE_TOTAL_BUILTIN      // A/B switch: the form of rounds 1-2
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xA, 0xF, false));   // row_bcast:15
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xC, 0xF, false));   // row_bcast:31
-#else
     asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf" : "+v"(v));
     asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" : "+v"(v));
-#endif
     return v;
 }
 

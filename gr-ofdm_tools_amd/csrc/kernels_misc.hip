@@ -423,9 +423,6 @@ __global__ void set_flag_kernel(int *flag, int v) { *flag = v; }
 // block to finish reduces the group rows - with __threadfence() it took 60 us (an agent-scope release / acquire
 // writes back / invalidates the XCD's whole L2 from each of ~1000 workgroups), with agent-scope atomic stores / loads
 // for the group rows instead of fences 10-20 us.
-#ifndef OTH_CHAIN_TAIL_DIRECT
-#define OTH_CHAIN_TAIL_DIRECT 1
-#endif
 template <bool MAX>
 __global__ __launch_bounds__(256) void chain_reduce_kernel(const float *partial, float *scratch, int W, int nfft, int rows_per_group) {
     __shared__ double red[3][64][4];
@@ -531,7 +528,7 @@ int chain_tail_groups(int W, int nfft) {
     if (W <= 128) return 0;
     // 8192 / 16384 points: the state kernel alone has 512 / 1024 workgroups and 8 / 4 team rows per thread - one launch
     // instead of two (same-box A/B: -0.5 ... -1 % of the push; at 2048 / 4096 points the direct form is 1.4-4 % SLOWER)
-    if (OTH_CHAIN_TAIL_DIRECT && nfft >= 8192 && W <= 1536) return 0;
+    if (nfft >= 8192 && W <= 1536) return 0;
     // ~12 rows per group gives nfft / 256 x G ~ 1024 workgroups at every size; at most 256 groups, so that the state
     // kernel (nfft / 16 workgroups) never walks more than four rows per thread
     int g = (W + 11) / 12;
@@ -703,13 +700,9 @@ __global__ __launch_bounds__(256) void bin_threshold_ma_kernel(const float *psd,
 // The 4096 + M - 1 inputs of a block's 4096 outputs are staged in LDS first (coalesced; one pad word per 16 so that
 // the per-thread runs, 16 apart, fall into different banks): the taps then cost LDS reads, not dependent global loads
 // (35 us -> 5 us for 64 rows of 16384 at M = 163).
-#ifndef OTH_MA_RUN
-#define OTH_MA_RUN 8       // outputs per thread: 8.9 us for config 5's 64 rows of 16384 against 11.2 at 16 and 15.4 at 32 (tile 4096;
-#endif                   // tiles of 1024 / 2048 at 4-16 per thread: 7.8-10.3 us - the kernel is a latency chain, tools/archive/decide_probe.py)
-#ifndef OTH_MA_TILE
-#define OTH_MA_TILE 4096
-#endif
-constexpr int kMaTile = OTH_MA_TILE, kMaRun = OTH_MA_RUN, kMaMaxM = 1024, kMaThreads = kMaTile / kMaRun;
+// kMaRun outputs per thread: 8.9 us for config 5's 64 rows of 16384 against 11.2 at 16 and 15.4 at 32 (tile 4096; tiles of
+// 1024 / 2048 at 4-16 per thread: 7.8-10.3 us - the kernel is a latency chain, tools/archive/decide_probe.py)
+constexpr int kMaTile = 4096, kMaRun = 8, kMaMaxM = 1024, kMaThreads = kMaTile / kMaRun;
 // movavg_run_kernel holds 67.6 KB of STATIC LDS: more than the 64 KB a workgroup may have on every target but gfx950
 // (160 KB per CU) - this library is built for gfx950 only (Makefile ARCH); a change of --offload-arch must shrink the tile
 static_assert((kMaTile + kMaMaxM) * 5 / 4 * sizeof(float) + (kMaTile * 9 / 8) * sizeof(double) <= 160 * 1024, "movavg_run_kernel's LDS");
@@ -723,7 +716,7 @@ __global__ __launch_bounds__(kMaThreads) void movavg_run_kernel(const float *psd
     // sums / largest magnitudes of the staged inputs in blocks of kMaRun (round 5): a thread's run starts on a block
     // boundary, so its first M-tap sum is M / kMaRun block sums + M % kMaRun taps - 23 LDS reads at M = 163 where the
     // tap-by-tap sum made 163 in 21 dependent trips (measured: no faster by itself - the kernel's 9-11 us are launch,
-    // staging and write-back latency, see OTH_MA_RUN).  A double sum of float32 taps is exact over the same range as before, so the order in
+    // staging and write-back latency, see kMaRun).  A double sum of float32 taps is exact over the same range as before, so the order in
     // which it is formed does not show.
     constexpr int kMaBlocks = (kMaTile + kMaMaxM) / kMaRun + 1;
     __shared__ double bsum[kMaBlocks];

@@ -137,31 +137,14 @@ struct FinalizeArgs {
 
 // Every launcher returns hipSuccess / error of the launch only (asynchronous).
 hipError_t launch_welch_generic(int nfft, const WelchArgs &a, hipStream_t s);
-// welch4096.hip is built once per variant tag (Makefile W4096_VARIANTS); nfft 4096, nperseg 4096, y == nullptr
+// welch4096.hip is built once per variant tag (Makefile: dpp, pipe); nfft 4096, nperseg 4096, y == nullptr
 #define OTH_DECL_W4096(tag)                                                     \
     hipError_t launch_welch_tuned4096_##tag(const WelchArgs &a, hipStream_t s); \
     int tuned4096_blocks_per_cu_##tag();
 OTH_DECL_W4096(dpp)
-#ifdef OTH_EXPERIMENTS
-OTH_DECL_W4096(diag)
-OTH_DECL_W4096(exp1)
-OTH_DECL_W4096(exp2)
-OTH_DECL_W4096(exp3)
-OTH_DECL_W4096(exp4)
-#endif
 OTH_DECL_W4096(pipe)
 // welch4096ws.hip: wave-specialised producer/consumer form; step 2048, detrend needs WelchArgs.fd
-// (built once per tag like welch4096.hip)
 OTH_DECL_W4096(ws)
-// welch4096ws2.hip: the same arithmetic in one 1024-thread workgroup per CU, two runs of segments (A/B variant "ws2");
-// WelchArgs.y = first sample of the second run, WelchArgs.nseg = segments per run, two partial rows per workgroup
-OTH_DECL_W4096(ws2)
-#ifdef OTH_EXPERIMENTS
-OTH_DECL_W4096(wsx1)
-OTH_DECL_W4096(wsx2)
-OTH_DECL_W4096(wsx3)
-OTH_DECL_W4096(wsx4)
-#endif
 // csd4096.hip: two-channel cross spectrum, nfft = nperseg = 4096
 hipError_t launch_csd_tuned4096(const WelchArgs &a, hipStream_t s);
 int csd4096_blocks_per_cu();

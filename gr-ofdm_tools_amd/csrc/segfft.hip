@@ -49,18 +49,10 @@ template <int R> struct Geo {
 };
 
 enum { LOAD_HALF = 0, LOAD_FULL = 1 };
-#ifndef OTH_SEG_R2_DPP
-#define OTH_SEG_R2_DPP 1      // 512 points: last radix-2 stage through DPP instead of an LDS exchange
-#endif
-#ifndef OTH_CHAIN_WIN_LDS
-#define OTH_CHAIN_WIN_LDS 1
-#endif
-#ifndef OTH_CHAIN_PLAIN_MASK
-#define OTH_CHAIN_PLAIN_MASK 7       // chain builds: passes (bit 0: pass 1, bit 1: pass 2, bit 2: pass 3) that take the
-#endif                               // multiply-then-add butterflies - their single rows are compared bin by bin
-#ifndef OTH_CHAIN_WPS
-#define OTH_CHAIN_WPS 3      // waves per SIMD of the chain build (2: no spills at all, but half the speed)
-#endif
+// chain builds: passes (bit 0: pass 1, bit 1: pass 2, bit 2: pass 3) that take the multiply-then-add butterflies - their
+// single rows are compared bin by bin
+constexpr int kChainPlainMask = 7;
+constexpr int kChainWps = 3;      // waves per SIMD of the chain build (2: no spills at all, but half the speed)
 enum { ACC_SUM = 0, ACC_WSUM = 1, ACC_MAX = 2, ACC_NONE = 3 };
 
 // Image accesses are explicit ds_read_b64 / ds_write_b64 at (swizzled lane base) + immediate.  A wave's LDS
@@ -170,11 +162,11 @@ __global__ __launch_bounds__(Geo<R>::BLOCK, WPS) void seg_kernel(SegArgs p) {
     const int wg = blockIdx.x * TPB + team, W = p.wg_per_stream, stream = blockIdx.y;
     // (the fused chain keeps the LDS exchange: measured 71 % of the roofline with it against 54 % through DPP - the
     // exchange's wait is where its three waves per SIMD take turns at the memory pipe)
-    constexpr bool R2DPP = R == 2 && !CHAIN && (OTH_SEG_R2_DPP != 0);
+    constexpr bool R2DPP = R == 2 && !CHAIN;      // 512 points: last radix-2 stage through DPP instead of an LDS exchange
     // butterfly form per pass.  256 points (two passes): the multiply-then-add form in pass 2 costs 19 % of the launch
     // (four teams per wave: that build is issue-bound) and measures the same accuracy (tools/acc_rows.py), so only
     // pass 1 takes it there
-    constexpr int PLM = kDft16Plain ? 7 : (CHAIN ? ((OTH_CHAIN_PLAIN_MASK) & (R == 1 ? 1 : 7)) : 0);
+    constexpr int PLM = CHAIN ? (kChainPlainMask & (R == 1 ? 1 : 7)) : 0;
     constexpr bool PL1 = (PLM & 1) != 0, PL2 = (PLM & 2) != 0, PL3 = (PLM & 4) != 0;
     // asm register pairs as 2-float vectors only where the `double` form left stack slots behind (struct Pair above)
     constexpr bool kPairVec = false;      // (see struct Pair: the by-value converters alone remove the stack slots)
@@ -184,7 +176,7 @@ __global__ __launch_bounds__(Geo<R>::BLOCK, WPS) void seg_kernel(SegArgs p) {
     // WIN_LDS (the chain build): the sixteen window values of a thread live in LDS as four float4 and are read
     // per segment - sixteen registers less, which is what keeps the build's spills out of the segment loop (a
     // spill reload waits on vmcnt and with it on the prefetch in flight)
-    constexpr bool WIN_LDS = CHAIN && (OTH_CHAIN_WIN_LDS != 0);
+    constexpr bool WIN_LDS = CHAIN;
     float4 *wl = reinterpret_cast<float4 *>(red + 16) + t;      // [4][T] float4, one table per workgroup
     // the six stored twiddle powers of pass 1 (sub-wave teams) / pass 2 (4096 points) go the same way where the
     // build would otherwise still spill: [3][T] and [3][R] float4 behind the window table
@@ -565,15 +557,6 @@ __global__ __launch_bounds__(Geo<R>::BLOCK, WPS) void seg_kernel(SegArgs p) {
 //      2 frequency domain in the consumer, X -= mean FFT(w) on the bins |k| < 256 (SegArgs.fd; needs a window whose
 //        spectrum is confined to those bins, as welch4096ws.hip).
 enum { WS_STOP = 0, WS_DATA = 1 };
-#ifndef OTH_SEGWS_SPREAD
-#define OTH_SEGWS_SPREAD 0      // A/B (round 4): two loads at four places of the producer step: +3.5 % time at 1024, +0.8 % at 2048 - not the scanner kernel (whose 16 waves x 16 loads per step fill the queue)
-#endif
-#ifndef OTH_SEGWS_DEEP
-#define OTH_SEGWS_DEEP 0
-#endif
-#ifndef OTH_SEGWS_STORED_TW1
-#define OTH_SEGWS_STORED_TW1 (!OTH_SEGWS_DEEP)
-#endif
 
 template <int R, int DET, bool PILOT = false>
 __global__ __launch_bounds__(32 * R, 4) void segws_kernel(SegArgs p) {
@@ -600,22 +583,14 @@ __global__ __launch_bounds__(32 * R, 4) void segws_kernel(SegArgs p) {
         float win[16];
 #pragma unroll
         for (int a = 0; a < 16; ++a) win[a] = p.win[T * a + t];
-#if OTH_SEGWS_STORED_TW1
         float2 tw1[16];      // all fifteen pass-1 twiddles W_N^(k0 t) in registers: the producer has the room (no accumulators)
 #pragma unroll
         for (int k = 1; k < 16; ++k) tw1[k] = p.tw[(k * t) & (N - 1)];
-#else
-        const Pow6 tw1 = {p.tw[t], p.tw[(2 * t) & (N - 1)], p.tw[(3 * t) & (N - 1)], p.tw[(4 * t) & (N - 1)],
-                          p.tw[(8 * t) & (N - 1)], p.tw[(12 * t) & (N - 1)]};
-#endif
-        // The new half of segment s is half-block s + 1, requested one segment before it is consumed.  OTH_SEGWS_DEEP:
-        // two buffers alternate and a half-block is requested TWO segments ahead - measured no faster (42-43 % against
+        // The new half of segment s is half-block s + 1, requested one segment before it is consumed.  tried: two
+        // buffers that alternate, a half-block requested TWO segments ahead - measured no faster (42-43 % against
         // 43-45 %: it costs the registers of the stored pass-1 twiddles), although a build without the loads runs 19 %
         // faster; the loads cost through the memory system, not through their latency.
         float2 kw[8], nA[8];
-#if OTH_SEGWS_DEEP
-        float2 nB[8];
-#endif
         float2 prev_new = make_float2(0.f, 0.f);
         const float2 pv = load_pilot(PILOT ? p.pilot : nullptr, stream);      // PILOT: off every sample as it arrives
         const int sched = p.sched;
@@ -647,29 +622,15 @@ __global__ __launch_bounds__(32 * R, 4) void segws_kernel(SegArgs p) {
                 kw[a] = make_float2(r.x * win[a], r.y * win[a]);
                 sum = cadd(sum, r);
             }
-#ifndef OTH_SEGWS_NOLOAD      // (timing experiment: -DOTH_SEGWS_NOLOAD keeps re-using the first loaded halves)
-            const float2 *xn = half(s + (OTH_SEGWS_DEEP ? 3 : 2));
-            // the next half's eight loads, two at each of four places of the step instead of one burst (round 4: the
-            // scanner kernel's lesson - a burst fills the memory pipeline's queue and the issuing wave stands still)
-            auto spread = [&](int grp) {
-#if OTH_SEGWS_SPREAD
-                __builtin_amdgcn_sched_barrier(0);
+            const float2 *xn = half(s + 2);
+            // the next half's eight loads in one burst.  tried: two at each of four places of the step, as in the scanner
+            // kernel (whose 16 waves x 16 loads per step fill the queue): +3.5 % time at 1024 points, +0.8 % at 2048
+            // (kept as a lambda: written in line the same loads are scheduled differently)
+            auto load_next = [&]() {
 #pragma unroll
-                for (int a = 2 * grp; a < 2 * grp + 2; ++a) nxt[a] = load_once(xn + T * a);
-                __builtin_amdgcn_sched_barrier(0);
-#else
-                if (grp == 0) {
-#pragma unroll
-                    for (int a = 0; a < 8; ++a) nxt[a] = load_once(xn + T * a);
-                }
-#endif
+                for (int a = 0; a < 8; ++a) nxt[a] = load_once(xn + T * a);
             };
-            spread(0);
-#else
-            auto spread = [&](int) {};
-#pragma unroll
-            for (int a = 0; a < 8; ++a) asm volatile("" : "+v"(nxt[a].x), "+v"(nxt[a].y));
-#endif
+            load_next();
             if (sched == 2 && t == 0) {
                 if (s == sb) ticket = atomicAdd(p.queue + stream, 1u);
                 if (s == se - 1) ctrl[2] = (int)ticket;
@@ -690,24 +651,14 @@ __global__ __launch_bounds__(32 * R, 4) void segws_kernel(SegArgs p) {
                 if ((t & 63) == 63) red[q * 4 + (t >> 6)] = cadd(sum, other);
                 prev_new = sum;
             }
-            spread(1);
             prio_compute();
             dft16(v);
             prio_latency();
-            spread(2);
-#if OTH_SEGWS_STORED_TW1
             static_for<0, 16>([&](auto kc) {
                 constexpr int k0 = decltype(kc)::value;
                 const float2 val = k0 ? cmul(v[r16(k0)], tw1[k0]) : v[0];
                 lds_write_imm<8 * (512 * (k0 >> P) + R * (k0 & KP & ~KM))>((img + b_w1) ^ (8u * R * (k0 & KM)), val);
             });
-#else
-            twiddle_pow16(v, tw1, [&](auto kc, float2 val) {
-                constexpr int k0 = decltype(kc)::value;
-                lds_write_imm<8 * (512 * (k0 >> P) + R * (k0 & KP & ~KM))>((img + b_w1) ^ (8u * R * (k0 & KM)), val);
-            });
-#endif
-            spread(3);
             if (t == 0) ctrl[q] = WS_DATA;
             lds_barrier();
             ++it;
@@ -717,26 +668,13 @@ __global__ __launch_bounds__(32 * R, 4) void segws_kernel(SegArgs p) {
             se = s1;
             if (sched) chunk_range_of(p.nseg, p.nbig, p.chunk, p.tail_chunk, cur, sb, se);
             if (sb < se) {
-                const float2 *x0 = half(sb), *x1 = half(sb + 1), *x2 = half(sb + 2);
+                const float2 *x0 = half(sb), *x1 = half(sb + 1);
 #pragma unroll
                 for (int a = 0; a < 8; ++a) kw[a] = x0[T * a];
 #pragma unroll
                 for (int a = 0; a < 8; ++a) nA[a] = load_once(x1 + T * a);
-#if OTH_SEGWS_DEEP
-#pragma unroll
-                for (int a = 0; a < 8; ++a) nB[a] = load_once(x2 + T * a);
-#else
-                (void)x2;
-#endif
             }
-#if OTH_SEGWS_DEEP
-            for (long long s = sb; s < se; s += 2) {
-                segment(s, nA);
-                if (s + 1 < se) segment(s + 1, nB);
-            }
-#else
             for (long long s = sb; s < se; ++s) segment(s, nA);
-#endif
             if (sched == 0) break;
             // ctrl[2] was written before the barrier of the chunk's last segment
             cur = (sched == 1) ? cur + W : (long long)W + __builtin_amdgcn_readfirstlane(ctrl[2]);
@@ -878,7 +816,7 @@ template <int R> int occupancy_ws() {
 // image(s) + sums + tickets, and for the chain build the window table (4 x T float4) and twiddle tables
 template <int R, bool CHAIN> constexpr size_t seg_lds_bytes() {
     return Geo<R>::LDS_BYTES +
-           ((CHAIN && OTH_CHAIN_WIN_LDS) ? (4 * Geo<R>::T + (R <= 2 ? 3 * Geo<R>::T : 0) + (R == 16 ? 3 * R : 0)) * sizeof(float4) : 0);
+           (CHAIN ? (4 * Geo<R>::T + (R <= 2 ? 3 * Geo<R>::T : 0) + (R == 16 ? 3 * R : 0)) * sizeof(float4) : 0);
 }
 
 template <int R, int LOAD, bool DETREND, bool CHAIN, int WPS, int NA = 16> hipError_t launch_one(const SegArgs &a, hipStream_t s) {
@@ -930,7 +868,7 @@ template <int R, int NA> int occupancy_pad(int kind) {
 
 // kind: 0 Welch step = N/2 (half kept in registers), 1 Welch any step, 2 chain.  wps4: the 128-VGPR build of kind 0.
 template <int R> hipError_t launch_r(const SegArgs &a, int kind, bool wps4, hipStream_t s) {
-    if (kind == 2) return launch_one<R, LOAD_FULL, false, true, OTH_CHAIN_WPS>(a, s);
+    if (kind == 2) return launch_one<R, LOAD_FULL, false, true, kChainWps>(a, s);
     if constexpr (R == 16) {
         return hipErrorInvalidValue;      // the Welch average at 4096 has its own kernels (welch4096*.hip)
     } else {
@@ -943,7 +881,7 @@ template <int R> hipError_t launch_r(const SegArgs &a, int kind, bool wps4, hipS
 }
 
 template <int R> int occupancy_r(int kind, bool wps4) {
-    if (kind == 2) return occupancy_one<R, LOAD_FULL, false, true, OTH_CHAIN_WPS>();
+    if (kind == 2) return occupancy_one<R, LOAD_FULL, false, true, kChainWps>();
     if constexpr (R == 16) {
         return 1;
     } else {
@@ -1003,10 +941,10 @@ hipError_t launch_seg_padded(int nfft, int nperseg, const SegArgs &a, int kind, 
 // epilogue |X|^2 x 1) with an overlapped step; with a.detrend each segment's own mean comes off before the window - a build
 // of its own (DETREND and CHAIN), no pilot.
 template <int R> hipError_t launch_rows_r(const SegArgs &a, hipStream_t s) {
-    if (!a.detrend) return launch_one<R, LOAD_FULL, false, true, OTH_CHAIN_WPS>(a, s);
+    if (!a.detrend) return launch_one<R, LOAD_FULL, false, true, kChainWps>(a, s);
     const dim3 grid((a.wg_per_stream + Geo<R>::TPB - 1) / Geo<R>::TPB, a.nstreams);
     constexpr size_t lds = seg_lds_bytes<R, true>();
-    hipLaunchKernelGGL((seg_kernel<R, LOAD_FULL, true, true, OTH_CHAIN_WPS>), grid, dim3(Geo<R>::BLOCK), lds, s, a);
+    hipLaunchKernelGGL((seg_kernel<R, LOAD_FULL, true, true, kChainWps>), grid, dim3(Geo<R>::BLOCK), lds, s, a);
     return hipGetLastError();
 }
 

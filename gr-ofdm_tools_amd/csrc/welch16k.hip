@@ -15,14 +15,7 @@
 // 16 waves per CU = 4 per SIMD at <= 128 VGPRs.  Four workgroup barriers per segment.
 #include "fft4096.hip.h"
 
-#ifndef OTH_16K_NT
-#define OTH_16K_NT 1           // segments do not overlap: every sample is read once
-#endif
-#if OTH_16K_NT
-#define OTH_16K_LOAD(p) load_once(p)
-#else
-#define OTH_16K_LOAD(p) (*(p))
-#endif
+// Segments do not overlap, every sample is read once: the sample loads are non-temporal (load_once).
 
 namespace oth {
 namespace {
@@ -175,7 +168,7 @@ __global__ __launch_bounds__(256 * F) void welch16k_kernel(WelchArgs p) {
                     for (int j = 0; j < NJ; ++j)
 #pragma unroll
                         for (int a = 0; a < H; ++a) {
-                            keep[H * j + a] = OTH_16K_LOAD(xs + 4096 * a + T16 * j);
+                            keep[H * j + a] = load_once(xs + 4096 * a + T16 * j);
                             if (PILOT) keep[H * j + a] = csub(keep[H * j + a], pv);
                             sumf = cadd(sumf, keep[H * j + a]);
                         }
@@ -184,7 +177,7 @@ __global__ __launch_bounds__(256 * F) void welch16k_kernel(WelchArgs p) {
                 for (int j = 0; j < NJ; ++j)
 #pragma unroll
                     for (int a = 0; a < H; ++a) {
-                        float2 r = OTH_16K_LOAD(xs + 4096 * (H + a) + T16 * j);
+                        float2 r = load_once(xs + 4096 * (H + a) + T16 * j);
                         if (PILOT) r = csub(r, pv);
                         v[F * j + a] = keep[H * j + a];
                         v[F * j + H + a] = r;
@@ -196,7 +189,7 @@ __global__ __launch_bounds__(256 * F) void welch16k_kernel(WelchArgs p) {
                     if (s == sb) {
 #pragma unroll
                         for (int j = 0; j < 2; ++j) {
-                            keep[j] = OTH_16K_LOAD(xs + T16 * j);
+                            keep[j] = load_once(xs + T16 * j);
                             if (PILOT) keep[j] = csub(keep[j], pv);
                         }
                     }
@@ -208,7 +201,7 @@ __global__ __launch_bounds__(256 * F) void welch16k_kernel(WelchArgs p) {
                         if (PAD && (a != 0 || j >= 4)) v[F * j + a] = make_float2(0.f, 0.f);
                         else if (PADHALF && j < 2) v[F * j + a] = keep[j];
                         else {
-                            v[F * j + a] = OTH_16K_LOAD(xs + 4096 * a + T16 * j);
+                            v[F * j + a] = load_once(xs + 4096 * a + T16 * j);
                             if (PILOT) v[F * j + a] = csub(v[F * j + a], pv);      // (the padding zeros stay zeros)
                         }
                     }
@@ -390,7 +383,7 @@ __global__ __launch_bounds__(256 * F, 4) void chain16k_kernel(SegArgs p) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
-            for (int a = 0; a < F; ++a) d[F * j + a] = OTH_16K_LOAD(xs + 4096 * a + T16 * j);
+            for (int a = 0; a < F; ++a) d[F * j + a] = load_once(xs + 4096 * a + T16 * j);
     };
     float2 nxt[PREFETCH ? 16 : 1];
     bool primed = false;

@@ -33,39 +33,13 @@
 
 #include "fft16k.hip.h"
 
-#ifndef OTH_X1_PPLACES
-#define OTH_X1_PPLACES 0x22222222u     // the same for the pipelined kernel (places: see its `spread`)
-#endif
-#ifndef OTH_X1H_FAKEWIN
-#define OTH_X1H_FAKEWIN 0
-#endif
-#ifndef OTH_X1H_WIN_EARLY
-#define OTH_X1H_WIN_EARLY 0  // 50 %-overlap kernel, A/B: 1 = the window values of a step are requested at the end of the step before (no gain: 16384 points 0.3874-0.3907 against 0.3855-0.3876 ms, 8192 points 0.3694-0.3753 against 0.3789 ms on the builds without a pilot, and the PILOT builds then spill 16 registers)
-#endif
-#ifndef OTH_X1_DIAG
-#define OTH_X1_DIAG 0        // 1: per-wave phase cycle counters behind the partial sums (tools/archive/diag_x1.py)
-#endif
-#if OTH_X1_DIAG
-#define X1_STAMP(i)                                                      \
-    do {                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                               \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();    \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                              \
-        phase[i] += now_ - last_;                                        \
-        last_ = now_;                                                    \
-        __builtin_amdgcn_sched_barrier(0);                               \
-    } while (0)
-#define X1_DRAIN_VM() __builtin_amdgcn_s_waitcnt(0x0F70)
-#define X1_DRAIN_LGKM() __builtin_amdgcn_s_waitcnt(0xC07F)
-#else
-#define X1_STAMP(i) do { } while (0)
-#define X1_DRAIN_VM() do { } while (0)
-#define X1_DRAIN_LGKM() do { } while (0)
-#endif
 
 namespace oth {
 namespace {
 
+// how many of a segment's sixteen loads the pipelined kernel issues at each of the eight places of a step (one nibble
+// per place, see its `spread`): two at each
+constexpr unsigned X1_PPLACES = 0x22222222u;
 constexpr int X1_RED = 8;                      // chunk tickets (two slots, by chunk parity)
 // NW = waves per workgroup = N / 1024: 16 (N = 16384, one workgroup per CU) or 8 (N = 8192, two per CU; round 5)
 template <int NW = 16> constexpr size_t x1_lds_bytes() { return (NW * XREG + X1_RED) * sizeof(float2); }
@@ -228,10 +202,6 @@ __global__ __launch_bounds__(1024) void welch16k1x_kernel(WelchArgs p) {
     const int sched = p.sched;
     const long long nchunks = sched ? chunk_count(p) : 1;
     int par = 0;
-#if OTH_X1_DIAG
-    unsigned long long phase[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long last_ = __builtin_amdgcn_s_memtime();
-#endif
     for (long long cur = sched ? wg : 0; cur < nchunks;) {
         long long sb = s0, se = s1;
         if (sched) chunk_range(p, cur, sb, se);
@@ -245,27 +215,17 @@ __global__ __launch_bounds__(1024) void welch16k1x_kernel(WelchArgs p) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) v[r] = make_float2(v[r].x * win[r], v[r].y * win[r]);
             }
-            X1_STAMP(7);
-            X1_DRAIN_VM();
-            X1_STAMP(0);
             prio_compute();
             dft16(v);                                              // pass 1: r -> k0
             prio_latency();
-            X1_STAMP(1);
             lds_barrier();      // 1: every wave is through with the previous segment's exchanges (A reads, B in its region)
-            X1_STAMP(2);
             if (sched == 2 && s == sb && tid == 0) lnext[par] = (int)atomicAdd(p.queue + stream, 1u);
             scatter_pow16<XREG>(v, wa, a1, a4);                    // x W_N^(k0 tid) -> [k0][w][l]
-            X1_DRAIN_LGKM();
-            X1_STAMP(3);
             lds_barrier();      // 2
-            X1_STAMP(4);
             dft16_from_lds<64>(v, ra, [] { prio_compute(); });     // pass 2: w -> k1
             prio_latency();
             wave_lds_sync();
             scatter_pow16<XROW>(v, wb, b1, b4);                    // x W_1024^(k1 l) -> row k1, column l of this wave's region
-            X1_DRAIN_LGKM();
-            X1_STAMP(5);
             wave_lds_sync();
             dft16_from_lds<4>(v, rb, [] { prio_compute(); });      // pass 3: g -> k2
             twiddle_pow16_inplace(v, c1, c4);                      // x W_64^(k2 q)
@@ -275,7 +235,6 @@ __global__ __launch_bounds__(1024) void welch16k1x_kernel(WelchArgs p) {
                 const float2 X = v[r16(k2)];
                 acc[k2] = fmaf(X.x, X.x, fmaf(X.y, X.y, acc[k2]));
             }
-            X1_STAMP(6);
         }
         if (sched == 0) break;
         cur = (sched == 1) ? cur + W : (long long)W + lnext[par];
@@ -286,14 +245,6 @@ __global__ __launch_bounds__(1024) void welch16k1x_kernel(WelchArgs p) {
     float *dst = p.partial + ((size_t)stream * W + wg) * N + tid;
 #pragma unroll
     for (int k2 = 0; k2 < 16; ++k2) dst[1024 * k2] = acc[k2];
-#if OTH_X1_DIAG
-    if (l == 0) {
-        unsigned long long *st = reinterpret_cast<unsigned long long *>(p.partial + (size_t)p.nstreams * W * N) +
-                                 128 * ((size_t)stream * W + wg) + 8 * wv;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) st[i] = phase[i];
-    }
-#endif
 }
 
 }  // namespace
@@ -389,8 +340,8 @@ template <int STRIDE> __device__ __forceinline__ void lds_issue16(f2v (&r)[16], 
 #undef OTH_LDS_READ
 }
 
-// The software-pipelined form (the default).  Per-wave phase stamps of the plain loop above (tools/archive/diag_x1.py,
-// profiles/r04_x1_phases.txt) showed the two halves of a segment badly matched: between barrier 1 and barrier 2 every
+// The software-pipelined form (the default).  Per-wave phase stamps of the plain loop above
+// (profiles/r04_x1_phases.txt) showed the two halves of a segment badly matched: between barrier 1 and barrier 2 every
 // wave only multiplies by the pass-1 twiddles and writes exchange A - the CU's LDS store path is the limit (16 waves x
 // 16 ds_write_b64) and the SIMDs idle - while everything else (passes 2, 3, 4, the accumulation, the next pass 1)
 // queues up between barrier 2 and barrier 1, where the four waves of a SIMD take turns oldest first (they reach
@@ -419,7 +370,7 @@ struct X1Sched {
 // + 4096 bitrev2(q) of thread (wave k0, lane 4 k1 + q), times 1, -1, -1 or i); the first call has s = -1 and zeros.
 template <int NW, bool WINDOW, class Epi>
 __device__ __forceinline__ void x1_pipe_body(const float2 *xb, long long step, const X1Sched &sc, int wg, int W, const float *win,
-                                             const float2 *tw, float2 *lds, Epi &epi, unsigned long long *diag_out) {
+                                             const float2 *tw, float2 *lds, Epi &epi) {
     int *lnext = reinterpret_cast<int *>(lds + NW * XREG);
     const int tid = threadIdx.x;
     const int wv = tid >> 6, l = tid & 63, g = l >> 2, q = l & 3;
@@ -459,10 +410,6 @@ __device__ __forceinline__ void x1_pipe_body(const float2 *xb, long long step, c
     bool live = sched ? cur < nchunks : s0 < s1;
     int s = sb, sp = -1;            // this segment, the one before (whose tail runs in this step)
     int par = 0;
-#if OTH_X1_DIAG
-    unsigned long long phase[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long last_ = __builtin_amdgcn_s_memtime();
-#endif
     f2v pfr[16];      // the next segment's samples as the pinned loads deliver them (valid behind the vmcnt wait)
     f2v rB[16];       // exchange-B values of the segment before; zeros in front of the first one
 #pragma unroll
@@ -502,19 +449,13 @@ __device__ __forceinline__ void x1_pipe_body(const float2 *xb, long long step, c
 #pragma unroll
             for (int r = 0; r < 16; ++r) pf[r] = make_float2(pf[r].x * wv16[r], pf[r].y * wv16[r]);
         }
-        X1_STAMP(7);
-        X1_DRAIN_VM();
-        X1_STAMP(0);
         prio_compute();
         dft16(pf);                                             // P1
         prio_latency();
-        X1_STAMP(1);
         lds_barrier_arrived16(rB);      // 1 (also waits for this wave's exchange-B reads of the segment before: rB valid)
-        X1_STAMP(2);
         const bool first_of_chunk = s == sb;
         if (sched == 2 && first_of_chunk && tid == 0) lnext[par] = (int)atomicAdd(sc.queue, 1u);
         twiddle6_exa<NW>(pf, wa, a6);                          // WA
-        X1_STAMP(3);
         // The segment after this one: its loads go out two at a time over the whole step.  A ticket (dynamic schedule)
         // is drawn with a chunk's FIRST segment and published before barrier 2 of that segment, so at the chunk's last
         // segment it is known here - the launcher never makes one-segment chunks except the very last one of a stream,
@@ -542,9 +483,9 @@ __device__ __forceinline__ void x1_pipe_body(const float2 *xb, long long step, c
         auto spread = [&](auto gc) {
             // place grp of the step (0: after the exchange-A writes, 1: after the tail's butterflies, 2: after its
             // twiddles, 3: end of the tail, 4: behind barrier 2, 5: between pass 2's layers, 6: after pass 2, 7: after
-            // the exchange-B writes) issues nibble grp of OTH_X1_PPLACES of the next segment's sixteen loads
+            // the exchange-B writes) issues nibble grp of X1_PPLACES of the next segment's sixteen loads
             constexpr int grp = decltype(gc)::value;
-            constexpr unsigned plan = OTH_X1_PPLACES;
+            constexpr unsigned plan = X1_PPLACES;
             static_assert(((plan >> 0) & 15) + ((plan >> 4) & 15) + ((plan >> 8) & 15) + ((plan >> 12) & 15) + ((plan >> 16) & 15) +
                               ((plan >> 20) & 15) + ((plan >> 24) & 15) + ((plan >> 28) & 15) == 16,
                           "the eight places must issue exactly the sixteen rows of a segment");
@@ -564,9 +505,7 @@ __device__ __forceinline__ void x1_pipe_body(const float2 *xb, long long step, c
         tail([&] { spread(integral_constant<int, 1>{}); }, [&] { spread(integral_constant<int, 2>{}); });      // T3
         spread(integral_constant<int, 3>{});
         prio_latency();
-        X1_STAMP(4);
         lds_barrier();      // 2
-        X1_STAMP(5);
         spread(integral_constant<int, 4>{});
         {                                                      // RA
             float2 v[16];
@@ -583,7 +522,6 @@ __device__ __forceinline__ void x1_pipe_body(const float2 *xb, long long step, c
             wave_lds_sync();
             lds_issue16<4>(rB, rb);
         }
-        X1_STAMP(6);
         have_prev = true;
         live = more;
         sp = s;
@@ -594,12 +532,6 @@ __device__ __forceinline__ void x1_pipe_body(const float2 *xb, long long step, c
         lds_arrived16(rB);
         tail([] {}, [] {});
     }
-#if OTH_X1_DIAG
-    if (l == 0 && diag_out) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) diag_out[8 * wv + i] = phase[i];
-    }
-#endif
 }
 
 // Welch average: sum of |X|^2 per bin; partial rows in finalize layout 4
@@ -624,11 +556,7 @@ __global__ __launch_bounds__(64 * NW, 4) void welch16k1x_pipe_kernel(WelchArgs p
 #pragma unroll
     for (int k = 0; k < 16; ++k) epi.acc[k] = 0.f;
     const X1Sched sc{(int)p.nseg, (int)p.nbig, p.chunk, p.tail_chunk, p.sched, p.queue ? p.queue + stream : nullptr};
-    unsigned long long *diag = nullptr;
-#if OTH_X1_DIAG
-    diag = reinterpret_cast<unsigned long long *>(p.partial + (size_t)p.nstreams * W * N) + 128 * ((size_t)stream * W + wg);
-#endif
-    x1_pipe_body<NW, WINDOW>(p.x + (size_t)stream * p.stream_stride, p.step, sc, wg, W, p.win, p.tw, lds, epi, diag);
+    x1_pipe_body<NW, WINDOW>(p.x + (size_t)stream * p.stream_stride, p.step, sc, wg, W, p.win, p.tw, lds, epi);
     float *dst = p.partial + ((size_t)stream * W + wg) * N + threadIdx.x;
 #pragma unroll
     for (int k2 = 0; k2 < 16; ++k2) dst[64 * NW * k2] = epi.acc[k2];      // finalize layout 4 (16384) / 5 (8192)
@@ -751,7 +679,7 @@ __global__ __launch_bounds__(64 * NW, 4) void chain16k1x_kernel(SegArgs p) {
     epi.halves = NW == 8;
     epi.row_base = (size_t)stream * (size_t)(p.nseg - p.store_from);
     const X1Sched sc{(int)p.nseg, (int)p.nbig, p.chunk, p.tail_chunk, p.sched, p.queue ? p.queue + stream : nullptr};
-    x1_pipe_body<NW, WINDOW>(p.x + (size_t)stream * p.stream_stride + p.first, p.step, sc, wg, W, p.win, p.tw, lds, epi, nullptr);
+    x1_pipe_body<NW, WINDOW>(p.x + (size_t)stream * p.stream_stride + p.first, p.step, sc, wg, W, p.win, p.tw, lds, epi);
     if (p.partial) {
         float *dst = p.partial + ((size_t)stream * W + wg) * N + tid;
 #pragma unroll
@@ -866,41 +794,23 @@ __global__ __launch_bounds__(64 * NW, 4) void welch16k1x_half_kernel(WelchArgs p
             for (int r = 0; r < 8; ++r) load_row_nt(nxt[r], voff, x0 + 512 * NW * (8 + r));
             vm_arrive8(keep, first);      // (nxt has landed as well; the step below says so where it takes it)
         }
-#if OTH_X1H_WIN_EARLY      // A/B (no gain, see the macro): the window values of a step requested at the END of the step before
-        float wv16[16];
-        auto request_window = [&]() {
-            const char *wbase = reinterpret_cast<const char *>(p.win);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) load_win(wv16[r], 4u * tid, wbase + 256 * NW * r);
-        };
-        request_window();
-#endif
         for (long long s = sb; s < se; ++s) {
             float2 v[16];
             prio_latency();
-#if !OTH_X1H_WIN_EARLY
+            // tried: the window values requested at the end of the step before: no gain (16384 points 0.3874-0.3907 against
+            // 0.3855-0.3876 ms), and the PILOT builds then spill 16 registers
             float wv16[16];      // (declared per step: held across the loop edge they cost the PILOT builds 17 spilled registers)
-#if OTH_X1H_FAKEWIN      // timing experiment only (wrong values): what the window loads and their wait cost
-            float ax = a1.x, ay = a1.y;
-            asm volatile("" : "+v"(ax), "+v"(ay));      // (not loop-invariant to the compiler: no sixteen hoisted registers)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) wv16[r] = fmaf(ax, 0.03f * (float)r, 0.5f - ay * 0.01f * (float)r);
-#else
             {
                 const char *wbase = reinterpret_cast<const char *>(p.win);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) load_win(wv16[r], 4u * tid, wbase + 256 * NW * r);
             }
-#endif
-#endif
             // the new half (requested during the step before, or above) and the window values: the new half comes out of
             // its loading registers in the same statement that waits for it (vm_arrive8: it outlives the next loads into
             // them as the kept half, and a copy the compiler makes for that may not stand in front of the wait)
             float2 fresh[8];
             vm_arrive8(fresh, nxt);
-#if !OTH_X1H_FAKEWIN
             vm_arrived_win16(wv16);
-#endif
             float2 sum = make_float2(0.f, 0.f), sumf = make_float2(0.f, 0.f);
             if (s == sb) {      // the chunk's first half arrives raw
 #pragma unroll
@@ -971,9 +881,6 @@ __global__ __launch_bounds__(64 * NW, 4) void welch16k1x_half_kernel(WelchArgs p
             twiddle_table16<4, 1, false>(v, nullptr, tabC + q, tc);
             prefetch(6);
             quad_dft4_dpp(v, qk.x, qk.y, qk.z, qk.w);              // pass 4
-#if OTH_X1H_WIN_EARLY
-            request_window();      // (in front of the quad butterfly the PILOT builds spilled the kept half: 20 registers)
-#endif
             if (DET == 2) {
                 // X[k] -= mean FFT(w)[k] where FFT(w) is not negligible: register k2 = 0 of lanes (k1 = 0, q = 0) and k2 = 15
                 // of lanes (k1 = 15, q = 3) - lanes 0 and 63 of every wave; their table entries come from L2 when they are

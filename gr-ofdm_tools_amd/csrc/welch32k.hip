@@ -42,24 +42,6 @@ namespace oth {
 namespace {
 
 constexpr int W32_M = 16384, W32_N = 32768;
-// -DW32_DIAG=1 (make EXP=1 EXTRA=-DW32_DIAG=1; tools/w32_phases.py): cycle counts of eight phases of a step per wave, written
-// behind the partial rows (1 KiB per workgroup)
-#ifndef W32_DIAG
-#define W32_DIAG 0
-#endif
-#if W32_DIAG
-#define W32_STAMP(i)                                                     \
-    do {                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                               \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();    \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                              \
-        phase[i] += now_ - last_;                                        \
-        last_ = now_;                                                    \
-        __builtin_amdgcn_sched_barrier(0);                               \
-    } while (0)
-#else
-#define W32_STAMP(i) do { } while (0)
-#endif
 // LDS behind the sixteen exchange regions: the waves' sample totals and the twiddle seeds - W_32768^tid of every thread
 // (radix-2 step and, squared, pass 1), W_65536^tid (the front step of the 65536-point form), W and W^4 of passes 2 and 3 per
 // lane (W_1024^l, W_64^q) - so that the transforms wait for no vector-memory load.  Each pass rebuilds its other powers from
@@ -232,14 +214,10 @@ __global__ __launch_bounds__(1024) void welch32k_kernel(W32kArgs p) {
     float accA[16], accB[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) accA[k] = accB[k] = 0.f;
-#if W32_DIAG
-    unsigned long long phase[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long last_ = __builtin_amdgcn_s_memtime();
-#endif
 
     // one 16384-point transform of v (in place: thread (w, l) holds n = tid + 1024 r) added to acc; `handover`: a workgroup
     // barrier in front of the exchange-A writes (every wave through with the reads of the transform before)
-    auto transform = [&](float2 (&v)[16], float (&acc)[16], bool handover, int ph) {
+    auto transform = [&](float2 (&v)[16], float (&acc)[16], bool handover) {
         const int t = opaque(tid), wv = t >> 6, l = t & 63, g = l >> 2, q = l & 3;
         float2 *wa = lds + t;                                // exchange A write: + XREG k0 (k0 < 8), wa8 + XREG (k0 - 8)
         float2 *wa8 = wa + opaque(8 * XREG);                 // (a VALUE the compiler cannot fold; the pointer stays an LDS pointer)
@@ -249,14 +227,12 @@ __global__ __launch_bounds__(1024) void welch32k_kernel(W32kArgs p) {
         prio_compute();
         dft16(v);                                              // pass 1: r -> k0
         prio_latency();
-        W32_STAMP(ph);
         if (handover) lds_barrier();
         {
             const float2 d = dtab[t], a1 = cmul(d, d), a2 = cmul(a1, a1);      // W_M^tid = (W_N^tid)^2 and its fourth power
             scatter_pow16_exa(v, wa, wa8, a1, cmul(a2, a2));                   // x W_M^(k0 tid) -> [k0][w][l]
         }
         lds_barrier();
-        W32_STAMP(ph + 1);
         dft16_from_lds<64>(v, ra, [] { prio_compute(); });     // pass 2: w -> k1
         prio_latency();
         wave_lds_sync();
@@ -279,7 +255,6 @@ __global__ __launch_bounds__(1024) void welch32k_kernel(W32kArgs p) {
             const float2 X = v[r16(k2)];
             acc[k2] = fmaf(X.x, X.x, fmaf(X.y, X.y, acc[k2]));
         }
-        W32_STAMP(ph + 2);
     };
 
     // The segment loop, specialised on the half a FRONT workgroup takes (a run-time branch around the odd half's twiddle inside the
@@ -287,7 +262,7 @@ __global__ __launch_bounds__(1024) void welch32k_kernel(W32kArgs p) {
     auto run = [&](auto half_) {
     constexpr int H = decltype(half_)::value;
     // (!FRONT) The second half of a segment - rows x[n + M] - is requested one transform ahead: while the second transform of
-    // the step before runs, the registers of its first transform's data are free.  The phase stamps (tools/w32_phases.py)
+    // the step before runs, the registers of its first transform's data are free.  Per-wave phase stamps (NOTES, round 6)
     // showed 40 % of a step between the first load and the mean's barrier with all 32 rows requested at the top.
     f2v pre[16];
     auto prefetch = [&](long long s2) {
@@ -315,7 +290,6 @@ __global__ __launch_bounds__(1024) void welch32k_kernel(W32kArgs p) {
             for (int r = 0; r < 16; ++r) load_row8(la[r], ut8, xs + 1024 * r);
             vm_arrived16(la);
             vm_arrived16(pre);
-            W32_STAMP(0);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 va[r] = make_float2(la[r].x, la[r].y);
@@ -360,7 +334,6 @@ __global__ __launch_bounds__(1024) void welch32k_kernel(W32kArgs p) {
             ty *= 1.0 / W32_N;
             mhi = make_float2((float)tx, (float)ty);
             mlo = make_float2((float)(tx - (double)mhi.x), (float)(ty - (double)mhi.y));
-            W32_STAMP(1);
         } else {
             win_issue(0);
             win_issue(1);
@@ -538,24 +511,14 @@ __global__ __launch_bounds__(1024) void welch32k_kernel(W32kArgs p) {
                 vb[r] = cmul(csub(y0, y1), cmul(d1, make_float2(W32_RE[r], W32_IM[r])));
             }
         }
-        W32_STAMP(2);
-        transform(va, accA, !DETREND, 3);
+        transform(va, accA, !DETREND);
         if (!FRONT) prefetch(s + W < p.nseg ? s + W : s);      // (no branch: the last step asks for its own rows again)
-        transform(vb, accB, true, 5);
+        transform(vb, accB, true);
     }
     };
     if (FRONT && h) run(std::integral_constant<int, 1>{});
     else run(std::integral_constant<int, 0>{});
 
-#if W32_DIAG
-    if ((threadIdx.x & 63) == 0) {      // phases: 0 loads, 1 sums + mean barrier, 2 window + radix 2, 3 pass 1 a, 4 exch A + barrier a, 5 rest of a,
-                                        // (5 also: pass 1 b), 6 handover barrier + exch A + barrier b, 7 rest of b
-        unsigned long long *st = reinterpret_cast<unsigned long long *>(p.partial + (size_t)W * (FRONT ? 2 * W32_N : W32_N)) +
-                                 128 * (size_t)b + 8 * (threadIdx.x >> 6);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) st[i] = phase[i];
-    }
-#endif
     // FRONT: row `slot` of [W][65536], half h; position p of that half holds bin 2 (layout-7 bin of p) + h (finalize layout 8)
     float *dst = p.partial + (FRONT ? (size_t)slot * (2 * W32_N) + (size_t)h * W32_N : (size_t)b * W32_N) + tid;
 #pragma unroll

@@ -46,9 +46,6 @@
 #ifndef OTH_W4096_PIPE
 #define OTH_W4096_PIPE 0     // 1: 50 %-overlap pipeline - the overlapped half stays in registers, the next
 #endif                       //    half is prefetched, pass-1 twiddles are rebuilt from two powers (needs step 2048)
-#ifndef OTH_W4096_DIAG
-#define OTH_W4096_DIAG 0     // 1: diagnostic build, every workgroup stamps start/end time + XCC id
-#endif
 #define OTH_CAT2(a, b) a##b
 #define OTH_CAT(a, b) OTH_CAT2(a, b)
 
@@ -57,20 +54,6 @@
 namespace oth {
 
 namespace {
-
-#if OTH_W4096_DIAG
-#define OTH_STAMP(i)                                                     \
-    do {                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                               \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();    \
-        __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0): s_memtime */  \
-        phase[i] += now_ - last_;                                        \
-        last_ = now_;                                                    \
-        __builtin_amdgcn_sched_barrier(0);                               \
-    } while (0)
-#else
-#define OTH_STAMP(i)
-#endif
 
 // NA = nperseg / 256: rows a < NA of a segment hold samples, the rest is the zero padding up to 4096
 // (NA = 16: nperseg = nfft; NA = 4: the sweeper's nperseg = nfft / 4, spectrum_sweeper.py:263).
@@ -84,11 +67,6 @@ __global__ __launch_bounds__(T4, OTH_W4096_PIPE ? 4 : 1) void welch4096_kernel(W
     const int t = threadIdx.x;
     const int hi = t >> 4, lo = t & 15;
     const int wg = blockIdx.x, W = p.wg_per_stream, stream = blockIdx.y;
-#if OTH_W4096_DIAG
-    const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
-    unsigned long long phase[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long last_ = __builtin_amdgcn_s_memtime();
-#endif
     const long long s0 = (p.nseg * wg) / W, s1 = (p.nseg * (wg + 1)) / W;
     const float2 *xb = p.x + (size_t)stream * p.stream_stride;
 
@@ -153,11 +131,6 @@ __global__ __launch_bounds__(T4, OTH_W4096_PIPE ? 4 : 1) void welch4096_kernel(W
       for (long long s = sb; s < se; ++s) {
         float2 v[16];
         prio_latency();
-        OTH_STAMP(5);       // loop overhead / chunk prologue
-#if OTH_W4096_DIAG && OTH_W4096_PIPE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // diagnostic only: isolate the wait for the prefetch
-        OTH_STAMP(6);
-#endif
 #if OTH_W4096_PIPE
 #pragma unroll
         for (int a = 0; a < 8; ++a) {
@@ -210,9 +183,7 @@ __global__ __launch_bounds__(T4, OTH_W4096_PIPE ? 4 : 1) void welch4096_kernel(W
             if ((t & 63) == 0) red[t >> 6] = sum;
         }
 #endif
-        OTH_STAMP(0);       // loads issued, sums reduced
         lds_barrier();     // A: previous segment's LDS reads are done; red[] visible
-        OTH_STAMP(1);       // wait at barrier A
         prio_compute();
         if (sched == 2 && t == 0) {
             // draw the next chunk while this one is being transformed; publish it in the last segment
@@ -254,44 +225,22 @@ __global__ __launch_bounds__(T4, OTH_W4096_PIPE ? 4 : 1) void welch4096_kernel(W
 #pragma unroll
         for (int k0 = 1; k0 < 16; ++k0) lx[k0 * RS + w1] = cmul(v[r16(k0)], tw1[k0]);
 #endif
-        OTH_STAMP(2);       // detrend, window, pass 1, exchange-1 writes
         lds_barrier();     // B
-        OTH_STAMP(3);       // wait at barrier B
 
         // pass 2: thread (k0,c) gathers b, DFT over b, twiddle W256^(k1 c)
-#if OTH_W4096_DIAG
-#pragma unroll
-        for (int b = 0; b < 16; ++b) v[b] = lx[r1 + b * 17];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        OTH_STAMP(7);       // exchange-1 reads landed
-        prio_compute();
-        dft16(v);
-#else
         dft16_from_lds<17>(v, lx + r1, [] { prio_compute(); });      // ordered reads, counted waits (fft4096.hip.h)
-#endif
         prio_latency();
         wave_lds_sync();   // the 16 lanes of this k0 have all read region k0
         scatter_pow16<17>(v, lx + w2, c1, c4);
         wave_lds_sync();
-        OTH_STAMP(8);       // second butterfly, W256 twiddles, exchange-2 writes issued
 
         // pass 3: thread (k0,k1) gathers c, DFT over c, accumulate |X|^2
-#if OTH_W4096_DIAG
-#pragma unroll
-        for (int c = 0; c < 16; ++c) v[c] = lx[r2 + c];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        OTH_STAMP(9);       // exchange-2 writes + reads landed
-        prio_compute();
-        dft16(v);
-#else
         dft16_from_lds<1>(v, lx + r2, [] { prio_compute(); });
-#endif
 #pragma unroll
         for (int k2 = 0; k2 < 16; ++k2) {
             const float2 X = v[r16(k2)];
             acc[k2] = fmaf(X.x, X.x, fmaf(X.y, X.y, acc[k2]));
         }
-        OTH_STAMP(4);       // passes 2 and 3
       }
       if (sched == 0) break;
       cur = (sched == 1) ? cur + W : (long long)W + *lnext;   // *lnext was written before barrier B
@@ -301,22 +250,6 @@ __global__ __launch_bounds__(T4, OTH_W4096_PIPE ? 4 : 1) void welch4096_kernel(W
     float *dst = p.partial + ((size_t)stream * W + wg) * 4096;
 #pragma unroll
     for (int k2 = 0; k2 < 16; ++k2) dst[256 * k2 + t] = acc[k2];
-#if OTH_W4096_DIAG
-    if (t == 0) {   // stamps live behind the partial sums, in memory nothing else reads
-        unsigned long long *dbg =
-            reinterpret_cast<unsigned long long *>(p.partial + (size_t)p.nstreams * W * 4096) + 4 * ((size_t)stream * W + wg);
-        dbg[0] = t_start;
-        dbg[1] = __builtin_amdgcn_s_memrealtime();
-        dbg[2] = __builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20);   // HW_REG_XCC_ID, bits [3:0]
-        dbg[3] = (unsigned long long)(s1 - s0);
-    }
-    if ((t & 63) == 0) {   // per-wave phase cycle sums, 12 x u64 per wave behind the 32-byte records
-        unsigned long long *ph = reinterpret_cast<unsigned long long *>(p.partial + (size_t)p.nstreams * W * 4096) +
-                                 4 * (size_t)p.nstreams * W + 12 * (((size_t)stream * W + wg) * 4 + (t >> 6));
-#pragma unroll
-        for (int i = 0; i < 12; ++i) ph[i] = phase[i];
-    }
-#endif
 }
 
 }  // namespace

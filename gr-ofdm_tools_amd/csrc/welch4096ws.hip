@@ -21,54 +21,14 @@
 // barrier pass 2 of image[it & 1] (its LDS reads in one batch with the item word), then, once the item word
 // says it is a segment, exchange 2, pass 3 and the accumulation.  The consumer is the critical path (443
 // VALU instructions per step against the producer's 336): its butterflies run at a higher wave priority.
-#ifndef OTH_WS_TAG
-#define OTH_WS_TAG ws
-#endif
 // The samples are read once (a chunk's first half twice, by two workgroups far apart in time): non-temporal
-// loads keep them from displacing the twiddle / window tables and the partial sums in L2 (-1.4 % kernel time).
-#ifndef OTH_WS_NT_LOADS
-#define OTH_WS_NT_LOADS 1
-#endif
-#if OTH_WS_NT_LOADS
-#define OTH_WS_LOAD(p) load_once(p)
-#else
-#define OTH_WS_LOAD(p) (*(p))
-#endif
-#if OTH_WS_NT_LOADS > 1
-#define OTH_WS_LOAD_HEAD(p) load_once(p)
-#else
-#define OTH_WS_LOAD_HEAD(p) (*(p))
-#endif
-// 1: the producer keeps six pass-1 twiddle powers (W^1,2,3,4,8,12: nine products per segment instead of thirteen) and
+// loads (load_once) keep them from displacing the twiddle / window tables and the partial sums in L2 (-1.4 % kernel
+// time); the first half of a chunk's head, which a second workgroup reads again, stays a plain load.
+// The producer keeps six pass-1 twiddle powers (W^1,2,3,4,8,12: nine products per segment instead of thirteen) and
 // pays for their eight registers by reading the second half of its window values from an 8 KiB LDS table per step
 // (same-box A/B, five interleaved runs each: 0.5855 against 0.5906 ms = -0.9 %, profiles/r03_ab_headline_pow6.txt)
-#ifndef OTH_WS_POW6
-#define OTH_WS_POW6 1
-#endif
-#ifndef OTH_WS_SPREAD
-#define OTH_WS_SPREAD 0      // A/B: 2 = four loads before and four after the producer's butterfly; 3 = 2 + 4 + 2 (after the exchange writes)
-#endif
-#ifndef OTH_WS_DIAG
-#define OTH_WS_DIAG 0        // 1: per-wave phase cycle counters behind the partial sums (tools/archive/diag_ws.py)
-#endif
-// wave priorities: producer latency sections / butterflies, consumer latency sections / butterflies
-#ifndef OTH_WS_PAL
-#define OTH_WS_PAL 2
-#endif
-#ifndef OTH_WS_PAC
-#define OTH_WS_PAC 0
-#endif
-#ifndef OTH_WS_PAS           // producer: twiddles + exchange-1 writes
-#define OTH_WS_PAS OTH_WS_PAL
-#endif
-#ifndef OTH_WS_PBL
-#define OTH_WS_PBL 2
-#endif
-#ifndef OTH_WS_PBC
-#define OTH_WS_PBC 1         // the consumer is the critical path: its butterflies go ahead of the producer's (-4.5 %)
-#endif
-#define OTH_CAT2(a, b) a##b
-#define OTH_CAT(a, b) OTH_CAT2(a, b)
+// tried: the eight loads of a step spread over 2 / 3 places instead of one burst, no gain (NOTES 8,
+// profiles/r05_ab_headline_spread_loads.txt)
 
 #include <type_traits>
 #include "fft4096.hip.h"
@@ -76,25 +36,16 @@
 namespace oth {
 namespace {
 
-#if OTH_WS_DIAG
-#define WS_STAMP(i)                                                      \
-    do {                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                               \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();    \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                              \
-        phase[i] += now_ - last_;                                        \
-        last_ = now_;                                                    \
-        __builtin_amdgcn_sched_barrier(0);                               \
-    } while (0)
-#else
-#define WS_STAMP(i)
-#endif
-
 constexpr int TWS = 512;
 constexpr int WS_RED = 32;                 // float2: per image the four producer waves' segment sums (8 slots each)
 constexpr int WS_CTRL = 16;                // ints: item kind per image [0..1], next-chunk ticket [4]
-constexpr size_t WS_WIN_BYTES = OTH_WS_POW6 ? 256 * 2 * sizeof(float4) : 0;      // window values 8..15 of every producer thread
+constexpr size_t WS_WIN_BYTES = 256 * 2 * sizeof(float4);      // window values 8..15 of every producer thread
 constexpr size_t WS_LDS_BYTES = (2 * LDS_X + WS_RED) * sizeof(float2) + WS_CTRL * sizeof(int) + WS_WIN_BYTES;
+
+// wave priorities: producer latency sections / butterflies / twiddles + exchange-1 writes, consumer latency sections /
+// butterflies
+constexpr int WS_PAL = 2, WS_PAC = 0, WS_PAS = WS_PAL, WS_PBL = 2;
+constexpr int WS_PBC = 1;                  // the consumer is the critical path: its butterflies go ahead of the producer's (-4.5 %)
 
 enum { ITEM_STOP = 0, ITEM_DATA = 1, ITEM_BUBBLE = 2 };
 
@@ -119,15 +70,10 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
 
     // LDS addresses inside an image (float2): exchange-1 write/read, exchange-2 write/read
     const int w1 = hi * 17 + lo, r1 = hi * RS + lo, w2 = hi * RS + lo, r2 = hi * RS + lo * 17;
-#if OTH_WS_DIAG
-    unsigned long long phase[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long last_ = __builtin_amdgcn_s_memtime();
-#endif
 
     if (producer) {
         // ------------------------------------------------------------------ producer
-        float win[OTH_WS_POW6 ? 8 : 16];
-#if OTH_WS_POW6
+        float win[8];
         float4 *wl = reinterpret_cast<float4 *>(ctrl + WS_CTRL) + t;      // [2][256] float4: win[8..11], win[12..15]
 #pragma unroll
         for (int a = 0; a < 8; ++a) win[a] = p.win[256 * a + t];
@@ -135,13 +81,6 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
         wl[256] = make_float4(p.win[256 * 12 + t], p.win[256 * 13 + t], p.win[256 * 14 + t], p.win[256 * 15 + t]);
         const float2 b1 = p.tw[t], b2 = p.tw[2 * t], b3 = p.tw[3 * t], b4 = p.tw[4 * t], b8 = p.tw[8 * t],
                      b12 = p.tw[(12 * t) & 4095];
-#else
-#pragma unroll
-        for (int a = 0; a < 16; ++a) win[a] = p.win[256 * a + t];
-        // pass-1 twiddle seeds W4096^t, W4096^(4t): the fifteen twiddles are multiplied out per segment (keeping
-        // even W^2, W^3, W^8, W^12 in registers as well spills at the 128-VGPR cap)
-        const float2 b1 = p.tw[t], b4 = p.tw[4 * t];
-#endif
         float2 kw[8], nxt[8];
         float2 prev_new = make_float2(0.f, 0.f);     // this wave's sum of the previous segment's new half
         // PILOT (every detrending plan but OTH_DETREND_CONSTANT_FAST): WelchArgs.pilot comes off every sample as it arrives, so the transform and
@@ -166,20 +105,19 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {      // one scalar base per pair of rows: offsets t and t + 256 (immediate)
                 const float2 *xj = xs + 512 * j;
-                kw[2 * j] = OTH_WS_LOAD_HEAD(xj + (unsigned)t);      // raw: the chunk's first item windows them in place
-                kw[2 * j + 1] = OTH_WS_LOAD_HEAD(xj + ((unsigned)t + 256u));
+                kw[2 * j] = *(xj + (unsigned)t);      // raw: the chunk's first item windows them in place
+                kw[2 * j + 1] = *(xj + ((unsigned)t + 256u));
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float2 *xj = xs + 2048 + 512 * j;
-                nxt[2 * j] = OTH_WS_LOAD(xj + (unsigned)t);
-                nxt[2 * j + 1] = OTH_WS_LOAD(xj + ((unsigned)t + 256u));
+                nxt[2 * j] = load_once(xj + (unsigned)t);
+                nxt[2 * j + 1] = load_once(xj + ((unsigned)t + 256u));
             }
         };
         auto step_end = [&](int item) {
             if (t == 0) ctrl[it & 1] = item;
             lds_barrier();
-            WS_STAMP(4);
             ++it;
         };
         // One segment: image (it & 1).  Every flavour leaves the same state behind - kw = windowed first half of the
@@ -190,20 +128,11 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
             constexpr int MODE = decltype(mode_)::value;
             const int q = it & 1;
             float2 *lx = img + q * LDS_X;
-            __builtin_amdgcn_s_setprio(OTH_WS_PAL);
+            __builtin_amdgcn_s_setprio(WS_PAL);
             float2 v[16];
-#if OTH_WS_DIAG
-            WS_STAMP(5);
-            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-            WS_STAMP(0);
-#endif
             float2 sumf = make_float2(0.f, 0.f), sum = make_float2(0.f, 0.f);
-#if OTH_WS_POW6
             const float4 wa = wl[0], wb = wl[256];      // own slots: no barrier needed
             const float wh[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};      // window values 8..15, this step only
-#else
-            const float *wh = win + 8;
-#endif
             if (FIRST) {
 #pragma unroll
                 for (int a = 0; a < 8; ++a) {      // kw still holds the raw first half of the chunk's first segment
@@ -227,22 +156,17 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
                 if (publish) ctrl[4] = (int)ticket;
             }
             const float2 *xn = xb + (size_t)uni(s + 2) * 2048;      // (MODE 0 only)
-            auto load_pairs = [&](int j0, int j1) {
+            // one burst of eight loads (kept as a lambda: written in line the same loads are scheduled differently)
+            auto load_next = [&]() {
 #pragma unroll
-                for (int j = j0; j < j1; ++j) {
+                for (int j = 0; j < 4; ++j) {
                     const float2 *xj = xn + 512 * j;
-                    nxt[2 * j] = OTH_WS_LOAD(xj + (unsigned)t);
-                    nxt[2 * j + 1] = OTH_WS_LOAD(xj + ((unsigned)t + 256u));
+                    nxt[2 * j] = load_once(xj + (unsigned)t);
+                    nxt[2 * j + 1] = load_once(xj + ((unsigned)t + 256u));
                 }
             };
             if (MODE == 0) {
-#if OTH_WS_SPREAD      // A/B (round 5): the eight loads of a step at two / three places instead of one burst
-                __builtin_amdgcn_sched_barrier(0);
-                load_pairs(0, OTH_WS_SPREAD == 2 ? 2 : 1);
-                __builtin_amdgcn_sched_barrier(0);
-#else
-                load_pairs(0, 4);
-#endif
+                load_next();
             } else if (MODE == 1) {
                 load_chunk_head(nsb);
             }
@@ -254,34 +178,10 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
                 if ((t & 63) == 63) red[q * 8 + wave] = cadd(sum, other);
                 prev_new = sum;
             }
-            WS_STAMP(1);
-            __builtin_amdgcn_s_setprio(OTH_WS_PAC);
+            __builtin_amdgcn_s_setprio(WS_PAC);
             dft16(v);
-            WS_STAMP(2);
-            __builtin_amdgcn_s_setprio(OTH_WS_PAS);
-#if OTH_WS_SPREAD
-            if (MODE == 0) {
-                __builtin_amdgcn_sched_barrier(0);
-                load_pairs(OTH_WS_SPREAD == 2 ? 2 : 1, OTH_WS_SPREAD == 2 ? 4 : 3);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#endif
-#if OTH_WS_POW6
+            __builtin_amdgcn_s_setprio(WS_PAS);
             scatter_pow16_six<RS>(v, lx + w1, b1, b2, b3, b4, b8, b12);
-#else
-            scatter_pow16<RS>(v, lx + w1, b1, b4);
-#endif
-#if OTH_WS_DIAG
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            WS_STAMP(3);
-#endif
-#if OTH_WS_SPREAD == 3
-            if (MODE == 0) {
-                __builtin_amdgcn_sched_barrier(0);
-                load_pairs(3, 4);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#endif
             step_end(ITEM_DATA);
         };
 
@@ -376,9 +276,8 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
         // barrier of step `it`, then what the producer left in image it & 1: the item kind and, in the same batch
         // of LDS reads (harmless when it is not a segment), the exchange-1 reads and the per-wave sums
         auto next_item = [&]() -> int {
-            __builtin_amdgcn_s_setprio(OTH_WS_PBL);
+            __builtin_amdgcn_s_setprio(WS_PBL);
             lds_barrier();
-            WS_STAMP(4);
             const int q = it & 1;
             const float2 *lq = img + q * LDS_X;
             // one batch of LDS reads: the item word and the four per-wave sums (used only after the butterfly, so
@@ -386,7 +285,7 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
             // Pass 2 therefore runs before the item word is looked at - on junk in an idle step and in the last.
             const int kind = ctrl[q];
             const float2 h0 = red[q * 8], h1 = red[q * 8 + 1], h2 = red[q * 8 + 2], h3 = red[q * 8 + 3];
-            dft16_from_lds<17>(v, lq + r1, [] { __builtin_amdgcn_s_setprio(OTH_WS_PBC); });
+            dft16_from_lds<17>(v, lq + r1, [] { __builtin_amdgcn_s_setprio(WS_PBC); });
             if (DETREND) {
                 const float2 tot = cadd(cadd(h0, h1), cadd(h2, h3));
                 mean = make_float2(tot.x * (1.0f / 4096.0f), tot.y * (1.0f / 4096.0f));
@@ -402,23 +301,16 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
             while (item == ITEM_BUBBLE) item = next_item();
             if (item == ITEM_STOP) break; // the producer left after the barrier of the step that published it
             float2 *lx = img + ((it & 1) ^ 1) * LDS_X;      // v holds pass 2 of image (it - 1) & 1
-#if OTH_WS_DIAG
-            WS_STAMP(5);
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            WS_STAMP(0);
-#endif
-            WS_STAMP(1);
-            __builtin_amdgcn_s_setprio(OTH_WS_PBL);
+            __builtin_amdgcn_s_setprio(WS_PBL);
             lx[w2] = v[r16(0)];           // in place: each thread rewrites exactly the sixteen elements it read
 #pragma unroll
             for (int k1 = 1; k1 < 16; ++k1) lx[w2 + k1 * 17] = cmul(v[r16(k1)], tw2[k1]);
             wave_lds_sync();              // exchange 2 stays inside the wave: program order is enough
-            WS_STAMP(2);
             // exchange-2 reads as ordered ds_read_b64, the first butterfly layer on counted waits (-1.7 % kernel
             // time against the sixteen plain reads, which hipcc pairs into ds_read2_b64 behind one lgkmcnt(0);
             // the same treatment of the exchange-1 reads, which needs the butterfly before the item word is
             // looked at, gave 1.3 % back)
-            dft16_from_lds<1>(v, lx + r2, [] { __builtin_amdgcn_s_setprio(OTH_WS_PBC); });
+            dft16_from_lds<1>(v, lx + r2, [] { __builtin_amdgcn_s_setprio(WS_PBC); });
             if (DETREND) {                // X[k] -= mean * FFT(w)[k] where FFT(w) is not negligible
                 v[r16(0)] = make_float2(v[r16(0)].x - (mean.x * fw.x - mean.y * fw.y),
                                         v[r16(0)].y - (mean.x * fw.y + mean.y * fw.x));
@@ -430,7 +322,6 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
                 const float2 X = v[r16(k2)];
                 acc[k2] = fmaf(X.x, X.x, fmaf(X.y, X.y, acc[k2]));
             }
-            WS_STAMP(3);
             item = next_item();
         }
         // bin k0 + 16 k1 + 256 k2 of this workgroup sits at t + 256 k2 (finalize_kernel layout 1)
@@ -438,19 +329,11 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
 #pragma unroll
         for (int k2 = 0; k2 < 16; ++k2) dst[256 * k2 + t] = acc[k2];
     }
-#if OTH_WS_DIAG
-    if ((tid & 63) == 0) {   // 8 waves x 8 phase counters per workgroup, behind the partial sums
-        unsigned long long *ph = reinterpret_cast<unsigned long long *>(p.partial + (size_t)p.nstreams * W * 4096) +
-                                 64 * ((size_t)stream * W + wg) + 8 * (tid >> 6);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ph[i] = phase[i];
-    }
-#endif
 }
 
 }  // namespace
 
-int OTH_CAT(tuned4096_blocks_per_cu_, OTH_WS_TAG)() {
+int tuned4096_blocks_per_cu_ws() {
     static int cached = 0;
     if (cached) return cached;
     int n = 0;
@@ -459,7 +342,7 @@ int OTH_CAT(tuned4096_blocks_per_cu_, OTH_WS_TAG)() {
     return cached = n;
 }
 
-hipError_t OTH_CAT(launch_welch_tuned4096_, OTH_WS_TAG)(const WelchArgs &a, hipStream_t s) {
+hipError_t launch_welch_tuned4096_ws(const WelchArgs &a, hipStream_t s) {
     const dim3 grid(a.wg_per_stream, a.nstreams);
     static bool armed[64] = {};        // 70 KiB of dynamic LDS needs the opt-in, once per device
     int dev = 0;

@@ -71,7 +71,7 @@ def test_exception_barrier_of_the_abi_host_files(tmp_path):
     an error code (a bad_alloc crossing ctypes would be std::terminate and take the flowgraph down).  The barrier is the
     OTH_TRY / OTH_CATCH pair of csrc/abi_barrier.h; csrc/barrier_probe.cpp puts the SAME macros around an entry point
     that raises on request and is built here with g++ (no GPU, no HIP) - the product library carries no such hook
-    (round 5's oth__debug_throw is gone from it; the stamp / tail readers are in the `make EXP=1` build only)."""
+    (round 5's oth__debug_throw is gone from it, and so are the stamp / tail readers of the diagnostic kernel builds)."""
     import subprocess
     from ofdm_tools import _hip
     csrc = os.path.join(ROOT, 'gr-ofdm_tools_amd', 'csrc')

@@ -619,10 +619,10 @@ def test_chain_latest_wins_on_the_coverage_kernel(ctx, hip):
         check_single_rows(rows, ref[-3:])
         ch.reset()
         rows, n = ch.push(x[:N * 7 + 5], max_rows=1)          # kept vectors 1, 3, 5 -> rows 0..2
-        rows2, n2 = ch.push(x[N * 7 + 5:], max_rows=1)
+        rows_b, n2 = ch.push(x[N * 7 + 5:], max_rows=1)
         assert n + n2 == 20
         check_single_rows(rows[0], ref[n - 1])
-        check_single_rows(rows2[0], ref[-1])
+        check_single_rows(rows_b[0], ref[-1])
         from ofdm_tools import windows
         mag, peak = R.chain_psd_logger(x, N, decim=2)
         ch = ctx.chain(N, windows.blackmanharris(N), False, hip.EPI_MAG, 2)
