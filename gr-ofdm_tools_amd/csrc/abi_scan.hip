@@ -24,6 +24,14 @@ int oth_rows_group_mean(oth_ctx *c, const float *rows_host, size_t nrows, int nf
 
 static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
+// movingaverage() takes 1 <= int(srch_bins) <= nfft: with a longer window np.convolve swaps its arguments and the
+// reference returns int(srch_bins) values - another length and centring, which no nfft-long answer reproduces
+static const char *srch_bins_error(double srch_bins, int nfft) {
+    if (!(srch_bins >= 1.0)) return "bad argument (srch_bins must be >= 1)";
+    if (srch_bins >= (double)nfft + 1.0) return "int(srch_bins) must not exceed nfft (the reference's moving average changes length there)";
+    return nullptr;
+}
+
 // -> device pointers to the channel slice bounds, uploading them only when they differ from the cached copy
 static int channel_bounds_dev(oth_ctx *c, int nch, const int *lo, const int *hi, const int **dlo, const int **dhi) {
     *dlo = *dhi = nullptr;
@@ -61,8 +69,8 @@ int oth_channel_power(oth_ctx *c, const float *psd_host, int nfft, double srch_b
                       const int *hi, float *power_out, float *movavg_out) {
     OTH_TRY
     CtxGuard guard_(c);
-    if (!c || !psd_host || !lo || !hi || !power_out || nfft < 1 || nch < 1 || !(srch_bins >= 1.0))
-        return fail(c, OTH_ERR_INVALID, "bad argument (srch_bins must be >= 1)");
+    if (!c || !psd_host || !lo || !hi || !power_out || nfft < 1 || nch < 1) return fail(c, OTH_ERR_INVALID, "bad argument");
+    if (const char *why = srch_bins_error(srch_bins, nfft)) return fail(c, OTH_ERR_INVALID, why);
     for (int i = 0; i < nch; ++i)
         if (lo[i] < 0 || hi[i] > nfft) return fail(c, OTH_ERR_INVALID, "channel slice outside [0, nfft]");
     if (use_device(c)) return OTH_ERR_HIP;
@@ -90,8 +98,8 @@ int oth_bin_threshold(oth_ctx *c, const float *psd_host, int nrows, int nfft, do
                       unsigned char *mask_out, float *noise_out) {
     OTH_TRY
     CtxGuard guard_(c);
-    if (!c || !psd_host || !mask_out || nrows < 1 || nfft < 1 || !(srch_bins >= 1.0))
-        return fail(c, OTH_ERR_INVALID, "bad argument (srch_bins must be >= 1)");
+    if (!c || !psd_host || !mask_out || nrows < 1 || nfft < 1) return fail(c, OTH_ERR_INVALID, "bad argument");
+    if (const char *why = srch_bins_error(srch_bins, nfft)) return fail(c, OTH_ERR_INVALID, why);
     if (use_device(c)) return OTH_ERR_HIP;
     const size_t nb = (size_t)nrows * nfft;
     const size_t o_mask = sizeof(float) * nb, o_noise = up16(o_mask + nb);
@@ -117,8 +125,9 @@ int oth_scan_decide_dev(oth_ctx *c, const float *psd_rows_dev, int nrows, int nf
                         float *power_out) {
     OTH_TRY
     CtxGuard guard_(c);
-    if (!c || !psd_rows_dev || nrows < 1 || nfft < 1 || nch < 0 || !(srch_bins >= 1.0) || (nch && (!lo || !hi || !power_out)))
-        return fail(c, OTH_ERR_INVALID, "bad argument (srch_bins must be >= 1)");
+    if (!c || !psd_rows_dev || nrows < 1 || nfft < 1 || nch < 0 || (nch && (!lo || !hi || !power_out)))
+        return fail(c, OTH_ERR_INVALID, "bad argument");
+    if (const char *why = srch_bins_error(srch_bins, nfft)) return fail(c, OTH_ERR_INVALID, why);
     for (int i = 0; i < nch; ++i)
         if (lo[i] < 0 || hi[i] > nfft) return fail(c, OTH_ERR_INVALID, "channel slice outside [0, nfft]");
     if (use_device(c)) return OTH_ERR_HIP;
@@ -149,9 +158,9 @@ int oth_scan_decide_dev_out(oth_ctx *c, const float *psd_rows_dev, int nrows, in
                             float *power_dev) {
     OTH_TRY
     CtxGuard guard_(c);
-    if (!c || !psd_rows_dev || !noise_dev || nrows < 1 || nfft < 1 || nch < 0 || !(srch_bins >= 1.0) ||
-        (nch && (!lo || !hi || !power_dev)))
-        return fail(c, OTH_ERR_INVALID, "bad argument (srch_bins must be >= 1)");
+    if (!c || !psd_rows_dev || !noise_dev || nrows < 1 || nfft < 1 || nch < 0 || (nch && (!lo || !hi || !power_dev)))
+        return fail(c, OTH_ERR_INVALID, "bad argument");
+    if (const char *why = srch_bins_error(srch_bins, nfft)) return fail(c, OTH_ERR_INVALID, why);
     for (int i = 0; i < nch; ++i)
         if (lo[i] < 0 || hi[i] > nfft) return fail(c, OTH_ERR_INVALID, "channel slice outside [0, nfft]");
     if (use_device(c)) return OTH_ERR_HIP;

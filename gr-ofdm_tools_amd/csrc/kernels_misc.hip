@@ -601,6 +601,10 @@ hipError_t launch_group_mean(const float *rows, long long ngroups, int nfft, int
     return hipGetLastError();
 }
 
+// min() that keeps a NaN, as numpy's min / amin do (fminf drops it): the noise floor of a row with a NaN bin is NaN
+// and its mask all zero, like the reference's movingaverage(...).min()
+__device__ __forceinline__ float nan_min(float a, float b) { return (a != a || a < b) ? a : b; }
+
 // movingaverage(): np.convolve(psd, ones(M)/sb, 'same'), M = int(sb):
 // same[i] = (1/sb) * sum_{j<M} psd[i + (M-1)/2 - j]  (terms outside [0,N) dropped), then abs.
 // blockIdx.y = PSD row (batched scanner: one row per channel stream).
@@ -644,7 +648,7 @@ __global__ __launch_bounds__(256) void bin_threshold_kernel(const float *psd, in
     __shared__ float red[4];
     const float *row = psd + (size_t)blockIdx.x * nfft;
     const int M = (int)srch_bins;
-    float mn = 3.4e38f;
+    float mn = INFINITY;
     for (int i = threadIdx.x; i < nfft; i += 256) {
         const int top = i + (M - 1) / 2;
         double s = 0.0;
@@ -652,13 +656,13 @@ __global__ __launch_bounds__(256) void bin_threshold_kernel(const float *psd, in
             const int n = top - j;
             if (n >= 0 && n < nfft) s += (double)row[n];
         }
-        mn = fminf(mn, (float)fabs(s / srch_bins));
+        mn = nan_min(mn, (float)fabs(s / srch_bins));
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mn = fminf(mn, __shfl_xor(mn, off, 64));
+    for (int off = 32; off > 0; off >>= 1) mn = nan_min(mn, __shfl_xor(mn, off, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
     __syncthreads();
-    const float noise = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+    const float noise = nan_min(nan_min(red[0], red[1]), nan_min(red[2], red[3]));
     if (threadIdx.x == 0 && noise_out) noise_out[blockIdx.x] = noise;
     const float level = noise * thr;
     for (int i = threadIdx.x; i < nfft; i += 256) mask[(size_t)blockIdx.x * nfft + i] = row[i] > level ? 1 : 0;
@@ -671,13 +675,13 @@ __global__ __launch_bounds__(256) void bin_threshold_ma_kernel(const float *psd,
     __shared__ float red[4];
     const float *row = psd + (size_t)blockIdx.x * nfft;
     const double *ma = movavg + (size_t)blockIdx.x * nfft;
-    float mn = 3.4e38f;
-    for (int i = threadIdx.x; i < nfft; i += 256) mn = fminf(mn, (float)ma[i]);
+    float mn = INFINITY;
+    for (int i = threadIdx.x; i < nfft; i += 256) mn = nan_min(mn, (float)ma[i]);
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mn = fminf(mn, __shfl_xor(mn, off, 64));
+    for (int off = 32; off > 0; off >>= 1) mn = nan_min(mn, __shfl_xor(mn, off, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
     __syncthreads();
-    const float noise = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+    const float noise = nan_min(nan_min(red[0], red[1]), nan_min(red[2], red[3]));
     if (threadIdx.x == 0 && noise_out) noise_out[blockIdx.x] = noise;
     if (!mask) return;
     const float level = noise * thr;
@@ -755,7 +759,7 @@ __global__ __launch_bounds__(kMaThreads) void movavg_run_kernel(const float *psd
     }
     __syncthreads();
     const int t0 = threadIdx.x * kMaRun, i0 = base + t0;              // output i0 + r takes xs[t0 + r .. t0 + r + M - 1]
-    float mn = 3.4e38f;
+    float mn = INFINITY;
     if (i0 < nfft) {
         double s = 0.0;
         float big = 0.f;                  // largest |tap| this run has added so far
@@ -806,25 +810,28 @@ __global__ __launch_bounds__(kMaThreads) void movavg_run_kernel(const float *psd
             big = fmaxf(big, fabsf(in));
             s += (double)in;
             s -= (double)tout[r];
-            if (fabs(s) < (double)big * (1.0 / 16777216.0)) {      // a carrier > 2^24 x the window's content has just left
+            // a carrier > 2^24 x the window's content has just left - or the sum is not finite: an inf / NaN tap stays in a
+            // sliding sum (inf - inf) after it has left the window, in a direct sum it leaves with its window, as in
+            // np.convolve
+            if (!(fabs(s) >= (double)big * (1.0 / 16777216.0))) {
                 big = 0.f;
                 s = direct(t0 + r);
             }
             v = fabs(s * inv);
             ys[ma_pad(t0 + r)] = v;
-            if (i0 + r < nfft) mn = fminf(mn, (float)v);          // (nfft is a multiple of the run in practice; ys[] behind
-        }                                                          // the row's end is never copied out)
+            if (i0 + r < nfft) mn = nan_min(mn, (float)v);        // (a cut last run: ys[] behind the row's end is never
+        }                                                          // copied out)
     }
     __syncthreads();
     for (int k = threadIdx.x; k < kMaTile && base + k < nfft; k += kMaThreads) out[base + k] = ys[ma_pad(k)];
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mn = fminf(mn, __shfl_xor(mn, off, 64));
+    for (int off = 32; off > 0; off >>= 1) mn = nan_min(mn, __shfl_xor(mn, off, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
     __syncthreads();
     if (threadIdx.x == 0) {
         float m = red[0];
 #pragma unroll
-        for (int w = 1; w < kMaThreads / 64; ++w) m = fminf(m, red[w]);
+        for (int w = 1; w < kMaThreads / 64; ++w) m = nan_min(m, red[w]);
         tile_min[blockIdx.y * gridDim.x + blockIdx.x] = m;
     }
 }
@@ -837,7 +844,7 @@ __global__ __launch_bounds__(256) void scan_post_kernel(const float *psd, const 
                                                         int ntiles, int nfft, float thr, int nmb, int nch, const int *lo,
                                                         const int *hi, unsigned char *mask, float *noise, float *power) {
     float floor_ = tile_min[blockIdx.y * ntiles];
-    for (int k = 1; k < ntiles; ++k) floor_ = fminf(floor_, tile_min[blockIdx.y * ntiles + k]);
+    for (int k = 1; k < ntiles; ++k) floor_ = nan_min(floor_, tile_min[blockIdx.y * ntiles + k]);
     if (blockIdx.x == 0 && threadIdx.x == 0) noise[blockIdx.y] = floor_;
     if ((int)blockIdx.x < nmb) {
         if (!mask) return;
@@ -869,6 +876,9 @@ __global__ __launch_bounds__(256) void scan_post_kernel(const float *psd, const 
 
 int scan_decide_tiles(int nfft) { return (nfft + kMaTile - 1) / kMaTile; }
 
+// Two doors: the tiled run kernels above take rows of a multiple of four bins at 16-byte aligned addresses (float4 /
+// uchar4 mask stores) with int(srch_bins) <= kMaMaxM (the halo in LDS); every other call takes the direct form
+// (movavg_kernel, channel_sum_kernel, bin_threshold_ma_kernel).  Both compute the same thing.
 hipError_t launch_scan_decide(const float *psd, int nrows, int nfft, double srch_bins, float thr, int nch, const int *lo,
                               const int *hi, double *movavg, float *tile_min, unsigned char *mask, float *noise, float *power,
                               hipStream_t s) {

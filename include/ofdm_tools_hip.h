@@ -367,7 +367,11 @@ int oth_channel_power(oth_ctx *ctx, const float *psd_host, int nfft, double srch
 /* Per-bin energy detection for the batched scanner (BASELINE config 5; the per-bin analogue of the
  * channel threshold of spectrum_sensor_v2.py:465-477): noise = min_k movingaverage(psd)[k],
  * mask[k] = psd[k] > thr_leveler * noise.  nrows PSD rows of nfft bins each (host); mask_out is
- * uint8[nrows][nfft], noise_out float[nrows] (nullable). */
+ * uint8[nrows][nfft], noise_out float[nrows] (nullable).
+ * The moving average here, in oth_channel_power and in oth_scan_decide_dev[_out] is np.convolve's: an output is inf / NaN
+ * exactly where its window holds an inf / NaN bin.  The minimum is numpy's: one NaN output makes the row's noise floor NaN
+ * and its mask all zero.  1 <= int(srch_bins) <= nfft, else OTH_ERR_INVALID: with a longer window the reference's
+ * movingaverage returns int(srch_bins) values in another centring, which no nfft-long result is. */
 int oth_bin_threshold(oth_ctx *ctx, const float *psd_host, int nrows, int nfft, double srch_bins,
                       float thr_leveler, unsigned char *mask_out, float *noise_out);
 
@@ -375,7 +379,8 @@ int oth_bin_threshold(oth_ctx *ctx, const float *psd_host, int nrows, int nfft, 
  * rows): moving average once per row, channel slice sums (src_power, ofdm_cr_tools.py:232-249), noise floor and
  * per-bin mask (as oth_bin_threshold) in one launch sequence on context-owned scratch - no copy of the rows, no
  * allocation per call.  Host outputs: mask_out uint8[nrows][nfft] (nullable), noise_out float[nrows] (nullable),
- * power_out float[nrows][nch] (required when nch > 0). */
+ * power_out float[nrows][nch] (required when nch > 0).  Slices are Python's psd[lo:hi] with 0 <= lo, hi <= nfft (lo >= hi:
+ * empty, sum 0).  Non-finite bins, NaN and the noise floor, int(srch_bins) <= nfft: as oth_bin_threshold. */
 int oth_scan_decide_dev(oth_ctx *ctx, const float *psd_rows_dev, int nrows, int nfft, double srch_bins,
                         float thr_leveler, int nch, const int *lo, const int *hi, unsigned char *mask_out,
                         float *noise_out, float *power_out);
