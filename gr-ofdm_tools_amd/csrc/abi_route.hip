@@ -27,7 +27,7 @@ const W4096Variant *w4096_variant(int step, bool fd_ok, const std::string &want)
     const W4096Variant *pick = (step == 2048) ? (fd_ok ? ws : pipe) : dpp;
     if (!want.empty())
         for (const auto &v : kVariants)
-            if (want == v.tag) pick = &v;
+            if (want == v.tag || (want == "wsgen" && !strcmp(v.tag, "ws"))) pick = &v;      // "wsgen": ws, general-window producer
     // the wave-specialised build detrends in the frequency domain: only with a confined window spectrum
     if (pick->fd && !fd_ok) pick = pipe;
     // the pipelined builds keep the overlapped half in registers: only for step = nperseg / 2

@@ -77,6 +77,7 @@ struct oth_plan {
     size_t pilot_cap = 0;
     bool fast_detrend = false;         // OTH_DETREND_CONSTANT_FAST: the builds without the pilot (WelchArgs.pilot)
     bool rect_window = false;          // every window value is 1 (window == NULL or boxcar): builds without the multiply
+    bool compl_window = false;         // w[n] + w[n + nfft / 2] = 1 to one float32 ulp (window_is_complementary, abi_welch.hip)
     float *d_partial = nullptr;
     size_t partial_cap = 0;
     float *d_reduce = nullptr;         // stage-1 output of the two-stage partial-sum reduction

@@ -102,6 +102,15 @@ bool window_spectrum_table_1x(const std::vector<float> &w, int n, std::vector<fl
     return true;
 }
 
+// Acceptance test of welch4096ws's complementary-window producer (WelchArgs.compl_win): in double, on the float window
+// the plan was given, |w[n] + w[n + N / 2] - 1| <= 2^-23 for every n - one float32 ulp at 1.  SciPy's default periodic Hann
+// measures 3.0e-8, a quarter of it; flattop, Blackman-Harris and boxcar miss by 0.5 ... 1.1 and keep the general build.
+bool window_is_complementary(const std::vector<float> &w, int n) {
+    for (int i = 0; i < n / 2; ++i)
+        if (!(std::fabs((double)w[i] + (double)w[i + n / 2] - 1.0) <= 1.1920928955078125e-07)) return false;
+    return true;
+}
+
 int segments(const oth_plan *p, size_t nsamples, long long *nseg) {
     if (nsamples < (size_t)p->nperseg) return OTH_ERR_INVALID;
     *nseg = (long long)((nsamples - (size_t)p->noverlap) / (size_t)p->step);
@@ -212,6 +221,8 @@ int run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
         a.fd = fd_tab;
         a.pilot = pilot;
         a.pilot_inline = r.pilot == 2 ? 1 : 0;
+        // (read by launch_welch_tuned4096_ws only; the tuning word "wsgen" keeps the general build: the A/B and the parity tests)
+        a.compl_win = p->compl_window && p->tune_variant != "wsgen" ? 1 : 0;
         Timed tm(c);
         switch (r.kern) {
             case RK_W4096: HIPCHK(c, r.variant->launch(a, c->stream)); break;
@@ -436,6 +447,7 @@ int oth_welch_plan(oth_ctx *c, int nfft, int nperseg, int noverlap, const float 
          ((nfft == 8192 || nfft == 16384) && nperseg == nfft && window_spectrum_table_16k(w, nfft, fd)))) {
         e = upload_table(c, &p->d_fd, fd);
     }
+    p->compl_window = nfft == 4096 && nperseg == 4096 && window_is_complementary(w, nfft);      // the welch4096ws route's shape
     std::vector<float> fd1x;
     if (e == hipSuccess && detrend == OTH_DETREND_CONSTANT && (nfft == 16384 || nfft == 8192) && nperseg == nfft &&
         window_spectrum_table_1x(w, nfft, fd1x)) {
@@ -534,6 +546,8 @@ int oth_plan_set_tuning(oth_plan *p, const char *variant, int sched, int chunk, 
                      !strcmp(variant, "csd1") ||                                // the one-role two-channel kernel
                      !strcmp(variant, "fd") || !strcmp(variant, "td") ||        // detrend form only (run_average)
                      !strcmp(variant, "plaunch") ||                             // pilot from its own launch (run_average)
+                     !strcmp(variant, "wsgen") ||                               // "ws" with the general-window producer also where the
+                                                                                // window is complementary (the A/B of WelchArgs.compl_win)
                      !strcmp(variant, "16k4") || !strcmp(variant, "16kplain") ||  // 16384 points: the 4 x 4096 build / the
                                                                                 // un-pipelined one-exchange build
                      !strcmp(variant, "8kws") || !strcmp(variant, "8k1role") ||  // 8192 points, 50 % overlap: role-split / one-role

@@ -22,6 +22,12 @@
 // prefetched, four waves per SIMD.  The fifteen pass-2 twiddles are multiplied out of two seeds per step (52 VALU).
 // tried: the fifteen kept in registers (no room beside 32 accumulators at 128 VGPRs), and read from a 2 KiB LDS table
 // between the butterfly layers of pass 2 (0.3126 against 0.3111 ms, 0.3495 against 0.3486 ms: no gain, NOTES 4.1c).
+// tried: welch4096ws.hip's complementary-window producers (WelchArgs.compl_win; here eight of the sixteen window registers
+// would go, for stored pass-1 twiddle powers: 650 -> 620 VALU per two segments with six stored).  Does not fit: beside the
+// consumers' 32 accumulators the allocation already stands at 127 VGPRs, and with four, six, eight or ten stored powers
+// both flavours came out at 128 VGPRs with 24-96 B of scratch (one reload per segment in the PILOT hot loop, 4-28
+// accesses in the one-segment-chunk path), with and without the fence that keeps item()'s flavours apart there.  This
+// kernel ignores compl_win.  (Its consumers load two seeds, not fifteen twiddles: one s_waitcnt vmcnt in their loop, left as it is.)
 //
 // The two pairs run the same chunk schedule (Px draws the tickets, Py reads them), so x_s and y_s are always in
 // the same step.  Frequency-domain detrend as in welch4096ws.hip (needs WelchArgs.fd).

@@ -274,6 +274,30 @@ __device__ __forceinline__ void scatter_pow16_six(const float2 (&v)[16], float2 
     }
 }
 
+// The same scatter with 6 + NM stored powers: pm = W^5, W^6, W^7, W^9, W^10, W^11, ... in that order (NM = 3: nine stored,
+// six products; NM = 4: ten, five).  Each remaining product is formed at the store that uses it (formed ahead of the
+// stores they cost 14-18 spilled registers).
+__host__ __device__ constexpr int pow16_slot(int k) { return k - 5 - (k >> 2) + 1; }      // k = 5, 6, 7, 9, 10, 11, 13, ... -> 0, 1, 2, ...
+template <int STRIDE, int NM>
+__device__ __forceinline__ void scatter_pow16_stored(const float2 (&v)[16], float2 *out, float2 p1, float2 p2, float2 p3, float2 p4,
+                                                     float2 p8, float2 p12, const float2 (&pm)[NM]) {
+    float2 wj[4], wi[4];
+    wj[1] = p1, wj[2] = p2, wj[3] = p3;
+    wi[1] = p4, wi[2] = p8, wi[3] = p12;
+    asm volatile("" : "+v"(wj[1].x), "+v"(wj[1].y), "+v"(wj[2].x), "+v"(wj[2].y), "+v"(wj[3].x), "+v"(wj[3].y));
+    out[0] = v[0];
+#pragma unroll
+    for (int k = 1; k < 16; ++k) {
+        const int i = k >> 2, j = k & 3;
+        float2 w;
+        if (i == 0) w = wj[j];
+        else if (j == 0) w = wi[i];
+        else if (pow16_slot(k) < NM) w = pm[pow16_slot(k) < NM ? pow16_slot(k) : 0];
+        else w = cmul(wi[i], wj[j]);
+        out[STRIDE * k] = cmul(v[r16(k)], w);
+    }
+}
+
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();

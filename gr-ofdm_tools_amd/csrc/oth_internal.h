@@ -46,6 +46,10 @@ struct WelchArgs {
     // transform (5.9 us + a dependent-launch gap per step).  The pilot only has to be NEAR the mean; every workgroup reads
     // the same samples in the same order, so all hold the same bits.
     int pilot_inline;
+    // 1 (welch4096ws only): the plan's window satisfies w[n] + w[n + nfft / 2] = 1 to one float32 ulp (SciPy's periodic
+    // Hann; checked in double at plan time), so the producer forms r w[n + nfft / 2] as fma(-r, w[n], r) and holds no
+    // window value in a register.  0: the general build, any window.
+    int compl_win;
 };
 
 // Launch description of segfft.hip: segment transforms of 1024 / 2048 / 4096 points by teams of nfft / 16

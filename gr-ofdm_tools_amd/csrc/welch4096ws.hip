@@ -27,8 +27,21 @@
 // The producer keeps six pass-1 twiddle powers (W^1,2,3,4,8,12: nine products per segment instead of thirteen) and
 // pays for their eight registers by reading the second half of its window values from an 8 KiB LDS table per step
 // (same-box A/B, five interleaved runs each: 0.5855 against 0.5906 ms = -0.9 %, profiles/r03_ab_headline_pow6.txt)
+// Complementary windows (welch4096ws_compl_kernel; WelchArgs.compl_win, checked at plan time: w[n] + w[n + 2048] = 1 to one
+// float32 ulp - SciPy's periodic Hann, the reference's call): r w[n + 2048] = fma(-r, w[n], r), so window rows 8..15 are not
+// needed, rows 0..7 take their place in the LDS table and no window value stays in a register.  The kept half stays
+// UNWINDOWED: its product with w[n] contracts into the two additions of the first butterfly layer (windowed ahead, the
+// pair cost sixteen instructions more than the general form), so the window costs what it did and the eight freed
+// registers plus what the form leaves over hold thirteen pass-1 twiddle powers (two products per segment; fourteen and
+// fifteen spill in the PILOT flavour).  Producer hot loop 311 -> 281 VALU per segment at 128 VGPRs, no scratch
+// (same-box A/B against the parent library with the change below, alternating runs of bench.py: kernel 0.5993-0.6013
+// against 0.6132-0.6147 ms = -2.3 %, step 0.613-0.616 against 0.627-0.630 ms, profiles/ab_headline_compl.txt)
+// The consumer waits ONCE for its table loads, in front of its loop: fifteen s_waitcnt vmcnt(n) per segment, one in front
+// of each pass-2 twiddle product, are gone from the critical path (measured together with the above, not on its own)
 // tried: the eight loads of a step spread over 2 / 3 places instead of one burst, no gain (NOTES 8,
 // profiles/r05_ab_headline_spread_loads.txt)
+// not tried: the two components of the segment sum reduced in one interleaved DPP sequence (ten s_nop per segment in the
+// producer, which is not the critical path)
 
 #include <type_traits>
 #include "fft4096.hip.h"
@@ -49,8 +62,15 @@ constexpr int WS_PBC = 1;                  // the consumer is the critical path:
 
 enum { ITEM_STOP = 0, ITEM_DATA = 1, ITEM_BUBBLE = 2 };
 
-template <bool DETREND, bool PILOT = false>
-__global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
+#ifndef OTH_WS_COMPL_POWERS
+#define OTH_WS_COMPL_POWERS 13
+#endif
+constexpr int WS_COMPL_POWERS = OTH_WS_COMPL_POWERS;      // pass-1 twiddle powers the complementary-window producer stores
+                                                          // (6 ... 15; thirteen is the most that fits without scratch)
+
+// COMPL: the complementary-window producer (w[n] + w[n + 2048] = 1, see the file header); everything else is shared
+template <bool DETREND, bool PILOT, bool COMPL>
+__device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
     static_assert(DETREND || !PILOT, "the pilot belongs to the detrend");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float2 *img = reinterpret_cast<float2 *>(smem);             // two images of LDS_X float2
@@ -73,14 +93,23 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
 
     if (producer) {
         // ------------------------------------------------------------------ producer
-        float win[8];
-        float4 *wl = reinterpret_cast<float4 *>(ctrl + WS_CTRL) + t;      // [2][256] float4: win[8..11], win[12..15]
+        float win[COMPL ? 1 : 8];      // (COMPL: no window value stays in a register)
+        float4 *wl = reinterpret_cast<float4 *>(ctrl + WS_CTRL) + t;      // [2][256] float4: win[8..11], win[12..15] (COMPL: 0..3, 4..7)
+        constexpr int WROW = COMPL ? 0 : 8;
+        if constexpr (!COMPL) {
 #pragma unroll
-        for (int a = 0; a < 8; ++a) win[a] = p.win[256 * a + t];
-        wl[0] = make_float4(p.win[256 * 8 + t], p.win[256 * 9 + t], p.win[256 * 10 + t], p.win[256 * 11 + t]);
-        wl[256] = make_float4(p.win[256 * 12 + t], p.win[256 * 13 + t], p.win[256 * 14 + t], p.win[256 * 15 + t]);
+            for (int a = 0; a < 8; ++a) win[a] = p.win[256 * a + t];
+        }
+        wl[0] = make_float4(p.win[256 * WROW + t], p.win[256 * (WROW + 1) + t], p.win[256 * (WROW + 2) + t], p.win[256 * (WROW + 3) + t]);
+        wl[256] = make_float4(p.win[256 * (WROW + 4) + t], p.win[256 * (WROW + 5) + t], p.win[256 * (WROW + 6) + t],
+                              p.win[256 * (WROW + 7) + t]);
         const float2 b1 = p.tw[t], b2 = p.tw[2 * t], b3 = p.tw[3 * t], b4 = p.tw[4 * t], b8 = p.tw[8 * t],
                      b12 = p.tw[(12 * t) & 4095];
+        float2 bm[WS_COMPL_POWERS - 6 > 0 && COMPL ? WS_COMPL_POWERS - 6 : 1];      // COMPL: W^5, W^6, W^7, W^9, ... (pow16_slot)
+        if constexpr (COMPL) {
+#pragma unroll
+            for (int k = 0; k < WS_COMPL_POWERS - 6; ++k) bm[k] = p.tw[((5 + k + k / 3) * t) & 4095];
+        }
         float2 kw[8], nxt[8];
         float2 prev_new = make_float2(0.f, 0.f);     // this wave's sum of the previous segment's new half
         // PILOT (every detrending plan but OTH_DETREND_CONSTANT_FAST): WelchArgs.pilot comes off every sample as it arrives, so the transform and
@@ -128,26 +157,38 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
             constexpr int MODE = decltype(mode_)::value;
             const int q = it & 1;
             float2 *lx = img + q * LDS_X;
+            // COMPL: the flavours keep their own code - hoisted above the branch between two of them, their common head
+            // loses the contraction of the window products into the butterflies and spills 4-26 registers
+            if constexpr (COMPL) asm volatile("; item %0 %1" ::"n"((int)FIRST), "n"(MODE));
             __builtin_amdgcn_s_setprio(WS_PAL);
             float2 v[16];
             float2 sumf = make_float2(0.f, 0.f), sum = make_float2(0.f, 0.f);
             const float4 wa = wl[0], wb = wl[256];      // own slots: no barrier needed
-            const float wh[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};      // window values 8..15, this step only
+            const float wh[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};      // window values 8..15 (COMPL: 0..7), this step only
             if (FIRST) {
 #pragma unroll
                 for (int a = 0; a < 8; ++a) {      // kw still holds the raw first half of the chunk's first segment
                     if (PILOT) kw[a] = csub(kw[a], pv);
                     sumf = cadd(sumf, kw[a]);
-                    kw[a] = make_float2(kw[a].x * win[a], kw[a].y * win[a]);
+                    if constexpr (!COMPL) kw[a] = make_float2(kw[a].x * win[a], kw[a].y * win[a]);
                 }
             }
 #pragma unroll
             for (int a = 0; a < 8; ++a) {      // the new half is windowed for both of its roles as it arrives
                 const float2 r = PILOT ? csub(nxt[a], pv) : nxt[a];
-                v[a] = kw[a];
-                v[8 + a] = make_float2(r.x * wh[a], r.y * wh[a]);
-                if (MODE == 0) kw[a] = make_float2(r.x * win[a], r.y * win[a]);      // (else kw is reloaded below)
-                sum = cadd(sum, r);
+                if constexpr (COMPL) {
+                    // kw is the kept half UNWINDOWED: its product with w[n] is contracted into the first butterfly layer's
+                    // two additions (as the general build's r w[n + 2048] is), so keeping it costs nothing;
+                    // r w[n + 2048] = r (1 - w[n]) = fma(-r, w[n], r): one rounding, no second window value
+                    v[a] = make_float2(kw[a].x * wh[a], kw[a].y * wh[a]);
+                    v[8 + a] = make_float2(fmaf(-r.x, wh[a], r.x), fmaf(-r.y, wh[a], r.y));
+                    if (MODE == 0) kw[a] = r;
+                } else {
+                    v[a] = kw[a];
+                    v[8 + a] = make_float2(r.x * wh[a], r.y * wh[a]);
+                    if (MODE == 0) kw[a] = make_float2(r.x * win[a], r.y * win[a]);      // (else kw is reloaded below)
+                }
+                sum = (COMPL && a == 0) ? r : cadd(sum, r);      // (COMPL: no 0 + r in front of the chain)
             }
             // dynamic schedule: the ticket of the chunk after this one is drawn with the chunk's first segment and
             // published (a wait for the atomic's return) before this step's loads go out, one step later if possible
@@ -181,7 +222,8 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
             __builtin_amdgcn_s_setprio(WS_PAC);
             dft16(v);
             __builtin_amdgcn_s_setprio(WS_PAS);
-            scatter_pow16_six<RS>(v, lx + w1, b1, b2, b3, b4, b8, b12);
+            if constexpr (COMPL) scatter_pow16_stored<RS>(v, lx + w1, b1, b2, b3, b4, b8, b12, bm);
+            else scatter_pow16_six<RS>(v, lx + w1, b1, b2, b3, b4, b8, b12);
             step_end(ITEM_DATA);
         };
 
@@ -272,6 +314,16 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
         for (int k = 0; k < 16; ++k) acc[k] = 0.f;
         float2 v[16];
         float2 mean = make_float2(0.f, 0.f);
+        // The table loads above are this role's only vector-memory operations.  One wait here, with the values made opaque:
+        // the compiler otherwise carries their wait-count state into the loop and re-emits an s_waitcnt vmcnt(n) in front
+        // of every pass-2 twiddle product of every step (fifteen issue turns of the critical path per segment).
+        asm volatile("s_waitcnt vmcnt(0)"
+                     : "+v"(tw2[1].x), "+v"(tw2[1].y), "+v"(tw2[2].x), "+v"(tw2[2].y), "+v"(tw2[3].x), "+v"(tw2[3].y), "+v"(tw2[4].x),
+                       "+v"(tw2[4].y), "+v"(tw2[5].x), "+v"(tw2[5].y), "+v"(tw2[6].x), "+v"(tw2[6].y), "+v"(tw2[7].x), "+v"(tw2[7].y));
+        asm volatile("" : "+v"(tw2[8].x), "+v"(tw2[8].y), "+v"(tw2[9].x), "+v"(tw2[9].y), "+v"(tw2[10].x), "+v"(tw2[10].y),
+                          "+v"(tw2[11].x), "+v"(tw2[11].y), "+v"(tw2[12].x), "+v"(tw2[12].y), "+v"(tw2[13].x), "+v"(tw2[13].y));
+        asm volatile("" : "+v"(tw2[14].x), "+v"(tw2[14].y), "+v"(tw2[15].x), "+v"(tw2[15].y), "+v"(fw.x), "+v"(fw.y), "+v"(fw.z),
+                          "+v"(fw.w));
         int it = 0;
         // barrier of step `it`, then what the producer left in image it & 1: the item kind and, in the same batch
         // of LDS reads (harmless when it is not a segment), the exchange-1 reads and the per-wave sums
@@ -331,6 +383,15 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
     }
 }
 
+template <bool DETREND, bool PILOT = false>
+__global__ __launch_bounds__(TWS, 4) void welch4096ws_kernel(WelchArgs p) {
+    welch4096ws_body<DETREND, PILOT, false>(p);
+}
+template <bool DETREND, bool PILOT = false>
+__global__ __launch_bounds__(TWS, 4) void welch4096ws_compl_kernel(WelchArgs p) {
+    welch4096ws_body<DETREND, PILOT, true>(p);
+}
+
 }  // namespace
 
 int tuned4096_blocks_per_cu_ws() {
@@ -352,12 +413,20 @@ hipError_t launch_welch_tuned4096_ws(const WelchArgs &a, hipStream_t s) {
         hipError_t e = hipSuccess;
         for (const void *fn : {reinterpret_cast<const void *>(welch4096ws_kernel<true, true>),
                                reinterpret_cast<const void *>(welch4096ws_kernel<true, false>),
-                               reinterpret_cast<const void *>(welch4096ws_kernel<false, false>)})
+                               reinterpret_cast<const void *>(welch4096ws_kernel<false, false>),
+                               reinterpret_cast<const void *>(welch4096ws_compl_kernel<true, true>),
+                               reinterpret_cast<const void *>(welch4096ws_compl_kernel<true, false>),
+                               reinterpret_cast<const void *>(welch4096ws_compl_kernel<false, false>)})
             if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WS_LDS_BYTES);
         if (e != hipSuccess) return e;
         big_lds = true;
     }
-    if (a.detrend && (a.pilot || a.pilot_inline))
+    const bool pilot = a.detrend && (a.pilot || a.pilot_inline);
+    if (a.compl_win) {      // w[n] + w[n + 2048] = 1 (plan-time check, abi_welch.hip window_is_complementary)
+        if (pilot) hipLaunchKernelGGL((welch4096ws_compl_kernel<true, true>), grid, dim3(TWS), WS_LDS_BYTES, s, a);
+        else if (a.detrend) hipLaunchKernelGGL((welch4096ws_compl_kernel<true, false>), grid, dim3(TWS), WS_LDS_BYTES, s, a);
+        else hipLaunchKernelGGL((welch4096ws_compl_kernel<false, false>), grid, dim3(TWS), WS_LDS_BYTES, s, a);
+    } else if (pilot)
         hipLaunchKernelGGL((welch4096ws_kernel<true, true>), grid, dim3(TWS), WS_LDS_BYTES, s, a);
     else if (a.detrend)
         hipLaunchKernelGGL((welch4096ws_kernel<true, false>), grid, dim3(TWS), WS_LDS_BYTES, s, a);

@@ -213,7 +213,8 @@ int oth_plan_out_len(oth_plan *plan, int *n);
 #define OTH_HOSTWAIT_POLL 0
 #define OTH_HOSTWAIT_SYNC 1
 int oth_plan_set_hostwait(oth_plan *plan, int mode);
-/* Launch tuning for A/B tools and the parity suite: which build of the 4096-point kernel ("dpp", "pipe", "ws") or
+/* Launch tuning for A/B tools and the parity suite: which build of the 4096-point kernel ("dpp", "pipe", "ws"; "wsgen": "ws"
+ * with the general-window producer also where the window is complementary, w[n] + w[n + nfft / 2] = 1, as periodic Hann) or
  * of the 256 ... 2048-point kernels ("seg3", "seg4": registers held to 3 / 4 waves per SIMD; NULL or "" = the
  * library's choice), or only the detrend form of the size's default kernel ("fd": after the transform even below 8
  * segments per stream of an OTH_DETREND_CONSTANT_FAST plan; "td": before it at any length), the one-role kernel at 8192 points /
