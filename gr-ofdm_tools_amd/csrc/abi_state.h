@@ -133,6 +133,10 @@ struct oth_plan {
     AnyTables rows_any;                // the any-length tables of a power-of-two plan's rows (p->any serves the others)
     long long bias_nseg = 0;           // _median_bias(bias_nseg) = bias, cached
     double bias = 1.0;
+    // multitaper plans (oth_mtm_plan, abi_mtm.hip): ntapers > 0; run_average hands every launch to mtm_run, d_win stays null
+    int ntapers = 0;
+    float *d_tapers = nullptr;         // [ntapers][nfft], zero-extended behind nperseg
+    float *d_coef = nullptr;           // [ntapers] c_k: normalised weight (over the taper's energy with OTH_SCALE_DENSITY)
 };
 
 struct oth_chain {
@@ -411,4 +415,11 @@ int any_run(oth_ctx *c, AnyTables &t, const float2 *x, const float2 *y, long lon
 inline size_t any_fft_nat_scratch(const AnyShape &sh) { return 2 * (size_t)sh.L; }
 int any_fft_nat(oth_ctx *c, const AnyTables &t, float2 *data, float2 *scratch);
 void host_fft_pow2(std::vector<double> &re, std::vector<double> &im);
+
+// ---- abi_mtm.hip: multitaper plans ------------------------------------------------------------------------------------------
+// the averaging launch of a multitaper plan (run_average branches here before resolve_recipe): W partial rows per stream
+// in natural order (finalize layout 0) into p->d_partial
+int mtm_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t stride, int *W_out);
+// OTH_ERR_UNSUPPORTED with the reason: `what` is not available on a multitaper plan
+int refuse_mtm(oth_plan *p, const char *what, const char *why);
 }  // namespace oth

@@ -125,6 +125,13 @@ int run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
     if (segments(p, nsamples, &nseg) != OTH_OK)
         return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
     const bool csd = (y != nullptr);
+    if (p->ntapers) {      // multitaper plans: mtm.hip, before any routing
+        if (csd) return refuse_mtm(p, "the cross spectrum", "the taper loop holds one channel");
+        if (int rc = mtm_run(p, x, nseg, nstreams, stride, W_out)) return rc;
+        *nseg_out = nseg;
+        *layout_out = 0;
+        return OTH_OK;
+    }
     LaunchRecipe r;
     const char *why = "";
     if (int rrc = resolve_recipe(shape_of(p), csd, nseg, nstreams, c->cu_count, runtime_bpc, &r, &why))
@@ -480,6 +487,8 @@ int oth_plan_destroy(oth_plan *p) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     if (p->d_win) hipFree(p->d_win);
+    if (p->d_tapers) hipFree(p->d_tapers);
+    if (p->d_coef) hipFree(p->d_coef);
     if (p->d_wpm) hipFree(p->d_wpm);
     if (p->d_fd) hipFree(p->d_fd);
     if (p->d_fd1x) hipFree(p->d_fd1x);
@@ -520,6 +529,7 @@ int oth_plan_set_kernel(oth_plan *p, int which) {
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
     if (which < OTH_KERNEL_AUTO || which > OTH_KERNEL_TUNED) return fail(p->ctx, OTH_ERR_INVALID, "unknown kernel id");
+    if (p->ntapers && which == OTH_KERNEL_TUNED) return refuse_mtm(p, "OTH_KERNEL_TUNED", "no tuned kernel carries the taper loop");
     p->kernel = which;
     return OTH_OK;
     OTH_CATCH((p ? p->ctx : nullptr))
@@ -541,6 +551,7 @@ int oth_plan_set_tuning(oth_plan *p, const char *variant, int sched, int chunk, 
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
     if (sched < -1 || sched > OTH_SCHED_DYNAMIC || chunk < 0 || tail_chunk < 0)
         return fail(p->ctx, OTH_ERR_INVALID, "bad tuning value");
+    if (p->ntapers && variant && *variant) return refuse_mtm(p, "a kernel build variant", "mtm_kernel has one build per size");
     if (variant && *variant) {
         bool known = !strcmp(variant, "seg3") || !strcmp(variant, "seg4") || !strcmp(variant, "segws") ||   // 1024 / 2048
                      !strcmp(variant, "csd1") ||                                // the one-role two-channel kernel
@@ -590,6 +601,8 @@ int oth_plan_set_average(oth_plan *p, int mode) {
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
     if (mode != OTH_AVERAGE_MEAN && mode != OTH_AVERAGE_MEDIAN) return fail(p->ctx, OTH_ERR_INVALID, "unknown average mode");
+    if (p->ntapers && mode == OTH_AVERAGE_MEDIAN)
+        return refuse_mtm(p, "OTH_AVERAGE_MEDIAN", "the taper loop sums the segments' estimates and keeps no per-segment rows");
     if (p->nseg_total || p->carry)
         return fail(p->ctx, OTH_ERR_STATE, "an accumulation is in progress (oth_welch_finalize or oth_welch_reset first)");
     p->average = mode;
@@ -603,6 +616,7 @@ int oth_welch_segments_dev(oth_plan *p, const void *iq_dev, size_t nsamples, flo
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
     oth_ctx *c = p->ctx;
+    if (p->ntapers) return refuse_mtm(p, "oth_welch_segments_dev", "the taper loop sums the segments' estimates and keeps no per-segment rows");
     if (!iq_dev || !rows_dev) return fail(c, OTH_ERR_INVALID, "bad argument");
     long long nseg = 0;
     if (segments(p, nsamples, &nseg) != OTH_OK) return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
@@ -1059,6 +1073,7 @@ int oth_csd_exec_dev(oth_plan *p, const void *x_dev, const void *y_dev, size_t n
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
     if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_csd_exec_dev");
+    if (p->ntapers) return refuse_mtm(p, "oth_csd_exec_dev", "the taper loop holds one channel");
     oth_ctx *c = p->ctx;
     if (!x_dev || !y_dev) return fail(c, OTH_ERR_INVALID, "x/y is NULL");
     if (p->db) return fail(c, OTH_ERR_UNSUPPORTED, "dB output is not defined for the cross spectrum");
@@ -1075,6 +1090,7 @@ int oth_csd_partial_dev(oth_plan *p, const void *x_dev, const void *y_dev, size_
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
     if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_csd_partial_dev");
+    if (p->ntapers) return refuse_mtm(p, "oth_csd_partial_dev", "the taper loop holds one channel");
     oth_ctx *c = p->ctx;
     if (!x_dev || !y_dev || !sums_out_dev) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (nsamples < (size_t)p->nperseg) return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
@@ -1091,6 +1107,7 @@ int oth_csd_scale_dev(oth_plan *p, const float *sums_dev, uint64_t nseg_total, f
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
     if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_csd_scale_dev");
+    if (p->ntapers) return refuse_mtm(p, "oth_csd_scale_dev", "the taper loop holds one channel");
     oth_ctx *c = p->ctx;
     if (!sums_dev || !nseg_total) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (use_device(c)) return OTH_ERR_HIP;
@@ -1106,6 +1123,7 @@ int oth_csd_exec(oth_plan *p, const void *x, const void *y, size_t nsamples, int
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
     if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_csd_exec");
+    if (p->ntapers) return refuse_mtm(p, "oth_csd_exec", "the taper loop holds one channel");
     oth_ctx *c = p->ctx;
     if (!x || !y) return fail(c, OTH_ERR_INVALID, "x/y is NULL");
     if (p->db) return fail(c, OTH_ERR_UNSUPPORTED, "dB output is not defined for the cross spectrum");

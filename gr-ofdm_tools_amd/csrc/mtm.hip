@@ -1,0 +1,214 @@
+// Multitaper (Thomson) PSD: per segment K orthogonal tapers on the SAME samples, sum_k c_k |FFT((x - mean) v_k)|^2, for
+// every power-of-two size 64..16384 on the LDS Stockham FFT of fft_lds.hip.h.
+//
+// The shape is the opposite of Welch's: few segments (often one: a work()-sized vector, one row per scanner channel), many
+// streams, K transforms per segment.  The work items of a stream are its (segment, taper) pairs, taper index fastest; a
+// workgroup walks one contiguous run of them, so a single segment with K tapers spreads over K workgroups and a long
+// launch over about the resident capacity, each workgroup loading a segment once for all of its tapers.
+//
+// Per segment (only when the run enters a new one): a pilot - the mean of the segment's first 64 samples, formed by the
+// first wave - comes off every sample, then the residual mean (a block sum) comes off.  Taken directly in float32 the
+// mean of a segment under a 35-sigma offset leaves up to 2.8e-4 of relative bin error (4096 points, NW 2, K 3); with the
+// pilot the sums run over values of the noise's size and the worst bin reads 1.1e-5.
+// Per item: taper product into LDS, fft_lds, acc += c_k |X|^2 in registers.  The run's row goes to
+// partial[stream][workgroup][N] in natural bin order (finalize layout 0); the finalize kernels add the rows in a fixed
+// order, so a result depends on the launch shape only - bit-identical from run to run.
+//
+// KEEP (below 8192 points): the detrended samples of the segment stay in registers across its tapers (N / T complex values
+// per thread).  At 16384 points (1024 threads, 128 registers per lane) they do not fit next to the butterflies' operands
+// without scratch (28 bytes per lane), and at 8192 points they cost the second resident workgroup of a CU (134 registers
+// against 82): those builds keep the pilot and the residual mean instead and read the samples again per taper - from L2,
+// one tile against the fourteen tile passes a transform moves through LDS.  Measured on one session, alternating: 8192 points
+// 1.07 against 1.21 ms for 2^25 samples with K 4 and 0.062 against 0.069 ms for 64 single segments with K 7 in favour of
+// re-reading; 4096 points 1.77 against 1.54 ms for 2^26 samples with K 4 in favour of the registers (three workgroups per
+// CU against four).  profiles/mtm_keep_ab.txt.
+#include "fft_lds.hip.h"
+#include "oth_internal.h"
+
+#include <atomic>
+
+namespace oth {
+namespace {
+
+__device__ __forceinline__ float2 mtm_wave_sum(float2 v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        v.x += __shfl_xor(v.x, off, 64);
+        v.y += __shfl_xor(v.y, off, 64);
+    }
+    return v;
+}
+
+// Sum of v over the workgroup in a fixed order; ends with every thread holding it.  `red` has T / 64 + 1 slots.
+template <int T> __device__ __forceinline__ float2 mtm_block_sum(float2 v, float2 *red, int tid) {
+    v = mtm_wave_sum(v);
+    if ((tid & 63) == 0) red[1 + (tid >> 6)] = v;
+    __syncthreads();
+    float2 s = make_float2(0.f, 0.f);
+#pragma unroll
+    for (int w = 0; w < T / 64; ++w) s = cadd(s, red[1 + w]);
+    return s;
+}
+
+constexpr int kMtmPilot = 64;      // samples behind the pilot (the first wave's lanes)
+
+// the mean of the segment's first min(64, nperseg) samples, the same bits in every thread (red[0])
+__device__ __forceinline__ float2 mtm_pilot(const float2 *__restrict__ xs, int nperseg, float2 *red, int tid) {
+    if (tid < kMtmPilot) {
+        const int np = nperseg < kMtmPilot ? nperseg : kMtmPilot;
+        float2 t = tid < np ? xs[tid] : make_float2(0.f, 0.f);
+        t = mtm_wave_sum(t);
+        const float inv = 1.0f / (float)np;
+        if (tid == 0) red[0] = make_float2(t.x * inv, t.y * inv);
+    }
+    __syncthreads();
+    return red[0];
+}
+
+template <int N, int T, bool KEEP> __global__ __launch_bounds__(T) void mtm_kernel(MtmArgs p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float2 *buf = reinterpret_cast<float2 *>(smem);
+    float2 *red = buf + N;      // [0] the pilot, [1 ...] the block sum's wave rows
+    constexpr int NQ = N / T;
+    const int tid0 = threadIdx.x;
+    const int wg = blockIdx.x, W = p.wg_per_stream, stream = blockIdx.y, K = p.ntapers;
+    const long long items = p.nseg * K;
+    const long long i0 = (items * wg) / W, i1 = (items * (wg + 1)) / W;
+    const float2 *xb = p.x + (size_t)stream * p.stream_stride;
+
+    float acc[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = 0.f;
+    float2 v[KEEP ? NQ : 1];
+    float2 pil = make_float2(0.f, 0.f), mean = make_float2(0.f, 0.f);      // of the current segment
+
+    long long s = i0 / K, cur = -1;
+    int k = (int)(i0 - s * K);
+    for (long long i = i0; i < i1; ++i) {
+        // an opaque copy of the thread index per item: the index arithmetic of the seven passes is a handful of integer
+        // instructions, and hoisted out of this loop it would hold registers that the butterflies need
+        int tid = tid0;
+        asm volatile("" : "+v"(tid));
+        const float2 *xs = xb + s * p.step;
+        if (s != cur) {
+            cur = s;
+            if (p.detrend) pil = mtm_pilot(xs, p.nperseg, red, tid);
+            float2 sum = make_float2(0.f, 0.f);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int n = tid + q * T;
+                const float2 r = (n < p.nperseg) ? csub(xs[n], pil) : make_float2(0.f, 0.f);
+                if constexpr (KEEP) v[q] = r;
+                sum = cadd(sum, r);
+            }
+            if (p.detrend) {
+                const float2 tot = mtm_block_sum<T>(sum, red, tid);
+                const float inv = 1.0f / (float)p.nperseg;
+                mean = make_float2(tot.x * inv, tot.y * inv);
+            }
+            if constexpr (KEEP) {
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const int n = tid + q * T;
+                    v[q] = (n < p.nperseg) ? csub(v[q], mean) : make_float2(0.f, 0.f);
+                }
+            }
+        }
+        const float *__restrict__ w = p.tapers + (size_t)k * N;      // zero-extended to N
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int n = tid + q * T;
+            float2 r;
+            if constexpr (KEEP) {
+                r = v[q];
+            } else {
+                r = (n < p.nperseg) ? csub(csub(xs[n], pil), mean) : make_float2(0.f, 0.f);      // the same arithmetic as KEEP
+            }
+            const float wn = w[n];
+            buf[n] = make_float2(r.x * wn, r.y * wn);
+        }
+        __syncthreads();
+        fft_lds<N, T>(buf, p.tw, tid);
+        const float c = p.coef[k];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const float2 X = buf[tid + q * T];
+            acc[q] = fmaf(c, fmaf(X.x, X.x, X.y * X.y), acc[q]);
+        }
+        __syncthreads();
+        if (++k == K) {
+            k = 0;
+            ++s;
+        }
+    }
+    float *dst = p.partial + ((size_t)stream * W + wg) * N;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) dst[tid0 + q * T] = acc[q];
+}
+
+constexpr bool mtm_keep(int n) { return n < 8192; }
+constexpr int kMtmMaxDevices = 64;
+
+size_t mtm_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + 32 * sizeof(float2); }
+
+// The dynamic-LDS attribute of a build (tiles above 64 KiB) is armed once per device, not per launch.
+template <int N> hipError_t mtm_arm(int device) {
+    constexpr int T = generic_threads(N);
+    static std::atomic<bool> armed[kMtmMaxDevices];
+    const size_t lds = mtm_lds_bytes(N);
+    if (lds <= 64 * 1024) return hipSuccess;
+    const bool cached = device >= 0 && device < kMtmMaxDevices;
+    if (cached && armed[device].load(std::memory_order_acquire)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(mtm_kernel<N, T, mtm_keep(N)>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess && cached) armed[device].store(true, std::memory_order_release);
+    return e;
+}
+
+#define OTH_MTM_FOR_EACH_N(X) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192) X(16384)
+
+}  // namespace
+
+int mtm_blocks_per_cu(int nfft, int device) {
+    int n = 0;
+    switch (nfft) {
+#define X(N)                                                                                                        \
+    case N: {                                                                                                       \
+        constexpr int T = generic_threads(N);                                                                       \
+        static std::atomic<int> cached{0};                                                                          \
+        if ((n = cached.load(std::memory_order_acquire)) > 0) return n;                                             \
+        if (mtm_arm<N>(device) != hipSuccess ||                                                                     \
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, mtm_kernel<N, T, mtm_keep(N)>, T, mtm_lds_bytes(N)) != \
+                hipSuccess)                                                                                         \
+            n = 0;                                                                                                  \
+        if (n > 0) cached.store(n, std::memory_order_release);                                                      \
+        break;                                                                                                      \
+    }
+        OTH_MTM_FOR_EACH_N(X)
+#undef X
+        default: break;
+    }
+    return n;
+}
+
+hipError_t launch_mtm(int nfft, const MtmArgs &a, int device, hipStream_t s) {
+    const dim3 grid(a.wg_per_stream, a.nstreams);
+    const size_t lds = mtm_lds_bytes(nfft);
+    hipError_t e;
+    switch (nfft) {
+#define X(N)                                                                                    \
+    case N: {                                                                                   \
+        constexpr int T = generic_threads(N);                                                   \
+        if ((e = mtm_arm<N>(device)) != hipSuccess) return e;                                   \
+        hipLaunchKernelGGL((mtm_kernel<N, T, mtm_keep(N)>), grid, dim3(T), lds, s, a);          \
+        break;                                                                                  \
+    }
+        OTH_MTM_FOR_EACH_N(X)
+#undef X
+        default:
+            return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace oth

@@ -363,4 +363,24 @@ void median_bind_scratch(MedianArgs &a, unsigned *scratch);
 long long median_seg_per_wg(long long nseg, int nfft, int nstreams, int cu_count);
 hipError_t launch_median_select(const MedianArgs &a, hipStream_t s);
 
+// ---- mtm.hip: multitaper PSD, sum_k c_k |FFT((x - mean) v_k)|^2 per segment, nfft a power of two 64 ... 16384 ----------
+struct MtmArgs {
+    const float2 *x;        // device IQ, stream 0
+    const float *tapers;    // [ntapers][nfft], each taper zero-extended behind nperseg
+    const float *coef;      // [ntapers] c_k
+    const float2 *tw;       // W_nfft^k, nfft entries
+    float *partial;         // [nstreams][wg_per_stream][nfft] partial sums, natural bin order
+    long long nseg;         // segments per stream
+    size_t stream_stride;   // samples between streams
+    int nperseg;
+    int step;
+    int detrend;            // != 0: each segment's own mean comes off (pilot + residual)
+    int ntapers;
+    int wg_per_stream;      // workgroups of a stream: each walks a contiguous run of the nseg x ntapers (segment, taper) items
+    int nstreams;
+};
+// resident workgroups per CU of the build (occupancy calculator: needs a device; 0 when it fails)
+int mtm_blocks_per_cu(int nfft, int device);
+hipError_t launch_mtm(int nfft, const MtmArgs &a, int device, hipStream_t s);
+
 }  // namespace oth

@@ -71,6 +71,9 @@ SIGNATURES = {
     'oth_plan_set_hostwait': (C.c_int, [_p, C.c_int]),
     'oth_plan_set_average': (C.c_int, [_p, C.c_int]),
     'oth_welch_segments_dev': (C.c_int, [_p, _p, C.c_size_t, _p, C.c_uint64, _u64p]),
+    'oth_dpss': (C.c_int, [C.c_int, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    'oth_mtm_plan': (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, _f, _f, C.c_int, C.c_int, C.c_double, C.c_int,
+                               C.c_int, _pp]),
     'oth_plan_set_tuning': (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int, C.c_int]),
     'oth_welch_exec': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _u64p]),
     'oth_welch_exec_async': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _u64p]),
@@ -290,6 +293,15 @@ class Context(object):
         if average_code(average) != AVERAGE_MEAN:
             plan.set_average(average)
         return plan
+
+    def mtm_plan(self, nfft, nperseg=None, noverlap=0, nw=4.0, ntapers=None, tapers=None, weights='unity',
+                 detrend=DETREND_CONSTANT, scaling=SCALE_DENSITY, fs=1.0, fftshift=False, trim_bins=0, db=False):
+        """Multitaper (Thomson) PSD plan (oth_mtm_plan): per segment sum_k c_k |FFT((x - mean) v_k)|^2 over ntapers
+        tapers, mean over segments.  tapers=None: the Slepian sequences windows.dpss(nperseg, nw, ntapers), ntapers=None
+        meaning int(2 nw) - 1; or an array [ntapers, nperseg].  weights: 'unity', 'eigen' (the concentration ratios;
+        Slepian tapers only) or ntapers non-negative values.  -> a WelchPlan-compatible MtmPlan."""
+        return MtmPlan(self, nfft, nperseg, noverlap, nw, ntapers, tapers, weights, detrend, scaling, fs, fftshift,
+                       trim_bins, db)
 
     def chain(self, nfft, window=None, fftshift=True, epilogue=EPI_MAG2, keep_one_in_n=1):
         return Chain(self, nfft, window, fftshift, epilogue, keep_one_in_n)
@@ -642,6 +654,70 @@ def _csd_scale_dev(self, sums_dptr, nseg_total, pxx=0, pyy=0, pxy=0, cxy=0):
 WelchPlan.csd_exec_dev = _csd_exec_dev
 WelchPlan.csd_partial_dev = _csd_partial_dev
 WelchPlan.csd_scale_dev = _csd_scale_dev
+
+
+def mtm_weights(weights, ntapers, slepian=True):
+    """'unity' -> None (uniform), 'eigen' -> 'eigen' (the plan's concentration ratios: its own Slepian tapers only), an
+    array -> float32 [ntapers]; anything the library would refuse is a ValueError here, before it is called."""
+    if isinstance(weights, str):
+        if weights == 'unity':
+            return None
+        if weights != 'eigen':
+            raise ValueError("weights must be 'unity', 'eigen' or an array, not %r" % (weights,))
+        if not slepian:
+            raise ValueError("weights='eigen' needs the plan's own Slepian tapers (tapers=None)")
+        return 'eigen'
+    w = np.asarray(weights, np.float64)
+    if w.shape != (ntapers,):
+        raise ValueError('weights must have ntapers=%d entries' % ntapers)
+    w32 = np.ascontiguousarray(w, np.float32)
+    if not np.all(np.isfinite(w32)) or np.any(w < 0.0) or not w32.sum() > 0.0:
+        raise ValueError('weights must be finite, non-negative and have a positive sum')
+    return w32
+
+
+class MtmPlan(WelchPlan):
+    """A WelchPlan whose averaging launch is the multitaper kernel: exec / exec_async / poll / wait / exec_dev /
+    partial_dev / scale_dev / accumulate / finalize / reset as WelchPlan's; the median average, the per-segment rows,
+    the cross spectrum, KERNEL_TUNED and build variants raise HipError (OTH_ERR_UNSUPPORTED)."""
+
+    def __init__(self, ctx, nfft, nperseg, noverlap, nw, ntapers, tapers, weights, detrend, scaling, fs, fftshift,
+                 trim_bins, db):
+        from . import windows
+        self.ctx = ctx
+        self._tickets, self._last_ticket, self._tickets_lock = set(), 0, threading.Lock()
+        nperseg = int(nfft if nperseg is None else nperseg)
+        noverlap = int(noverlap)
+        self.nfft, self.nperseg, self.noverlap = int(nfft), nperseg, noverlap
+        self.step = nperseg - noverlap
+        ratios, slepian = None, tapers is None
+        if slepian:
+            ntapers = int(2 * nw) - 1 if ntapers is None else int(ntapers)
+            if ntapers < 1:
+                raise ValueError('ntapers must be at least 1 (nw=%r gives int(2 nw) - 1 = %d)' % (nw, ntapers))
+        else:
+            tapers = np.ascontiguousarray(tapers, np.float32)
+            if tapers.ndim != 2 or tapers.shape[1] != nperseg or (ntapers is not None and tapers.shape[0] != int(ntapers)):
+                raise ValueError('tapers must have shape [ntapers, nperseg=%d]' % nperseg)
+            ntapers = tapers.shape[0]
+        w = mtm_weights(weights, ntapers, slepian)
+        if slepian:
+            tapers, ratios = windows.dpss(nperseg, nw, ntapers, return_ratios=True)
+        if isinstance(w, str):
+            w = np.ascontiguousarray(ratios, np.float32)
+        t = np.ascontiguousarray(tapers, np.float32)
+        self.ntapers = ntapers
+        self.tapers, self.ratios = t, ratios
+        h = C.c_void_p()
+        ctx.check(ctx.lib.oth_mtm_plan(ctx.h, int(nfft), nperseg, noverlap, self.ntapers, _fptr(t),
+                                       _fptr(w) if w is not None else None, int(detrend), int(scaling), float(fs),
+                                       1 if fftshift else 0, int(trim_bins), C.byref(h)), 'oth_mtm_plan')
+        self.h = h
+        n = C.c_int()
+        ctx.check(ctx.lib.oth_plan_out_len(h, C.byref(n)), 'oth_plan_out_len')
+        self.out_len = n.value
+        if db:
+            ctx.check(ctx.lib.oth_plan_set_output_db(h, 1), 'oth_plan_set_output_db')
 
 
 class Chain(object):

@@ -45,6 +45,17 @@ def _welch_plan(ctx, nfft, window_name, Sf, npts=None, use='exec', average='mean
     return (key, make) if use == 'async' else ctx.cached_plan(key, make)
 
 
+def _mtm_plan(ctx, nfft, Sf, npts=None, NW=4.0, K=None, use='exec'):
+    """The multitaper estimate of one capture: Slepian tapers of half-bandwidth NW over nperseg = min(nfft, len) samples (the
+    nperseg rule of _welch_plan: a vector shorter than nfft is one zero-padded segment), K = int(2 NW) - 1 of them by
+    default, unit weights, density scaling, no overlap, fftshift.  -> (cache key, factory) with use='async', else the plan."""
+    nperseg = nfft if npts is None else min(int(nfft), int(npts))
+    K = int(2 * NW) - 1 if K is None else int(K)
+    key = ('mtm', use, nfft, nperseg, float(NW), K, float(Sf))
+    make = lambda: ctx.mtm_plan(nfft, nperseg=nperseg, noverlap=0, nw=float(NW), ntapers=K, fs=float(Sf), fftshift=True)
+    return (key, make) if use == 'async' else ctx.cached_plan(key, make)
+
+
 def _exec_async_pooled(ctx, key, make, vector):
     """exec_async() on the first plan of the shape's pool (cache keys key + (0,), key + (1,), ...) whose next ticket lands
     in an output-ring slot no uncollected ticket holds (WelchPlan.next_ticket_slot_free: the library keeps launch t in
@@ -123,6 +134,21 @@ def _enqueue_fft(vector, nFFT, Sf, ctx):
         lambda: ctx.welch_plan(nFFT, nperseg=npts, noverlap=0, window=windows.flattop(total)[:nFFT],
                                detrend=_hip.DETREND_NONE, scaling=_hip.SCALE_RAW, fftshift=True), vector)
     return plan, ticket, (lambda psd: psd / np.float32(nFFT))
+
+
+def _enqueue_mtm(vector, nFFT, Sf, ctx, NW=4.0, K=7):
+    """The scan's PSD as a multitaper estimate (NW 4, K 7) as a ticket: -> (plan, ticket, post)."""
+    plan, ticket = _exec_async_pooled(ctx, *_mtm_plan(ctx, nFFT, Sf, len(vector), NW, K, use='async'), vector=vector)
+    return plan, ticket, None
+
+
+def src_power_mtm(vector, npts, nFFT, Fr, Sf, bb_freqs, srch_bins, NW=4.0, K=None, ctx=None):
+    """src_power_welch with the multitaper estimate in place of the flat-top Welch PSD: -> (psd, axis, channel sums)."""
+    ctx = ctx or _hip.default_context()
+    plan, ticket, _ = _enqueue_mtm(vector, nFFT, Sf, ctx, NW, K)
+    psd = plan.wait(ticket)
+    axis = np.fft.fftshift(np.fft.fftfreq(nFFT, 1.0 / Sf))
+    return psd, axis, _plain_channel_sums(psd, Fr, Sf, bb_freqs, srch_bins, ctx)
 
 
 def src_power_welch(vector, npts, nFFT, Fr, Sf, bb_freqs, srch_bins, ctx=None, average='mean'):
@@ -215,20 +241,34 @@ def welch_power_estimate(vector, nFFT, Sf, ctx=None, average='mean'):
     return float(np.sum(_welch_plan(ctx, nFFT, 'hann', Sf, len(vector), average=average).exec(vector), dtype=np.float64))
 
 
+def mtm_plot_dB(data, Sf, fc, nfft, NW=4.0, K=None, ctx=None):
+    """welch_plot_dB with the multitaper estimate (Slepian tapers, half-bandwidth NW, K tapers)."""
+    ctx = ctx or _hip.default_context()
+    psd = _mtm_plan(ctx, nfft, Sf, len(data), NW, K).exec(data)
+    axis = np.fft.fftshift(np.fft.fftfreq(nfft, 1.0 / Sf))
+    return [item + fc for item in axis], [10 * math.log10(item + 1e-20) for item in psd]
+
+
+def mtm_power_estimate(vector, nFFT, Sf, NW=4.0, K=None, ctx=None):
+    """welch_power_estimate with the multitaper estimate: the sum over bins of the density."""
+    ctx = ctx or _hip.default_context()
+    return float(np.sum(_mtm_plan(ctx, nFFT, Sf, len(vector), NW, K).exec(vector), dtype=np.float64))
+
+
 class SpectrumScan(object):
     """The legacy sensor's scan (reference: ofdm_cr_tools.py:471-537; its matplotlib branch is not carried over), split
     where the GPU works: the constructor enqueues the PSD of the chosen method ('welch': flat-top Welch, 'fft': one
-    flat-top periodogram) through ``oth_welch_exec_async`` and returns at once - the sample buffer may be reused;
+    flat-top periodogram, 'mtm': the multitaper estimate with NW 4 and 7 Slepian tapers) through ``oth_welch_exec_async`` and returns at once - the sample buffer may be reused;
     ``poll(noise_estimate)`` returns None while the launch is running, ``wait(noise_estimate)`` blocks.  Both finish with
     the channel sums on the device, the noise estimate ``ne <- (1 - a) ne + a min(p)``, the threshold ``ne * thr_leveler``
     and the channel frequencies whose power exceeds it: -> (threshold, channel powers, noise estimate, occupied [Hz])."""
-    _ENQUEUE = {'welch': _enqueue_welch, 'fft': _enqueue_fft}
+    _ENQUEUE = {'welch': _enqueue_welch, 'fft': _enqueue_fft, 'mtm': _enqueue_mtm}
 
     def __init__(self, vct_sample, fc, channel_rate, srch_bw, n_fft, samp_rate, method, thr_leveler, alpha_avg, ctx=None):
         try:
             enqueue = self._ENQUEUE[method]
         except KeyError:
-            raise ValueError("method must be 'welch' or 'fft'")
+            raise ValueError("method must be 'welch', 'fft' or 'mtm'")
         self.ctx = ctx or _hip.default_context()
         self.nfft = n_fft or int(2 ** math.ceil(math.log(len(vct_sample), 2)))
         self.samp_rate, self.thr_leveler, self.alpha_avg = samp_rate, thr_leveler, alpha_avg

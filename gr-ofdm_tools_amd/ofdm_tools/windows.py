@@ -5,8 +5,11 @@ string (``window='hann'`` default at ofdm_cr_tools.py:322,342, ``'flattop'`` at
 ofdm_cr_tools.py:214 and spectrum_sweeper.py:263); ``blackmanharris`` mirrors
 ``gnuradio.filter.window.blackmanharris`` (symmetric, psd_logger.py:47,
 local_worker.py:62) and ``flattop`` the symmetric ``sg.flattop(npts)`` of
-ofdm_cr_tools.py:175.
+ofdm_cr_tools.py:175.  ``dpss`` returns the Slepian tapers of the multitaper plans
+(``scipy.signal.windows.dpss`` with ``Kmax``), computed by the library's host-only ``oth_dpss``.
 """
+import ctypes
+
 import numpy as np
 
 _FLATTOP = (0.21557895, 0.41663158, 0.277263158, 0.083578947, 0.006947368)
@@ -44,3 +47,21 @@ def flattop(npts):
     if npts == 1:
         return np.ones(1)
     return _cosine_sum(_FLATTOP, npts, npts - 1)
+
+
+def dpss(n, nw, kmax, return_ratios=False):
+    """scipy.signal.windows.dpss(n, nw, kmax, return_ratios=...): the kmax Slepian sequences of length n with the largest
+    concentration in [-nw / n, nw / n], float64 [kmax, n], unit L2 norm, SciPy's signs; with return_ratios also their
+    concentration ratios, float64 [kmax].  Runs on the host (oth_dpss: no context, no GPU)."""
+    from . import _hip
+    n, kmax, nw = int(n), int(kmax), float(nw)
+    if n < 2 or not 0.0 < nw < 0.5 * n or not 1 <= kmax <= n:
+        raise ValueError('dpss needs n >= 2, 0 < nw < n / 2 and 1 <= kmax <= n (got n=%d, nw=%r, kmax=%d)' % (n, nw, kmax))
+    lib = _hip.load()
+    tapers = np.empty((kmax, n), np.float64)
+    ratios = np.empty(kmax, np.float64)
+    dp = ctypes.POINTER(ctypes.c_double)
+    rc = lib.oth_dpss(n, nw, kmax, tapers.ctypes.data_as(dp), ratios.ctypes.data_as(dp) if return_ratios else None)
+    if rc != _hip.OK:
+        raise _hip.HipError(rc, 'oth_dpss', lib.oth_last_error(None).decode())
+    return (tapers, ratios) if return_ratios else tapers

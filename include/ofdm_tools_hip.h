@@ -245,6 +245,40 @@ int oth_plan_set_average(oth_plan *plan, int mode);
 int oth_welch_segments_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, float *rows_dev, uint64_t capacity_rows,
                            uint64_t *nseg_out);
 
+/* MULTITAPER (Thomson) PSD.  Additions inside ABI 6 (OTH_ABI_VERSION stays 6): a caller probes for them by the symbols
+ * oth_dpss / oth_mtm_plan.  The estimator for SHORT captures - one work()-sized vector, one row per scanner channel -
+ * where Welch can only lower the variance by cutting the capture into shorter segments: K orthogonal Slepian tapers on the
+ * same samples give the variance of K averages at a known bandwidth of 2 NW bins.
+ *
+ * oth_dpss: the kmax Slepian sequences (DPSS) of length n and time-half-bandwidth nw with the largest concentration, as
+ * scipy.signal.windows.dpss(n, nw, kmax, return_ratios=True): tapers[k][n] by falling eigenvalue, each of unit L2 norm,
+ * SciPy's signs (even orders: positive sum; odd orders: the first entry whose square exceeds max(1e-7, 1 / n) is
+ * positive); ratios[k] (may be NULL) the concentration sum_{m,n} v_k[m] A[m - n] v_k[n], A[0] = 2 W, A[d] =
+ * sin(2 pi W d) / (pi d), W = nw / n.  Host only, double throughout, no context and no GPU: eigenpairs of the symmetric
+ * tridiagonal Slepian matrix by bisection and inverse iteration, O(n) memory (n = 16384, kmax = 7: 0.14 s on one core).  Needs n >= 2,
+ * 0 < nw < n / 2, 1 <= kmax <= n; anything else is OTH_ERR_INVALID (text in oth_last_error(NULL)). */
+int oth_dpss(int n, double nw, int kmax, double *tapers, double *ratios);
+/* oth_mtm_plan: an ordinary oth_plan - the exec forms, oth_plan_set_output_db, _set_hostwait, _out_len and _destroy apply
+ * unchanged.  Per stream: segments as oth_welch_plan's; each segment's own mean comes off (every detrend mode other than
+ * OTH_DETREND_NONE means this); X_k = FFT_nfft((x_s - m_s) v_k), zero-padded when nperseg < nfft; the segment's estimate
+ * is sum_k c_k |X_k|^2 with the weights a_k normalised to sum 1 (weights == NULL: uniform) and
+ *   OTH_SCALE_DENSITY  c_k = a_k / sum_n v_k[n]^2, the result over fs
+ *   OTH_SCALE_RAW      c_k = a_k
+ *   OTH_SCALE_OVER_N2  c_k = a_k, the result over nfft^2;
+ * the output is the mean over segments, then the plan's fftshift, trim and dB.  One taper and NULL weights: the Welch plan
+ * of that window.  tapers: [ntapers][nperseg] host floats (any real tapers; oth_dpss gives Slepian's).
+ * nfft: a power of two from 64 to 16384 (others: OTH_ERR_UNSUPPORTED); 1 <= nperseg <= nfft, any value; 0 <= noverlap <
+ * nperseg; 1 <= ntapers <= 64; weights finite, non-negative, with a positive sum.
+ * One launch per call whatever ntapers (csrc/mtm.hip: the (segment, taper) pairs of a stream are spread over workgroups in
+ * contiguous runs, a segment is loaded once for all of a run's tapers); sums in a fixed order, bit-identical run to run.
+ * Works: oth_welch_exec, _exec_async / _poll / _wait, _exec_dev with nstreams (at most 65535), _partial_dev / _scale_dev,
+ * _accumulate / _finalize / _reset.  Refused with OTH_ERR_UNSUPPORTED and the reason in oth_last_error(): OTH_SCALE_SPECTRUM
+ * (an odd taper sums to zero), oth_plan_set_average(MEDIAN), oth_welch_segments_dev, every oth_csd_* call,
+ * oth_plan_set_kernel(TUNED), a non-empty variant in oth_plan_set_tuning.  oth_plan_set_schedule is accepted and has no
+ * effect. */
+int oth_mtm_plan(oth_ctx *ctx, int nfft, int nperseg, int noverlap, int ntapers, const float *tapers, const float *weights,
+                 int detrend, int scaling, double fs, int fftshift, int trim_bins, oth_plan **out);
+
 /* one-shot: nsamples complex64 -> psd_out[nfft - 2*trim] (host).  Blocking: returns when the PSD is in psd_out.  The
  * last launch writes the row and a completion word into pinned host memory and the call polls that word (no interrupt
  * wake-up; after 20 ms it falls back to a stream synchronisation, which also reports a failed launch;
