@@ -1093,6 +1093,7 @@ int oth_csd_partial_dev(oth_plan *p, const void *x_dev, const void *y_dev, size_
     if (p->ntapers) return refuse_mtm(p, "oth_csd_partial_dev", "the taper loop holds one channel");
     oth_ctx *c = p->ctx;
     if (!x_dev || !y_dev || !sums_out_dev) return fail(c, OTH_ERR_INVALID, "bad argument");
+    if (p->db) return fail(c, OTH_ERR_UNSUPPORTED, "dB output is not defined for the cross spectrum");
     if (nsamples < (size_t)p->nperseg) return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
     if (use_device(c)) return OTH_ERR_HIP;
     const int N = p->nfft;
@@ -1110,6 +1111,7 @@ int oth_csd_scale_dev(oth_plan *p, const float *sums_dev, uint64_t nseg_total, f
     if (p->ntapers) return refuse_mtm(p, "oth_csd_scale_dev", "the taper loop holds one channel");
     oth_ctx *c = p->ctx;
     if (!sums_dev || !nseg_total) return fail(c, OTH_ERR_INVALID, "bad argument");
+    if (p->db) return fail(c, OTH_ERR_UNSUPPORTED, "dB output is not defined for the cross spectrum");
     if (use_device(c)) return OTH_ERR_HIP;
     HIPCHK(c, launch_csd_scale(sums_dev, p->nfft, p->scale / (double)nseg_total, p->fftshift, p->trim, pxx_dev,
                                pyy_dev, pxy_dev, cxy_dev, c->stream));

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(T4, 3) void csd4096_kernel(WelchArgs p) {
                 axx[k2] = fmaf(x.x, x.x, fmaf(x.y, x.y, axx[k2]));
                 ayy[k2] = fmaf(y.x, y.x, fmaf(y.y, y.y, ayy[k2]));
                 are[k2] = fmaf(x.x, y.x, fmaf(x.y, y.y, are[k2]));      // conj(X) Y
-                aim[k2] = fmaf(x.x, y.y, fmaf(-x.y, y.x, aim[k2]));
+                aim[k2] += cross_im(x, y);
             }
         }
         if (sched == 0) break;

@@ -307,7 +307,7 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
                 axx[j] = fmaf(X.x, X.x, fmaf(X.y, X.y, axx[j]));
                 ayy[j] = fmaf(Y.x, Y.x, fmaf(Y.y, Y.y, ayy[j]));
                 are[j] = fmaf(X.x, Y.x, fmaf(X.y, Y.y, are[j]));
-                aim[j] = fmaf(X.x, Y.y, fmaf(-X.y, Y.x, aim[j]));
+                aim[j] += cross_im(X, Y);
             }
             item = next_item();
         }
@@ -361,7 +361,11 @@ hipError_t launch_csd_tuned4096ws(const WelchArgs &a_in, hipStream_t s) {
             if (!zero_fd[dev]) {
                 float4 *z = nullptr;
                 hipError_t e = hipMalloc(&z, 256 * sizeof(float4));
-                if (e == hipSuccess) e = hipMemset(z, 0, 256 * sizeof(float4));      // synchronous: visible to every stream after it
+                // hipMemset of device memory may return before the fill has run, and a non-blocking stream is not ordered
+                // behind it: the first launch then read whatever the block held before (a freed window-spectrum table of
+                // an earlier plan took the DC line out of a plan WITHOUT detrend).  Once per device: wait for it.
+                if (e == hipSuccess) e = hipMemset(z, 0, 256 * sizeof(float4));
+                if (e == hipSuccess) e = hipDeviceSynchronize();
                 if (e != hipSuccess) return e;
                 zero_fd[dev] = z;
             }

@@ -313,7 +313,7 @@ template <int T, int STORE, bool TWLDS, bool C1> __global__ __launch_bounds__(T)
                             acc[0][q] = fmaf(Xv.x, Xv.x, fmaf(Xv.y, Xv.y, acc[0][q]));
                             acc[1][q] = fmaf(Yv.x, Yv.x, fmaf(Yv.y, Yv.y, acc[1][q]));
                             acc[2][q] = fmaf(Xv.x, Yv.x, fmaf(Xv.y, Yv.y, acc[2][q]));       // conj(X) Y
-                            acc[3][q] = fmaf(Xv.x, Yv.y, fmaf(-Xv.y, Yv.x, acc[3][q]));
+                            acc[3][q] += cross_im(Xv, Yv);
                         }
                     } else {
                         const int nat = i * a.nat_i + t * a.nat_t + c * a.nat_c;

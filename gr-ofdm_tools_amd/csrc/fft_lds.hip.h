@@ -20,6 +20,18 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
 }
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+// Im(conj(X) Y) = X.x Y.y - X.y Y.x for the two-channel sums, with BOTH products rounded before they are subtracted (no
+// contraction into an fma): the form is antisymmetric in X and Y bit for bit, so a channel against itself gives exactly 0 in
+// every segment and Im Pxy = 0 - as numpy's complex product does.  fmaf(X.x, Y.y, fmaf(-X.y, Y.x, acc)) left the rounding
+// error of one product per segment there (|Im Pxy| ~ 3e-8 Pxx).  Two VALU operations more per bin and segment pair.
+// The empty asm statements make the products opaque: under -ffp-contract=fast the backend fuses a multiply into the
+// subtraction whatever `#pragma clang fp contract(off)` says.
+__device__ __forceinline__ float cross_im(float2 X, float2 Y) {
+    float a = X.x * Y.y, b = X.y * Y.x;
+    asm("" : "+v"(a));
+    asm("" : "+v"(b));
+    return a - b;
+}
 // WelchArgs.pilot / SegArgs.pilot of one stream as a wave-uniform value (two scalar registers; zero without a table).
 // The pilot of a stream: the average of its eight probe means (oth_internal.h: kPilotProbes), added in one fixed order so
 // that every wave of the launch holds the same bits.  (Round 5 tried the MEDIAN of the probe means, so that one probe

@@ -176,7 +176,7 @@ template <int L2, bool CSD> __global__ __launch_bounds__(256) void tl_k2_kernel(
                 acc[0][q] = fmaf(X[q].x, X[q].x, fmaf(X[q].y, X[q].y, acc[0][q]));
                 acc[1][q] = fmaf(Y[q].x, Y[q].x, fmaf(Y[q].y, Y[q].y, acc[1][q]));
                 acc[2][q] = fmaf(X[q].x, Y[q].x, fmaf(X[q].y, Y[q].y, acc[2][q]));       // conj(X) Y
-                acc[3][q] = fmaf(X[q].x, Y[q].y, fmaf(-X[q].y, Y[q].x, acc[3][q]));
+                acc[3][q] += cross_im(X[q], Y[q]);
             }
         }
     }

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(T) void welch_generic_kernel(WelchArgs p) {
                 acc[1][q] = fmaf(Y.x, Y.x, fmaf(Y.y, Y.y, acc[1][q]));
                 // conj(X) * Y
                 acc[2][q] = fmaf(X[q].x, Y.x, fmaf(X[q].y, Y.y, acc[2][q]));
-                acc[3][q] = fmaf(X[q].x, Y.y, fmaf(-X[q].y, Y.x, acc[3][q]));
+                acc[3][q] += cross_im(X[q], Y);
             }
             __syncthreads();
         }

@@ -51,6 +51,25 @@ __device__ __forceinline__ int unshifted(int ks, int n) {
     return p >= n ? p - n : p;
 }
 
+// Output stage of the two-channel path, shared by the finalize kernels and csd_scale_kernel.  An inf sample leaves NaN in
+// every bin of SciPy's result (its transform multiplies the inf by twiddle zeros); here the register butterflies of the
+// 4096-point kernels leave inf where all terms of a bin agree in sign (56 bins of 4096 measured) and NaN elsewhere, the LDS
+// kernels NaN everywhere.  SciPy's result is the specification (include/ofdm_tools_hip.h): a power that is not finite, and
+// a cross term with a part that is not finite, leave as NaN on every route.  Cxy = |Sxy|^2 / (Sxx Syy) on the raw sums
+// (0 / 0 = NaN for a silent channel, inf / inf = NaN).
+__device__ __forceinline__ void csd_store(double sxx, double syy, double sre, double sim, double scale, size_t o, float *pxx,
+                                          float *pyy, float *pxy, float *cxy) {
+    const double nan = __builtin_nan("");
+    const bool cross_ok = isfinite(sre) && isfinite(sim);
+    if (pxx) pxx[o] = (float)(isfinite(sxx) ? sxx * scale : nan);
+    if (pyy) pyy[o] = (float)(isfinite(syy) ? syy * scale : nan);
+    if (pxy) {
+        pxy[2 * o] = (float)(cross_ok ? sre * scale : nan);
+        pxy[2 * o + 1] = (float)(cross_ok ? sim * scale : nan);
+    }
+    if (cxy) cxy[o] = (float)((sre * sre + sim * sim) / (sxx * syy));
+}
+
 // Completion word for a polling host (FinalizeArgs.host_seq; round 5).  Called by EVERY thread of the block after its
 // last output store (the outputs of such a launch are pinned host memory).  Every wave that stored outputs makes them
 // visible at system scope with a RELEASE fence (L2 write-back + wait for the wave's stores; no acquire: an acquire would
@@ -114,14 +133,7 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinalizeArgs a) {
                 a.out0[o] = a.db ? (float)(10.0 * log10(v)) : (float)v;
             }
         } else {
-            const double pxx = s[0] * a.scale, pyy = s[1] * a.scale, re = s[2] * a.scale, im = s[3] * a.scale;
-            if (a.out0) a.out0[o] = (float)pxx;
-            if (a.out1) a.out1[o] = (float)pyy;
-            if (a.out2) {
-                a.out2[2 * o] = (float)re;
-                a.out2[2 * o + 1] = (float)im;
-            }
-            if (a.out3) a.out3[o] = (float)((s[2] * s[2] + s[3] * s[3]) / (s[0] * s[1]));
+            csd_store(s[0], s[1], s[2], s[3], a.scale, o, a.out0, a.out1, a.out2, a.out3);
         }
     }
     finalize_signal<false>(a);      // the stores above are wave 0's (slice 0)
@@ -198,13 +210,7 @@ __global__ __launch_bounds__(256) void finalize_wide_kernel(FinalizeArgs a) {
                 a.out0[o] = a.db ? (float)(10.0 * log10(v)) : (float)v;
             }
         } else {      // as finalize_kernel: Pxx, Pyy, Pxy, Cxy
-            if (a.out0) a.out0[o] = (float)(t[0] * a.scale);
-            if (a.out1) a.out1[o] = (float)(t[1] * a.scale);
-            if (a.out2) {
-                a.out2[2 * o] = (float)(t[2] * a.scale);
-                a.out2[2 * o + 1] = (float)(t[3] * a.scale);
-            }
-            if (a.out3) a.out3[o] = (float)((t[2] * t[2] + t[3] * t[3]) / (t[0] * t[1]));
+            csd_store(t[0], t[1], t[2], t[3], a.scale, o, a.out0, a.out1, a.out2, a.out3);
         }
     }
     finalize_signal<false>(a);      // the stores above are wave 0's (threads < POS)
@@ -367,13 +373,7 @@ __global__ void csd_scale_kernel(const float *sums, int nfft, double scale, int 
     const int ks = i + trim;
     const int k = fftshift ? unshifted(ks, nfft) : ks;
     const double xx = sums[k], yy = sums[nfft + k], re = sums[2 * nfft + 2 * k], im = sums[2 * nfft + 2 * k + 1];
-    if (pxx) pxx[i] = (float)(xx * scale);
-    if (pyy) pyy[i] = (float)(yy * scale);
-    if (pxy) {
-        pxy[2 * i] = (float)(re * scale);
-        pxy[2 * i + 1] = (float)(im * scale);
-    }
-    if (cxy) cxy[i] = (float)((re * re + im * im) / (xx * yy));
+    csd_store(xx, yy, re, im, scale, (size_t)i, pxx, pyy, pxy, cxy);
 }
 
 hipError_t launch_csd_scale(const float *sums, int nfft, double scale, int fftshift, int trim, float *pxx, float *pyy,

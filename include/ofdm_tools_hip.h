@@ -318,7 +318,20 @@ int oth_welch_reset(oth_plan *plan);
  * Semantics of scipy.signal.csd / coherence with the plan's Welch parameters;
  * produces the first input of coherence_detector (coherence_detector.py:45).
  * Outputs (host, natural FFT order unless the plan has fftshift): pxx, pyy,
- * cxy are float[nfft]; pxy is interleaved re,im float[2*nfft].  Any may be NULL. */
+ * cxy are float[nfft]; pxy is interleaved re,im float[2*nfft].  Any may be NULL.
+ *
+ * Degenerate inputs: SciPy's result is the specification, on every route (tests/test_csd_gpu.py).  A silent channel
+ * gives Pyy = Pxy = 0 exactly and Cxy = 0 / 0 = NaN in every bin.  A NaN or inf sample in one channel makes that channel's
+ * power, Pxy and Cxy NaN in every bin and leaves the other channel's power untouched (the output stage writes NaN for
+ * every sum that is not finite - an inf sample leaves NaN in all bins of SciPy's transform, inf in some of this one's -
+ * so sums that overflow float32 read NaN too, never inf).  A channel against itself gives
+ * Im Pxy = 0 exactly (Im(conj(X) Y) is formed from two rounded products, antisymmetric bit for bit) and Cxy = 1.
+ * Gains that are powers of two leave Cxy unchanged.
+ *
+ * dB output is not defined for a complex cross spectrum: on a plan with oth_plan_set_output_db(1) EVERY oth_csd_* call -
+ * _exec, _exec_dev, and the raw sums and scale stage _partial_dev / _scale_dev with them - returns OTH_ERR_UNSUPPORTED
+ * before anything is launched; the plan and the context stay usable.  OTH_KERNEL_TUNED covers the two-channel path at
+ * nfft = nperseg = 4096 only and is refused (OTH_ERR_UNSUPPORTED) elsewhere; the plan works again under OTH_KERNEL_AUTO. */
 int oth_csd_exec(oth_plan *plan, const void *x, const void *y, size_t nsamples, int src_is_device,
                  float *pxx, float *pyy, float *pxy, float *cxy, uint64_t *nseg_out);
 
