@@ -71,15 +71,6 @@ void host_fft_pow2(std::vector<double> &re, std::vector<double> &im) {      // i
     }
 }
 
-
-void any_tables_free(AnyTables &t) {
-    if (t.chirp) hipFree(t.chirp);
-    if (t.midtab) hipFree(t.midtab);
-    if (t.ws) hipFree(t.ws);
-    if (t.mean) hipFree(t.mean);
-    t = AnyTables{};
-}
-
 // tables of a length-nfft transform; the caller synchronises the stream before the host vectors die (done here)
 int any_tables_init(oth_ctx *c, int nfft, AnyTables *t) {
     if (any_describe(nfft, &t->sh))
@@ -105,13 +96,12 @@ int any_tables_init(oth_ctx *c, int nfft, AnyTables *t) {
         }
         host_fft_pow2(bre, bim);
         for (int k = 0; k < M; ++k) mt[k] = make_float2((float)(bre[k] / M), (float)(bim[k] / M));
-        hipError_t e = hipMalloc(&t->chirp, sizeof(float2) * N);
-        if (e == hipSuccess) e = hipMalloc(&t->midtab, sizeof(float2) * M);
-        if (e == hipSuccess) e = hipMemcpyAsync(t->chirp, ch.data(), sizeof(float2) * N, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(t->midtab, mt.data(), sizeof(float2) * M, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        hipError_t e = t->chirp.upload(c, ch.data(), sizeof(float2) * N);
+        if (e == hipSuccess) e = t->midtab.upload(c, mt.data(), sizeof(float2) * M);
+        hipError_t es = hipStreamSynchronize(c->stream);      // also after a failure: the host vectors die here
+        if (e == hipSuccess) e = es;
         if (e != hipSuccess) {
-            any_tables_free(*t);
+            *t = AnyTables{};
             return fail(c, OTH_ERR_HIP, std::string("any-length tables: ") + hipGetErrorString(e));
         }
     }
@@ -152,10 +142,10 @@ int any_run(oth_ctx *c, AnyTables &t, const float2 *x, const float2 *y, long lon
     if (B < 1) B = 1;
     if (B > nseg) B = nseg;
     int rc;
-    if (two && (rc = ensure(c, &t.ws, &t.ws_cap, sizeof(float2) * (size_t)L * nch * (size_t)B))) return rc;
+    if (two && (rc = t.ws.ensure(c, sizeof(float2) * (size_t)L * nch * (size_t)B))) return rc;
     // (the fast two-level route keeps sub-block sums there instead: at most B * seg_step / kTlSub + nperseg / kTlSub of them)
     const size_t nsums = nch * ((size_t)B * (size_t)(seg_step / kTlSub + 1) + (size_t)(nperseg / kTlSub) + 1);
-    if (detrend && (rc = ensure(c, &t.mean, &t.mean_cap, sizeof(float4) * std::max(nch * (size_t)B, nsums)))) return rc;
+    if (detrend && (rc = t.mean.ensure(c, sizeof(float4) * std::max(nch * (size_t)B, nsums)))) return rc;
     AnyFftDesc d_one{}, d_col{}, d_row{};
     if (two) {
         any_make_desc(sh.L1, sh.C, t.tw, L, &d_col);
@@ -175,12 +165,12 @@ int any_run(oth_ctx *c, AnyTables &t, const float2 *x, const float2 *y, long lon
         a.seg_step = seg_step;
         a.nperseg = nperseg;
         a.win = win;
-        a.mean = detrend ? t.mean : nullptr;
+        a.mean = detrend ? t.mean.get() : nullptr;
         a.mean_ch_stride = (size_t)B;
-        a.ws = t.ws;
+        a.ws = t.ws.get();
         a.ws_seg_stride = (size_t)L;
         a.ws_ch_stride = (size_t)L * (size_t)B;
-        a.midtab = t.midtab;
+        a.midtab = t.midtab.get();
         a.partial = partial;
         a.nbins = N;
         a.first_chunk = s0 == 0;
@@ -195,32 +185,32 @@ int any_run(oth_ctx *c, AnyTables &t, const float2 *x, const float2 *y, long lon
             const bool blocks = detrend && nperseg % kTlSub == 0 && seg_step % kTlSub == 0;      // (t.mean holds B float4 = B double2)
             TlArgs ta{};
             ta.x = x, ta.y = y, ta.first = cfirst, ta.seg_step = seg_step, ta.nperseg = nperseg, ta.win = win;
-            ta.ws = t.ws, ta.ws_seg_stride = (size_t)L, ta.ws_ch_stride = (size_t)L * (size_t)B, ta.nseg = nb, ta.tw = t.tw;
+            ta.ws = t.ws.get(), ta.ws_seg_stride = (size_t)L, ta.ws_ch_stride = (size_t)L * (size_t)B, ta.nseg = nb, ta.tw = t.tw;
             ta.partial = partial, ta.first_chunk = s0 == 0;
             if (blocks) {
                 ta.nsub = nperseg / kTlSub, ta.sub_step = (int)(seg_step / kTlSub);
                 const long long nblk = (nb - 1) * ta.sub_step + ta.nsub;
                 ta.aux_ch_stride = (size_t)nblk;
-                ta.bsum = reinterpret_cast<const double2 *>(t.mean);
+                ta.bsum = reinterpret_cast<const double2 *>(t.mean.get());
                 for (int ch = 0; ch < nch; ++ch)
-                    HIPCHK(c, launch_tl_blocksum(ch ? y : x, cfirst, nblk, reinterpret_cast<double2 *>(t.mean) + (size_t)ch * nblk, c->stream));
+                    HIPCHK(c, launch_tl_blocksum(ch ? y : x, cfirst, nblk, reinterpret_cast<double2 *>(t.mean.get()) + (size_t)ch * nblk, c->stream));
             } else if (detrend) {
-                ta.mean = t.mean;
+                ta.mean = t.mean.get();
                 ta.aux_ch_stride = (size_t)B;
                 for (int ch = 0; ch < nch; ++ch)
-                    HIPCHK(c, launch_tl_mean(ch ? y : x, cfirst, seg_step, nperseg, nb, t.mean + (size_t)ch * B, c->stream));
+                    HIPCHK(c, launch_tl_mean(ch ? y : x, cfirst, seg_step, nperseg, nb, t.mean.get() + (size_t)ch * B, c->stream));
             }
             HIPCHK(c, launch_tl_k1(L, ta, c->stream));
             HIPCHK(c, launch_tl_k2(L, ta, W, c->stream));
             continue;
         }
-        if (detrend) HIPCHK(c, launch_any_mean(x, y, cfirst, seg_step, nperseg, nb, t.mean, (size_t)B, c->stream));
+        if (detrend) HIPCHK(c, launch_any_mean(x, y, cfirst, seg_step, nperseg, nb, t.mean.get(), (size_t)B, c->stream));
         if (!two) {
             // one launch: a workgroup per segment (rows W of the partial buffer), nothing leaves LDS
             a.f = d_one;
             a.es = 1, a.tile_stride = 0, a.cs = 1, a.inv_n = 1.0f / (float)L;
             a.load_op = 1;
-            a.chirp = blu ? t.chirp : nullptr;
+            a.chirp = blu ? t.chirp.get() : nullptr;
             a.mid_op = blu ? 1 : 0;
             a.nat_i = 1, a.pp_i = 1;
             HIPCHK(c, launch_any_fft(a, 1, rows ? gy_rows : W, 1, rows ? 3 : acc_store, c->stream));
@@ -231,7 +221,7 @@ int any_run(oth_ctx *c, AnyTables &t, const float2 *x, const float2 *y, long lon
         k1.f = d_col;
         k1.es = sh.L2, k1.tile_stride = sh.C, k1.cs = 1, k1.inv_n = 1.0f / (float)sh.L1;
         k1.load_op = 1;
-        k1.chirp = blu ? t.chirp : nullptr;
+        k1.chirp = blu ? t.chirp.get() : nullptr;
         k1.twbig = t.tw;
         k1.tw_t = sh.C, k1.tw_c = 1;
         HIPCHK(c, launch_any_fft(k1, sh.L2 / sh.C, gy_rows, nch, 0, c->stream));
@@ -271,11 +261,11 @@ int any_fft_nat(oth_ctx *c, const AnyTables &t, float2 *data, float2 *scratch) {
     if (any_describe(sh.L, &in)) return fail(c, OTH_ERR_INTERNAL, "Bluestein length has no route");
     float2 *A = scratch, *tmp = scratch + sh.L;
     int rc;
-    HIPCHK(c, launch_any_ew(0, A, data, nullptr, t.chirp, sh.L, sh.nfft, 0, 0, c->stream));      // a = x c, zero padded to M
+    HIPCHK(c, launch_any_ew(0, A, data, nullptr, t.chirp.get(), sh.L, sh.nfft, 0, 0, c->stream));      // a = x c, zero padded to M
     if ((rc = any_fft_nat_inner(c, in, t.tw, A, tmp))) return rc;
-    HIPCHK(c, launch_any_ew(1, A, A, nullptr, t.midtab, sh.L, sh.L, 0, 0, c->stream));            // conj(A B / M)
+    HIPCHK(c, launch_any_ew(1, A, A, nullptr, t.midtab.get(), sh.L, sh.L, 0, 0, c->stream));            // conj(A B / M)
     if ((rc = any_fft_nat_inner(c, in, t.tw, A, tmp))) return rc;
-    HIPCHK(c, launch_any_ew(2, data, A, nullptr, t.chirp, sh.nfft, sh.nfft, 0, 0, c->stream));    // X = conj(.) c
+    HIPCHK(c, launch_any_ew(2, data, A, nullptr, t.chirp.get(), sh.nfft, sh.nfft, 0, 0, c->stream));    // X = conj(.) c
     return OTH_OK;
 }
 }  // namespace oth

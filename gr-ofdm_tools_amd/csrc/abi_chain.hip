@@ -16,7 +16,7 @@ int oth_chain_create(oth_ctx *c, int nfft, const float *window, int fftshift, in
     if (epilogue < OTH_EPI_MAG || epilogue > OTH_EPI_MAG2_OVER_N2) return fail(c, OTH_ERR_INVALID, "unknown epilogue");
     if (keep_one_in_n < 1) return fail(c, OTH_ERR_INVALID, "keep_one_in_n must be >= 1");
     if (use_device(c)) return OTH_ERR_HIP;
-    oth_chain *h = new (std::nothrow) oth_chain();
+    std::unique_ptr<oth_chain> h(new (std::nothrow) oth_chain());
     if (!h) return fail(c, OTH_ERR_NOMEM, "host allocation failed");
     h->ctx = c;
     h->nfft = nfft;
@@ -24,32 +24,26 @@ int oth_chain_create(oth_ctx *c, int nfft, const float *window, int fftshift, in
     h->epilogue = epilogue;
     h->keep_n = h->count = keep_one_in_n;
     int rc = any_route ? any_tables_init(c, nfft, &h->any) : get_twiddles(c, nfft, &h->d_tw);
-    if (rc) {
-        delete h;
-        return rc;
-    }
+    if (rc) return rc;
     std::vector<float> w(nfft);
     h->rect = true;
     for (int i = 0; i < nfft; ++i) {
         w[i] = window ? window[i] : 1.0f;
         if (w[i] != 1.0f) h->rect = false;
     }
-    hipError_t e = hipMalloc(&h->d_win, sizeof(float) * nfft);
-    if (e == hipSuccess) e = hipMalloc(&h->d_iir, sizeof(float) * nfft);
-    if (e == hipSuccess) e = hipMalloc(&h->d_peak, sizeof(float) * nfft);
-    if (e == hipSuccess) e = hipMalloc(&h->d_peak_init, sizeof(int));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&h->h_tail, sizeof(float2) * nfft, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->tail_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->d_win, w.data(), sizeof(float) * nfft, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h->d_iir, 0, sizeof(float) * nfft, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h->d_peak, 0, sizeof(float) * nfft, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h->d_peak_init, 0, sizeof(int), c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        oth_chain_destroy(h);
-        return fail(c, OTH_ERR_HIP, std::string("chain setup: ") + hipGetErrorString(e));
-    }
-    *out = h;
+    hipError_t e = h->d_win.upload(c, w.data(), sizeof(float) * nfft);
+    if (e == hipSuccess) e = h->d_iir.alloc(sizeof(float) * nfft);
+    if (e == hipSuccess) e = h->d_peak.alloc(sizeof(float) * nfft);
+    if (e == hipSuccess) e = h->d_peak_init.alloc(sizeof(int));
+    if (e == hipSuccess) e = h->h_tail.alloc(sizeof(float2) * nfft);
+    if (e == hipSuccess) e = h->tail_ev.create();
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_iir.get(), 0, sizeof(float) * nfft, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_peak.get(), 0, sizeof(float) * nfft, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_peak_init.get(), 0, sizeof(int), c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);      // also after a failure: w dies here
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, OTH_ERR_HIP, std::string("chain setup: ") + hipGetErrorString(e));
+    *out = h.release();
     return OTH_OK;
     OTH_CATCH(c)
 }
@@ -61,24 +55,6 @@ int oth_chain_destroy(oth_chain *h) {
     oth_ctx *c = h->ctx;
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
-    if (h->d_win) hipFree(h->d_win);
-    if (h->d_buf) hipFree(h->d_buf);
-    if (h->d_rows) hipFree(h->d_rows);
-    if (h->d_iir) hipFree(h->d_iir);
-    if (h->d_peak) hipFree(h->d_peak);
-    if (h->d_peak_init) hipFree(h->d_peak_init);
-    if (h->d_stage) hipFree(h->d_stage);
-    if (h->d_partial) hipFree(h->d_partial);
-    if (h->d_tail) hipFree(h->d_tail);
-    if (h->d_out) hipFree(h->d_out);
-    if (h->h_tail) hipHostFree(h->h_tail);
-    if (h->tail_ev) hipEventDestroy(h->tail_ev);
-    any_tables_free(h->any);
-    for (int i = 0; i < oth_chain::kRing; ++i) {
-        if (h->h_in[i]) hipHostFree(h->h_in[i]);
-        if (h->h_row[i]) hipHostFree(h->h_row[i]);
-        if (h->ev[i]) hipEventDestroy(h->ev[i]);
-    }
     delete h;
     return OTH_OK;
     OTH_CATCH((h ? h->ctx : nullptr))
@@ -132,9 +108,9 @@ int oth_chain_reset(oth_chain *h) {
     if (!h) return fail(nullptr, OTH_ERR_INVALID, "chain is NULL");
     oth_ctx *c = h->ctx;
     if (use_device(c)) return OTH_ERR_HIP;
-    HIPCHK(c, hipMemsetAsync(h->d_iir, 0, sizeof(float) * h->nfft, c->stream));
-    HIPCHK(c, hipMemsetAsync(h->d_peak, 0, sizeof(float) * h->nfft, c->stream));
-    HIPCHK(c, hipMemsetAsync(h->d_peak_init, 0, sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(h->d_iir.get(), 0, sizeof(float) * h->nfft, c->stream));
+    HIPCHK(c, hipMemsetAsync(h->d_peak.get(), 0, sizeof(float) * h->nfft, c->stream));
+    HIPCHK(c, hipMemsetAsync(h->d_peak_init.get(), 0, sizeof(int), c->stream));
     h->peak_flag_set = false;
     h->leftover = 0;
     h->leftover_stale = false;
@@ -165,7 +141,7 @@ static int chain_launch_fused(oth_chain *h, const float2 *x, long long first_vec
     a.x = x;
     a.stream_stride = 0;
     a.nstreams = 1;
-    a.win = h->d_win;
+    a.win = h->d_win.get();
     a.tw = h->d_tw;
     a.step = (long long)h->keep_n * N;
     a.first = first_vec * N;
@@ -182,8 +158,8 @@ static int chain_launch_fused(oth_chain *h, const float2 *x, long long first_vec
         a.acc_end = a.store_from;
         a.l2 = h->alpha >= 1.f ? -INFINITY : log2f(1.0f - h->alpha);
         if (give) {
-            if ((rc = ensure(c, &h->d_rows, &h->rows_cap, sizeof(float) * (size_t)give * N))) return rc;
-            a.rows = h->d_rows;      // raw |X|^2 rows; the tail kernel turns them into dB rows
+            if ((rc = h->d_rows.ensure(c, sizeof(float) * (size_t)give * N))) return rc;
+            a.rows = h->d_rows.get();      // raw |X|^2 rows; the tail kernel turns them into dB rows
         }
     } else if (h->do_peak) {
         a.acc_mode = 2;
@@ -205,10 +181,10 @@ static int chain_launch_fused(oth_chain *h, const float2 *x, long long first_vec
     const long long W = a.wg_per_stream;
     int groups = 0;
     if (a.acc_mode != 3) {
-        if ((rc = ensure(c, &h->d_partial, &h->partial_cap, sizeof(float) * (size_t)W * N))) return rc;
-        a.partial = h->d_partial;
+        if ((rc = h->d_partial.ensure(c, sizeof(float) * (size_t)W * N))) return rc;
+        a.partial = h->d_partial.get();
         groups = chain_tail_groups((int)W, N);
-        if (groups && (rc = ensure(c, &h->d_tail, &h->tail_cap, sizeof(float) * (size_t)groups * N))) return rc;
+        if (groups && (rc = h->d_tail.ensure(c, sizeof(float) * (size_t)groups * N))) return rc;
     }
     // 16384 points: the one-exchange pipelined loop (welch16k1x.hip, round 4); OTH_CHAIN16K=old keeps the 4 x 4096 build
     // (A/B).  At 8192 points the chain stays on the 2 x 4096 build: the 8-wave one-exchange loop with the chain's epilogue
@@ -224,13 +200,13 @@ static int chain_launch_fused(oth_chain *h, const float2 *x, long long first_vec
         h->ops += 1;
         if (a.acc_mode != 3) h->ops += (groups ? 2 : 1) + ((a.acc_mode == 1 && give > 8) ? 1 : 0);      // [reduce +] state [+ rows]
         if (a.acc_mode != 3)
-            HIPCHK(c, launch_chain_tail(h->d_partial, groups ? h->d_tail : nullptr, (int)W, N, big ? (x1 ? (N == 16384 ? 4 : 5) : (N == 16384 ? 2 : 3)) : 0,
+            HIPCHK(c, launch_chain_tail(h->d_partial.get(), groups ? h->d_tail.get() : nullptr, (int)W, N, big ? (x1 ? (N == 16384 ? 4 : 5) : (N == 16384 ? 2 : 3)) : 0,
                                         h->fftshift, a.acc_mode, a.acc_end,
-                                        h->alpha, h->kdb, h->d_iir, h->d_peak, h->d_rows, h->do_iir ? give : 0, rows_last,
+                                        h->alpha, h->kdb, h->d_iir.get(), h->d_peak.get(), h->d_rows.get(), h->do_iir ? give : 0, rows_last,
                                         c->stream));
     }
     if (a.acc_mode == 2 && !h->peak_flag_set) {      // the coverage path (rows_epilogue_kernel) reads the flag
-        HIPCHK(c, launch_set_flag(h->d_peak_init, 1, c->stream));
+        HIPCHK(c, launch_set_flag(h->d_peak_init.get(), 1, c->stream));
         h->ops += 1;
         h->peak_flag_set = true;
     }
@@ -250,13 +226,13 @@ static int chain_launch(oth_chain *h, const float2 *x, long long first_vec, long
         first_vec += (nrows - give) * h->keep_n;
         nrows = give;
     }
-    int rc = ensure(c, &h->d_rows, &h->rows_cap, sizeof(float) * (size_t)nrows * N);
+    int rc = h->d_rows.ensure(c, sizeof(float) * (size_t)nrows * N);
     if (rc) return rc;
     PgramArgs a;
     a.x = x;
-    a.win = h->d_win;
+    a.win = h->d_win.get();
     a.tw = h->d_tw;
-    a.rows = h->d_rows;
+    a.rows = h->d_rows.get();
     a.first_vec = first_vec;
     a.nrows = nrows;
     a.keep_n = h->keep_n;
@@ -265,8 +241,8 @@ static int chain_launch(oth_chain *h, const float2 *x, long long first_vec, long
     a.scale = h->epilogue == OTH_EPI_MAG2_OVER_N2 ? (float)(1.0 / ((double)N * (double)N)) : 1.0f;
     if (h->any.sh.kind != ANY_NONE) {      // lengths outside the power-of-two kernels (fft_any.hip)
         Timed tm(c);
-        if ((rc = any_run(c, h->any, x, nullptr, first_vec * N, (long long)h->keep_n * N, N, h->d_win, false, nrows, nullptr, 0,
-                          h->d_rows, a.epilogue, a.scale, a.fftshift)))
+        if ((rc = any_run(c, h->any, x, nullptr, first_vec * N, (long long)h->keep_n * N, N, h->d_win.get(), false, nrows, nullptr, 0,
+                          h->d_rows.get(), a.epilogue, a.scale, a.fftshift)))
             return rc;
     } else {
         Timed tm(c);
@@ -274,13 +250,13 @@ static int chain_launch(oth_chain *h, const float2 *x, long long first_vec, long
     }
     h->ops += h->any.sh.kind == ANY_NONE ? 1 : 3;      // (the any-length routes: one to three launches per chunk)
     if (h->do_iir || h->do_peak) {
-        HIPCHK(c, launch_rows_epilogue(h->d_rows, nrows, N, h->alpha, h->kdb, h->d_iir, h->d_peak, h->d_peak_init,
+        HIPCHK(c, launch_rows_epilogue(h->d_rows.get(), nrows, N, h->alpha, h->kdb, h->d_iir.get(), h->d_peak.get(), h->d_peak_init.get(),
                                        h->do_iir, h->do_peak, c->stream));
         h->ops += h->do_peak ? 2 : 1;
     }
     if (h->do_peak && nrows > 0) h->peak_flag_set = true;
     if (rows_last && give > 0) {      // (rows_last may be pinned host memory - the asynchronous work() form: hipMemcpyDefault)
-        HIPCHK(c, hipMemcpyAsync(rows_last, h->d_rows + (size_t)(nrows - give) * N, sizeof(float) * (size_t)give * N,
+        HIPCHK(c, hipMemcpyAsync(rows_last, h->d_rows.get() + (size_t)(nrows - give) * N, sizeof(float) * (size_t)give * N,
                                  hipMemcpyDefault, c->stream));
         h->ops += 1;
     }
@@ -295,12 +271,12 @@ static int chain_feed(oth_chain *h, const float2 *src, size_t nsamples, float *r
     oth_ctx *c = h->ctx;
     const int N = h->nfft;
     if (h->leftover_stale) return fail(c, OTH_ERR_STATE, "chain: host-only samples of the partial vector were not uploaded");
-    int rc = ensure(c, &h->d_buf, &h->buf_cap, sizeof(float2) * (size_t)N);
+    int rc = h->d_buf.ensure(c, sizeof(float2) * (size_t)N);
     if (rc) return rc;
     bool head = false;           // a vector completed in d_buf
     if (h->leftover) {
         const size_t take = nsamples < (size_t)N - h->leftover ? nsamples : (size_t)N - h->leftover;
-        HIPCHK(c, hipMemcpyAsync(h->d_buf + h->leftover, src, take * sizeof(float2), hipMemcpyDeviceToDevice,
+        HIPCHK(c, hipMemcpyAsync(h->d_buf.get() + h->leftover, src, take * sizeof(float2), hipMemcpyDeviceToDevice,
                                  c->stream));
         h->ops += 1;
         h->leftover += take;
@@ -330,13 +306,13 @@ static int chain_feed(oth_chain *h, const float2 *src, size_t nsamples, float *r
     }
     const long long give_body = k_body < (long long)capacity ? k_body : (long long)capacity;
     const long long give_head = k_head < (long long)capacity - give_body ? k_head : (long long)capacity - give_body;
-    if (k_head && (rc = chain_launch(h, h->d_buf, 0, 1, rows_dev, rows_dev ? give_head : 0))) return rc;
+    if (k_head && (rc = chain_launch(h, h->d_buf.get(), 0, 1, rows_dev, rows_dev ? give_head : 0))) return rc;
     if (k_body && (rc = chain_launch(h, src, first, k_body, rows_dev ? rows_dev + (size_t)give_head * N : nullptr,
                                      rows_dev ? give_body : 0)))
         return rc;
     const size_t used = (size_t)nvec * N, keep = nsamples - used;
     if (keep) {      // d_buf is free again: a completed head vector has been consumed by the launch above (stream order)
-        HIPCHK(c, hipMemcpyAsync(h->d_buf, src + used, keep * sizeof(float2), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(h->d_buf.get(), src + used, keep * sizeof(float2), hipMemcpyDeviceToDevice, c->stream));
         h->ops += 1;
         h->leftover = keep;
     }
@@ -350,11 +326,11 @@ static int chain_feed(oth_chain *h, const float2 *src, size_t nsamples, float *r
 static int chain_upload_tail(oth_chain *h) {
     if (!h->leftover_stale) return OTH_OK;
     oth_ctx *c = h->ctx;
-    int rc = ensure(c, &h->d_buf, &h->buf_cap, sizeof(float2) * (size_t)h->nfft);
+    int rc = h->d_buf.ensure(c, sizeof(float2) * (size_t)h->nfft);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(h->d_buf + h->tail_from, h->h_tail + h->tail_from,
+    HIPCHK(c, hipMemcpyAsync(h->d_buf.get() + h->tail_from, h->h_tail.get() + h->tail_from,
                              (h->leftover - h->tail_from) * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(h->tail_ev, c->stream));
+    HIPCHK(c, hipEventRecord(h->tail_ev.get(), c->stream));
     h->tail_ev_live = true;
     h->ops += 1;
     h->leftover_stale = false;
@@ -365,7 +341,7 @@ static int chain_upload_tail(oth_chain *h) {
 // path that enqueues work, which reports it)
 static bool chain_tail_writable(oth_chain *h) {
     if (!h->tail_ev_live) return true;
-    if (hipEventSynchronize(h->tail_ev) != hipSuccess) return false;
+    if (hipEventSynchronize(h->tail_ev.get()) != hipSuccess) return false;
     h->tail_ev_live = false;
     return true;
 }
@@ -403,19 +379,19 @@ int oth_chain_push(oth_chain *h, const void *iq, size_t nsamples, int src_is_dev
     h->ops = 0;
     if ((rc = chain_upload_tail(h))) return rc;
     if (!src_is_device) {
-        if ((rc = ensure(c, &h->d_stage, &h->stage_cap, nsamples * sizeof(float2)))) return rc;
-        HIPCHK(c, hipMemcpyAsync(h->d_stage, iq, nsamples * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-        src = h->d_stage;
+        if ((rc = h->d_stage.ensure(c, nsamples * sizeof(float2)))) return rc;
+        HIPCHK(c, hipMemcpyAsync(h->d_stage.get(), iq, nsamples * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+        src = h->d_stage.get();
     }
     // rows this call can produce at most: one completed leftover vector + the full vectors of the new samples
     size_t cap = rows_out ? rows_capacity : 0;
     const size_t most = nsamples / N + 2;
     if (cap > most) cap = most;
-    if (cap && (rc = ensure(c, &h->d_out, &h->out_cap, sizeof(float) * cap * N))) return rc;
+    if (cap && (rc = h->d_out.ensure(c, sizeof(float) * cap * N))) return rc;
     uint64_t nrows = 0;
-    if ((rc = chain_feed(h, src, nsamples, cap ? h->d_out : nullptr, cap, &nrows))) return rc;
+    if ((rc = chain_feed(h, src, nsamples, cap ? h->d_out.get() : nullptr, cap, &nrows))) return rc;
     const size_t give = nrows < cap ? (size_t)nrows : cap;
-    if (give) HIPCHK(c, hipMemcpyAsync(rows_out, h->d_out, sizeof(float) * give * N, hipMemcpyDeviceToHost, c->stream));
+    if (give) HIPCHK(c, hipMemcpyAsync(rows_out, h->d_out.get(), sizeof(float) * give * N, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));      // the caller's buffer and rows_out are the caller's again
     if (nrows_out) *nrows_out = nrows;
     return OTH_OK;
@@ -439,7 +415,7 @@ static bool chain_push_dropped(oth_chain *h, const float2 *src, size_t nsamples)
         if (L + take < N) {                // it stays partial: keep the new samples on the host
             if (!chain_tail_writable(h)) return false;
             if (!h->leftover_stale) h->tail_from = L;
-            memcpy(h->h_tail + L, src, take * sizeof(float2));
+            memcpy(h->h_tail.get() + L, src, take * sizeof(float2));
             h->leftover = L + take;
             h->leftover_stale = true;
             return true;
@@ -454,7 +430,7 @@ static bool chain_push_dropped(oth_chain *h, const float2 *src, size_t nsamples)
     const size_t keep = rest - (size_t)nvec * N;
     if (keep && count == 1) return false;      // the vector that begins here will be kept
     if (keep && !chain_tail_writable(h)) return false;
-    if (keep) memcpy(h->h_tail, src + (size_t)nvec * N, keep * sizeof(float2));
+    if (keep) memcpy(h->h_tail.get(), src + (size_t)nvec * N, keep * sizeof(float2));
     h->leftover = keep;
     h->leftover_stale = keep != 0;
     h->tail_from = 0;
@@ -487,12 +463,12 @@ int oth_chain_push_async(oth_chain *h, const void *iq_host, size_t nsamples, uin
     }
     if (use_device(c)) return OTH_ERR_HIP;
     if (!h->ev[slot]) {
-        HIPCHK(c, hipEventCreateWithFlags(&h->ev[slot], hipEventDisableTiming));
-        HIPCHK(c, hipHostMalloc((void **)&h->h_row[slot], sizeof(float) * N, hipHostMallocDefault));
+        HIPCHK(c, h->ev[slot].create());
+        HIPCHK(c, h->h_row[slot].alloc(sizeof(float) * N));
     } else {
         // h_in[slot] / h_row[slot] belong to the slot's last real push - kRing tickets ago, or more when dropped tickets
         // (noop) came in between - until its event completes; waits only when the GPU is still that far behind
-        HIPCHK(c, hipEventSynchronize(h->ev[slot]));
+        HIPCHK(c, hipEventSynchronize(h->ev[slot].get()));
     }
     h->noop[slot] = false;
     // host-only samples of the partial vector (skipped by dropped pushes) go up in front of the new ones
@@ -503,20 +479,20 @@ int oth_chain_push_async(oth_chain *h, const void *iq_host, size_t nsamples, uin
     const bool wait_copy = pinned_src && bytes > kPinnedRingMax;
     const size_t in_bytes = (direct || wait_copy ? 0 : bytes) + tail_bytes;
     int rc;
-    if ((rc = grow_pinned(c, &h->h_in[slot], &h->h_in_cap[slot], in_bytes))) return rc;
+    if ((rc = h->h_in[slot].grow(c, in_bytes))) return rc;
     uint64_t nrows = 0;
     if (nsamples) {
-        if ((rc = ensure(c, &h->d_stage, &h->stage_cap, tail_bytes + bytes))) return rc;
-        char *pin = (char *)h->h_in[slot];
-        if (tail) memcpy(pin, h->h_tail + h->tail_from, tail_bytes);
+        if ((rc = h->d_stage.ensure(c, tail_bytes + bytes))) return rc;
+        char *pin = (char *)h->h_in[slot].get();
+        if (tail) memcpy(pin, h->h_tail.get() + h->tail_from, tail_bytes);
         if (wait_copy) {
-            if ((rc = copy_in_and_wait(c, h->d_stage + tail, iq_host, bytes))) return rc;
+            if ((rc = copy_in_and_wait(c, h->d_stage.get() + tail, iq_host, bytes))) return rc;
         } else if (direct) {      // the runtime's staged copy returns once the caller's buffer has been read
-            HIPCHK(c, hipMemcpyAsync(h->d_stage + tail, iq_host, bytes, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(h->d_stage.get() + tail, iq_host, bytes, hipMemcpyHostToDevice, c->stream));
         } else {
             memcpy(pin + tail_bytes, iq_host, bytes);      // the scheduler's buffer dies when work() returns
         }
-        if (in_bytes) HIPCHK(c, hipMemcpyAsync(h->d_stage, pin, in_bytes, hipMemcpyHostToDevice, c->stream));
+        if (in_bytes) HIPCHK(c, hipMemcpyAsync(h->d_stage.get(), pin, in_bytes, hipMemcpyHostToDevice, c->stream));
         h->ops += (direct || wait_copy) && tail ? 2 : 1;
         const size_t leftover0 = h->leftover;
         const int count0 = h->count;
@@ -525,14 +501,14 @@ int oth_chain_push_async(oth_chain *h, const void *iq_host, size_t nsamples, uin
             h->leftover_stale = false;
         }
         // the latest row goes from the closing kernel straight into the slot's pinned row (device-visible host memory)
-        if ((rc = chain_feed(h, h->d_stage, tail + nsamples, h->h_row[slot], 1, &nrows))) {
+        if ((rc = chain_feed(h, h->d_stage.get(), tail + nsamples, h->h_row[slot].get(), 1, &nrows))) {
             h->leftover = leftover0;      // the stream position stays where it was: h_tail still holds the samples
             h->leftover_stale = tail != 0;
             h->count = count0;
             return rc;
         }
     }
-    HIPCHK(c, hipEventRecord(h->ev[slot], c->stream));
+    HIPCHK(c, hipEventRecord(h->ev[slot].get(), c->stream));
     h->ticket_of[slot] = ticket;
     h->nrows_of[slot] = nrows;
     h->next_ticket = ticket + 1;
@@ -558,7 +534,7 @@ static int chain_collect(oth_chain *h, uint64_t ticket, float *row_out, uint64_t
         if (nrows_out) *nrows_out = 0;
         return OTH_OK;
     }
-    hipError_t e = wait ? hipEventSynchronize(h->ev[slot]) : hipEventQuery(h->ev[slot]);
+    hipError_t e = wait ? hipEventSynchronize(h->ev[slot].get()) : hipEventQuery(h->ev[slot].get());
     if (e == hipErrorNotReady) {
         if (ready) *ready = 0;
         return OTH_OK;
@@ -566,7 +542,7 @@ static int chain_collect(oth_chain *h, uint64_t ticket, float *row_out, uint64_t
     if (e != hipSuccess) return fail(c, OTH_ERR_HIP, std::string("event: ") + hipGetErrorString(e));
     if (ready) *ready = 1;
     if (nrows_out) *nrows_out = h->nrows_of[slot];
-    if (row_out && h->nrows_of[slot]) memcpy(row_out, h->h_row[slot], sizeof(float) * h->nfft);
+    if (row_out && h->nrows_of[slot]) memcpy(row_out, h->h_row[slot].get(), sizeof(float) * h->nfft);
     return OTH_OK;
 }
 
@@ -592,7 +568,7 @@ int oth_chain_wait(oth_chain *h, uint64_t ticket, float *row_out, uint64_t *nrow
             if (nrows_out) *nrows_out = 0;
             return OTH_OK;
         }
-        ev = h->ev[slot];
+        ev = h->ev[slot].get();
     }
     hipError_t e = hipEventSynchronize(ev);
     if (e != hipSuccess) return fail(h->ctx, OTH_ERR_HIP, std::string("event: ") + hipGetErrorString(e));
@@ -627,7 +603,7 @@ int oth_chain_get_peak(oth_chain *h, float *peak_out) {
     CtxGuard guard_(h ? h->ctx : nullptr);
     if (!h || !peak_out) return fail(h ? h->ctx : nullptr, OTH_ERR_INVALID, "bad argument");
     oth_ctx *c = h->ctx;
-    HIPCHK(c, hipMemcpyAsync(peak_out, h->d_peak, sizeof(float) * h->nfft, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(peak_out, h->d_peak.get(), sizeof(float) * h->nfft, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return OTH_OK;
     OTH_CATCH((h ? h->ctx : nullptr))
@@ -638,7 +614,7 @@ int oth_chain_get_iir(oth_chain *h, float *lin_out) {
     CtxGuard guard_(h ? h->ctx : nullptr);
     if (!h || !lin_out) return fail(h ? h->ctx : nullptr, OTH_ERR_INVALID, "bad argument");
     oth_ctx *c = h->ctx;
-    HIPCHK(c, hipMemcpyAsync(lin_out, h->d_iir, sizeof(float) * h->nfft, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(lin_out, h->d_iir.get(), sizeof(float) * h->nfft, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return OTH_OK;
     OTH_CATCH((h ? h->ctx : nullptr))

@@ -34,18 +34,19 @@ int fail_nothrow(oth_ctx *c, int code, const char *what) noexcept {
     return code;
 }
 
+hipStream_t ctx_stream(const oth_ctx *c) { return c->stream; }
+
 int use_device(oth_ctx *c) {
     HIPCHK(c, hipSetDevice(c->device));
     return OTH_OK;
 }
 
 int copy_in_and_wait(oth_ctx *c, void *dst, const void *src, size_t bytes) {
-    hipEvent_t ev = nullptr;
-    HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    Event ev;
+    HIPCHK(c, ev.create());
     hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(ev, c->stream);
-    if (e == hipSuccess) e = hipEventSynchronize(ev);
-    hipEventDestroy(ev);
+    if (e == hipSuccess) e = hipEventRecord(ev.get(), c->stream);
+    if (e == hipSuccess) e = hipEventSynchronize(ev.get());
     if (e != hipSuccess) return fail(c, OTH_ERR_HIP, std::string("host copy: ") + hipGetErrorString(e));
     return OTH_OK;
 }
@@ -53,7 +54,7 @@ int copy_in_and_wait(oth_ctx *c, void *dst, const void *src, size_t bytes) {
 int get_twiddles(oth_ctx *c, int nfft, const float2 **out) {
     auto it = c->twiddles.find(nfft);
     if (it != c->twiddles.end()) {
-        *out = it->second;
+        *out = it->second.get();
         return OTH_OK;
     }
     std::vector<float2> h(nfft);
@@ -61,22 +62,11 @@ int get_twiddles(oth_ctx *c, int nfft, const float2 **out) {
         const double a = -2.0 * M_PI * (double)k / (double)nfft;
         h[k] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
-    float2 *d = nullptr;
-    HIPCHK(c, hipMalloc(&d, sizeof(float2) * nfft));
-    HIPCHK(c, hipMemcpyAsync(d, h.data(), sizeof(float2) * nfft, hipMemcpyHostToDevice, c->stream));
+    DevBuf<float2> d;
+    HIPCHK(c, d.upload(c, h.data(), sizeof(float2) * nfft));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->twiddles[nfft] = d;
-    *out = d;
-    return OTH_OK;
-}
-
-int grow_pinned(oth_ctx *c, void **buf, size_t *cap, size_t bytes) {
-    if (*cap >= bytes) return OTH_OK;
-    if (*buf) HIPCHK(c, hipHostFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    HIPCHK(c, hipHostMalloc(buf, bytes + bytes / 2 + 4096, hipHostMallocDefault));
-    *cap = bytes + bytes / 2 + 4096;
+    *out = d.get();
+    c->twiddles[nfft] = std::move(d);
     return OTH_OK;
 }
 }  // namespace oth
@@ -119,13 +109,11 @@ static int ctx_create(int device_id, void *stream, bool adopt, oth_ctx **out) {
     if (e != hipSuccess || n <= 0)
         return fail(nullptr, OTH_ERR_HIP, "no HIP device available (libofdmtools_hip has no CPU fallback)");
     if (device_id < 0 || device_id >= n) return fail(nullptr, OTH_ERR_INVALID, "device_id out of range");
-    oth_ctx *c = new (std::nothrow) oth_ctx();
+    std::unique_ptr<oth_ctx> c(new (std::nothrow) oth_ctx());
     if (!c) return fail(nullptr, OTH_ERR_NOMEM, "host allocation failed");
     c->device = device_id;
-    if ((e = hipSetDevice(device_id)) != hipSuccess) {
-        delete c;
+    if ((e = hipSetDevice(device_id)) != hipSuccess)
         return fail(nullptr, OTH_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) {
         c->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -135,22 +123,18 @@ static int ctx_create(int device_id, void *stream, bool adopt, oth_ctx **out) {
         c->stream = reinterpret_cast<hipStream_t>(stream);
         c->own_stream = false;
     } else {
-        if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) {
-            delete c;
+        if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess)
             return fail(nullptr, OTH_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-        }
         c->own_stream = true;
     }
-    if (hipMalloc(&c->sink, 256) != hipSuccess || hipMalloc(&c->acc4, 4 * sizeof(double)) != hipSuccess ||
-        hipMalloc(&c->queue, 65 * sizeof(unsigned)) != hipSuccess ||
-        hipMemsetAsync(c->queue, 0, 65 * sizeof(unsigned), c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) {
-        delete c;
+    if (c->sink.alloc(256) != hipSuccess || c->acc4.alloc(4 * sizeof(double)) != hipSuccess ||
+        c->queue.alloc(65 * sizeof(unsigned)) != hipSuccess ||
+        hipMemsetAsync(c->queue.get(), 0, 65 * sizeof(unsigned), c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
         return fail(nullptr, OTH_ERR_NOMEM, "hipMalloc failed for context scratch");
-    }
     c->queue_clean = true;
-    c->done_count = c->queue + 64;     // zero now; every signalling finalize launch leaves it at zero again
-    *out = c;
+    c->done_count = c->queue.get() + 64;     // zero now; every signalling finalize launch leaves it at zero again
+    *out = c.release();
     return OTH_OK;
 }
 
@@ -170,24 +154,16 @@ int oth_ctx_destroy(oth_ctx *c) {
     if (!c) return OTH_OK;
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
-    for (auto &ev : c->events) {
-        hipEventDestroy(ev.first);
-        hipEventDestroy(ev.second);
-    }
-    for (auto &ev : c->free_events) {
-        hipEventDestroy(ev.first);
-        hipEventDestroy(ev.second);
-    }
-    for (auto &kv : c->twiddles) hipFree(kv.second);
-    if (c->sink) hipFree(c->sink);
-    if (c->acc4) hipFree(c->acc4);
-    if (c->queue) hipFree(c->queue);
-    if (c->scratch) hipFree(c->scratch);
-    if (c->d_bounds) hipFree(c->d_bounds);
-    if (c->h_bounds) hipHostFree(c->h_bounds);
-    if (c->bounds_ev) hipEventDestroy(c->bounds_ev);
-    if (c->own_stream) hipStreamDestroy(c->stream);
     delete c;
+    return OTH_OK;
+    OTH_CATCH(nullptr)
+}
+
+int oth__debug_live_resources(int *device_buffers, int *pinned_buffers, int *events) {
+    OTH_TRY
+    if (device_buffers) *device_buffers = g_live_device.load();
+    if (pinned_buffers) *pinned_buffers = g_live_pinned.load();
+    if (events) *events = g_live_events.load();
     return OTH_OK;
     OTH_CATCH(nullptr)
 }
@@ -228,9 +204,9 @@ int oth_ctx_get_timing(oth_ctx *c, double *total_ms, uint64_t *launches, int res
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (auto &ev : c->events) {
         float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, ev.first, ev.second));
+        HIPCHK(c, hipEventElapsedTime(&ms, ev.first.get(), ev.second.get()));
         c->total_ms += ms;
-        c->free_events.push_back(ev);
+        c->free_events.push_back(std::move(ev));
     }
     c->events.clear();
     if (total_ms) *total_ms = c->total_ms;
@@ -302,22 +278,20 @@ int oth_stream_read_probe(oth_ctx *c, const void *dptr, size_t bytes, int repeat
     CtxGuard guard_(c);
     if (!c || !dptr || bytes < 16 || repeats == 0 || !ms_per_pass) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (use_device(c)) return OTH_ERR_HIP;
-    hipEvent_t a, b;
-    HIPCHK(c, hipEventCreate(&a));
-    HIPCHK(c, hipEventCreate(&b));
+    Event a, b;
+    HIPCHK(c, a.create(hipEventDefault));
+    HIPCHK(c, b.create(hipEventDefault));
     // repeats < 0: the 8-bytes-per-lane variant (the access width of the FFT kernels' sample loads), |repeats| passes
     const bool narrow = repeats < 0;
     if (narrow) repeats = -repeats;
-    auto probe = [&]() { return narrow ? launch_read_probe8(dptr, bytes, c->sink, c->stream) : launch_read_probe(dptr, bytes, c->sink, c->stream); };
+    auto probe = [&]() { return narrow ? launch_read_probe8(dptr, bytes, c->sink.get(), c->stream) : launch_read_probe(dptr, bytes, c->sink.get(), c->stream); };
     HIPCHK(c, probe());   // warm-up
-    HIPCHK(c, hipEventRecord(a, c->stream));
+    HIPCHK(c, hipEventRecord(a.get(), c->stream));
     for (int i = 0; i < repeats; ++i) HIPCHK(c, probe());
-    HIPCHK(c, hipEventRecord(b, c->stream));
-    HIPCHK(c, hipEventSynchronize(b));
+    HIPCHK(c, hipEventRecord(b.get(), c->stream));
+    HIPCHK(c, hipEventSynchronize(b.get()));
     float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, a, b));
-    hipEventDestroy(a);
-    hipEventDestroy(b);
+    HIPCHK(c, hipEventElapsedTime(&ms, a.get(), b.get()));
     *ms_per_pass = (double)ms / repeats;
     return OTH_OK;
     OTH_CATCH(c)
@@ -328,10 +302,10 @@ int oth_iq_power(oth_ctx *c, const void *iq_dev, size_t nsamples, double *mean_r
     CtxGuard guard_(c);
     if (!c || !iq_dev || !nsamples) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (use_device(c)) return OTH_ERR_HIP;
-    HIPCHK(c, hipMemsetAsync(c->acc4, 0, 4 * sizeof(double), c->stream));
-    HIPCHK(c, launch_iq_power((const float2 *)iq_dev, nsamples, c->acc4, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->acc4.get(), 0, 4 * sizeof(double), c->stream));
+    HIPCHK(c, launch_iq_power((const float2 *)iq_dev, nsamples, c->acc4.get(), c->stream));
     double h[4];
-    HIPCHK(c, hipMemcpyAsync(h, c->acc4, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h, c->acc4.get(), sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const double mr = h[0] / nsamples, mi = h[1] / nsamples;
     if (mean_re) *mean_re = mr;

@@ -143,18 +143,18 @@ int mtm_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t s
     const int bpc = std::max(1, mtm_blocks_per_cu(N, c->device));
     const long long resident = (long long)c->cu_count * bpc;
     const int W = (int)std::min(items, std::max<long long>(K, resident / nstreams));
-    int rc = ensure(c, &p->d_partial, &p->partial_cap, sizeof(float) * (size_t)nstreams * W * N);
+    int rc = p->d_partial.ensure(c, sizeof(float) * (size_t)nstreams * W * N);
     {
         const int groups = std::max(kReduceGroups, finalize_row_groups(N, W, 1));
-        if (!rc) rc = ensure(c, &p->d_reduce, &p->reduce_cap, sizeof(float) * (size_t)nstreams * groups * N);
+        if (!rc) rc = p->d_reduce.ensure(c, sizeof(float) * (size_t)nstreams * groups * N);
     }
     if (rc) return rc;
     MtmArgs a{};
     a.x = x;
-    a.tapers = p->d_tapers;
-    a.coef = p->d_coef;
+    a.tapers = p->d_tapers.get();
+    a.coef = p->d_coef.get();
     a.tw = p->d_tw;
-    a.partial = p->d_partial;
+    a.partial = p->d_partial.get();
     a.nseg = nseg;
     a.stream_stride = stride;
     a.nperseg = p->nperseg;
@@ -231,23 +231,17 @@ int oth_mtm_plan(oth_ctx *c, int nfft, int nperseg, int noverlap, int ntapers, c
     CtxGuard guard_(c);
     if (!c || !out) return fail(c, OTH_ERR_INVALID, "ctx/out is NULL");
     *out = nullptr;
-    if (nfft < 1) return fail(c, OTH_ERR_INVALID, "nfft must be positive");
-    if (!mtm_size(nfft))
+    // the refusals of its own in front of the shared checks (OTH_SCALE_SPECTRUM before the range check of plan_begin)
+    if (nfft >= 1 && !mtm_size(nfft))
         return fail(c, OTH_ERR_UNSUPPORTED, "multitaper plans take a transform length that is a power of two from 64 to 16384, not " +
                                                 std::to_string(nfft));
-    if (nperseg < 1 || nperseg > nfft) return fail(c, OTH_ERR_INVALID, "need 1 <= nperseg <= nfft");
-    if (noverlap < 0 || noverlap >= nperseg) return fail(c, OTH_ERR_INVALID, "need 0 <= noverlap < nperseg");
-    if (ntapers < 1 || ntapers > 64) return fail(c, OTH_ERR_INVALID, "need 1 <= ntapers <= 64");
-    if (!tapers) return fail(c, OTH_ERR_INVALID, "tapers is NULL");
-    if (detrend != OTH_DETREND_NONE && detrend != OTH_DETREND_CONSTANT && detrend != OTH_DETREND_CONSTANT_EXACT &&
-        detrend != OTH_DETREND_CONSTANT_FAST)
-        return fail(c, OTH_ERR_INVALID, "unknown detrend");
-    if (detrend != OTH_DETREND_NONE) detrend = OTH_DETREND_CONSTANT;      // every mode: each segment's own mean
     if (scaling == OTH_SCALE_SPECTRUM)
         return fail(c, OTH_ERR_UNSUPPORTED, "OTH_SCALE_SPECTRUM is not defined for multitaper plans: an odd taper sums to zero");
-    if (scaling < OTH_SCALE_RAW || scaling > OTH_SCALE_SPECTRUM) return fail(c, OTH_ERR_INVALID, "unknown scaling");
-    if (trim_bins < 0 || 2 * trim_bins >= nfft) return fail(c, OTH_ERR_INVALID, "trim_bins out of range");
-    if (!(fs > 0.0)) return fail(c, OTH_ERR_INVALID, "fs must be positive");
+    std::unique_ptr<oth_plan> p;
+    if (int rc = plan_begin(c, nfft, nperseg, noverlap, detrend, scaling, fs, fftshift, trim_bins, &p)) return rc;
+    p->fast_detrend = false;      // every mode: each segment's own mean
+    if (ntapers < 1 || ntapers > 64) return fail(c, OTH_ERR_INVALID, "need 1 <= ntapers <= 64");
+    if (!tapers) return fail(c, OTH_ERR_INVALID, "tapers is NULL");
     double wsum = 0.0;
     for (int k = 0; k < ntapers; ++k) {
         const double w = weights ? (double)weights[k] : 1.0;
@@ -271,42 +265,21 @@ int oth_mtm_plan(oth_ctx *c, int nfft, int nperseg, int noverlap, int ntapers, c
         }
         coef[k] = (float)ck;
     }
-    if (use_device(c)) return OTH_ERR_HIP;
-    oth_plan *p = new (std::nothrow) oth_plan();
-    if (!p) return fail(c, OTH_ERR_NOMEM, "host allocation failed");
-    p->ctx = c;
-    p->nfft = nfft;
-    p->nperseg = nperseg;
-    p->noverlap = noverlap;
-    p->step = nperseg - noverlap;
-    p->detrend = detrend;
-    p->scaling = scaling;
-    p->fs = fs;
-    p->fftshift = fftshift != 0;
-    p->trim = trim_bins;
     p->ntapers = ntapers;
-    if (const char *e = getenv("OTH_HOSTWAIT")) p->hostwait = !strcmp(e, "sync") ? 1 : 0;
     switch (scaling) {
         case OTH_SCALE_DENSITY: p->scale = 1.0 / fs; break;      // the tapers' energies are in c_k
         case OTH_SCALE_OVER_N2: p->scale = 1.0 / ((double)nfft * (double)nfft); break;
         default: p->scale = 1.0;
     }
-    if (int rc = get_twiddles(c, nfft, &p->d_tw)) {
-        delete p;
-        return rc;
-    }
-    hipError_t e = hipMalloc(&p->d_tapers, sizeof(float) * tab.size());
-    if (e == hipSuccess) e = hipMalloc(&p->d_coef, sizeof(float) * coef.size());
-    if (e == hipSuccess) e = hipMalloc(&p->d_sum, sizeof(float) * nfft);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->d_tapers, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->d_coef, coef.data(), sizeof(float) * coef.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(p->d_sum, 0, sizeof(float) * nfft, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // the host tables go out of scope
-    if (e != hipSuccess) {
-        oth_plan_destroy(p);
-        return fail(c, OTH_ERR_HIP, std::string("plan setup: ") + hipGetErrorString(e));
-    }
-    *out = p;
+    if (int rc = get_twiddles(c, nfft, &p->d_tw)) return rc;
+    hipError_t e = p->d_tapers.upload(c, tab.data(), sizeof(float) * tab.size());
+    if (e == hipSuccess) e = p->d_coef.upload(c, coef.data(), sizeof(float) * coef.size());
+    if (e == hipSuccess) e = p->d_sum.alloc(sizeof(float) * nfft);
+    if (e == hipSuccess) e = hipMemsetAsync(p->d_sum.get(), 0, sizeof(float) * nfft, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);      // also after a failure: the host tables die here
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, OTH_ERR_HIP, std::string("plan setup: ") + hipGetErrorString(e));
+    *out = p.release();
     return OTH_OK;
     OTH_CATCH(c)
 }

@@ -310,8 +310,8 @@ PlanShape shape_of(const oth_plan *p) {
     s.step = p->step;
     s.detrend = p->detrend != OTH_DETREND_NONE;
     s.fast_detrend = p->fast_detrend;
-    s.fd_ok = p->d_fd != nullptr;
-    s.fd1x_ok = p->d_fd1x != nullptr;
+    s.fd_ok = p->d_fd.get() != nullptr;
+    s.fd1x_ok = p->d_fd1x.get() != nullptr;
     s.rect_window = p->rect_window;
     s.kernel = p->kernel;
     s.sched = p->sched;

@@ -11,9 +11,9 @@ int oth_rows_group_mean(oth_ctx *c, const float *rows_host, size_t nrows, int nf
     if (use_device(c)) return OTH_ERR_HIP;
     const size_t ngroups = nrows / group;
     const size_t in_bytes = sizeof(float) * ngroups * group * nfft, out_bytes = sizeof(float) * ngroups * nfft;
-    int rc = ensure(c, &c->scratch, &c->scratch_cap, in_bytes + out_bytes);
+    int rc = c->scratch.ensure(c, in_bytes + out_bytes);
     if (rc) return rc;
-    float *d_in = (float *)c->scratch, *d_out = (float *)(c->scratch + in_bytes);
+    float *d_in = (float *)c->scratch.get(), *d_out = (float *)(c->scratch.get() + in_bytes);
     HIPCHK(c, hipMemcpyAsync(d_in, rows_host, in_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, launch_group_mean(d_in, (long long)ngroups, nfft, group, d_out, c->stream));
     HIPCHK(c, hipMemcpyAsync(out_host, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -37,31 +37,23 @@ static int channel_bounds_dev(oth_ctx *c, int nch, const int *lo, const int *hi,
     *dlo = *dhi = nullptr;
     if (nch <= 0) return OTH_OK;
     const size_t n = 2 * (size_t)nch;
-    bool same = c->d_bounds && c->bounds_host.size() == n;
+    bool same = c->d_bounds.get() && c->bounds_host.size() == n;
     for (int i = 0; same && i < nch; ++i) same = c->bounds_host[i] == lo[i] && c->bounds_host[nch + i] == hi[i];
     if (!same) {
-        if (n > c->bounds_cap) {
-            if (c->bounds_ev) HIPCHK(c, hipEventSynchronize(c->bounds_ev));
-            HIPCHK(c, hipStreamSynchronize(c->stream));      // kernels may still read the old device copy
-            if (c->d_bounds) hipFree(c->d_bounds);
-            if (c->h_bounds) hipHostFree(c->h_bounds);
-            c->d_bounds = c->h_bounds = nullptr;
-            c->bounds_cap = 0;
-            c->bounds_host.clear();
-            if (hipMalloc(&c->d_bounds, sizeof(int) * n) != hipSuccess) return fail(c, OTH_ERR_NOMEM, "device allocation failed");
-            HIPCHK(c, hipHostMalloc((void **)&c->h_bounds, sizeof(int) * n, hipHostMallocDefault));
-            c->bounds_cap = n;
-        }
-        if (!c->bounds_ev) HIPCHK(c, hipEventCreateWithFlags(&c->bounds_ev, hipEventDisableTiming));
-        else HIPCHK(c, hipEventSynchronize(c->bounds_ev));      // the previous upload has read the pinned words
-        memcpy(c->h_bounds, lo, sizeof(int) * nch);
-        memcpy(c->h_bounds + nch, hi, sizeof(int) * nch);
-        HIPCHK(c, hipMemcpyAsync(c->d_bounds, c->h_bounds, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->bounds_ev, c->stream));
-        c->bounds_host.assign(c->h_bounds, c->h_bounds + n);
+        c->bounds_host.clear();      // nothing is cached until the new upload is enqueued
+        if (!c->bounds_ev) HIPCHK(c, c->bounds_ev.create());
+        else HIPCHK(c, hipEventSynchronize(c->bounds_ev.get()));      // the previous upload has read the pinned words
+        // (a longer list: ensure() drains the stream before it frees - kernels may still read the old device copy)
+        if (int rc = c->d_bounds.ensure(c, sizeof(int) * n)) return rc;
+        if (int rc = c->h_bounds.grow(c, sizeof(int) * n)) return rc;
+        memcpy(c->h_bounds.get(), lo, sizeof(int) * nch);
+        memcpy(c->h_bounds.get() + nch, hi, sizeof(int) * nch);
+        HIPCHK(c, hipMemcpyAsync(c->d_bounds.get(), c->h_bounds.get(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(c->bounds_ev.get(), c->stream));
+        c->bounds_host.assign(c->h_bounds.get(), c->h_bounds.get() + n);
     }
-    *dlo = c->d_bounds;
-    *dhi = c->d_bounds + nch;
+    *dlo = c->d_bounds.get();
+    *dhi = c->d_bounds.get() + nch;
     return OTH_OK;
 }
 
@@ -77,9 +69,9 @@ int oth_channel_power(oth_ctx *c, const float *psd_host, int nfft, double srch_b
     const size_t o_psd = 0, o_ma = up16(o_psd + sizeof(float) * nfft), o_maf = up16(o_ma + sizeof(double) * nfft),
                  o_lo = up16(o_maf + sizeof(float) * nfft), o_hi = up16(o_lo + sizeof(int) * nch),
                  o_pw = up16(o_hi + sizeof(int) * nch), bytes = up16(o_pw + sizeof(float) * nch);
-    int rc = ensure(c, &c->scratch, &c->scratch_cap, bytes);
+    int rc = c->scratch.ensure(c, bytes);
     if (rc) return rc;
-    unsigned char *d = c->scratch;
+    unsigned char *d = c->scratch.get();
     HIPCHK(c, hipMemcpyAsync(d + o_psd, psd_host, sizeof(float) * nfft, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d + o_lo, lo, sizeof(int) * nch, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d + o_hi, hi, sizeof(int) * nch, hipMemcpyHostToDevice, c->stream));
@@ -103,9 +95,9 @@ int oth_bin_threshold(oth_ctx *c, const float *psd_host, int nrows, int nfft, do
     if (use_device(c)) return OTH_ERR_HIP;
     const size_t nb = (size_t)nrows * nfft;
     const size_t o_mask = sizeof(float) * nb, o_noise = up16(o_mask + nb);
-    int rc = ensure(c, &c->scratch, &c->scratch_cap, o_noise + sizeof(float) * nrows);
+    int rc = c->scratch.ensure(c, o_noise + sizeof(float) * nrows);
     if (rc) return rc;
-    unsigned char *d = c->scratch;
+    unsigned char *d = c->scratch.get();
     HIPCHK(c, hipMemcpyAsync(d, psd_host, sizeof(float) * nb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, launch_bin_threshold((const float *)d, nrows, nfft, srch_bins, thr_leveler, d + o_mask,
                                    (float *)(d + o_noise), c->stream));
@@ -135,9 +127,9 @@ int oth_scan_decide_dev(oth_ctx *c, const float *psd_rows_dev, int nrows, int nf
     const size_t o_ma = 0, o_mask = up16(o_ma + sizeof(double) * nb), o_noise = up16(o_mask + nb),
                  o_pw = up16(o_noise + sizeof(float) * nrows), o_tm = up16(o_pw + sizeof(float) * nrows * (nch + 1)),
                  bytes = up16(o_tm + sizeof(float) * nrows * scan_decide_tiles(nfft));
-    int rc = ensure(c, &c->scratch, &c->scratch_cap, bytes);
+    int rc = c->scratch.ensure(c, bytes);
     if (rc) return rc;
-    unsigned char *d = c->scratch;
+    unsigned char *d = c->scratch.get();
     const int *dlo = nullptr, *dhi = nullptr;
     if ((rc = channel_bounds_dev(c, nch, lo, hi, &dlo, &dhi))) return rc;
     HIPCHK(c, launch_scan_decide(psd_rows_dev, nrows, nfft, srch_bins, thr_leveler, nch, dlo,
@@ -166,9 +158,9 @@ int oth_scan_decide_dev_out(oth_ctx *c, const float *psd_rows_dev, int nrows, in
     if (use_device(c)) return OTH_ERR_HIP;
     const size_t nb = (size_t)nrows * nfft;
     const size_t o_tm = up16(sizeof(double) * nb), bytes = up16(o_tm + sizeof(float) * nrows * scan_decide_tiles(nfft));
-    int rc = ensure(c, &c->scratch, &c->scratch_cap, bytes);
+    int rc = c->scratch.ensure(c, bytes);
     if (rc) return rc;
-    unsigned char *d = c->scratch;
+    unsigned char *d = c->scratch.get();
     const int *dlo = nullptr, *dhi = nullptr;      // cached on the device: no host copy on the steady-state path
     if ((rc = channel_bounds_dev(c, nch, lo, hi, &dlo, &dhi))) return rc;
     HIPCHK(c, launch_scan_decide(psd_rows_dev, nrows, nfft, srch_bins, thr_leveler, nch, dlo, dhi, (double *)d,
@@ -184,9 +176,9 @@ static int xcorr_any(oth_ctx *c, const void *a, size_t na, const void *b, size_t
     int rc = any_tables_init(c, L, &t);
     if (rc) return rc;
     const size_t nsc = any_fft_nat_scratch(t.sh), nout = (size_t)(L - L / 2);
-    rc = ensure(c, &c->scratch, &c->scratch_cap, sizeof(float2) * (2 * (size_t)L + nsc) + sizeof(float) * nout);
+    rc = c->scratch.ensure(c, sizeof(float2) * (2 * (size_t)L + nsc) + sizeof(float) * nout);
     if (!rc) {
-        float2 *A = (float2 *)c->scratch, *Bv = A + L, *sc = Bv + L;
+        float2 *A = (float2 *)c->scratch.get(), *Bv = A + L, *sc = Bv + L;
         float *o = (float *)(sc + nsc);
         auto run = [&]() -> int {
             int r;
@@ -210,8 +202,7 @@ static int xcorr_any(oth_ctx *c, const void *a, size_t na, const void *b, size_t
         };
         rc = run();
     }
-    if (rc) hipStreamSynchronize(c->stream);
-    any_tables_free(t);
+    if (rc) hipStreamSynchronize(c->stream);      // the tables are released on return
     return rc;
 }
 
@@ -225,8 +216,8 @@ static int xcorr_impl(oth_ctx *c, const void *a, size_t na, const void *b, size_
     const float2 *tw = nullptr;
     int rc = get_twiddles(c, L, &tw);
     if (rc) return rc;
-    if ((rc = ensure(c, &c->scratch, &c->scratch_cap, sizeof(float2) * 3 * (size_t)L))) return rc;
-    float2 *d = (float2 *)c->scratch;
+    if ((rc = c->scratch.ensure(c, sizeof(float2) * 3 * (size_t)L))) return rc;
+    float2 *d = (float2 *)c->scratch.get();
     HIPCHK(c, hipMemsetAsync(d, 0, sizeof(float2) * 3 * L, c->stream));
     HIPCHK(c, hipMemcpyAsync(d, a, sizeof(float2) * na, hipMemcpyHostToDevice, c->stream));
     if (mode == 0) HIPCHK(c, hipMemcpyAsync(d + L, b, sizeof(float2) * nb, hipMemcpyHostToDevice, c->stream));

@@ -5,6 +5,7 @@
 #include "../../include/ofdm_tools_hip.h"
 #include "oth_internal.h"
 #include "abi_barrier.h"
+#include "abi_mem.h"
 
 #include <algorithm>
 #include <cmath>
@@ -12,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -27,41 +29,42 @@ struct oth_ctx {
     std::string err;
     std::string name;
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
+    std::vector<std::pair<Event, Event>> events;      // timing pairs recorded since the last oth_ctx_get_timing
+    std::vector<std::pair<Event, Event>> free_events;
     double total_ms = 0.0;
     uint64_t launches = 0;
-    std::map<int, float2 *> twiddles;
-    float *sink = nullptr;
-    double *acc4 = nullptr;
-    unsigned *queue = nullptr;         // 64 chunk tickets for the dynamic segment schedule
-    unsigned *done_count = nullptr;    // arrival counter of a finalize launch that signals a polling host (FinalizeArgs)
+    std::map<int, DevBuf<float2>> twiddles;      // W_n^k per length (get_twiddles): plans, chains and tables borrow them
+    DevBuf<float> sink;
+    DevBuf<double> acc4;
+    DevBuf<unsigned> queue;            // 64 chunk tickets for the dynamic segment schedule
+    unsigned *done_count = nullptr;    // arrival counter of a finalize launch that signals a polling host (FinalizeArgs):
+                                       // word 64 of `queue`
     std::recursive_mutex mu;           // every entry point that takes this context (or a plan / chain of it) holds it
     bool queue_clean = false;          // all zero on the stream's timeline (finalize_kernel re-zeroes what a launch used)
     int queue_used = 0;                // counters the last averaging launch drew from
-    unsigned char *scratch = nullptr;  // device scratch of the small ops (channel power, decision stage, xcorr): grown on
-    size_t scratch_cap = 0;            // demand, never freed per call
+    DevBuf<unsigned char> scratch;     // device scratch of the small ops (channel power, decision stage, xcorr): grown on
+                                       // demand, never freed per call
     // channel slice bounds of the decision stage (oth_scan_decide_dev*): a scanner passes the same lo / hi on every
     // call, so they live on the device and are uploaded again only when their contents change - through a pinned
     // staging buffer, so that the upload is a real asynchronous copy (from pageable memory hipMemcpyAsync may hold the
     // host until the stream has drained, which would make the "asynchronous" entry points wait for the PSD kernels)
     std::vector<int> bounds_host;      // lo[nch] then hi[nch], as last uploaded
-    int *d_bounds = nullptr;
-    int *h_bounds = nullptr;           // pinned
-    size_t bounds_cap = 0;             // ints
-    hipEvent_t bounds_ev = nullptr;    // behind the last upload: the pinned words may be rewritten after it
+    DevBuf<int> d_bounds;
+    PinnedBuf<int> h_bounds;
+    Event bounds_ev;                   // behind the last upload: the pinned words may be rewritten after it
+    ~oth_ctx() {
+        if (own_stream) hipStreamDestroy(stream);
+    }
 };
 
 // Device tables and scratch of the any-length route (fft_any.hip) of one plan / chain
 struct AnyTables {
     AnyShape sh{};                     // kind ANY_NONE: not in use
-    const float2 *tw = nullptr;        // W_L^k, L entries (the context's table cache owns it)
-    float2 *chirp = nullptr;           // Bluestein c[n] = exp(-i pi n^2 / nfft), nfft entries
-    float2 *midtab = nullptr;          // Bluestein FFT_M(conj c) / M, M entries by natural index
-    float2 *ws = nullptr;              // workspace [channel][segment of the chunk][L]
-    size_t ws_cap = 0;
-    float4 *mean = nullptr;            // [channel][segment of the chunk] hi / lo means
-    size_t mean_cap = 0;
+    const float2 *tw = nullptr;        // W_L^k, L entries (borrowed: the context's twiddle cache owns it)
+    DevBuf<float2> chirp;              // Bluestein c[n] = exp(-i pi n^2 / nfft), nfft entries
+    DevBuf<float2> midtab;             // Bluestein FFT_M(conj c) / M, M entries by natural index
+    DevBuf<float2> ws;                 // workspace [channel][segment of the chunk][L]
+    DevBuf<float4> mean;               // [channel][segment of the chunk] hi / lo means
 };
 
 struct oth_plan {
@@ -69,50 +72,43 @@ struct oth_plan {
     int nfft = 0, nperseg = 0, noverlap = 0, step = 0, detrend = 0, scaling = 0, fftshift = 0, trim = 0;
     int db = 0, kernel = OTH_KERNEL_AUTO, sched = OTH_SCHED_DYNAMIC;
     double fs = 1.0, scale = 1.0;      // scale applies to the MEAN over segments
-    float *d_win = nullptr;
-    const float2 *d_tw = nullptr;
-    float4 *d_fd = nullptr;            // window spectrum for the frequency-domain detrend (welch4096ws), or nullptr
-    float4 *d_fd1x = nullptr;          // the same for welch16k1x_half_kernel (16384 points, spectrum confined to |k| < 16)
-    float2 *d_pilot = nullptr;         // per-stream pilots of the frequency-domain detrend (WelchArgs.pilot)
-    size_t pilot_cap = 0;
+    DevBuf<float> d_win;
+    const float2 *d_tw = nullptr;      // borrowed: the context's twiddle cache owns it
+    DevBuf<float4> d_fd;               // window spectrum for the frequency-domain detrend (welch4096ws), or empty
+    DevBuf<float4> d_fd1x;             // the same for welch16k1x_half_kernel (16384 points, spectrum confined to |k| < 16)
+    DevBuf<float2> d_pilot;            // per-stream pilots of the frequency-domain detrend (WelchArgs.pilot)
     bool fast_detrend = false;         // OTH_DETREND_CONSTANT_FAST: the builds without the pilot (WelchArgs.pilot)
     bool rect_window = false;          // every window value is 1 (window == NULL or boxcar): builds without the multiply
     bool compl_window = false;         // w[n] + w[n + nfft / 2] = 1 to one float32 ulp (window_is_complementary, abi_welch.hip)
-    float *d_partial = nullptr;
-    size_t partial_cap = 0;
-    float *d_reduce = nullptr;         // stage-1 output of the two-stage partial-sum reduction
-    size_t reduce_cap = 0;
-    float *d_out = nullptr;            // [4][nfft] + pxy extra
-    size_t out_cap = 0;
+    DevBuf<float> d_partial;
+    DevBuf<float> d_reduce;            // stage-1 output of the two-stage partial-sum reduction
+    DevBuf<float> d_out;               // [4][nfft] + pxy extra
     // Host-output ring of oth_welch_exec / _exec_async (round 5).  The finalize launch writes the PSD straight into a
     // pinned, device-visible row (no copy-engine hop) and then a completion word next to it (FinalizeArgs.host_seq);
     // the host polls that word instead of sleeping in hipStreamSynchronize.  A slot is reused kOutRing launches later.
     static constexpr int kOutRing = 4;
-    float *h_out = nullptr;            // pinned [kOutRing][nfft]
-    unsigned *h_seq = nullptr;         // pinned [kOutRing]: low 32 bits of the ticket whose row is complete
+    PinnedBuf<float> h_out;            // [kOutRing][nfft]
+    PinnedBuf<unsigned> h_seq;         // [kOutRing]: low 32 bits of the ticket whose row is complete
     uint64_t out_ticket[kOutRing] = {0, 0, 0, 0};
     uint64_t out_nseg[kOutRing] = {0, 0, 0, 0};
     uint64_t next_out_ticket = 1;
     bool pilot_launch = false;         // A/B + parity: the pilot from pilot_mean_kernel also where the kernel could form it
     std::string last_recipe;           // recipe_text() of the last averaging launch (oth__debug_last_recipe)
-    float2 *d_stage = nullptr;         // host-input staging (x then y)
-    size_t stage_cap = 0;
+    DevBuf<float2> d_stage;            // host-input staging (x then y)
     // streaming state
-    float *d_sum = nullptr;            // raw sum |X|^2, natural order
-    float *d_wpm = nullptr;            // 65536-point plans on welch32k.hip: w[n] + w[n + 32768], then w[n] - w[n + 32768] (n < 32768)
+    DevBuf<float> d_sum;               // raw sum |X|^2, natural order
+    DevBuf<float> d_wpm;               // 65536-point plans on welch32k.hip: w[n] + w[n + 32768], then w[n] - w[n + 32768] (n < 32768)
     uint64_t nseg_total = 0;
     size_t carry = 0;                  // samples kept at the front of d_stream
-    float2 *d_stream = nullptr;
-    size_t stream_cap = 0;
+    DevBuf<float2> d_stream;
     // launch tuning (A/B tools and the parity suite): the OTH_W4096_* environment variables are read ONCE, when
     // the plan is created; oth_plan_set_tuning() changes them afterwards.  0 / -1 / empty = library default.
     std::string tune_variant;
     int tune_sched = -1, tune_chunk = 0, tune_tail = 0;
     // pinned staging ring of the streaming form (oth_welch_accumulate): the caller's buffer is copied here, the
     // H2D copy and the kernels are enqueued, and the call returns without waiting for the GPU
-    void *h_ring[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t h_ring_cap[4] = {0, 0, 0, 0};
-    hipEvent_t h_ring_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    PinnedBuf<char> h_ring[4];
+    Event h_ring_ev[4];                // behind the H2D copy out of the slot
     unsigned h_ring_next = 0;
     AnyTables any;                     // any.sh.kind != ANY_NONE: the plan's length runs through fft_any.hip
     // Blocking oth_welch_exec calls on one plan run one at a time (enqueue + collect under this mutex; the CONTEXT lock is
@@ -124,54 +120,44 @@ struct oth_plan {
     // d_rows ([stream][segment][nfft], grown on demand: ensure() drains the stream before it frees, so a queued ticket
     // never reads a freed buffer), median.hip selects into d_med, finalize_kernel scales by scale / bias
     int average = OTH_AVERAGE_MEAN;
-    float *d_rows = nullptr;
-    size_t rows_cap = 0;
-    float *d_med = nullptr;            // [nstreams][nfft] medians, natural bin order
-    size_t med_cap = 0;
-    unsigned *d_msel = nullptr;        // radix-select scratch (median_scratch_words)
-    size_t msel_cap = 0;
+    DevBuf<float> d_rows;
+    DevBuf<float> d_med;               // [nstreams][nfft] medians, natural bin order
+    DevBuf<unsigned> d_msel;           // radix-select scratch (median_scratch_words)
     AnyTables rows_any;                // the any-length tables of a power-of-two plan's rows (p->any serves the others)
     long long bias_nseg = 0;           // _median_bias(bias_nseg) = bias, cached
     double bias = 1.0;
     // multitaper plans (oth_mtm_plan, abi_mtm.hip): ntapers > 0; run_average hands every launch to mtm_run, d_win stays null
     int ntapers = 0;
-    float *d_tapers = nullptr;         // [ntapers][nfft], zero-extended behind nperseg
-    float *d_coef = nullptr;           // [ntapers] c_k: normalised weight (over the taper's energy with OTH_SCALE_DENSITY)
+    DevBuf<float> d_tapers;            // [ntapers][nfft], zero-extended behind nperseg
+    DevBuf<float> d_coef;              // [ntapers] c_k: normalised weight (over the taper's energy with OTH_SCALE_DENSITY)
 };
 
 struct oth_chain {
     oth_ctx *ctx = nullptr;
     int nfft = 0, fftshift = 0, epilogue = 0, keep_n = 1, count = 1;
-    float *d_win = nullptr;
-    const float2 *d_tw = nullptr;
-    float2 *d_buf = nullptr;           // leftover + new samples
-    size_t buf_cap = 0;
+    DevBuf<float> d_win;
+    const float2 *d_tw = nullptr;      // borrowed: the context's twiddle cache owns it
+    DevBuf<float2> d_buf;              // leftover + new samples
     size_t leftover = 0;               // samples at the front of d_buf
-    float *d_rows = nullptr;
-    size_t rows_cap = 0;
+    DevBuf<float> d_rows;
     int do_iir = 0, do_peak = 0;
     float alpha = 0.f, kdb = 0.f;
-    float *d_iir = nullptr, *d_peak = nullptr;
-    int *d_peak_init = nullptr;
-    float2 *d_stage = nullptr;         // host input lands here (H2D), then feeds the kernels
-    size_t stage_cap = 0;
-    float *d_partial = nullptr;        // per-team accumulator rows of the fused kernel
-    size_t partial_cap = 0;
-    float *d_tail = nullptr;           // group rows of the two-launch cross-team reduction
-    size_t tail_cap = 0;
+    DevBuf<float> d_iir, d_peak;
+    DevBuf<int> d_peak_init;
+    DevBuf<float2> d_stage;            // host input lands here (H2D), then feeds the kernels
+    DevBuf<float> d_partial;           // per-team accumulator rows of the fused kernel
+    DevBuf<float> d_tail;              // group rows of the two-launch cross-team reduction
     bool peak_flag_set = false;        // d_peak_init is 1 on the stream's timeline
     bool rect = false;                 // the window is all ones (fft_vcc's `()`): the 8192 / 16384 chain skips the multiply
     int kernel = OTH_KERNEL_AUTO;      // OTH_KERNEL_GENERIC forces the coverage kernels (parity tests)
-    float *d_out = nullptr;            // rows handed back by the host-output forms
-    size_t out_cap = 0;
+    DevBuf<float> d_out;               // rows handed back by the host-output forms
     // asynchronous work() form (oth_chain_push_async): pinned input ring + pinned latest-row ring.  A slot is
     // reused kRing tickets later; before it is written again the push waits for the event of the slot's last push that
     // enqueued work - however many dropped tickets lie in between - which costs nothing once the GPU has caught up.
     static constexpr int kRing = 4;
-    void *h_in[kRing] = {nullptr, nullptr, nullptr, nullptr};
-    size_t h_in_cap[kRing] = {0, 0, 0, 0};
-    float *h_row[kRing] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev[kRing] = {nullptr, nullptr, nullptr, nullptr};      // recorded behind the D2H of the slot's row
+    PinnedBuf<char> h_in[kRing];
+    PinnedBuf<float> h_row[kRing];
+    Event ev[kRing];                   // recorded behind the D2H of the slot's row
     uint64_t ticket_of[kRing] = {0, 0, 0, 0};
     uint64_t nrows_of[kRing] = {0, 0, 0, 0};
     uint64_t next_ticket = 1;
@@ -185,8 +171,8 @@ struct oth_chain {
     // push that enqueues work uploads them first; set_keep_one_in_n may make the vector a kept one meanwhile.
     bool leftover_stale = false;
     size_t tail_from = 0;
-    float2 *h_tail = nullptr;          // nfft samples, pinned
-    hipEvent_t tail_ev = nullptr;      // recorded behind push / push_dev's upload from h_tail
+    PinnedBuf<float2> h_tail;          // nfft samples
+    Event tail_ev;                     // recorded behind push / push_dev's upload from h_tail
     bool tail_ev_live = false;         // ... which a dropped push waits for before it rewrites h_tail
 };
 
@@ -204,8 +190,6 @@ constexpr size_t kPinnedRingMax = 64u << 20;
 // staged by the runtime before hipMemcpyAsync returns.
 bool host_ptr_is_pinned(const void *p);
 
-int fail(oth_ctx *c, int code, const std::string &msg);
-
 // Serialises the entry points per context: GNU Radio runs each block's work() on its own thread and the
 // blocks of one process share the default context (scratch buffers, ticket counters, timing events).
 struct CtxGuard {
@@ -219,13 +203,6 @@ struct CtxGuard {
     CtxGuard(const CtxGuard &) = delete;
     CtxGuard &operator=(const CtxGuard &) = delete;
 };
-
-#define HIPCHK(c, expr)                                                                                 \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return fail((c), OTH_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));           \
-    } while (0)
 
 // The exception barrier of the C ABI (include/ofdm_tools_hip.h: "nothing throws or aborts").  Every extern "C" body
 // sits between OTH_TRY and OTH_CATCH(context): a std::bad_alloc (std::vector / std::string growth), a
@@ -243,71 +220,34 @@ int copy_in_and_wait(oth_ctx *c, void *dst, const void *src, size_t bytes);
 
 int get_twiddles(oth_ctx *c, int nfft, const float2 **out);
 
-template <typename P> int ensure(oth_ctx *c, P **ptr, size_t *cap, size_t need_bytes) {
-    if (*cap >= need_bytes && *ptr) return OTH_OK;
-    if (*ptr) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(*ptr));
-        *ptr = nullptr;
-        *cap = 0;
-    }
-    void *p = nullptr;
-    hipError_t e = hipMalloc(&p, need_bytes);
-    if (e != hipSuccess) return fail(c, OTH_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    *ptr = reinterpret_cast<P *>(p);
-    *cap = need_bytes;
-    return OTH_OK;
-}
-
-// grow while keeping the first keep_bytes
-template <typename P> int ensure_keep(oth_ctx *c, P **ptr, size_t *cap, size_t need_bytes, size_t keep_bytes) {
-    if (*cap >= need_bytes && *ptr) return OTH_OK;
-    void *p = nullptr;
-    const size_t newcap = need_bytes + need_bytes / 4;
-    hipError_t e = hipMalloc(&p, newcap);
-    if (e != hipSuccess) return fail(c, OTH_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    if (*ptr) {
-        if (keep_bytes) HIPCHK(c, hipMemcpyAsync(p, *ptr, keep_bytes, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(*ptr));
-    }
-    *ptr = reinterpret_cast<P *>(p);
-    *cap = newcap;
-    return OTH_OK;
-}
-
-// A pinned host buffer of at least `bytes` (the staging rings): a short one is freed and replaced by one half as large
-// again (+ 4 KiB), so that a caller whose chunks grow slowly does not reallocate on every call.
-int grow_pinned(oth_ctx *c, void **buf, size_t *cap, size_t bytes);
-
 struct Timed {
     oth_ctx *c;
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;
     explicit Timed(oth_ctx *ctx) : c(ctx) {
         if (!c->timing) return;
         if (c->events.size() >= 8192) {   // fold what we have
             hipStreamSynchronize(c->stream);
             for (auto &ev : c->events) {
                 float ms = 0.f;
-                if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) c->total_ms += ms;
-                c->free_events.push_back(ev);
+                if (hipEventElapsedTime(&ms, ev.first.get(), ev.second.get()) == hipSuccess) c->total_ms += ms;
+                c->free_events.push_back(std::move(ev));
             }
             c->events.clear();
         }
         if (!c->free_events.empty()) {
-            a = c->free_events.back().first;
-            b = c->free_events.back().second;
+            a = std::move(c->free_events.back().first);
+            b = std::move(c->free_events.back().second);
             c->free_events.pop_back();
-        } else if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
-            a = b = nullptr;
+        } else if (a.create(hipEventDefault) != hipSuccess || b.create(hipEventDefault) != hipSuccess) {
+            a.reset();
             return;
         }
-        hipEventRecord(a, c->stream);
+        hipEventRecord(a.get(), c->stream);
     }
     ~Timed() {
         if (!a) return;
-        hipEventRecord(b, c->stream);
-        c->events.emplace_back(a, b);
+        hipEventRecord(b.get(), c->stream);
+        c->events.emplace_back(std::move(a), std::move(b));
         c->launches++;
     }
 };
@@ -405,7 +345,6 @@ std::string recipe_text(const LaunchRecipe &r, int nfft);
 PlanShape shape_of(const oth_plan *p);
 
 // ---- abi_any.hip: the any-length host driver (fft_any.hip, fft_tl.hip, welch32k.hip) --------------------------------------
-void any_tables_free(AnyTables &t);
 int any_tables_init(oth_ctx *c, int nfft, AnyTables *t);
 int any_partial_rows(const AnyShape &sh, long long nseg, int cu_count);
 int any_run(oth_ctx *c, AnyTables &t, const float2 *x, const float2 *y, long long first, long long seg_step, int nperseg,
@@ -415,6 +354,12 @@ int any_run(oth_ctx *c, AnyTables &t, const float2 *x, const float2 *y, long lon
 inline size_t any_fft_nat_scratch(const AnyShape &sh) { return 2 * (size_t)sh.L; }
 int any_fft_nat(oth_ctx *c, const AnyTables &t, float2 *data, float2 *scratch);
 void host_fft_pow2(std::vector<double> &re, std::vector<double> &im);
+
+// ---- abi_welch.hip -----------------------------------------------------------------------------------------------------------
+// What oth_welch_plan and oth_mtm_plan share: the checks of the arguments both take, then a fresh plan on the context's
+// device with the common fields set (the detrend code normalised, OTH_HOSTWAIT read).  The caller adds its tables.
+int plan_begin(oth_ctx *c, int nfft, int nperseg, int noverlap, int detrend, int scaling, double fs, int fftshift, int trim_bins,
+               std::unique_ptr<oth_plan> *out);
 
 // ---- abi_mtm.hip: multitaper plans ------------------------------------------------------------------------------------------
 // the averaging launch of a multitaper plan (run_average branches here before resolve_recipe): W partial rows per stream

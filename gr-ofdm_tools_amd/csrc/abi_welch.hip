@@ -137,25 +137,25 @@ int run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
     if (int rrc = resolve_recipe(shape_of(p), csd, nseg, nstreams, c->cu_count, runtime_bpc, &r, &why))
         return fail(c, rrc, why);
     p->last_recipe = recipe_text(r, p->nfft);
-    int rc = ensure(c, &p->d_partial, &p->partial_cap, sizeof(float) * (size_t)nstreams * r.W * r.nch * p->nfft);
+    int rc = p->d_partial.ensure(c, sizeof(float) * (size_t)nstreams * r.W * r.nch * p->nfft);
     {
         const int groups = std::max(kReduceGroups, finalize_row_groups(p->nfft, r.W, r.nch));
-        if (!rc) rc = ensure(c, &p->d_reduce, &p->reduce_cap, sizeof(float) * (size_t)nstreams * groups * r.nch * p->nfft);
+        if (!rc) rc = p->d_reduce.ensure(c, sizeof(float) * (size_t)nstreams * groups * r.nch * p->nfft);
     }
     if (rc) return rc;
-    const float4 *fd_tab = r.form == 2 ? (r.use_fd1x ? p->d_fd1x : p->d_fd) : nullptr;
+    const float4 *fd_tab = r.form == 2 ? (r.use_fd1x ? p->d_fd1x.get() : p->d_fd.get()) : nullptr;
     // the pilot of every stream (WelchArgs.pilot): from its own launch, or formed in the kernel's prologue
     const float2 *pilot = nullptr;
     if (r.pilot == 1) {
-        rc = ensure(c, &p->d_pilot, &p->pilot_cap, sizeof(float2) * 2 * kPilotProbes * (size_t)nstreams);
+        rc = p->d_pilot.ensure(c, sizeof(float2) * 2 * kPilotProbes * (size_t)nstreams);
         if (rc) return rc;
-        HIPCHK(c, launch_pilot_mean(x, csd ? y : nullptr, stride, p->nperseg, p->step, nseg, nstreams, p->d_pilot, c->stream));
-        pilot = p->d_pilot;
+        HIPCHK(c, launch_pilot_mean(x, csd ? y : nullptr, stride, p->nperseg, p->step, nseg, nstreams, p->d_pilot.get(), c->stream));
+        pilot = p->d_pilot.get();
     }
     unsigned *queue = nullptr;
     if (r.tickets) {
-        queue = c->queue;
-        if (!c->queue_clean) HIPCHK(c, hipMemsetAsync(c->queue, 0, sizeof(unsigned) * 64, c->stream));
+        queue = c->queue.get();
+        if (!c->queue_clean) HIPCHK(c, hipMemsetAsync(c->queue.get(), 0, sizeof(unsigned) * 64, c->stream));
         c->queue_clean = false;      // until the finalize launch that follows has re-zeroed them
         c->queue_used = nstreams;
     }
@@ -165,17 +165,17 @@ int run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
             W32kArgs a{};
             a.x = x + (size_t)st * stride;
             a.first = 0, a.step = p->step, a.nseg = nseg;
-            a.win = p->d_win, a.tw = p->any.tw;
-            a.partial = p->d_partial + (size_t)st * r.W * p->nfft;
+            a.win = p->d_win.get(), a.tw = p->any.tw;
+            a.partial = p->d_partial.get() + (size_t)st * r.W * p->nfft;
             a.detrend = p->detrend != OTH_DETREND_NONE;
-            a.front = p->nfft == 65536, a.wpm = p->d_wpm;
+            a.front = p->nfft == 65536, a.wpm = p->d_wpm.get();
             HIPCHK(c, launch_welch32k(a, r.W, c->stream));
         }
     } else if (r.kern == RK_ANY) {
         Timed tm(c);
         for (int st = 0; st < nstreams; ++st) {
-            rc = any_run(c, p->any, x + (size_t)st * stride, csd ? y + (size_t)st * stride : nullptr, 0, p->step, p->nperseg, p->d_win,
-                         p->detrend != OTH_DETREND_NONE, nseg, p->d_partial + (size_t)st * r.W * r.nch * p->nfft, r.W, nullptr, 0,
+            rc = any_run(c, p->any, x + (size_t)st * stride, csd ? y + (size_t)st * stride : nullptr, 0, p->step, p->nperseg, p->d_win.get(),
+                         p->detrend != OTH_DETREND_NONE, nseg, p->d_partial.get() + (size_t)st * r.W * r.nch * p->nfft, r.W, nullptr, 0,
                          1.0f, 0, p->tune_variant == "anycov");
             if (rc) return rc;
         }
@@ -184,14 +184,14 @@ int run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
         g.x = x;
         g.stream_stride = stride;
         g.nstreams = nstreams;
-        g.win = p->d_win;
+        g.win = p->d_win.get();
         g.tw = p->d_tw;
         g.first = 0;
         g.step = p->step;
         g.nseg = nseg;
         g.detrend = p->detrend;
         g.chain = 0;
-        g.partial = p->d_partial;
+        g.partial = p->d_partial.get();
         g.wg_per_stream = r.W;
         g.sched = r.sched;
         g.chunk = r.chunk;
@@ -210,9 +210,9 @@ int run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
         WelchArgs a;
         a.x = x;
         a.y = y;
-        a.win = p->d_win;
+        a.win = p->d_win.get();
         a.tw = p->d_tw;
-        a.partial = p->d_partial;
+        a.partial = p->d_partial.get();
         a.nseg = nseg;
         a.stream_stride = stride;
         a.nperseg = p->nperseg;
@@ -254,7 +254,7 @@ int finalize_and_rearm(oth_ctx *c, FinalizeArgs &f, int nstreams) {
     f.queue_reset = nullptr;
     f.queue_n = 0;
     if (!c->queue_clean && c->queue_used > 0) {
-        f.queue_reset = c->queue;
+        f.queue_reset = c->queue.get();
         f.queue_n = c->queue_used;
     }
     HIPCHK(c, launch_finalize(f, nstreams, c->stream));
@@ -269,21 +269,14 @@ int finalize_and_rearm(oth_ctx *c, FinalizeArgs &f, int nstreams) {
 // reduced through d_reduce.  The caller adds the outputs, scale, shift, trim and accumulate.
 FinalizeArgs finalize_args(const oth_plan *p, int W, int layout, int nch) {
     FinalizeArgs f{};
-    f.partial = p->d_partial;
-    f.scratch = p->d_reduce;
+    f.partial = p->d_partial.get();
+    f.scratch = p->d_reduce.get();
     f.W = W;
     f.nfft = p->nfft;
     f.nch = nch;
     f.layout = layout;
     f.l1 = p->any.sh.L1, f.l2 = p->any.sh.L2;
     return f;
-}
-
-// device copy of a host table of oth_welch_plan (allocation + asynchronous upload; the plan synchronises once at the end)
-template <typename P> hipError_t upload_table(oth_ctx *c, P **dst, const std::vector<float> &h) {
-    hipError_t e = hipMalloc(dst, sizeof(float) * h.size());
-    if (e == hipSuccess) e = hipMemcpyAsync(*dst, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice, c->stream);
-    return e;
 }
 
 // ---- median average (OTH_AVERAGE_MEDIAN) --------------------------------------------------------------------------------
@@ -305,7 +298,7 @@ int median_rows(oth_plan *p, const float2 *x, int nstreams, size_t stride, long 
     oth_ctx *c = p->ctx;
     const int N = p->nfft;
     const size_t need = sizeof(float) * (size_t)nstreams * (size_t)nseg * (size_t)N;
-    if (int rc = ensure(c, &p->d_rows, &p->rows_cap, need)) {
+    if (int rc = p->d_rows.ensure(c, need)) {
         if (rc != OTH_ERR_NOMEM) return rc;
         return fail(c, rc, "per-segment rows workspace of " + std::to_string(need) +
                                " bytes (nstreams x nseg x nfft x 4 B) could not be allocated (" + c->err + ")");
@@ -316,7 +309,7 @@ int median_rows(oth_plan *p, const float2 *x, int nstreams, size_t stride, long 
         a.x = x;
         a.stream_stride = stride;
         a.nstreams = nstreams;
-        a.win = p->d_win;
+        a.win = p->d_win.get();
         a.tw = p->d_tw;
         a.first = 0;
         a.step = p->step;
@@ -324,7 +317,7 @@ int median_rows(oth_plan *p, const float2 *x, int nstreams, size_t stride, long 
         a.detrend = det ? 1 : 0;
         a.chain = 1;
         a.acc_mode = 3;      // rows only
-        a.rows = p->d_rows;
+        a.rows = p->d_rows.get();
         a.store_from = 0;
         a.epilogue = OTH_EPI_MAG2;
         a.scale = 1.0f;
@@ -340,35 +333,36 @@ int median_rows(oth_plan *p, const float2 *x, int nstreams, size_t stride, long 
             if (int rc = any_tables_init(c, N, t)) return rc;
     }
     for (int st = 0; st < nstreams; ++st)
-        if (int rc = any_run(c, *t, x + (size_t)st * stride, nullptr, 0, p->step, p->nperseg, p->d_win, det, nseg, nullptr, 0,
-                             p->d_rows + (size_t)st * nseg * N, OTH_EPI_MAG2, 1.0f, 0))
+        if (int rc = any_run(c, *t, x + (size_t)st * stride, nullptr, 0, p->step, p->nperseg, p->d_win.get(), det, nseg, nullptr, 0,
+                             p->d_rows.get() + (size_t)st * nseg * N, OTH_EPI_MAG2, 1.0f, 0))
             return rc;
     *route = kAnyKindName[t->sh.kind];
     return OTH_OK;
 }
 
-// rows + radix select: the medians of every bin of every stream land in p->d_med ([stream][nfft], unscaled)
+// rows + radix select: the medians of every bin of every stream land in p->d_med.get() ([stream][nfft], unscaled)
 int median_run(oth_plan *p, const float2 *x, size_t nsamples, int nstreams, size_t stride, long long *nseg_out) {
     oth_ctx *c = p->ctx;
     long long nseg = 0;
     if (segments(p, nsamples, &nseg) != OTH_OK) return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
     if (nseg >= (1LL << 31)) return fail(c, OTH_ERR_UNSUPPORTED, "median average: more than 2^31 segments per stream");
     const int N = p->nfft;
-    int rc = ensure(c, &p->d_med, &p->med_cap, sizeof(float) * (size_t)nstreams * N);
-    if (!rc) rc = ensure(c, &p->d_msel, &p->msel_cap, sizeof(unsigned) * median_scratch_words(N, nstreams));
-    if (rc) return rc;
     MedianArgs m{};
     m.nseg = nseg;
     m.nfft = N;
     m.nstreams = nstreams;
     m.seg_per_wg = median_seg_per_wg(nseg, N, nstreams, c->cu_count);
-    median_bind_scratch(m, p->d_msel);
-    m.med = p->d_med;
     const char *route = "";
     {
         Timed tm(c);      // rows producer + selection
-        if ((rc = median_rows(p, x, nstreams, stride, nseg, &route))) return rc;
-        m.rows = reinterpret_cast<const unsigned *>(p->d_rows);
+        // the rows workspace first: it is the one a large request is refused on, and the plan then holds what it held before
+        int rc = median_rows(p, x, nstreams, stride, nseg, &route);
+        if (!rc) rc = p->d_med.ensure(c, sizeof(float) * (size_t)nstreams * N);
+        if (!rc) rc = p->d_msel.ensure(c, sizeof(unsigned) * median_scratch_words(N, nstreams));
+        if (rc) return rc;
+        median_bind_scratch(m, p->d_msel.get());
+        m.med = p->d_med.get();
+        m.rows = reinterpret_cast<const unsigned *>(p->d_rows.get());
         HIPCHK(c, launch_median_select(m, c->stream));
     }
     p->last_recipe = std::string("kernel=median rows=") + route + " nfft=" + std::to_string(N) + " nseg=" + std::to_string(nseg) +
@@ -382,6 +376,39 @@ int median_run(oth_plan *p, const float2 *x, size_t nsamples, int nstreams, size
 }
 }  // namespace
 
+namespace oth {
+int plan_begin(oth_ctx *c, int nfft, int nperseg, int noverlap, int detrend, int scaling, double fs, int fftshift, int trim_bins,
+               std::unique_ptr<oth_plan> *out) {
+    if (nfft < 1) return fail(c, OTH_ERR_INVALID, "nfft must be positive");
+    if (nperseg < 1 || nperseg > nfft) return fail(c, OTH_ERR_INVALID, "need 1 <= nperseg <= nfft");
+    if (noverlap < 0 || noverlap >= nperseg) return fail(c, OTH_ERR_INVALID, "need 0 <= noverlap < nperseg");
+    if (detrend != OTH_DETREND_NONE && detrend != OTH_DETREND_CONSTANT && detrend != OTH_DETREND_CONSTANT_EXACT &&
+        detrend != OTH_DETREND_CONSTANT_FAST)
+        return fail(c, OTH_ERR_INVALID, "unknown detrend");
+    if (scaling < OTH_SCALE_RAW || scaling > OTH_SCALE_SPECTRUM) return fail(c, OTH_ERR_INVALID, "unknown scaling");
+    if (trim_bins < 0 || 2 * trim_bins >= nfft) return fail(c, OTH_ERR_INVALID, "trim_bins out of range");
+    if (!(fs > 0.0)) return fail(c, OTH_ERR_INVALID, "fs must be positive");
+    if (use_device(c)) return OTH_ERR_HIP;
+    std::unique_ptr<oth_plan> p(new (std::nothrow) oth_plan());
+    if (!p) return fail(c, OTH_ERR_NOMEM, "host allocation failed");
+    p->ctx = c;
+    p->nfft = nfft;
+    p->nperseg = nperseg;
+    p->noverlap = noverlap;
+    p->step = nperseg - noverlap;
+    p->fast_detrend = detrend == OTH_DETREND_CONSTANT_FAST;
+    p->detrend = detrend != OTH_DETREND_NONE ? OTH_DETREND_CONSTANT : OTH_DETREND_NONE;      // one operation: forms and builds
+                                                                                              // are run_average's choice
+    p->scaling = scaling;
+    p->fs = fs;
+    p->fftshift = fftshift != 0;
+    p->trim = trim_bins;
+    if (const char *e = getenv("OTH_HOSTWAIT")) p->hostwait = !strcmp(e, "sync") ? 1 : 0;      // initial value of oth_plan_set_hostwait
+    *out = std::move(p);
+    return OTH_OK;
+}
+}  // namespace oth
+
 extern "C" {
 /* ---- Welch ---------------------------------------------------------------- */
 
@@ -391,38 +418,15 @@ int oth_welch_plan(oth_ctx *c, int nfft, int nperseg, int noverlap, const float 
     CtxGuard guard_(c);
     if (!c || !out) return fail(c, OTH_ERR_INVALID, "ctx/out is NULL");
     *out = nullptr;
-    if (nfft < 1) return fail(c, OTH_ERR_INVALID, "nfft must be positive");
+    std::unique_ptr<oth_plan> p;
+    if (int rc = plan_begin(c, nfft, nperseg, noverlap, detrend, scaling, fs, fftshift, trim_bins, &p)) return rc;
     const bool any_route = !generic_supported(nfft);      // not a power of two in [64, 16384]: fft_any.hip
-    if (nperseg < 1 || nperseg > nfft) return fail(c, OTH_ERR_INVALID, "need 1 <= nperseg <= nfft");
-    if (noverlap < 0 || noverlap >= nperseg) return fail(c, OTH_ERR_INVALID, "need 0 <= noverlap < nperseg");
-    if (detrend != OTH_DETREND_NONE && detrend != OTH_DETREND_CONSTANT && detrend != OTH_DETREND_CONSTANT_EXACT &&
-        detrend != OTH_DETREND_CONSTANT_FAST)
-        return fail(c, OTH_ERR_INVALID, "unknown detrend");
-    const bool fast_detrend = detrend == OTH_DETREND_CONSTANT_FAST;
-    if (detrend != OTH_DETREND_NONE) detrend = OTH_DETREND_CONSTANT;      // one operation: forms and builds are run_average's choice
-    if (scaling < OTH_SCALE_RAW || scaling > OTH_SCALE_SPECTRUM) return fail(c, OTH_ERR_INVALID, "unknown scaling");
-    if (trim_bins < 0 || 2 * trim_bins >= nfft) return fail(c, OTH_ERR_INVALID, "trim_bins out of range");
-    if (!(fs > 0.0)) return fail(c, OTH_ERR_INVALID, "fs must be positive");
-    if (use_device(c)) return OTH_ERR_HIP;
-    oth_plan *p = new (std::nothrow) oth_plan();
-    if (!p) return fail(c, OTH_ERR_NOMEM, "host allocation failed");
-    p->ctx = c;
-    p->nfft = nfft;
-    p->nperseg = nperseg;
-    p->noverlap = noverlap;
-    p->step = nperseg - noverlap;
-    p->detrend = detrend;
-    p->fast_detrend = fast_detrend;
-    p->scaling = scaling;
-    p->fs = fs;
-    p->fftshift = fftshift != 0;
-    p->trim = trim_bins;
+    const bool det = p->detrend == OTH_DETREND_CONSTANT;
     if (const char *e = getenv("OTH_W4096_VARIANT")) p->tune_variant = e;      // read once, here
     if (const char *e = getenv("OTH_W4096_SCHED")) p->tune_sched = atoi(e);
     if (const char *e = getenv("OTH_W4096_CHUNK")) p->tune_chunk = atoi(e);
     if (const char *e = getenv("OTH_W4096_TAIL")) p->tune_tail = atoi(e);
     if (const char *e = getenv("OTH_PILOT_LAUNCH")) p->pilot_launch = atoi(e) != 0;
-    if (const char *e = getenv("OTH_HOSTWAIT")) p->hostwait = !strcmp(e, "sync") ? 1 : 0;      // initial value of oth_plan_set_hostwait
     std::vector<float> w(nfft, 0.f);   // zero-extended so that kernels may index [0, nfft)
     double s1 = 0.0, s2 = 0.0;
     p->rect_window = true;
@@ -438,43 +442,31 @@ int oth_welch_plan(oth_ctx *c, int nfft, int nperseg, int noverlap, const float 
         case OTH_SCALE_SPECTRUM: p->scale = 1.0 / (s1 * s1); break;
         default: p->scale = 1.0;
     }
-    int rc = any_route ? any_tables_init(c, nfft, &p->any) : get_twiddles(c, nfft, &p->d_tw);
-    if (rc) {
-        delete p;
-        return rc;
-    }
-    hipError_t e = hipMalloc(&p->d_win, sizeof(float) * nfft);
-    if (e == hipSuccess) e = hipMalloc(&p->d_sum, sizeof(float) * nfft);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->d_win, w.data(), sizeof(float) * nfft, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(p->d_sum, 0, sizeof(float) * nfft, c->stream);
-    std::vector<float> fd;
-    if (e == hipSuccess && detrend == OTH_DETREND_CONSTANT &&
-        ((nfft == 4096 && nperseg == 4096 && window_spectrum_table(w, fd)) ||
-         (nfft == 2048 && nperseg == 2048 && window_spectrum_table_seg(w, nfft, fd)) ||
-         ((nfft == 8192 || nfft == 16384) && nperseg == nfft && window_spectrum_table_16k(w, nfft, fd)))) {
-        e = upload_table(c, &p->d_fd, fd);
-    }
     p->compl_window = nfft == 4096 && nperseg == 4096 && window_is_complementary(w, nfft);      // the welch4096ws route's shape
-    std::vector<float> fd1x;
-    if (e == hipSuccess && detrend == OTH_DETREND_CONSTANT && (nfft == 16384 || nfft == 8192) && nperseg == nfft &&
-        window_spectrum_table_1x(w, nfft, fd1x)) {
-        e = upload_table(c, &p->d_fd1x, fd1x);
-    }
-    std::vector<float> wpm;
-    if (e == hipSuccess && any_route && nfft == 65536 && nperseg == 65536) {
+    // the host tables first, then the uploads: nothing between the first asynchronous copy and the synchronise can throw
+    std::vector<float> fd, fd1x, wpm;
+    const bool have_fd = det && ((nfft == 4096 && nperseg == 4096 && window_spectrum_table(w, fd)) ||
+                                 (nfft == 2048 && nperseg == 2048 && window_spectrum_table_seg(w, nfft, fd)) ||
+                                 ((nfft == 8192 || nfft == 16384) && nperseg == nfft && window_spectrum_table_16k(w, nfft, fd)));
+    const bool have_fd1x = det && (nfft == 16384 || nfft == 8192) && nperseg == nfft && window_spectrum_table_1x(w, nfft, fd1x);
+    if (any_route && nfft == 65536 && nperseg == 65536) {
         wpm.resize(65536);
         for (int n = 0; n < 32768; ++n) {
             wpm[n] = (float)((double)w[n] + (double)w[n + 32768]);
             wpm[32768 + n] = (float)((double)w[n] - (double)w[n + 32768]);
         }
-        e = upload_table(c, &p->d_wpm, wpm);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        oth_plan_destroy(p);
-        return fail(c, OTH_ERR_HIP, std::string("plan setup: ") + hipGetErrorString(e));
-    }
-    *out = p;
+    if (int rc = any_route ? any_tables_init(c, nfft, &p->any) : get_twiddles(c, nfft, &p->d_tw)) return rc;
+    hipError_t e = p->d_win.upload(c, w.data(), sizeof(float) * nfft);
+    if (e == hipSuccess) e = p->d_sum.alloc(sizeof(float) * nfft);
+    if (e == hipSuccess) e = hipMemsetAsync(p->d_sum.get(), 0, sizeof(float) * nfft, c->stream);
+    if (e == hipSuccess && have_fd) e = p->d_fd.upload(c, fd.data(), sizeof(float) * fd.size());
+    if (e == hipSuccess && have_fd1x) e = p->d_fd1x.upload(c, fd1x.data(), sizeof(float) * fd1x.size());
+    if (e == hipSuccess && !wpm.empty()) e = p->d_wpm.upload(c, wpm.data(), sizeof(float) * wpm.size());
+    const hipError_t es = hipStreamSynchronize(c->stream);      // also after a failure: the host tables die here
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, OTH_ERR_HIP, std::string("plan setup: ") + hipGetErrorString(e));
+    *out = p.release();
     return OTH_OK;
     OTH_CATCH(c)
 }
@@ -486,30 +478,6 @@ int oth_plan_destroy(oth_plan *p) {
     oth_ctx *c = p->ctx;
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
-    if (p->d_win) hipFree(p->d_win);
-    if (p->d_tapers) hipFree(p->d_tapers);
-    if (p->d_coef) hipFree(p->d_coef);
-    if (p->d_wpm) hipFree(p->d_wpm);
-    if (p->d_fd) hipFree(p->d_fd);
-    if (p->d_fd1x) hipFree(p->d_fd1x);
-    if (p->d_pilot) hipFree(p->d_pilot);
-    if (p->d_partial) hipFree(p->d_partial);
-    if (p->d_reduce) hipFree(p->d_reduce);
-    if (p->d_out) hipFree(p->d_out);
-    if (p->h_out) hipHostFree(p->h_out);
-    if (p->h_seq) hipHostFree(p->h_seq);
-    if (p->d_stage) hipFree(p->d_stage);
-    if (p->d_sum) hipFree(p->d_sum);
-    if (p->d_stream) hipFree(p->d_stream);
-    any_tables_free(p->any);
-    any_tables_free(p->rows_any);
-    if (p->d_rows) hipFree(p->d_rows);
-    if (p->d_med) hipFree(p->d_med);
-    if (p->d_msel) hipFree(p->d_msel);
-    for (int i = 0; i < 4; ++i) {
-        if (p->h_ring[i]) hipHostFree(p->h_ring[i]);
-        if (p->h_ring_ev[i]) hipEventDestroy(p->h_ring_ev[i]);
-    }
     delete p;
     return OTH_OK;
     OTH_CATCH((p ? p->ctx : nullptr))
@@ -630,7 +598,7 @@ int oth_welch_segments_dev(oth_plan *p, const void *iq_dev, size_t nsamples, flo
     for (long long s0 = 0; s0 < nseg; s0 += 65535) {
         const long long nb = std::min(65535LL, nseg - s0);
         FinalizeArgs f{};
-        f.partial = p->d_rows + (size_t)s0 * p->nfft;
+        f.partial = p->d_rows.get() + (size_t)s0 * p->nfft;
         f.out0 = rows_dev + (size_t)s0 * nout;
         f.scale = p->scale;
         f.W = 1;
@@ -661,7 +629,7 @@ static int welch_exec_dev_impl(oth_plan *p, const void *iq_dev, size_t nsamples,
         // one row of medians per stream: finalize_kernel applies scale / bias, fftshift, trim and dB
         if (int rc = median_run(p, (const float2 *)iq_dev, nsamples, nstreams, stream_stride, &nseg)) return rc;
         f = finalize_args(p, 1, 0, 1);
-        f.partial = p->d_med;
+        f.partial = p->d_med.get();
         f.scratch = nullptr;
         f.scale = p->scale / p->bias;
     } else {
@@ -698,13 +666,13 @@ int oth_welch_exec_dev(oth_plan *p, const void *iq_dev, size_t nsamples, int nst
 static int stage_host(oth_plan *p, const void *x, const void *y, size_t nsamples, const float2 **dx, const float2 **dy) {
     oth_ctx *c = p->ctx;
     const size_t bytes = nsamples * sizeof(float2);
-    int rc = ensure(c, &p->d_stage, &p->stage_cap, bytes * (y ? 2 : 1));
+    int rc = p->d_stage.ensure(c, bytes * (y ? 2 : 1));
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(p->d_stage, x, bytes, hipMemcpyHostToDevice, c->stream));
-    *dx = p->d_stage;
+    HIPCHK(c, hipMemcpyAsync(p->d_stage.get(), x, bytes, hipMemcpyHostToDevice, c->stream));
+    *dx = p->d_stage.get();
     if (y) {
-        HIPCHK(c, hipMemcpyAsync(p->d_stage + nsamples, y, bytes, hipMemcpyHostToDevice, c->stream));
-        *dy = p->d_stage + nsamples;
+        HIPCHK(c, hipMemcpyAsync(p->d_stage.get() + nsamples, y, bytes, hipMemcpyHostToDevice, c->stream));
+        *dy = p->d_stage.get() + nsamples;
     }
     return OTH_OK;
 }
@@ -763,16 +731,14 @@ bool poll_seq(const unsigned *word, unsigned want, double budget_ms) {
 int out_ring_init(oth_plan *p) {
     oth_ctx *c = p->ctx;
     if (p->h_out) return OTH_OK;
-    void *rows = nullptr, *seq = nullptr;
-    if (hipHostMalloc(&rows, sizeof(float) * p->nfft * oth_plan::kOutRing, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(&seq, sizeof(unsigned) * 16 * oth_plan::kOutRing, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        if (rows) hipHostFree(rows);
+    PinnedBuf<float> rows;
+    PinnedBuf<unsigned> seq;
+    if (rows.alloc(sizeof(float) * p->nfft * oth_plan::kOutRing) != hipSuccess ||
+        seq.alloc(sizeof(unsigned) * 16 * oth_plan::kOutRing) != hipSuccess)
         return fail(c, OTH_ERR_NOMEM, "pinned host allocation failed");
-    }
-    memset(seq, 0, sizeof(unsigned) * 16 * oth_plan::kOutRing);      // one word per 64-byte line
-    p->h_out = (float *)rows;
-    p->h_seq = (unsigned *)seq;
+    memset(seq.get(), 0, sizeof(unsigned) * 16 * oth_plan::kOutRing);      // one word per 64-byte line
+    p->h_out = std::move(rows);
+    p->h_seq = std::move(seq);
     return OTH_OK;
 }
 
@@ -782,12 +748,12 @@ int out_ring_init(oth_plan *p) {
 int ring_upload(oth_plan *p, void *dst, const void *src, size_t bytes) {
     oth_ctx *c = p->ctx;
     const unsigned slot = p->h_ring_next++ & 3u;
-    if (!p->h_ring_ev[slot]) HIPCHK(c, hipEventCreateWithFlags(&p->h_ring_ev[slot], hipEventDisableTiming));
-    else HIPCHK(c, hipEventSynchronize(p->h_ring_ev[slot]));
-    if (int rc = grow_pinned(c, &p->h_ring[slot], &p->h_ring_cap[slot], bytes)) return rc;
-    memcpy(p->h_ring[slot], src, bytes);
-    HIPCHK(c, hipMemcpyAsync(dst, p->h_ring[slot], bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(p->h_ring_ev[slot], c->stream));
+    if (!p->h_ring_ev[slot]) HIPCHK(c, p->h_ring_ev[slot].create());
+    else HIPCHK(c, hipEventSynchronize(p->h_ring_ev[slot].get()));
+    if (int rc = p->h_ring[slot].grow(c, bytes)) return rc;
+    memcpy(p->h_ring[slot].get(), src, bytes);
+    HIPCHK(c, hipMemcpyAsync(dst, p->h_ring[slot].get(), bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(p->h_ring_ev[slot].get(), c->stream));
     return OTH_OK;
 }
 
@@ -801,7 +767,7 @@ int welch_enqueue(oth_plan *p, const void *iq, size_t nsamples, int src_is_devic
     if (rc) return rc;
     const uint64_t ticket = p->next_out_ticket;
     const int slot = (int)(ticket % oth_plan::kOutRing);
-    unsigned *word = p->h_seq + 16 * slot;
+    unsigned *word = p->h_seq.get() + 16 * slot;
     // the slot's previous launch (kOutRing tickets ago) must have delivered before its row is written again
     if (p->out_ticket[slot] && !seq_reached(word, (unsigned)p->out_ticket[slot])) {
         if (!poll_seq(word, (unsigned)p->out_ticket[slot], kPollFallbackMs)) HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -815,19 +781,19 @@ int welch_enqueue(oth_plan *p, const void *iq, size_t nsamples, int src_is_devic
         if (!caller_blocks && bytes <= kPinnedStageMax) {
             // work()-sized buffers: through a pinned slot (as oth_welch_accumulate), so that the call returns at once -
             // from pageable memory hipMemcpyAsync may hold the host until the stream has drained
-            if ((rc = ensure(c, &p->d_stage, &p->stage_cap, bytes))) return rc;
-            if ((rc = ring_upload(p, p->d_stage, iq, bytes))) return rc;
-            dx = p->d_stage;
+            if ((rc = p->d_stage.ensure(c, bytes))) return rc;
+            if ((rc = ring_upload(p, p->d_stage.get(), iq, bytes))) return rc;
+            dx = p->d_stage.get();
         } else if (!caller_blocks && host_ptr_is_pinned(iq)) {
-            if ((rc = ensure(c, &p->d_stage, &p->stage_cap, bytes))) return rc;
-            if ((rc = copy_in_and_wait(c, p->d_stage, iq, bytes))) return rc;
-            dx = p->d_stage;
+            if ((rc = p->d_stage.ensure(c, bytes))) return rc;
+            if ((rc = copy_in_and_wait(c, p->d_stage.get(), iq, bytes))) return rc;
+            dx = p->d_stage.get();
         } else if ((rc = stage_host(p, iq, nullptr, nsamples, &dx, &dy))) {
             return rc;
         }
     }
     uint64_t nseg = 0;
-    if ((rc = welch_exec_dev_impl(p, dx, nsamples, 1, nsamples, p->h_out + (size_t)slot * p->nfft, &nseg, word,
+    if ((rc = welch_exec_dev_impl(p, dx, nsamples, 1, nsamples, p->h_out.get() + (size_t)slot * p->nfft, &nseg, word,
                                   (unsigned)ticket)))
         return rc;
     p->out_ticket[slot] = ticket;
@@ -845,9 +811,9 @@ int welch_collect(oth_plan *p, uint64_t ticket, float *psd_out, uint64_t *nseg_o
     uint64_t nseg;
     {
         CtxGuard guard_(c);
-        if (!ticket || !p->h_out || p->out_ticket[slot] != ticket)
+        if (!ticket || !p->h_out.get() || p->out_ticket[slot] != ticket)
             return fail(c, OTH_ERR_STATE, "ticket unknown or overwritten (the ring keeps the last 4 launches)");
-        word = p->h_seq + 16 * slot;
+        word = p->h_seq.get() + 16 * slot;
         nseg = p->out_nseg[slot];
     }
     bool done = seq_reached(word, (unsigned)ticket);
@@ -867,7 +833,7 @@ int welch_collect(oth_plan *p, uint64_t ticket, float *psd_out, uint64_t *nseg_o
         CtxGuard guard_(c);      // (a newer launch may have taken the slot while this thread was polling)
         if (p->out_ticket[slot] != ticket)
             return fail(c, OTH_ERR_STATE, "ticket overwritten while waiting (the ring keeps the last 4 launches)");
-        if (psd_out) memcpy(psd_out, p->h_out + (size_t)slot * p->nfft, sizeof(float) * (p->nfft - 2 * p->trim));
+        if (psd_out) memcpy(psd_out, p->h_out.get() + (size_t)slot * p->nfft, sizeof(float) * (p->nfft - 2 * p->trim));
     }
     if (nseg_out) *nseg_out = nseg;
     return OTH_OK;
@@ -956,7 +922,7 @@ int oth_welch_reset(oth_plan *p) {
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
     oth_ctx *c = p->ctx;
     if (use_device(c)) return OTH_ERR_HIP;
-    HIPCHK(c, hipMemsetAsync(p->d_sum, 0, sizeof(float) * p->nfft, c->stream));
+    HIPCHK(c, hipMemsetAsync(p->d_sum.get(), 0, sizeof(float) * p->nfft, c->stream));
     p->nseg_total = 0;
     p->carry = 0;
     return OTH_OK;
@@ -973,20 +939,20 @@ int oth_welch_accumulate(oth_plan *p, const void *iq_host, size_t nsamples) {
     if (!nsamples) return OTH_OK;
     if (use_device(c)) return OTH_ERR_HIP;
     const size_t total = p->carry + nsamples;
-    int rc = ensure_keep(c, &p->d_stream, &p->stream_cap, total * sizeof(float2), p->carry * sizeof(float2));
+    int rc = p->d_stream.ensure_keep(c, total * sizeof(float2), p->carry * sizeof(float2));
     if (rc) return rc;
     const bool pinned_src = nsamples * sizeof(float2) > kPinnedStageMax && host_ptr_is_pinned(iq_host);
     if (pinned_src && nsamples * sizeof(float2) > kPinnedRingMax) {
-        if ((rc = copy_in_and_wait(c, p->d_stream + p->carry, iq_host, nsamples * sizeof(float2)))) return rc;
+        if ((rc = copy_in_and_wait(c, p->d_stream.get() + p->carry, iq_host, nsamples * sizeof(float2)))) return rc;
     } else if (nsamples * sizeof(float2) > kPinnedStageMax && !pinned_src) {
         // large chunks: the runtime's own staged copy from pageable memory is faster than a host memcpy into a pinned
         // slot (55 against 33 GB/s at 32 MiB); it returns once the caller's buffer has been read.  (A pinned /
         // registered source would be read asynchronously: it takes the ring below whatever its size.)
-        HIPCHK(c, hipMemcpyAsync(p->d_stream + p->carry, iq_host, nsamples * sizeof(float2), hipMemcpyHostToDevice,
+        HIPCHK(c, hipMemcpyAsync(p->d_stream.get() + p->carry, iq_host, nsamples * sizeof(float2), hipMemcpyHostToDevice,
                                  c->stream));
     } else {
         // the caller's buffer is only valid during the call (sync_block.work contract): through the plan's pinned ring
-        if ((rc = ring_upload(p, p->d_stream + p->carry, iq_host, nsamples * sizeof(float2)))) return rc;
+        if ((rc = ring_upload(p, p->d_stream.get() + p->carry, iq_host, nsamples * sizeof(float2)))) return rc;
     }
     if (total < (size_t)p->nperseg) {
         p->carry = total;
@@ -994,9 +960,9 @@ int oth_welch_accumulate(oth_plan *p, const void *iq_host, size_t nsamples) {
     }
     long long nseg = 0;
     int W = 0, layout = 0;
-    if ((rc = run_average(p, p->d_stream, nullptr, total, 1, total, &nseg, &W, &layout))) return rc;
+    if ((rc = run_average(p, p->d_stream.get(), nullptr, total, 1, total, &nseg, &W, &layout))) return rc;
     FinalizeArgs f = finalize_args(p, W, layout, 1);
-    f.out0 = p->d_sum;
+    f.out0 = p->d_sum.get();
     f.scale = 1.0;
     f.nout = p->nfft;
     f.accumulate = 1;
@@ -1008,13 +974,13 @@ int oth_welch_accumulate(oth_plan *p, const void *iq_host, size_t nsamples) {
     if (keep) {
         // regions may overlap when keep > consumed: bounce through the partial-free tail of d_stage
         if (keep <= consumed) {
-            HIPCHK(c, hipMemcpyAsync(p->d_stream, p->d_stream + consumed, keep * sizeof(float2),
+            HIPCHK(c, hipMemcpyAsync(p->d_stream.get(), p->d_stream.get() + consumed, keep * sizeof(float2),
                                      hipMemcpyDeviceToDevice, c->stream));
         } else {
-            if ((rc = ensure(c, &p->d_stage, &p->stage_cap, keep * sizeof(float2)))) return rc;
-            HIPCHK(c, hipMemcpyAsync(p->d_stage, p->d_stream + consumed, keep * sizeof(float2),
+            if ((rc = p->d_stage.ensure(c, keep * sizeof(float2)))) return rc;
+            HIPCHK(c, hipMemcpyAsync(p->d_stage.get(), p->d_stream.get() + consumed, keep * sizeof(float2),
                                      hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(p->d_stream, p->d_stage, keep * sizeof(float2), hipMemcpyDeviceToDevice,
+            HIPCHK(c, hipMemcpyAsync(p->d_stream.get(), p->d_stage.get(), keep * sizeof(float2), hipMemcpyDeviceToDevice,
                                      c->stream));
         }
     }
@@ -1032,12 +998,12 @@ int oth_welch_finalize(oth_plan *p, float *psd_out, uint64_t *nseg_out) {
     if (!psd_out) return fail(c, OTH_ERR_INVALID, "psd_out is NULL");
     if (!p->nseg_total) return fail(c, OTH_ERR_STATE, "no complete segment accumulated yet");
     if (use_device(c)) return OTH_ERR_HIP;
-    int rc = ensure(c, &p->d_out, &p->out_cap, sizeof(float) * 5 * p->nfft);
+    int rc = p->d_out.ensure(c, sizeof(float) * 5 * p->nfft);
     if (rc) return rc;
     const int nout = p->nfft - 2 * p->trim;
-    HIPCHK(c, launch_scale(p->d_sum, p->d_out, p->nfft, p->scale / (double)p->nseg_total, p->fftshift, p->trim,
+    HIPCHK(c, launch_scale(p->d_sum.get(), p->d_out.get(), p->nfft, p->scale / (double)p->nseg_total, p->fftshift, p->trim,
                            p->db, c->stream));
-    HIPCHK(c, hipMemcpyAsync(psd_out, p->d_out, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(psd_out, p->d_out.get(), sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (nseg_out) *nseg_out = p->nseg_total;
     return oth_welch_reset(p);
@@ -1134,9 +1100,9 @@ int oth_csd_exec(oth_plan *p, const void *x, const void *y, size_t nsamples, int
     const float2 *dx = (const float2 *)x, *dy = (const float2 *)y;
     int rc;
     if (!src_is_device && (rc = stage_host(p, x, y, nsamples, &dx, &dy))) return rc;
-    if ((rc = ensure(c, &p->d_out, &p->out_cap, sizeof(float) * 5 * p->nfft))) return rc;
+    if ((rc = p->d_out.ensure(c, sizeof(float) * 5 * p->nfft))) return rc;
     const int nout = p->nfft - 2 * p->trim;
-    float *o0 = p->d_out, *o1 = p->d_out + p->nfft, *o2 = p->d_out + 2 * p->nfft, *o3 = p->d_out + 4 * p->nfft;
+    float *o0 = p->d_out.get(), *o1 = p->d_out.get() + p->nfft, *o2 = p->d_out.get() + 2 * p->nfft, *o3 = p->d_out.get() + 4 * p->nfft;
     if ((rc = csd_run(p, dx, dy, nsamples, false, o0, o1, o2, o3, nseg_out))) return rc;
     if (pxx) HIPCHK(c, hipMemcpyAsync(pxx, o0, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
     if (pyy) HIPCHK(c, hipMemcpyAsync(pyy, o1, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));

@@ -118,6 +118,7 @@ SIGNATURES = {
     'oth__debug_recipe': (C.c_int, [C.c_int] * 7 + [C.c_char_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_char_p,
                                                     C.c_size_t]),
     'oth__debug_last_recipe': (C.c_int, [_p, C.c_char_p, C.c_size_t]),
+    'oth__debug_live_resources': (C.c_int, [C.POINTER(C.c_int)] * 3),
 }
 
 _lib = None
@@ -152,6 +153,16 @@ def load():
             fn.argtypes = args
         _lib = lib
         return lib
+
+
+def live_resources():
+    """(device buffers, pinned host buffers, events) the library's contexts, plans and chains hold in this process right
+    now (oth__debug_live_resources; needs no device)."""
+    n = [C.c_int() for _ in range(3)]
+    rc = load().oth__debug_live_resources(*[C.byref(v) for v in n])
+    if rc != OK:
+        raise HipError(rc, 'oth__debug_live_resources', load().oth_last_error(None).decode())
+    return tuple(v.value for v in n)
 
 
 def _c64(x):

@@ -30,7 +30,7 @@ def test_header_declares_the_expected_surface():
     names = declared_symbols()
     for must in ('oth_ctx_create', 'oth_welch_plan', 'oth_welch_exec', 'oth_welch_accumulate',
                  'oth_welch_finalize', 'oth_csd_exec', 'oth_chain_push', 'oth_channel_power', 'oth_xcorr',
-                 'oth_last_error'):
+                 'oth_last_error', 'oth__debug_live_resources'):
         assert must in names
     assert len(names) >= 40
 
@@ -64,6 +64,24 @@ def test_no_cpu_fallback_without_gpu():
     import numpy as np
     with pytest.raises(_hip.HipError):
         T.welch_power_estimate(np.zeros(8192, np.complex64), 4096, 1.0)
+
+
+def test_live_resources_are_zero_without_a_context():
+    """oth__debug_live_resources needs no context and no device; a process that never created a context holds nothing.
+    Run in a process of its own: on a GPU machine other modules of this pytest process keep contexts alive."""
+    import subprocess
+    import sys
+    from ofdm_tools import _hip
+    if not os.path.exists(_hip.LIB_PATH):
+        pytest.skip('library not built yet')
+    code = ('import ctypes as C; from ofdm_tools import _hip; lib = _hip.load(); n = [C.c_int(-1) for _ in range(3)]; '
+            'assert lib.oth__debug_live_resources(*[C.byref(v) for v in n]) == 0; '
+            'assert lib.oth__debug_live_resources(None, None, None) == 0; '
+            'assert _hip.live_resources() == (0, 0, 0); print([v.value for v in n])')
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, 'gr-ofdm_tools_amd')] + sys.path),
+               OFDM_TOOLS_HIP_STANDALONE='1')      # (no torch import: nothing here touches a device)
+    out = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.strip() == '[0, 0, 0]', out.stdout + out.stderr
 
 
 def test_exception_barrier_of_the_abi_host_files(tmp_path):
