@@ -28,6 +28,11 @@
 // both flavours came out at 128 VGPRs with 24-96 B of scratch (one reload per segment in the PILOT hot loop, 4-28
 // accesses in the one-segment-chunk path), with and without the fence that keeps item()'s flavours apart there.  This
 // kernel ignores compl_win.  (Its consumers load two seeds, not fifteen twiddles: one s_waitcnt vmcnt in their loop, left as it is.)
+// The consumers' loop has the shape of welch4096ws.hip's (one instance of pass 2 on the data path, idle steps without one,
+// every control read of a batch issued by dft16_from_lds itself): the path a segment pair executes went from 559 to 527
+// VALU instructions (32 of 36 register copies in the loop header; scatter_pow16's four stay), and two compiler waits
+// left the read batches - an lgkmcnt(0) for the item word in front of the exchange-1 reads, an lgkmcnt(1) behind the
+// first counted wait of exchange 2.  121 / 127 VGPRs as before, no scratch.
 //
 // The two pairs run the same chunk schedule (Px draws the tickets, Py reads them), so x_s and y_s are always in
 // the same step.  Frequency-domain detrend as in welch4096ws.hip (needs WelchArgs.fd).
@@ -226,7 +231,7 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
             item(true_type{}, none{}, sb, 0, true);
             if (sched == 0) break;
             if (sched == 2) {
-                step_end(CS_BUBBLE);
+                step_end(CS_BUBBLE);      // the only idle step, always behind a segment: the consumers' loop relies on it
                 ncur = W + uni(ctrl0[4]);
             } else {
                 ncur = cur + W;
@@ -256,35 +261,55 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
         float2 v[16];
         int it = 0;
 
-        // barrier A of step `it`, then what the producer left in image it & 1: item word, sums, pass 2
+        // What the producer left in image q: pass 2, with the item word read by the helper in the same batch (read by the
+        // compiler in front of it, its readfirstlane drew an s_waitcnt lgkmcnt(0) in FRONT of the sixteen reads: one
+        // exposed LDS round trip behind every step's barrier before the batch even went out)
+        auto pass2 = [&](int q) -> int {
+            LdsCtl<true, false> c;
+            c.word_at = ctrl0 + q;
+            dft16_from_lds<17>(v, img + q * LDS_X + r1, [] { __builtin_amdgcn_s_setprio(CS_PBC); }, LdsNoMid(), &c);
+            return __builtin_amdgcn_readfirstlane(c.word);      // both streams run the same schedule
+        };
+        // barrier A of step `it`, then pass 2 of image it & 1
         auto next_item = [&]() -> int {
             __builtin_amdgcn_s_setprio(CS_PBL);
             lds_barrier();
-            const int q = it & 1;
-            const float2 *lq = img + q * LDS_X;
-            const int kind = __builtin_amdgcn_readfirstlane(ctrl0[q]);      // both streams run the same schedule
-            dft16_from_lds<17>(v, lq + r1, [] { __builtin_amdgcn_s_setprio(CS_PBC); });
+            const int kind = pass2(it & 1);
+            ++it;
+            return kind;
+        };
+        // the same step without pass 2: the barrier and the item word only
+        auto idle_step = [&]() -> int {
+            __builtin_amdgcn_s_setprio(CS_PBL);
+            lds_barrier();
+            const int kind = __builtin_amdgcn_readfirstlane(ctrl0[it & 1]);
             ++it;
             return kind;
         };
         if (PILOT && p.pilot_inline) lds_barrier();      // the producers' pilot barrier
+        // The loop as in welch4096ws.hip's consumer: one instance of pass 2 on the data path (the call at the body's end),
+        // idle steps that take the barrier and read the item word only, the loop's condition its only exit, and the
+        // accumulators pinned at the end of the body.  With next_item() also in an idle loop at the head the two
+        // instances' outputs sat in different registers: 36 v_mov per segment in the loop header.
+        // INVARIANT (as there): step 0 is a segment or the stop - the producers publish CS_BUBBLE only behind a
+        // one-segment chunk under sched == 2; entered with CS_BUBBLE the loop would accumulate pass 2 of junk
         int item = next_item();
-        for (;;) {
-            while (item == CS_BUBBLE) item = next_item();
-            if (item == CS_STOP) break;
+        while (item != CS_STOP) {
             const int q = (it & 1) ^ 1;   // the image whose pass 2 sits in v
             float2 *lx = img + q * LDS_X;
             __builtin_amdgcn_s_setprio(CS_PBL);
             scatter_pow16<17>(v, lx + w2, c1, c4);
             wave_lds_sync();
+            // image q's sums stay valid until the barrier of the next step: the helper reads them in front of the
+            // exchange-2 batch; the window-spectrum entries are fetched between the butterfly layers (mid(): behind the
+            // counted waits, with the second layer to hide behind)
             float4 fw = make_float4(0.f, 0.f, 0.f, 0.f);
-            float2 h0 = make_float2(0.f, 0.f), h1 = h0, h2 = h0, h3 = h0;
-            if (DETREND) {      // image q's sums stay valid until the barrier of the next step
-                fw = fwl[t];
-                h0 = red[q * 8], h1 = red[q * 8 + 1], h2 = red[q * 8 + 2], h3 = red[q * 8 + 3];
-            }
-            dft16_from_lds<1>(v, lx + r2, [] { __builtin_amdgcn_s_setprio(CS_PBC); });
+            LdsCtl<false, DETREND> c;
+            c.sums_at = red + q * 8;
+            dft16_from_lds<1>(v, lx + r2, [] { __builtin_amdgcn_s_setprio(CS_PBC); }, [&] { if (DETREND) fw = fwl[t]; }, &c);
             if (DETREND) {
+                const float2 h0 = make_float2(c.s[0].x, c.s[0].y), h1 = make_float2(c.s[0].z, c.s[0].w);
+                const float2 h2 = make_float2(c.s[1].x, c.s[1].y), h3 = make_float2(c.s[1].z, c.s[1].w);
                 const float2 tot = cadd(cadd(h0, h1), cadd(h2, h3));
                 const float2 mean = make_float2(tot.x * (1.0f / 4096.0f), tot.y * (1.0f / 4096.0f));
                 v[r16(0)] = make_float2(v[r16(0)].x - (mean.x * fw.x - mean.y * fw.y),
@@ -309,7 +334,16 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
                 are[j] = fmaf(X.x, Y.x, fmaf(X.y, Y.y, are[j]));
                 aim[j] += cross_im(X, Y);
             }
+            // the accumulation ends here (left free it is sunk below the rare branch behind the next pass 2)
+            asm volatile("" : "+v"(axx[0]), "+v"(axx[1]), "+v"(axx[2]), "+v"(axx[3]), "+v"(axx[4]), "+v"(axx[5]), "+v"(axx[6]), "+v"(axx[7]));
+            asm volatile("" : "+v"(ayy[0]), "+v"(ayy[1]), "+v"(ayy[2]), "+v"(ayy[3]), "+v"(ayy[4]), "+v"(ayy[5]), "+v"(ayy[6]), "+v"(ayy[7]));
+            asm volatile("" : "+v"(are[0]), "+v"(are[1]), "+v"(are[2]), "+v"(are[3]), "+v"(are[4]), "+v"(are[5]), "+v"(are[6]), "+v"(are[7]));
+            asm volatile("" : "+v"(aim[0]), "+v"(aim[1]), "+v"(aim[2]), "+v"(aim[3]), "+v"(aim[4]), "+v"(aim[5]), "+v"(aim[6]), "+v"(aim[7]));
             item = next_item();
+            if (__builtin_expect(item == CS_BUBBLE, 0)) {
+                do item = idle_step(); while (item == CS_BUBBLE);
+                if (item == CS_DATA) pass2((it & 1) ^ 1);      // its barrier was the idle step's
+            }
         }
         // channels xx, yy, re, im; bin k0 + 16 k1 + 256 k2 at t + 256 k2 (finalize_kernel layout 1)
         float *dst = p.partial + ((size_t)stream * W + wg) * 4 * 4096;

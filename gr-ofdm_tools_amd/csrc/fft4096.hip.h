@@ -141,10 +141,38 @@ __device__ __forceinline__ void dft8(float2 (&v)[8]) {
 // `issued()` runs once the reads are out (e.g. to drop the wave's priority for the butterflies).
 // `mid()` runs between the two butterfly layers, when every read of this call has returned: LDS reads issued there
 // (a twiddle table, say) have the second layer to hide behind and do not disturb the counted waits above them.
-template <int STRIDE, class F, class M>
-__device__ __forceinline__ void dft16_from_lds(float2 (&v)[16], const float2 *base, F issued, M mid) {
+//
+// Control reads (LdsCtl): what the caller wants from LDS in the same round trip - a word (WORD), eight floats (SUMS) - is
+// read by the helper IN FRONT of the sixteen, also as asm.  LDS returns in order, so the first counted wait covers them:
+// the sums become visible to the compiler right behind it, the word behind the last first-layer butterfly (its use is a
+// branch).  Read by the compiler instead they are older operations its own wait counting knows about, while it does not
+// see the sixteen: it guards their first use - scheduled into the first layer - with an s_waitcnt lgkmcnt(1) that in truth
+// waits for all the reads but one and voids the counted waits (welch4096ws: behind every step's barrier; csd4096ws: in
+// exchange 2, and an lgkmcnt(0) for the item word in FRONT of the exchange-1 reads).
+// None of the asm reads carries a "memory" clobber: they keep their place behind lds_barrier() / wave_lds_sync() and among
+// each other because asm volatile statements are not reordered against one another (the sixteen always relied on that).
+typedef float lds_f4 __attribute__((ext_vector_type(4)));
+template <bool WORD, bool SUMS> struct LdsCtl {
+    const int *word_at;          // in (WORD)
+    const float2 *sums_at;       // in (SUMS): eight floats, 16-byte aligned
+    int word;                    // out: *word_at (an asm output: not wave-uniform to the compiler, readfirstlane it before branching)
+    lds_f4 s[2];                 // out: sums_at[0..7]
+};
+struct LdsNoMid {
+    __device__ __forceinline__ void operator()() const {}
+};
+
+template <int STRIDE, class F, class M = LdsNoMid, bool WORD = false, bool SUMS = false>
+__device__ __forceinline__ void dft16_from_lds(float2 (&v)[16], const float2 *base, F issued, M mid = M(),
+                                               LdsCtl<WORD, SUMS> *ctl = nullptr) {
     const unsigned addr = (unsigned)(unsigned long long)base;      // LDS byte address = low half of the flat address
     double r[16];
+    if constexpr (WORD) asm volatile("ds_read_b32 %0, %1" : "=v"(ctl->word) : "v"((unsigned)(unsigned long long)ctl->word_at));
+    if constexpr (SUMS) {
+        const unsigned sa = (unsigned)(unsigned long long)ctl->sums_at;
+        asm volatile("ds_read_b128 %0, %1" : "=v"(ctl->s[0]) : "v"(sa));
+        asm volatile("ds_read_b128 %0, %1 offset:16" : "=v"(ctl->s[1]) : "v"(sa));
+    }
 #define OTH_LDS_READ(i) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(r[i]) : "v"(addr), "n"(8 * STRIDE * (i)))
     OTH_LDS_READ(0); OTH_LDS_READ(4); OTH_LDS_READ(8); OTH_LDS_READ(12);
     OTH_LDS_READ(1); OTH_LDS_READ(5); OTH_LDS_READ(9); OTH_LDS_READ(13);
@@ -155,11 +183,12 @@ __device__ __forceinline__ void dft16_from_lds(float2 (&v)[16], const float2 *ba
     // each wait also names an output of the butterfly before it, which keeps that butterfly in front of the wait
 #define OTH_LDS_WAIT(n, a, dep) \
     asm volatile("s_waitcnt lgkmcnt(" #n ")" : "+v"(r[a]), "+v"(r[a + 4]), "+v"(r[a + 8]), "+v"(r[a + 12]), "+v"(dep))
-    float dep = 0.f;
 #pragma unroll
     for (int a0 = 0; a0 < 4; ++a0) {
-        if (a0 == 0) OTH_LDS_WAIT(12, 0, dep);
-        else if (a0 == 1) OTH_LDS_WAIT(8, 1, v[0].x);
+        if (a0 == 0) {      // (nothing in front of it to name: a dummy operand cost a v_mov per call)
+            asm volatile("s_waitcnt lgkmcnt(12)" : "+v"(r[0]), "+v"(r[4]), "+v"(r[8]), "+v"(r[12]));
+            if constexpr (SUMS) asm volatile("" : "+v"(ctl->s[0]), "+v"(ctl->s[1]));      // back with the first four
+        } else if (a0 == 1) OTH_LDS_WAIT(8, 1, v[0].x);
         else if (a0 == 2) OTH_LDS_WAIT(4, 2, v[1].x);
         else OTH_LDS_WAIT(0, 3, v[2].x);
 #pragma unroll
@@ -167,12 +196,10 @@ __device__ __forceinline__ void dft16_from_lds(float2 (&v)[16], const float2 *ba
         dft4<false>(v[a0], v[a0 + 4], v[a0 + 8], v[a0 + 12]);
     }
 #undef OTH_LDS_WAIT
+    // the word becomes visible here, tied to outputs of the last butterfly
+    if constexpr (WORD) asm volatile("" : "+v"(ctl->word), "+v"(v[3].x), "+v"(v[15].y));
     mid();
     dft16_layer2(v);
-}
-template <int STRIDE, class F>
-__device__ __forceinline__ void dft16_from_lds(float2 (&v)[16], const float2 *base, F issued) {
-    dft16_from_lds<STRIDE>(v, base, issued, [] {});
 }
 
 // Non-temporal load of a sample that is read once: it does not displace the tables and partial sums in L2.
@@ -284,7 +311,12 @@ __device__ __forceinline__ void scatter_pow16_stored(const float2 (&v)[16], floa
     float2 wj[4], wi[4];
     wj[1] = p1, wj[2] = p2, wj[3] = p3;
     wi[1] = p4, wi[2] = p8, wi[3] = p12;
-    asm volatile("" : "+v"(wj[1].x), "+v"(wj[1].y), "+v"(wj[2].x), "+v"(wj[2].y), "+v"(wj[3].x), "+v"(wj[3].y));
+    // Opaque is only what the remaining products are formed from, one factor each: W^(4i) for every row i that still has a
+    // product.  An opaque copy of a loop-invariant register is a v_mov per call; with W^1, W^2, W^3 made opaque whatever
+    // NM, the thirteen-power producer paid six per segment for its two products (W^14, W^15), now two.
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (pow16_slot(4 * i + 3) >= NM) asm volatile("" : "+v"(wi[i].x), "+v"(wi[i].y));
     out[0] = v[0];
 #pragma unroll
     for (int k = 1; k < 16; ++k) {

@@ -38,6 +38,15 @@
 // against 0.6132-0.6147 ms = -2.3 %, step 0.613-0.616 against 0.627-0.630 ms, profiles/ab_headline_compl.txt)
 // The consumer waits ONCE for its table loads, in front of its loop: fifteen s_waitcnt vmcnt(n) per segment, one in front
 // of each pass-2 twiddle product, are gone from the critical path (measured together with the above, not on its own)
+// The consumer's EXECUTED path per segment went from 426 to 406 VALU instructions (the budget test read 407 on the former: it
+// leaves out a loop-header block that every segment ran through): one instance of pass 2 on the data path instead of two
+// whose outputs were copied into each other's registers (16 v_mov), the item word compared in scalar registers (2 v_cmp ->
+// 1 v_readfirstlane), no dummy operand on the first counted wait of a read batch (2 v_mov); and the item word and the
+// per-wave sums are read by dft16_from_lds itself, where the compiler's own reads in front of it drew an s_waitcnt
+// lgkmcnt(1) into the first butterfly layer behind every barrier.  Producer 281 -> 277 (two opaque copies of stored
+// twiddle powers instead of six).  Same-box A/B against the parent library, six alternating runs of bench.py each: step
+// 0.5766-0.5804 against 0.5835-0.5862 ms, kernel 0.5636-0.5658 against 0.5710-0.5722 ms = -1.2 %; SQ_INSTS_VALU 3.737e8 ->
+// 3.616e8, SQ_WAIT_INST_LDS -6.8 % per launch; outputs bit for bit the parent's (profiles/ab_headline_consumer_path.txt)
 // tried: the eight loads of a step spread over 2 / 3 places instead of one burst, no gain (NOTES 8,
 // profiles/r05_ab_headline_spread_loads.txt)
 // not tried: the two components of the segment sum reduced in one interleaved DPP sequence (ten s_nop per segment in the
@@ -293,7 +302,7 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
             item(true_type{}, none{}, sb, 0, true);
             if (sched == 0) break;
             if (sched == 2) {
-                step_end(ITEM_BUBBLE);
+                step_end(ITEM_BUBBLE);      // the only idle step there is, always behind a segment: the consumer's loop relies on it
                 ncur = W + uni(ctrl[4]);
             } else {
                 ncur = cur + W;
@@ -325,33 +334,54 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
         asm volatile("" : "+v"(tw2[14].x), "+v"(tw2[14].y), "+v"(tw2[15].x), "+v"(tw2[15].y), "+v"(fw.x), "+v"(fw.y), "+v"(fw.z),
                           "+v"(fw.w));
         int it = 0;
-        // barrier of step `it`, then what the producer left in image it & 1: the item kind and, in the same batch
-        // of LDS reads (harmless when it is not a segment), the exchange-1 reads and the per-wave sums
-        auto next_item = [&]() -> int {
-            __builtin_amdgcn_s_setprio(WS_PBL);
-            lds_barrier();
-            const int q = it & 1;
-            const float2 *lq = img + q * LDS_X;
-            // one batch of LDS reads: the item word and the four per-wave sums (used only after the butterfly, so
-            // their wait falls behind it), then pass 2's sixteen reads as full-rate ds_read_b64 on counted waits.
-            // Pass 2 therefore runs before the item word is looked at - on junk in an idle step and in the last.
-            const int kind = ctrl[q];
-            const float2 h0 = red[q * 8], h1 = red[q * 8 + 1], h2 = red[q * 8 + 2], h3 = red[q * 8 + 3];
-            dft16_from_lds<17>(v, lq + r1, [] { __builtin_amdgcn_s_setprio(WS_PBC); });
+        // What the producer left in image q: the item kind and, in the same batch of LDS reads (harmless when it is not a
+        // segment), the per-wave sums and pass 2's sixteen exchange-1 reads as full-rate ds_read_b64 on counted waits.
+        // Pass 2 therefore runs before the item word is looked at - on junk in an idle step and in the last.  All nineteen
+        // reads are the helper's: with the item word and the sums read by the compiler in front of it, the first add of
+        // the sums was scheduled into the first butterfly layer behind an s_waitcnt lgkmcnt(1), which waits for eighteen
+        // of the nineteen and made the counted waits void right behind every step's barrier.
+        auto pass2 = [&](int q) -> int {
+            LdsCtl<true, DETREND> c;
+            c.word_at = ctrl + q, c.sums_at = red + q * 8;
+            dft16_from_lds<17>(v, img + q * LDS_X + r1, [] { __builtin_amdgcn_s_setprio(WS_PBC); }, LdsNoMid(), &c);
             if (DETREND) {
+                const float2 h0 = make_float2(c.s[0].x, c.s[0].y), h1 = make_float2(c.s[0].z, c.s[0].w);
+                const float2 h2 = make_float2(c.s[1].x, c.s[1].y), h3 = make_float2(c.s[1].z, c.s[1].w);
                 const float2 tot = cadd(cadd(h0, h1), cadd(h2, h3));
                 mean = make_float2(tot.x * (1.0f / 4096.0f), tot.y * (1.0f / 4096.0f));
             }
+            return __builtin_amdgcn_readfirstlane(c.word);      // (an asm output counts as divergent)
+        };
+        // barrier of step `it`, then pass 2 of image it & 1
+        auto next_item = [&]() -> int {
+            __builtin_amdgcn_s_setprio(WS_PBL);
+            lds_barrier();
+            const int kind = pass2(it & 1);
+            ++it;
+            return kind;
+        };
+        // the same step without pass 2: the barrier and the item word only
+        auto idle_step = [&]() -> int {
+            __builtin_amdgcn_s_setprio(WS_PBL);
+            lds_barrier();
+            const int kind = ctrl[it & 1];
             ++it;
             return kind;
         };
         if (PILOT && p.pilot_inline) lds_barrier();      // the producers' pilot barrier
-        int item = next_item();           // nothing to consume in step 0
-        for (;;) {
-            // idle steps stay out of the path that updates the accumulators (with both in one conditional the
-            // sixteen accumulators were copied twice per step)
-            while (item == ITEM_BUBBLE) item = next_item();
-            if (item == ITEM_STOP) break; // the producer left after the barrier of the step that published it
+        // ONE instance of pass 2 feeds the body on the data path, the call at the body's end: with a second one in an idle
+        // loop at the loop's head - while (item == ITEM_BUBBLE) item = next_item(); - the two instances' outputs sat in
+        // different registers and every segment paid sixteen v_mov in the loop header.  Idle steps take their barrier and
+        // read the item word, nothing else; the segment behind them gets its pass 2 on the way out, on the rare edge.
+        // The loop's only exit is its own condition and the body is unconditional inside it: every further exit or
+        // conditional around the body makes the compiler's control-flow structurizer merge two versions of the sixteen
+        // accumulators per step (with the idle loop and the body in one conditional they were copied twice per step).
+        // INVARIANT the loop relies on: step 0 is a segment or the stop, never an idle step - the producer publishes
+        // ITEM_BUBBLE in one place only, behind a one-segment chunk under sched == 2, so a segment always comes first.
+        // Entered with ITEM_BUBBLE this loop would accumulate pass 2 of junk (the loop it replaces tolerated that);
+        // whoever gives the producer another idle step has to send the first item through the idle exit below as well.
+        int item = next_item();           // nothing to consume in front of step 0
+        while (item != ITEM_STOP) {       // (the producer left after the barrier of the step that published it)
             float2 *lx = img + ((it & 1) ^ 1) * LDS_X;      // v holds pass 2 of image (it - 1) & 1
             __builtin_amdgcn_s_setprio(WS_PBL);
             lx[w2] = v[r16(0)];           // in place: each thread rewrites exactly the sixteen elements it read
@@ -361,7 +391,7 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
             // exchange-2 reads as ordered ds_read_b64, the first butterfly layer on counted waits (-1.7 % kernel
             // time against the sixteen plain reads, which hipcc pairs into ds_read2_b64 behind one lgkmcnt(0);
             // the same treatment of the exchange-1 reads, which needs the butterfly before the item word is
-            // looked at, gave 1.3 % back)
+            // looked at, gave 1.3 % back - whether with or without the stray wait described at pass2 is not recorded)
             dft16_from_lds<1>(v, lx + r2, [] { __builtin_amdgcn_s_setprio(WS_PBC); });
             if (DETREND) {                // X[k] -= mean * FFT(w)[k] where FFT(w) is not negligible
                 v[r16(0)] = make_float2(v[r16(0)].x - (mean.x * fw.x - mean.y * fw.y),
@@ -374,7 +404,17 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
                 const float2 X = v[r16(k2)];
                 acc[k2] = fmaf(X.x, X.x, fmaf(X.y, X.y, acc[k2]));
             }
+            // the accumulation ends HERE: left free, the compiler sinks half of pass 3 and the sums of squares below the
+            // rare branch behind the next pass 2 - their only reader is the next trip - and spills 36-51 registers
+            asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]), "+v"(acc[6]),
+                              "+v"(acc[7]));
+            asm volatile("" : "+v"(acc[8]), "+v"(acc[9]), "+v"(acc[10]), "+v"(acc[11]), "+v"(acc[12]), "+v"(acc[13]),
+                              "+v"(acc[14]), "+v"(acc[15]));
             item = next_item();
+            if (__builtin_expect(item == ITEM_BUBBLE, 0)) {
+                do item = idle_step(); while (item == ITEM_BUBBLE);
+                if (item == ITEM_DATA) pass2((it & 1) ^ 1);      // its barrier was the idle step's
+            }
         }
         // bin k0 + 16 k1 + 256 k2 of this workgroup sits at t + 256 k2 (finalize_kernel layout 1)
         float *dst = p.partial + ((size_t)stream * W + wg) * 4096;
