@@ -1,6 +1,6 @@
 // C ABI, host side: multitaper (Thomson) PSD plans - the Slepian tapers (oth_dpss: host only, double), the plan
-// (oth_mtm_plan: an ordinary oth_plan whose averaging launch is mtm.hip's taper loop) and that launch (mtm_run, which
-// run_average branches to before any routing).
+// (oth_mtm_plan: an ordinary oth_plan whose averaging launch is mtm.hip's taper loop; oth_mtm_csd_plan: the same plan with
+// the two-channel calls open, on mtmcsd.hip) and that launch (mtm_run, which run_average branches to before any routing).
 #include "abi_state.h"
 
 namespace {
@@ -133,23 +133,33 @@ int refuse_mtm(oth_plan *p, const char *what, const char *why) {
     return fail(p->ctx, OTH_ERR_UNSUPPORTED, std::string(what) + " is not available on a multitaper plan: " + why);
 }
 
-int mtm_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t stride, int *W_out) {
+int mtm_csd_gate(oth_plan *p, const char *what) {
+    if (!p->ntapers || p->mtm_csd) return OTH_OK;
+    return refuse_mtm(p, what, "the taper loop holds one channel");
+}
+
+int mtm_run(oth_plan *p, const float2 *x, const float2 *y, long long nseg, int nstreams, size_t stride, int *W_out) {
     oth_ctx *c = p->ctx;
     const int N = p->nfft, K = p->ntapers;
+    const bool csd = y != nullptr;
+    const int nch = csd ? 4 : 1;
     if (nstreams > 65535) return fail(c, OTH_ERR_UNSUPPORTED, "multitaper plans take at most 65535 streams per launch");
     // the (segment, taper) items of a stream go to W workgroups in contiguous runs: one workgroup per taper at least (a
     // single segment spreads over K of them), and for long launches what the device holds at once
     const long long items = nseg * K;
-    const int bpc = std::max(1, mtm_blocks_per_cu(N, c->device));
+    const int bpc = std::max(1, csd ? mtmcsd_blocks_per_cu(N, c->device) : mtm_blocks_per_cu(N, c->device));
     const long long resident = (long long)c->cu_count * bpc;
     const int W = (int)std::min(items, std::max<long long>(K, resident / nstreams));
-    int rc = p->d_partial.ensure(c, sizeof(float) * (size_t)nstreams * W * N);
+    int rc = p->d_partial.ensure(c, sizeof(float) * (size_t)nstreams * W * nch * N);
     {
-        const int groups = std::max(kReduceGroups, finalize_row_groups(N, W, 1));
-        if (!rc) rc = p->d_reduce.ensure(c, sizeof(float) * (size_t)nstreams * groups * N);
+        const int groups = std::max(kReduceGroups, finalize_row_groups(N, W, nch));
+        if (!rc) rc = p->d_reduce.ensure(c, sizeof(float) * (size_t)nstreams * groups * nch * N);
     }
+    const size_t ws_points = csd ? mtmcsd_ws_points(N) : 0;
+    if (!rc && ws_points) rc = p->d_mtm_ws.ensure(c, sizeof(float2) * (size_t)nstreams * W * ws_points);
     if (rc) return rc;
-    MtmArgs a{};
+    MtmCsdArgs g{};
+    MtmArgs &a = g.m;
     a.x = x;
     a.tapers = p->d_tapers.get();
     a.coef = p->d_coef.get();
@@ -163,16 +173,80 @@ int mtm_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t s
     a.ntapers = K;
     a.wg_per_stream = W;
     a.nstreams = nstreams;
+    g.y = y;
+    g.ws = ws_points ? p->d_mtm_ws.get() : nullptr;
     {
         Timed tm(c);
-        HIPCHK(c, launch_mtm(N, a, c->device, c->stream));
+        HIPCHK(c, csd ? launch_mtmcsd(N, g, c->device, c->stream) : launch_mtm(N, a, c->device, c->stream));
     }
-    p->last_recipe = "kernel=mtm nfft=" + std::to_string(N) + " ntapers=" + std::to_string(K) + " W=" + std::to_string(W) +
-                     " nseg=" + std::to_string(nseg) + " nstreams=" + std::to_string(nstreams) + " bpc=" + std::to_string(bpc);
+    p->last_recipe = std::string(csd ? "kernel=mtmcsd" : "kernel=mtm") + " nfft=" + std::to_string(N) + " ntapers=" + std::to_string(K) +
+                     " W=" + std::to_string(W) + " nseg=" + std::to_string(nseg) + " nstreams=" + std::to_string(nstreams) +
+                     " bpc=" + std::to_string(bpc);
     *W_out = W;
     return OTH_OK;
 }
 }  // namespace oth
+
+namespace {
+// oth_mtm_plan and oth_mtm_csd_plan inside their barrier and context lock: one body; two_channel opens the oth_csd_* calls on
+// the plan (oth_plan::mtm_csd)
+int mtm_plan_create(oth_ctx *c, int nfft, int nperseg, int noverlap, int ntapers, const float *tapers, const float *weights,
+                    int detrend, int scaling, double fs, int fftshift, int trim_bins, bool two_channel, oth_plan **out) {
+    if (!c || !out) return fail(c, OTH_ERR_INVALID, "ctx/out is NULL");
+    *out = nullptr;
+    // the refusals of its own in front of the shared checks (OTH_SCALE_SPECTRUM before the range check of plan_begin)
+    if (nfft >= 1 && !mtm_size(nfft))
+        return fail(c, OTH_ERR_UNSUPPORTED, "multitaper plans take a transform length that is a power of two from 64 to 16384, not " +
+                                                std::to_string(nfft));
+    if (scaling == OTH_SCALE_SPECTRUM)
+        return fail(c, OTH_ERR_UNSUPPORTED, "OTH_SCALE_SPECTRUM is not defined for multitaper plans: an odd taper sums to zero");
+    std::unique_ptr<oth_plan> p;
+    if (int rc = plan_begin(c, nfft, nperseg, noverlap, detrend, scaling, fs, fftshift, trim_bins, &p)) return rc;
+    p->fast_detrend = false;      // every mode: each segment's own mean
+    if (ntapers < 1 || ntapers > 64) return fail(c, OTH_ERR_INVALID, "need 1 <= ntapers <= 64");
+    if (!tapers) return fail(c, OTH_ERR_INVALID, "tapers is NULL");
+    double wsum = 0.0;
+    for (int k = 0; k < ntapers; ++k) {
+        const double w = weights ? (double)weights[k] : 1.0;
+        if (!std::isfinite(w) || w < 0.0) return fail(c, OTH_ERR_INVALID, "weights must be finite and non-negative");
+        wsum += w;
+    }
+    if (!(wsum > 0.0) || !std::isfinite(wsum)) return fail(c, OTH_ERR_INVALID, "weights must have a positive sum");
+    std::vector<float> tab((size_t)ntapers * nfft, 0.f), coef(ntapers);      // zero-extended: the kernel indexes [0, nfft)
+    for (int k = 0; k < ntapers; ++k) {
+        double s2 = 0.0;
+        for (int i = 0; i < nperseg; ++i) {
+            const float t = tapers[(size_t)k * nperseg + i];
+            if (!std::isfinite(t)) return fail(c, OTH_ERR_INVALID, "taper values must be finite");
+            tab[(size_t)k * nfft + i] = t;
+            s2 += (double)t * (double)t;
+        }
+        double ck = (weights ? (double)weights[k] : 1.0) / wsum;
+        if (scaling == OTH_SCALE_DENSITY) {
+            if (!(s2 > 0.0)) return fail(c, OTH_ERR_INVALID, "taper " + std::to_string(k) + " is all zero");
+            ck /= s2;
+        }
+        coef[k] = (float)ck;
+    }
+    p->ntapers = ntapers;
+    p->mtm_csd = two_channel;
+    switch (scaling) {
+        case OTH_SCALE_DENSITY: p->scale = 1.0 / fs; break;      // the tapers' energies are in c_k
+        case OTH_SCALE_OVER_N2: p->scale = 1.0 / ((double)nfft * (double)nfft); break;
+        default: p->scale = 1.0;
+    }
+    if (int rc = get_twiddles(c, nfft, &p->d_tw)) return rc;
+    hipError_t e = p->d_tapers.upload(c, tab.data(), sizeof(float) * tab.size());
+    if (e == hipSuccess) e = p->d_coef.upload(c, coef.data(), sizeof(float) * coef.size());
+    if (e == hipSuccess) e = p->d_sum.alloc(sizeof(float) * nfft);
+    if (e == hipSuccess) e = hipMemsetAsync(p->d_sum.get(), 0, sizeof(float) * nfft, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);      // also after a failure: the host tables die here
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, OTH_ERR_HIP, std::string("plan setup: ") + hipGetErrorString(e));
+    *out = p.release();
+    return OTH_OK;
+}
+}  // namespace
 
 extern "C" {
 int oth_dpss(int n, double nw, int kmax, double *tapers, double *ratios) {
@@ -229,58 +303,15 @@ int oth_mtm_plan(oth_ctx *c, int nfft, int nperseg, int noverlap, int ntapers, c
                  int detrend, int scaling, double fs, int fftshift, int trim_bins, oth_plan **out) {
     OTH_TRY
     CtxGuard guard_(c);
-    if (!c || !out) return fail(c, OTH_ERR_INVALID, "ctx/out is NULL");
-    *out = nullptr;
-    // the refusals of its own in front of the shared checks (OTH_SCALE_SPECTRUM before the range check of plan_begin)
-    if (nfft >= 1 && !mtm_size(nfft))
-        return fail(c, OTH_ERR_UNSUPPORTED, "multitaper plans take a transform length that is a power of two from 64 to 16384, not " +
-                                                std::to_string(nfft));
-    if (scaling == OTH_SCALE_SPECTRUM)
-        return fail(c, OTH_ERR_UNSUPPORTED, "OTH_SCALE_SPECTRUM is not defined for multitaper plans: an odd taper sums to zero");
-    std::unique_ptr<oth_plan> p;
-    if (int rc = plan_begin(c, nfft, nperseg, noverlap, detrend, scaling, fs, fftshift, trim_bins, &p)) return rc;
-    p->fast_detrend = false;      // every mode: each segment's own mean
-    if (ntapers < 1 || ntapers > 64) return fail(c, OTH_ERR_INVALID, "need 1 <= ntapers <= 64");
-    if (!tapers) return fail(c, OTH_ERR_INVALID, "tapers is NULL");
-    double wsum = 0.0;
-    for (int k = 0; k < ntapers; ++k) {
-        const double w = weights ? (double)weights[k] : 1.0;
-        if (!std::isfinite(w) || w < 0.0) return fail(c, OTH_ERR_INVALID, "weights must be finite and non-negative");
-        wsum += w;
-    }
-    if (!(wsum > 0.0) || !std::isfinite(wsum)) return fail(c, OTH_ERR_INVALID, "weights must have a positive sum");
-    std::vector<float> tab((size_t)ntapers * nfft, 0.f), coef(ntapers);      // zero-extended: the kernel indexes [0, nfft)
-    for (int k = 0; k < ntapers; ++k) {
-        double s2 = 0.0;
-        for (int i = 0; i < nperseg; ++i) {
-            const float t = tapers[(size_t)k * nperseg + i];
-            if (!std::isfinite(t)) return fail(c, OTH_ERR_INVALID, "taper values must be finite");
-            tab[(size_t)k * nfft + i] = t;
-            s2 += (double)t * (double)t;
-        }
-        double ck = (weights ? (double)weights[k] : 1.0) / wsum;
-        if (scaling == OTH_SCALE_DENSITY) {
-            if (!(s2 > 0.0)) return fail(c, OTH_ERR_INVALID, "taper " + std::to_string(k) + " is all zero");
-            ck /= s2;
-        }
-        coef[k] = (float)ck;
-    }
-    p->ntapers = ntapers;
-    switch (scaling) {
-        case OTH_SCALE_DENSITY: p->scale = 1.0 / fs; break;      // the tapers' energies are in c_k
-        case OTH_SCALE_OVER_N2: p->scale = 1.0 / ((double)nfft * (double)nfft); break;
-        default: p->scale = 1.0;
-    }
-    if (int rc = get_twiddles(c, nfft, &p->d_tw)) return rc;
-    hipError_t e = p->d_tapers.upload(c, tab.data(), sizeof(float) * tab.size());
-    if (e == hipSuccess) e = p->d_coef.upload(c, coef.data(), sizeof(float) * coef.size());
-    if (e == hipSuccess) e = p->d_sum.alloc(sizeof(float) * nfft);
-    if (e == hipSuccess) e = hipMemsetAsync(p->d_sum.get(), 0, sizeof(float) * nfft, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);      // also after a failure: the host tables die here
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(c, OTH_ERR_HIP, std::string("plan setup: ") + hipGetErrorString(e));
-    *out = p.release();
-    return OTH_OK;
+    return mtm_plan_create(c, nfft, nperseg, noverlap, ntapers, tapers, weights, detrend, scaling, fs, fftshift, trim_bins, false, out);
+    OTH_CATCH(c)
+}
+
+int oth_mtm_csd_plan(oth_ctx *c, int nfft, int nperseg, int noverlap, int ntapers, const float *tapers, const float *weights,
+                     int detrend, int scaling, double fs, int fftshift, int trim_bins, oth_plan **out) {
+    OTH_TRY
+    CtxGuard guard_(c);
+    return mtm_plan_create(c, nfft, nperseg, noverlap, ntapers, tapers, weights, detrend, scaling, fs, fftshift, trim_bins, true, out);
     OTH_CATCH(c)
 }
 }  // extern "C"

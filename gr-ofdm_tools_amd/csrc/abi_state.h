@@ -130,6 +130,8 @@ struct oth_plan {
     int ntapers = 0;
     DevBuf<float> d_tapers;            // [ntapers][nfft], zero-extended behind nperseg
     DevBuf<float> d_coef;              // [ntapers] c_k: normalised weight (over the taper's energy with OTH_SCALE_DENSITY)
+    bool mtm_csd = false;              // oth_mtm_csd_plan only: the oth_csd_* calls run mtmcsd.hip instead of being refused
+    DevBuf<float2> d_mtm_ws;           // mtmcsd.hip's per-workgroup spectrum rows (MtmCsdArgs.ws; 16384 points only)
 };
 
 struct oth_chain {
@@ -364,7 +366,10 @@ int plan_begin(oth_ctx *c, int nfft, int nperseg, int noverlap, int detrend, int
 // ---- abi_mtm.hip: multitaper plans ------------------------------------------------------------------------------------------
 // the averaging launch of a multitaper plan (run_average branches here before resolve_recipe): W partial rows per stream
 // in natural order (finalize layout 0) into p->d_partial
-int mtm_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t stride, int *W_out);
+//   y != nullptr (plans of oth_mtm_csd_plan only): the two-channel launch, four rows per workgroup
+int mtm_run(oth_plan *p, const float2 *x, const float2 *y, long long nseg, int nstreams, size_t stride, int *W_out);
 // OTH_ERR_UNSUPPORTED with the reason: `what` is not available on a multitaper plan
 int refuse_mtm(oth_plan *p, const char *what, const char *why);
+// the oth_csd_* entry points: OTH_OK on a plan that holds two channels (every plan but oth_mtm_plan's), else refuse_mtm
+int mtm_csd_gate(oth_plan *p, const char *what);
 }  // namespace oth

@@ -126,8 +126,9 @@ int run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
         return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
     const bool csd = (y != nullptr);
     if (p->ntapers) {      // multitaper plans: mtm.hip, before any routing
-        if (csd) return refuse_mtm(p, "the cross spectrum", "the taper loop holds one channel");
-        if (int rc = mtm_run(p, x, nseg, nstreams, stride, W_out)) return rc;
+        if (csd)      // (the oth_csd_* entry points have asked already)
+            if (int rc = mtm_csd_gate(p, "the cross spectrum")) return rc;
+        if (int rc = mtm_run(p, x, y, nseg, nstreams, stride, W_out)) return rc;
         *nseg_out = nseg;
         *layout_out = 0;
         return OTH_OK;
@@ -1039,7 +1040,7 @@ int oth_csd_exec_dev(oth_plan *p, const void *x_dev, const void *y_dev, size_t n
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
     if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_csd_exec_dev");
-    if (p->ntapers) return refuse_mtm(p, "oth_csd_exec_dev", "the taper loop holds one channel");
+    if (int rc = mtm_csd_gate(p, "oth_csd_exec_dev")) return rc;
     oth_ctx *c = p->ctx;
     if (!x_dev || !y_dev) return fail(c, OTH_ERR_INVALID, "x/y is NULL");
     if (p->db) return fail(c, OTH_ERR_UNSUPPORTED, "dB output is not defined for the cross spectrum");
@@ -1056,7 +1057,7 @@ int oth_csd_partial_dev(oth_plan *p, const void *x_dev, const void *y_dev, size_
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
     if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_csd_partial_dev");
-    if (p->ntapers) return refuse_mtm(p, "oth_csd_partial_dev", "the taper loop holds one channel");
+    if (int rc = mtm_csd_gate(p, "oth_csd_partial_dev")) return rc;
     oth_ctx *c = p->ctx;
     if (!x_dev || !y_dev || !sums_out_dev) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (p->db) return fail(c, OTH_ERR_UNSUPPORTED, "dB output is not defined for the cross spectrum");
@@ -1074,7 +1075,7 @@ int oth_csd_scale_dev(oth_plan *p, const float *sums_dev, uint64_t nseg_total, f
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
     if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_csd_scale_dev");
-    if (p->ntapers) return refuse_mtm(p, "oth_csd_scale_dev", "the taper loop holds one channel");
+    if (int rc = mtm_csd_gate(p, "oth_csd_scale_dev")) return rc;
     oth_ctx *c = p->ctx;
     if (!sums_dev || !nseg_total) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (p->db) return fail(c, OTH_ERR_UNSUPPORTED, "dB output is not defined for the cross spectrum");
@@ -1091,7 +1092,7 @@ int oth_csd_exec(oth_plan *p, const void *x, const void *y, size_t nsamples, int
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
     if (p->average == OTH_AVERAGE_MEDIAN) return refuse_median(p, "oth_csd_exec");
-    if (p->ntapers) return refuse_mtm(p, "oth_csd_exec", "the taper loop holds one channel");
+    if (int rc = mtm_csd_gate(p, "oth_csd_exec")) return rc;
     oth_ctx *c = p->ctx;
     if (!x || !y) return fail(c, OTH_ERR_INVALID, "x/y is NULL");
     if (p->db) return fail(c, OTH_ERR_UNSUPPORTED, "dB output is not defined for the cross spectrum");

@@ -22,48 +22,13 @@
 // 1.07 against 1.21 ms for 2^25 samples with K 4 and 0.062 against 0.069 ms for 64 single segments with K 7 in favour of
 // re-reading; 4096 points 1.77 against 1.54 ms for 2^26 samples with K 4 in favour of the registers (three workgroups per
 // CU against four).  profiles/mtm_keep_ab.txt.
-#include "fft_lds.hip.h"
+#include "mtm_common.hip.h"
 #include "oth_internal.h"
 
 #include <atomic>
 
 namespace oth {
 namespace {
-
-__device__ __forceinline__ float2 mtm_wave_sum(float2 v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        v.x += __shfl_xor(v.x, off, 64);
-        v.y += __shfl_xor(v.y, off, 64);
-    }
-    return v;
-}
-
-// Sum of v over the workgroup in a fixed order; ends with every thread holding it.  `red` has T / 64 + 1 slots.
-template <int T> __device__ __forceinline__ float2 mtm_block_sum(float2 v, float2 *red, int tid) {
-    v = mtm_wave_sum(v);
-    if ((tid & 63) == 0) red[1 + (tid >> 6)] = v;
-    __syncthreads();
-    float2 s = make_float2(0.f, 0.f);
-#pragma unroll
-    for (int w = 0; w < T / 64; ++w) s = cadd(s, red[1 + w]);
-    return s;
-}
-
-constexpr int kMtmPilot = 64;      // samples behind the pilot (the first wave's lanes)
-
-// the mean of the segment's first min(64, nperseg) samples, the same bits in every thread (red[0])
-__device__ __forceinline__ float2 mtm_pilot(const float2 *__restrict__ xs, int nperseg, float2 *red, int tid) {
-    if (tid < kMtmPilot) {
-        const int np = nperseg < kMtmPilot ? nperseg : kMtmPilot;
-        float2 t = tid < np ? xs[tid] : make_float2(0.f, 0.f);
-        t = mtm_wave_sum(t);
-        const float inv = 1.0f / (float)np;
-        if (tid == 0) red[0] = make_float2(t.x * inv, t.y * inv);
-    }
-    __syncthreads();
-    return red[0];
-}
 
 template <int N, int T, bool KEEP> __global__ __launch_bounds__(T) void mtm_kernel(MtmArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -146,10 +111,7 @@ template <int N, int T, bool KEEP> __global__ __launch_bounds__(T) void mtm_kern
     for (int q = 0; q < NQ; ++q) dst[tid0 + q * T] = acc[q];
 }
 
-constexpr bool mtm_keep(int n) { return n < 8192; }
-constexpr int kMtmMaxDevices = 64;
-
-size_t mtm_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + 32 * sizeof(float2); }
+size_t mtm_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedSlots * sizeof(float2); }
 
 // The dynamic-LDS attribute of a build (tiles above 64 KiB) is armed once per device, not per launch.
 template <int N> hipError_t mtm_arm(int device) {
@@ -164,8 +126,6 @@ template <int N> hipError_t mtm_arm(int device) {
     if (e == hipSuccess && cached) armed[device].store(true, std::memory_order_release);
     return e;
 }
-
-#define OTH_MTM_FOR_EACH_N(X) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192) X(16384)
 
 }  // namespace
 

@@ -1,0 +1,49 @@
+// What the two multitaper kernels (mtm.hip: one channel, mtmcsd.hip: two) share: the fixed-order sums behind a segment's
+// pilot and residual mean, the rule for keeping a segment's samples in registers, and the list of sizes.
+#pragma once
+#include "fft_lds.hip.h"
+
+namespace oth {
+
+__device__ __forceinline__ float2 mtm_wave_sum(float2 v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        v.x += __shfl_xor(v.x, off, 64);
+        v.y += __shfl_xor(v.y, off, 64);
+    }
+    return v;
+}
+
+// Sum of v over the workgroup in a fixed order; ends with every thread holding it.  `red` has T / 64 + 1 slots.
+template <int T> __device__ __forceinline__ float2 mtm_block_sum(float2 v, float2 *red, int tid) {
+    v = mtm_wave_sum(v);
+    if ((tid & 63) == 0) red[1 + (tid >> 6)] = v;
+    __syncthreads();
+    float2 s = make_float2(0.f, 0.f);
+#pragma unroll
+    for (int w = 0; w < T / 64; ++w) s = cadd(s, red[1 + w]);
+    return s;
+}
+
+constexpr int kMtmPilot = 64;      // samples behind the pilot (the first wave's lanes)
+
+// the mean of the segment's first min(64, nperseg) samples, the same bits in every thread (red[0])
+__device__ __forceinline__ float2 mtm_pilot(const float2 *__restrict__ xs, int nperseg, float2 *red, int tid) {
+    if (tid < kMtmPilot) {
+        const int np = nperseg < kMtmPilot ? nperseg : kMtmPilot;
+        float2 t = tid < np ? xs[tid] : make_float2(0.f, 0.f);
+        t = mtm_wave_sum(t);
+        const float inv = 1.0f / (float)np;
+        if (tid == 0) red[0] = make_float2(t.x * inv, t.y * inv);
+    }
+    __syncthreads();
+    return red[0];
+}
+
+constexpr bool mtm_keep(int n) { return n < 8192; }      // mtm.hip's header: KEEP
+constexpr int kMtmMaxDevices = 64;
+constexpr int kMtmRedSlots = 32;                         // float2 slots of one `red` array (T / 64 + 1 <= 17 used)
+
+#define OTH_MTM_FOR_EACH_N(X) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192) X(16384)
+
+}  // namespace oth

@@ -74,6 +74,8 @@ SIGNATURES = {
     'oth_dpss': (C.c_int, [C.c_int, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'oth_mtm_plan': (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, _f, _f, C.c_int, C.c_int, C.c_double, C.c_int,
                                C.c_int, _pp]),
+    'oth_mtm_csd_plan': (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, _f, _f, C.c_int, C.c_int, C.c_double, C.c_int,
+                                   C.c_int, _pp]),
     'oth_plan_set_tuning': (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int, C.c_int]),
     'oth_welch_exec': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _u64p]),
     'oth_welch_exec_async': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _u64p]),
@@ -313,6 +315,15 @@ class Context(object):
         Slepian tapers only) or ntapers non-negative values.  -> a WelchPlan-compatible MtmPlan."""
         return MtmPlan(self, nfft, nperseg, noverlap, nw, ntapers, tapers, weights, detrend, scaling, fs, fftshift,
                        trim_bins, db)
+
+    def mtm_csd_plan(self, nfft, nperseg=None, noverlap=0, nw=4.0, ntapers=None, tapers=None, weights='unity',
+                     detrend=DETREND_CONSTANT, scaling=SCALE_DENSITY, fs=1.0, fftshift=False, trim_bins=0, db=False):
+        """Two-channel multitaper plan (oth_mtm_csd_plan): mtm_plan's arguments and checks; on top of everything an MtmPlan
+        does, csd / csd_exec_dev / csd_partial_dev / csd_scale_dev give Pxx, Pyy, Pxy = mean over segments of
+        sum_k c_k conj(X_k) Y_k and Cxy = |Pxy|^2 / (Pxx Pyy) - the three inputs of coherence_detector from one capture
+        pair.  -> MtmCsdPlan."""
+        return MtmCsdPlan(self, nfft, nperseg, noverlap, nw, ntapers, tapers, weights, detrend, scaling, fs, fftshift,
+                          trim_bins, db)
 
     def chain(self, nfft, window=None, fftshift=True, epilogue=EPI_MAG2, keep_one_in_n=1):
         return Chain(self, nfft, window, fftshift, epilogue, keep_one_in_n)
@@ -692,6 +703,8 @@ class MtmPlan(WelchPlan):
     partial_dev / scale_dev / accumulate / finalize / reset as WelchPlan's; the median average, the per-segment rows,
     the cross spectrum, KERNEL_TUNED and build variants raise HipError (OTH_ERR_UNSUPPORTED)."""
 
+    _CONSTRUCTOR = 'oth_mtm_plan'
+
     def __init__(self, ctx, nfft, nperseg, noverlap, nw, ntapers, tapers, weights, detrend, scaling, fs, fftshift,
                  trim_bins, db):
         from . import windows
@@ -720,15 +733,23 @@ class MtmPlan(WelchPlan):
         self.ntapers = ntapers
         self.tapers, self.ratios = t, ratios
         h = C.c_void_p()
-        ctx.check(ctx.lib.oth_mtm_plan(ctx.h, int(nfft), nperseg, noverlap, self.ntapers, _fptr(t),
-                                       _fptr(w) if w is not None else None, int(detrend), int(scaling), float(fs),
-                                       1 if fftshift else 0, int(trim_bins), C.byref(h)), 'oth_mtm_plan')
+        ctx.check(getattr(ctx.lib, self._CONSTRUCTOR)(ctx.h, int(nfft), nperseg, noverlap, self.ntapers, _fptr(t),
+                                                      _fptr(w) if w is not None else None, int(detrend), int(scaling),
+                                                      float(fs), 1 if fftshift else 0, int(trim_bins), C.byref(h)),
+                  self._CONSTRUCTOR)
         self.h = h
         n = C.c_int()
         ctx.check(ctx.lib.oth_plan_out_len(h, C.byref(n)), 'oth_plan_out_len')
         self.out_len = n.value
         if db:
             ctx.check(ctx.lib.oth_plan_set_output_db(h, 1), 'oth_plan_set_output_db')
+
+
+class MtmCsdPlan(MtmPlan):
+    """An MtmPlan on which the inherited two-channel calls - csd, csd_device_src, csd_exec_dev, csd_partial_dev,
+    csd_scale_dev - run the two-channel taper loop (oth_mtm_csd_plan) instead of raising."""
+
+    _CONSTRUCTOR = 'oth_mtm_csd_plan'
 
 
 class Chain(object):

@@ -8,7 +8,8 @@ The reference has no block that PRODUCES the coherence vector (SURVEY.md 8a row 
 coherence_estimator is that producer: two complex64 streams -> Welch cross spectrum ->
 magnitude-squared coherence |Pxy|^2 / (Pxx Pyy) (scipy.signal.coherence semantics, Hann,
 nperseg = nfft = N, 50 % overlap, detrend constant), fftshifted so that bin order matches the
-detector's axis ``range(-N/2, N/2) * Fr + tune_freq`` (:188).
+detector's axis ``range(-N/2, N/2) * Fr + tune_freq`` (:188).  With method='mtm' it is the
+two-channel multitaper estimate instead, whose Pxx / Pyy are the detector's MTM-L / MTM-R.
 """
 import numpy as np
 
@@ -86,16 +87,30 @@ class coherence_detector(sync_block):
 
 
 class coherence_estimator(sync_block):
-    """Two complex64 inputs -> fftshifted (Pxx, Pyy, Pxy, Cxy) every ``block_len`` samples."""
+    """Two complex64 inputs -> fftshifted (Pxx, Pyy, Pxy, Cxy) every ``block_len`` samples.
 
-    def __init__(self, N, sample_rate, block_len=None, ctx=None):
+    method='welch' (default): the Hann / 50 % Welch cross spectrum, ``block_len`` defaulting to 16 N.
+    method='mtm': the two-channel multitaper estimate (Context.mtm_csd_plan: K Slepian tapers of time-half-bandwidth NW,
+    K=None meaning int(2 NW) - 1, nperseg = N, no overlap) - the estimator for SHORT captures, where a Welch coherence
+    of few segments is biased high (one segment: identically 1).  ``block_len`` defaults to N, one segment; pxx and pyy
+    are then the detector's MTM-L and MTM-R inputs."""
+
+    def __init__(self, N, sample_rate, block_len=None, ctx=None, method='welch', NW=4.0, K=None):
+        if method not in ('welch', 'mtm'):
+            raise ValueError("method must be 'welch' or 'mtm', not %r" % (method,))
+        if method == 'mtm' and block_len is not None and int(block_len) < N:
+            raise ValueError('block_len=%d is shorter than one segment of N=%d samples' % (int(block_len), N))
         sync_block.__init__(self, 'coherence_estimator', [np.complex64, np.complex64], None)
         self.N = N
         self.sample_rate = sample_rate
-        self.block_len = int(block_len if block_len is not None else 16 * N)
+        self.method = method
+        self.block_len = int(block_len if block_len is not None else (16 * N if method == 'welch' else N))
         self.ctx = ctx or _hip.default_context()
-        self._plan = self.ctx.welch_plan(N, window=windows.get_window('hann', N), fs=float(sample_rate),
-                                         fftshift=True)
+        if method == 'welch':
+            self._plan = self.ctx.welch_plan(N, window=windows.get_window('hann', N), fs=float(sample_rate),
+                                             fftshift=True)
+        else:
+            self._plan = self.ctx.mtm_csd_plan(N, nw=NW, ntapers=K, fs=float(sample_rate), fftshift=True)
         self._x = np.empty(0, np.complex64)
         self._y = np.empty(0, np.complex64)
         self.pxx = self.pyy = self.pxy = self.cxy = None

@@ -246,7 +246,7 @@ int oth_welch_segments_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, 
                            uint64_t *nseg_out);
 
 /* MULTITAPER (Thomson) PSD.  Additions inside ABI 6 (OTH_ABI_VERSION stays 6): a caller probes for them by the symbols
- * oth_dpss / oth_mtm_plan.  The estimator for SHORT captures - one work()-sized vector, one row per scanner channel -
+ * oth_dpss / oth_mtm_plan / oth_mtm_csd_plan.  The estimator for SHORT captures - one work()-sized vector, one row per scanner channel -
  * where Welch can only lower the variance by cutting the capture into shorter segments: K orthogonal Slepian tapers on the
  * same samples give the variance of K averages at a known bandwidth of 2 NW bins.
  *
@@ -278,6 +278,23 @@ int oth_dpss(int n, double nw, int kmax, double *tapers, double *ratios);
  * effect. */
 int oth_mtm_plan(oth_ctx *ctx, int nfft, int nperseg, int noverlap, int ntapers, const float *tapers, const float *weights,
                  int detrend, int scaling, double fs, int fftshift, int trim_bins, oth_plan **out);
+/* oth_mtm_csd_plan (an addition inside ABI 6; probe by the symbol): a multitaper plan - arguments, checks, error texts and
+ * every call listed above as oth_mtm_plan's, the one-channel exec forms on the same kernel - on which the two-channel calls
+ * WORK: oth_csd_exec, _exec_dev, _partial_dev, _scale_dev (plans of oth_mtm_plan go on refusing them).  It produces the three
+ * inputs of coherence_detector - coherence, MTM-L, MTM-R - from one capture pair, where a Welch coherence is biased high by
+ * about 1 / nseg.  Per segment s (segmentation as oth_welch_plan's) each channel's own mean comes off,
+ * X_k = FFT_nfft((x_s - m_x) v_k), Y_k = FFT_nfft((y_s - m_y) v_k), and with oth_mtm_plan's c_k
+ *   Sxx = sum_s sum_k c_k |X_k|^2,  Syy = sum_s sum_k c_k |Y_k|^2,  Sxy = sum_s sum_k c_k conj(X_k) Y_k;
+ * Pxx, Pyy, Pxy = S scale / nseg, Cxy = |Pxy|^2 / (Pxx Pyy), then the plan's fftshift and trim; layouts as oth_csd_exec's.
+ * oth_csd_partial_dev leaves the raw float[4 nfft] sums (the c_k applied), oth_csd_scale_dev scales them; partials of ranks
+ * add.  One launch per call (csrc/mtmcsd.hip), sums in a fixed order, bit-identical run to run.
+ * Degenerate input: the two-channel contract below (the same output stage closes the launch).  K nseg = 1 - one taper on
+ * one segment - is a single periodogram pair and gives Cxy = 1 in every bin: the estimate needs K nseg >= 2.
+ * Refused with OTH_ERR_UNSUPPORTED as on oth_mtm_plan's plans: OTH_SCALE_SPECTRUM, OTH_AVERAGE_MEDIAN,
+ * oth_welch_segments_dev, OTH_KERNEL_TUNED, a non-empty tuning variant, sizes other than powers of two 64 ... 16384; and, as
+ * on Welch plans, dB output on any oth_csd_* call. */
+int oth_mtm_csd_plan(oth_ctx *ctx, int nfft, int nperseg, int noverlap, int ntapers, const float *tapers,
+                     const float *weights, int detrend, int scaling, double fs, int fftshift, int trim_bins, oth_plan **out);
 
 /* one-shot: nsamples complex64 -> psd_out[nfft - 2*trim] (host).  Blocking: returns when the PSD is in psd_out.  The
  * last launch writes the row and a completion word into pinned host memory and the call polls that word (no interrupt
