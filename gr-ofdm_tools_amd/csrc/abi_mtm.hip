@@ -147,7 +147,7 @@ int mtm_run(oth_plan *p, const float2 *x, const float2 *y, long long nseg, int n
     // the (segment, taper) items of a stream go to W workgroups in contiguous runs: one workgroup per taper at least (a
     // single segment spreads over K of them), and for long launches what the device holds at once
     const long long items = nseg * K;
-    const int bpc = std::max(1, csd ? mtmcsd_blocks_per_cu(N, c->device) : mtm_blocks_per_cu(N, c->device));
+    const int bpc = std::max(1, csd ? mtmcsd_blocks_per_cu(N) : mtm_blocks_per_cu(N));
     const long long resident = (long long)c->cu_count * bpc;
     const int W = (int)std::min(items, std::max<long long>(K, resident / nstreams));
     int rc = p->d_partial.ensure(c, sizeof(float) * (size_t)nstreams * W * nch * N);
@@ -177,7 +177,7 @@ int mtm_run(oth_plan *p, const float2 *x, const float2 *y, long long nseg, int n
     g.ws = ws_points ? p->d_mtm_ws.get() : nullptr;
     {
         Timed tm(c);
-        HIPCHK(c, csd ? launch_mtmcsd(N, g, c->device, c->stream) : launch_mtm(N, a, c->device, c->stream));
+        HIPCHK(c, csd ? launch_mtmcsd(N, g, c->stream) : launch_mtm(N, a, c->stream));
     }
     p->last_recipe = std::string(csd ? "kernel=mtmcsd" : "kernel=mtm") + " nfft=" + std::to_string(N) + " ntapers=" + std::to_string(K) +
                      " W=" + std::to_string(W) + " nseg=" + std::to_string(nseg) + " nstreams=" + std::to_string(nstreams) +

@@ -11,6 +11,7 @@
 // lives in LDS (16 KiB, conflict-free b32 reads) instead of 16 VGPRs, which keeps the kernel at
 // 3 workgroups per CU on both the VGPR and the LDS side (53 KiB each).
 #include "fft4096.hip.h"
+#include "launch.h"
 
 namespace oth {
 namespace {
@@ -130,14 +131,7 @@ __global__ __launch_bounds__(T4, 3) void csd4096_kernel(WelchArgs p) {
 
 }  // namespace
 
-int csd4096_blocks_per_cu() {
-    static int cached = 0;
-    if (cached) return cached;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, csd4096_kernel<true>, T4, CSD_LDS_BYTES) != hipSuccess || n < 1)
-        n = 2;
-    return cached = n;
-}
+int csd4096_blocks_per_cu() { return resident_blocks<csd4096_kernel<true>>(T4, CSD_LDS_BYTES, 2); }
 
 hipError_t launch_csd_tuned4096(const WelchArgs &a, hipStream_t s) {
     const dim3 grid(a.wg_per_stream, a.nstreams);

@@ -39,6 +39,7 @@
 #include <mutex>
 #include <type_traits>
 #include "fft4096.hip.h"
+#include "launch.h"
 
 namespace oth {
 namespace {
@@ -360,35 +361,18 @@ __global__ __launch_bounds__(TCS, 4) void csd4096ws_kernel(WelchArgs p) {
 
 }  // namespace
 
-int csd4096ws_blocks_per_cu() {
-    static int cached = 0;
-    if (cached) return cached;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, csd4096ws_kernel<true, false>, TCS, CS_LDS_BYTES) != hipSuccess || n < 1)
-        n = 1;
-    return cached = n;
-}
+int csd4096ws_blocks_per_cu() { return resident_blocks<csd4096ws_kernel<true, false>>(TCS, CS_LDS_BYTES); }
 
 hipError_t launch_csd_tuned4096ws(const WelchArgs &a_in, hipStream_t s) {
     WelchArgs a = a_in;
     const dim3 grid(a.wg_per_stream, a.nstreams);
-    static bool armed[64] = {};        // 140 KiB of dynamic LDS needs the opt-in, once per device
     // A plan WITHOUT detrend runs the detrending build on an all-zero window-spectrum table (round 6): X - mean * 0 is X
     // bit for bit, the per-wave sums cost the step ~1 %, and the build without them - csd4096ws_kernel<false, false> - was
     // the one two-channel build that spilled (five registers around the producer's chunk boundary; verdict r5).
     static float4 *zero_fd[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    bool &big_lds = armed[dev];
-    if (!big_lds) {
-        hipError_t e = hipSuccess;
-        for (const void *fn : {reinterpret_cast<const void *>(csd4096ws_kernel<true, true>),
-                               reinterpret_cast<const void *>(csd4096ws_kernel<true, false>)})
-            if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CS_LDS_BYTES);
-        if (e != hipSuccess) return e;
-        big_lds = true;
-    }
     if (!a.detrend) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
         {
             static std::mutex once;      // contexts of several threads may come here at the same time
             std::lock_guard<std::mutex> g(once);
@@ -409,11 +393,9 @@ hipError_t launch_csd_tuned4096ws(const WelchArgs &a_in, hipStream_t s) {
         a.pilot = nullptr;
         a.pilot_inline = 0;
     }
-    if (a.pilot || a.pilot_inline)
-        hipLaunchKernelGGL((csd4096ws_kernel<true, true>), grid, dim3(TCS), CS_LDS_BYTES, s, a);
-    else
-        hipLaunchKernelGGL((csd4096ws_kernel<true, false>), grid, dim3(TCS), CS_LDS_BYTES, s, a);
-    return hipGetLastError();
+    // 140 KiB of dynamic LDS: the opt-in is launch_lds's, once per build and device
+    if (a.pilot || a.pilot_inline) return launch_lds<csd4096ws_kernel<true, true>>(grid, dim3(TCS), CS_LDS_BYTES, s, a);
+    return launch_lds<csd4096ws_kernel<true, false>>(grid, dim3(TCS), CS_LDS_BYTES, s, a);
 }
 
 }  // namespace oth

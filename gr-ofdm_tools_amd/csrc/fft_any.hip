@@ -34,6 +34,7 @@
 // mean over as a float pair hi + lo; the stage subtracts hi (exact for samples near the mean), then lo.
 #include "fft4096.hip.h"
 #include "oth_internal.h"
+#include "launch.h"
 
 namespace oth {
 
@@ -529,11 +530,6 @@ void any_make_desc(int n, int C, const float2 *tw, int order, AnyFftDesc *d) {
     }
 }
 
-template <typename K> static hipError_t any_allow_lds(K kernel, size_t bytes) {
-    if (bytes <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 // grid = (tiles, rows of segments, channels for store 0); store: 0 plain, 1 accumulate, 2 two-channel accumulate, 3 rows
 hipError_t launch_any_fft(const AnyArgs &a, int tiles, int gy, int gz, int store, hipStream_t s) {
     const int points = a.f.n << a.f.logC;
@@ -541,11 +537,12 @@ hipError_t launch_any_fft(const AnyArgs &a, int tiles, int gy, int gz, int store
     const int T = any_threads_for(points);
     const size_t lds = ((size_t)points + (a.f.tw_lds ? (size_t)a.f.n : 0)) * sizeof(float2);
     const dim3 grid(tiles, gy, gz);
-    hipError_t e;
+    // A build's tile varies with the plan, so it opts in to the largest one (any_make_desc: 150 KiB with the table) once.
+    hipError_t e = hipSuccess;
 #define OTH_ANY_LAUNCH1(TT, ST, TW, CC)                                                                     \
     do {                                                                                                    \
-        if ((e = any_allow_lds(any_fft_kernel<TT, ST, TW, CC>, lds)) != hipSuccess) return e;               \
-        hipLaunchKernelGGL((any_fft_kernel<TT, ST, TW, CC>), grid, dim3(TT), lds, s, a);                    \
+        if (lds > 64 * 1024) e = arm_lds<any_fft_kernel<TT, ST, TW, CC>>(150 * 1024);                       \
+        if (e == hipSuccess) e = launch_lds<any_fft_kernel<TT, ST, TW, CC>>(grid, dim3(TT), lds, s, a);     \
     } while (0)
     // one transform per tile (logC == 0, column mode): the builds without column arithmetic
 #define OTH_ANY_LAUNCH(TT, ST)                                                                              \
@@ -575,7 +572,7 @@ hipError_t launch_any_fft(const AnyArgs &a, int tiles, int gy, int gz, int store
 #undef OTH_ANY_T
 #undef OTH_ANY_LAUNCH
 #undef OTH_ANY_LAUNCH1
-    return hipGetLastError();
+    return e;
 }
 
 hipError_t launch_any_mean(const float2 *x, const float2 *y, long long first, long long seg_step, int nperseg, long long nseg,

@@ -8,6 +8,7 @@
 //   xcorr / fac           ofdm_cr_tools.py:155-166
 #include "fft_lds.hip.h"
 #include "oth_internal.h"
+#include "launch.h"
 
 namespace oth {
 
@@ -202,77 +203,49 @@ bool generic_supported(int nfft) { return nfft >= 64 && nfft <= 16384 && (nfft &
 int generic_threads_for(int nfft) { return generic_threads(nfft); }
 size_t generic_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + 16 * sizeof(float2); }
 
-template <typename K> static hipError_t allow_lds(K kernel, size_t bytes) {
-    if (bytes <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)bytes);
-}
-
 #define OTH_FOR_EACH_N(X) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192) X(16384)
 
 hipError_t launch_welch_generic(int nfft, const WelchArgs &a, hipStream_t s) {
     const dim3 grid(a.wg_per_stream, a.nstreams);
     const size_t lds = generic_lds_bytes(nfft);
-    hipError_t e;
     switch (nfft) {
-#define X(N)                                                                                       \
-    case N: {                                                                                      \
-        constexpr int T = generic_threads(N);                                                      \
-        if (a.y) {                                                                                 \
-            if ((e = allow_lds(welch_generic_kernel<N, T, true>, lds)) != hipSuccess) return e;   \
-            hipLaunchKernelGGL((welch_generic_kernel<N, T, true>), grid, dim3(T), lds, s, a);     \
-        } else {                                                                                   \
-            if ((e = allow_lds(welch_generic_kernel<N, T, false>, lds)) != hipSuccess) return e;  \
-            hipLaunchKernelGGL((welch_generic_kernel<N, T, false>), grid, dim3(T), lds, s, a);    \
-        }                                                                                          \
-        break;                                                                                     \
+#define X(N)                                                                                                  \
+    case N: {                                                                                                 \
+        constexpr int T = generic_threads(N);                                                                 \
+        return a.y ? launch_lds<welch_generic_kernel<N, T, true>>(grid, dim3(T), lds, s, a)                   \
+                   : launch_lds<welch_generic_kernel<N, T, false>>(grid, dim3(T), lds, s, a);                 \
     }
         OTH_FOR_EACH_N(X)
 #undef X
         default:
             return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 hipError_t launch_pgram(int nfft, const PgramArgs &a, hipStream_t s) {
     const size_t lds = generic_lds_bytes(nfft);
     const int grid = (int)(a.nrows < 4096 ? a.nrows : 4096);
-    hipError_t e;
     switch (nfft) {
-#define X(N)                                                                          \
-    case N: {                                                                         \
-        constexpr int T = generic_threads(N);                                         \
-        if ((e = allow_lds(pgram_kernel<N, T>, lds)) != hipSuccess) return e;        \
-        hipLaunchKernelGGL((pgram_kernel<N, T>), dim3(grid), dim3(T), lds, s, a);    \
-        break;                                                                        \
-    }
+#define X(N) \
+    case N: return launch_lds<pgram_kernel<N, generic_threads(N)>>(dim3(grid), dim3(generic_threads(N)), lds, s, a);
         OTH_FOR_EACH_N(X)
 #undef X
         default:
             return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 hipError_t launch_xcorr(int L, const float2 *a, const float2 *b, const float2 *tw, float *out, int mode,
                         hipStream_t s) {
     const size_t lds = generic_lds_bytes(L);
-    hipError_t e;
     switch (L) {
-#define X(N)                                                                                         \
-    case N: {                                                                                        \
-        constexpr int T = generic_threads(N);                                                        \
-        if ((e = allow_lds(xcorr_kernel<N, T>, lds)) != hipSuccess) return e;                       \
-        hipLaunchKernelGGL((xcorr_kernel<N, T>), dim3(1), dim3(T), lds, s, a, b, tw, out, mode);    \
-        break;                                                                                       \
-    }
+#define X(N) \
+    case N: return launch_lds<xcorr_kernel<N, generic_threads(N)>>(dim3(1), dim3(generic_threads(N)), lds, s, a, b, tw, out, mode);
         OTH_FOR_EACH_N(X)
 #undef X
         default:
             return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 }  // namespace oth

@@ -24,8 +24,7 @@
 // CU against four).  profiles/mtm_keep_ab.txt.
 #include "mtm_common.hip.h"
 #include "oth_internal.h"
-
-#include <atomic>
+#include "launch.h"
 
 namespace oth {
 namespace {
@@ -113,62 +112,29 @@ template <int N, int T, bool KEEP> __global__ __launch_bounds__(T) void mtm_kern
 
 size_t mtm_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedSlots * sizeof(float2); }
 
-// The dynamic-LDS attribute of a build (tiles above 64 KiB) is armed once per device, not per launch.
-template <int N> hipError_t mtm_arm(int device) {
-    constexpr int T = generic_threads(N);
-    static std::atomic<bool> armed[kMtmMaxDevices];
-    const size_t lds = mtm_lds_bytes(N);
-    if (lds <= 64 * 1024) return hipSuccess;
-    const bool cached = device >= 0 && device < kMtmMaxDevices;
-    if (cached && armed[device].load(std::memory_order_acquire)) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(mtm_kernel<N, T, mtm_keep(N)>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess && cached) armed[device].store(true, std::memory_order_release);
-    return e;
-}
-
 }  // namespace
 
-int mtm_blocks_per_cu(int nfft, int device) {
-    int n = 0;
+#define OTH_MTM_KERNEL(N) mtm_kernel<N, generic_threads(N), mtm_keep(N)>
+
+int mtm_blocks_per_cu(int nfft) {
     switch (nfft) {
-#define X(N)                                                                                                        \
-    case N: {                                                                                                       \
-        constexpr int T = generic_threads(N);                                                                       \
-        static std::atomic<int> cached{0};                                                                          \
-        if ((n = cached.load(std::memory_order_acquire)) > 0) return n;                                             \
-        if (mtm_arm<N>(device) != hipSuccess ||                                                                     \
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, mtm_kernel<N, T, mtm_keep(N)>, T, mtm_lds_bytes(N)) != \
-                hipSuccess)                                                                                         \
-            n = 0;                                                                                                  \
-        if (n > 0) cached.store(n, std::memory_order_release);                                                      \
-        break;                                                                                                      \
-    }
+#define X(N) \
+    case N: return resident_blocks<OTH_MTM_KERNEL(N)>(generic_threads(N), mtm_lds_bytes(N), 0);
         OTH_MTM_FOR_EACH_N(X)
 #undef X
-        default: break;
+        default: return 0;
     }
-    return n;
 }
 
-hipError_t launch_mtm(int nfft, const MtmArgs &a, int device, hipStream_t s) {
+hipError_t launch_mtm(int nfft, const MtmArgs &a, hipStream_t s) {
     const dim3 grid(a.wg_per_stream, a.nstreams);
-    const size_t lds = mtm_lds_bytes(nfft);
-    hipError_t e;
     switch (nfft) {
-#define X(N)                                                                                    \
-    case N: {                                                                                   \
-        constexpr int T = generic_threads(N);                                                   \
-        if ((e = mtm_arm<N>(device)) != hipSuccess) return e;                                   \
-        hipLaunchKernelGGL((mtm_kernel<N, T, mtm_keep(N)>), grid, dim3(T), lds, s, a);          \
-        break;                                                                                  \
-    }
+#define X(N) \
+    case N: return launch_lds<OTH_MTM_KERNEL(N)>(grid, dim3(generic_threads(N)), mtm_lds_bytes(N), s, a);
         OTH_MTM_FOR_EACH_N(X)
 #undef X
-        default:
-            return hipErrorInvalidValue;
+        default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 }  // namespace oth

@@ -41,7 +41,6 @@ __device__ __forceinline__ float2 mtm_pilot(const float2 *__restrict__ xs, int n
 }
 
 constexpr bool mtm_keep(int n) { return n < 8192; }      // mtm.hip's header: KEEP
-constexpr int kMtmMaxDevices = 64;
 constexpr int kMtmRedSlots = 32;                         // float2 slots of one `red` array (T / 64 + 1 <= 17 used)
 
 #define OTH_MTM_FOR_EACH_N(X) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192) X(16384)

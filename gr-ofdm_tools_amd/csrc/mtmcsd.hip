@@ -37,8 +37,8 @@
 // products, exactly 0 for identical channels.  Every sum runs in a fixed order: a result depends on the launch shape only.
 #include "mtm_common.hip.h"
 #include "oth_internal.h"
+#include "launch.h"
 
-#include <atomic>
 #include <type_traits>
 
 namespace oth {
@@ -201,61 +201,29 @@ size_t mtmcsd_lds_bytes(int nfft) {
 constexpr int mtmcsd_threads(int n) { return n == 4096 ? 512 : n == 8192 ? 1024 : generic_threads(n); }
 #define OTH_MTMCSD_KERNEL(N) mtmcsd_kernel<N, mtmcsd_threads(N), mtm_keep(N), mtmcsd_two_buffers(N), mtmcsd_two_buffers(N)>
 
-// The dynamic-LDS attribute of a build (tiles above 64 KiB) is armed once per device, not per launch.
-template <int N> hipError_t mtmcsd_arm(int device) {
-    static std::atomic<bool> armed[kMtmMaxDevices];
-    const size_t lds = mtmcsd_lds_bytes(N);
-    if (lds <= 64 * 1024) return hipSuccess;
-    const bool cached = device >= 0 && device < kMtmMaxDevices;
-    if (cached && armed[device].load(std::memory_order_acquire)) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(OTH_MTMCSD_KERNEL(N)),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess && cached) armed[device].store(true, std::memory_order_release);
-    return e;
-}
-
 }  // namespace
 
 size_t mtmcsd_ws_points(int nfft) { return mtmcsd_two_buffers(nfft) ? 0 : (size_t)nfft; }
 
-int mtmcsd_blocks_per_cu(int nfft, int device) {
-    int n = 0;
+int mtmcsd_blocks_per_cu(int nfft) {
     switch (nfft) {
-#define X(N)                                                                                                           \
-    case N: {                                                                                                          \
-        static std::atomic<int> cached{0};                                                                             \
-        if ((n = cached.load(std::memory_order_acquire)) > 0) return n;                                                \
-        if (mtmcsd_arm<N>(device) != hipSuccess ||                                                                     \
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, OTH_MTMCSD_KERNEL(N), mtmcsd_threads(N),                  \
-                                                         mtmcsd_lds_bytes(N)) != hipSuccess)                           \
-            n = 0;                                                                                                     \
-        if (n > 0) cached.store(n, std::memory_order_release);                                                         \
-        break;                                                                                                         \
-    }
+#define X(N) \
+    case N: return resident_blocks<OTH_MTMCSD_KERNEL(N)>(mtmcsd_threads(N), mtmcsd_lds_bytes(N), 0);
         OTH_MTM_FOR_EACH_N(X)
 #undef X
-        default: break;
+        default: return 0;
     }
-    return n;
 }
 
-hipError_t launch_mtmcsd(int nfft, const MtmCsdArgs &a, int device, hipStream_t s) {
+hipError_t launch_mtmcsd(int nfft, const MtmCsdArgs &a, hipStream_t s) {
     const dim3 grid(a.m.wg_per_stream, a.m.nstreams);
-    const size_t lds = mtmcsd_lds_bytes(nfft);
-    hipError_t e;
     switch (nfft) {
-#define X(N)                                                                                        \
-    case N: {                                                                                       \
-        if ((e = mtmcsd_arm<N>(device)) != hipSuccess) return e;                                    \
-        hipLaunchKernelGGL((OTH_MTMCSD_KERNEL(N)), grid, dim3(mtmcsd_threads(N)), lds, s, a);       \
-        break;                                                                                      \
-    }
+#define X(N) \
+    case N: return launch_lds<OTH_MTMCSD_KERNEL(N)>(grid, dim3(mtmcsd_threads(N)), mtmcsd_lds_bytes(N), s, a);
         OTH_MTM_FOR_EACH_N(X)
 #undef X
-        default:
-            return hipErrorInvalidValue;
+        default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 }  // namespace oth

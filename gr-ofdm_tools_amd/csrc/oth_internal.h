@@ -380,8 +380,8 @@ struct MtmArgs {
     int nstreams;
 };
 // resident workgroups per CU of the build (occupancy calculator: needs a device; 0 when it fails)
-int mtm_blocks_per_cu(int nfft, int device);
-hipError_t launch_mtm(int nfft, const MtmArgs &a, int device, hipStream_t s);
+int mtm_blocks_per_cu(int nfft);
+hipError_t launch_mtm(int nfft, const MtmArgs &a, hipStream_t s);
 
 // ---- mtmcsd.hip: the same taper loop on two channels - sum_k c_k of |X_k|^2, |Y_k|^2, Re and Im conj(X_k) Y_k ----------
 struct MtmCsdArgs {
@@ -390,7 +390,7 @@ struct MtmCsdArgs {
     float2 *ws;             // [nstreams][wg_per_stream][mtmcsd_ws_points(nfft)]: where X's spectrum waits for Y's (16384 points)
 };
 size_t mtmcsd_ws_points(int nfft);      // 0: the build keeps both spectra in LDS
-int mtmcsd_blocks_per_cu(int nfft, int device);
-hipError_t launch_mtmcsd(int nfft, const MtmCsdArgs &a, int device, hipStream_t s);
+int mtmcsd_blocks_per_cu(int nfft);
+hipError_t launch_mtmcsd(int nfft, const MtmCsdArgs &a, hipStream_t s);
 
 }  // namespace oth

@@ -30,6 +30,7 @@
 // immediate; the constants take 4 / 8 / 16 values, so a segment spends 16 / 26 / 49 v_xor on addressing.
 #include <type_traits>
 #include "fft4096.hip.h"
+#include "launch.h"
 
 namespace oth {
 namespace {
@@ -797,21 +798,11 @@ template <int R> constexpr size_t segws_lds_bytes() { return 256 + 2 * (size_t)G
 
 template <int R, int DET> hipError_t launch_ws_one(const SegArgs &a, hipStream_t s) {
     const dim3 grid(a.wg_per_stream, a.nstreams);
-    if constexpr (DET != 0) {
-        if (a.pilot) {
-            hipLaunchKernelGGL((segws_kernel<R, DET, true>), grid, dim3(2 * Geo<R>::T), segws_lds_bytes<R>(), s, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((segws_kernel<R, DET>), grid, dim3(2 * Geo<R>::T), segws_lds_bytes<R>(), s, a);
-    return hipGetLastError();
+    if constexpr (DET != 0)
+        if (a.pilot) return launch_lds<segws_kernel<R, DET, true>>(grid, dim3(2 * Geo<R>::T), segws_lds_bytes<R>(), s, a);
+    return launch_lds<segws_kernel<R, DET>>(grid, dim3(2 * Geo<R>::T), segws_lds_bytes<R>(), s, a);
 }
-template <int R> int occupancy_ws() {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, segws_kernel<R, 2>, 2 * Geo<R>::T, segws_lds_bytes<R>()) != hipSuccess || n < 1)
-        n = 1;
-    return n;
-}
+template <int R> int occupancy_ws() { return resident_blocks<segws_kernel<R, 2>>(2 * Geo<R>::T, segws_lds_bytes<R>()); }
 
 // image(s) + sums + tickets, and for the chain build the window table (4 x T float4) and twiddle tables
 template <int R, bool CHAIN> constexpr size_t seg_lds_bytes() {
@@ -822,23 +813,13 @@ template <int R, bool CHAIN> constexpr size_t seg_lds_bytes() {
 template <int R, int LOAD, bool DETREND, bool CHAIN, int WPS, int NA = 16> hipError_t launch_one(const SegArgs &a, hipStream_t s) {
     const dim3 grid((a.wg_per_stream + Geo<R>::TPB - 1) / Geo<R>::TPB, a.nstreams);
     constexpr size_t lds = seg_lds_bytes<R, CHAIN>();
-    if constexpr (DETREND) {
-        if (a.pilot) {
-            hipLaunchKernelGGL((seg_kernel<R, LOAD, DETREND, CHAIN, WPS, NA, true>), grid, dim3(Geo<R>::BLOCK), lds, s, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((seg_kernel<R, LOAD, DETREND, CHAIN, WPS, NA>), grid, dim3(Geo<R>::BLOCK), lds, s, a);
-    return hipGetLastError();
+    if constexpr (DETREND)
+        if (a.pilot) return launch_lds<seg_kernel<R, LOAD, DETREND, CHAIN, WPS, NA, true>>(grid, dim3(Geo<R>::BLOCK), lds, s, a);
+    return launch_lds<seg_kernel<R, LOAD, DETREND, CHAIN, WPS, NA>>(grid, dim3(Geo<R>::BLOCK), lds, s, a);
 }
 
-template <int R, int LOAD, bool DETREND, bool CHAIN, int WPS, int NA = 16> int occupancy_one() {
-    int n = 0;
-    constexpr size_t lds = seg_lds_bytes<R, CHAIN>();
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, seg_kernel<R, LOAD, DETREND, CHAIN, WPS, NA>, Geo<R>::BLOCK, lds) != hipSuccess ||
-        n < 1)
-        n = 1;
-    return n * Geo<R>::TPB;
+template <int R, int LOAD, bool DETREND, bool CHAIN, int WPS, int NA = 16, bool PILOT = false> int occupancy_one() {
+    return resident_blocks<seg_kernel<R, LOAD, DETREND, CHAIN, WPS, NA, PILOT>>(Geo<R>::BLOCK, seg_lds_bytes<R, CHAIN>()) * Geo<R>::TPB;
 }
 
 // zero-padded Welch builds (nperseg = nfft / 4 or nfft / 2): kind 0 step = nperseg / 2, kind 1 any step
@@ -847,22 +828,14 @@ template <int R, int NA> hipError_t launch_pad(const SegArgs &a, int kind, hipSt
     if (kind == 0) return a.detrend ? launch_one<R, LOAD_HALF, true, false, WPS, NA>(a, s) : launch_one<R, LOAD_HALF, false, false, WPS, NA>(a, s);
     return a.detrend ? launch_one<R, LOAD_FULL, true, false, WPS, NA>(a, s) : launch_one<R, LOAD_FULL, false, false, WPS, NA>(a, s);
 }
-template <int R, int LOAD, bool DETREND, bool CHAIN, int WPS, int NA> int occupancy_one_pilot() {
-    int n = 0;
-    constexpr size_t lds = seg_lds_bytes<R, CHAIN>();
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, seg_kernel<R, LOAD, DETREND, CHAIN, WPS, NA, true>, Geo<R>::BLOCK, lds) !=
-            hipSuccess || n < 1)
-        n = 1;
-    return n * Geo<R>::TPB;
-}
 // The grid is sized once per plan shape, the launch then takes the build with or without the pilot: the smaller of the
 // two occupancies counts (at three waves per SIMD the NA = 8 builds sit at 126-130 VGPRs, i.e. on both sides of the
 // step between eight and six resident workgroups per CU).
 template <int R, int NA> int occupancy_pad(int kind) {
     constexpr int WPS = NA == 4 ? 4 : 3;
     const int plain = kind == 0 ? occupancy_one<R, LOAD_HALF, true, false, WPS, NA>() : occupancy_one<R, LOAD_FULL, true, false, WPS, NA>();
-    const int pilot = kind == 0 ? occupancy_one_pilot<R, LOAD_HALF, true, false, WPS, NA>()
-                                : occupancy_one_pilot<R, LOAD_FULL, true, false, WPS, NA>();
+    const int pilot = kind == 0 ? occupancy_one<R, LOAD_HALF, true, false, WPS, NA, true>()
+                                : occupancy_one<R, LOAD_FULL, true, false, WPS, NA, true>();
     return plain < pilot ? plain : pilot;
 }
 
@@ -896,22 +869,13 @@ bool seg_supported(int nfft) { return nfft == 256 || nfft == 512 || nfft == 1024
 
 // resident teams per CU (VGPR / LDS / wave-slot limited)
 int seg_teams_per_cu(int nfft, int kind, bool wps4) {
-    static int cache[5][3][2] = {};
-    const int ri = nfft == 1024 ? 0 : (nfft == 2048 ? 1 : (nfft == 4096 ? 2 : (nfft == 512 ? 3 : 4)));
-    int &c = cache[ri][kind][wps4 ? 1 : 0];
-    if (c) return c;
-    return c = nfft == 256 ? occupancy_r<1>(kind, wps4) : nfft == 512 ? occupancy_r<2>(kind, wps4)
-                           : (nfft == 1024 ? occupancy_r<4>(kind, wps4)
-                                           : (nfft == 2048 ? occupancy_r<8>(kind, wps4) : occupancy_r<16>(kind, wps4)));
+    return nfft == 256 ? occupancy_r<1>(kind, wps4) : nfft == 512 ? occupancy_r<2>(kind, wps4)
+                       : (nfft == 1024 ? occupancy_r<4>(kind, wps4)
+                                       : (nfft == 2048 ? occupancy_r<8>(kind, wps4) : occupancy_r<16>(kind, wps4)));
 }
 
 // the role-split build: Welch, step = nfft / 2; det: 0 none, 1 time domain (1024 only), 2 frequency domain (SegArgs.fd)
-int segws_teams_per_cu(int nfft) {
-    static int cache[2] = {};
-    int &c = cache[nfft == 1024 ? 0 : 1];
-    if (c) return c;
-    return c = nfft == 1024 ? occupancy_ws<4>() : occupancy_ws<8>();
-}
+int segws_teams_per_cu(int nfft) { return nfft == 1024 ? occupancy_ws<4>() : occupancy_ws<8>(); }
 
 hipError_t launch_segws(int nfft, const SegArgs &a, int det, hipStream_t s) {
     if (nfft == 1024) return det == 0 ? launch_ws_one<4, 0>(a, s) : (det == 1 ? launch_ws_one<4, 1>(a, s) : launch_ws_one<4, 2>(a, s));
@@ -924,11 +888,8 @@ bool seg_padded_supported(int nfft, int nperseg) {
 }
 
 int seg_padded_teams_per_cu(int nfft, int nperseg, int kind) {
-    static int cache[2][2][2] = {};
-    int &c = cache[nfft == 1024 ? 0 : 1][nperseg * 4 == nfft ? 0 : 1][kind ? 1 : 0];
-    if (c) return c;
-    if (nfft == 1024) return c = nperseg * 4 == nfft ? occupancy_pad<4, 4>(kind) : occupancy_pad<4, 8>(kind);
-    return c = nperseg * 4 == nfft ? occupancy_pad<8, 4>(kind) : occupancy_pad<8, 8>(kind);
+    if (nfft == 1024) return nperseg * 4 == nfft ? occupancy_pad<4, 4>(kind) : occupancy_pad<4, 8>(kind);
+    return nperseg * 4 == nfft ? occupancy_pad<8, 4>(kind) : occupancy_pad<8, 8>(kind);
 }
 
 hipError_t launch_seg_padded(int nfft, int nperseg, const SegArgs &a, int kind, hipStream_t s) {
@@ -943,9 +904,7 @@ hipError_t launch_seg_padded(int nfft, int nperseg, const SegArgs &a, int kind, 
 template <int R> hipError_t launch_rows_r(const SegArgs &a, hipStream_t s) {
     if (!a.detrend) return launch_one<R, LOAD_FULL, false, true, kChainWps>(a, s);
     const dim3 grid((a.wg_per_stream + Geo<R>::TPB - 1) / Geo<R>::TPB, a.nstreams);
-    constexpr size_t lds = seg_lds_bytes<R, true>();
-    hipLaunchKernelGGL((seg_kernel<R, LOAD_FULL, true, true, kChainWps>), grid, dim3(Geo<R>::BLOCK), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<seg_kernel<R, LOAD_FULL, true, true, kChainWps>>(grid, dim3(Geo<R>::BLOCK), seg_lds_bytes<R, true>(), s, a);
 }
 
 int seg_rows_teams_per_cu(int nfft) { return seg_teams_per_cu(nfft, 2, false); }

@@ -14,6 +14,7 @@
 // LDS: F regions of 16 x 272 float2 (139 KiB at F = 4: one workgroup per CU; 70 KiB at F = 2: two);
 // 16 waves per CU = 4 per SIMD at <= 128 VGPRs.  Four workgroup barriers per segment.
 #include "fft4096.hip.h"
+#include "launch.h"
 
 // Segments do not overlap, every sample is read once: the sample loads are non-temporal (load_once).
 
@@ -469,13 +470,7 @@ __global__ __launch_bounds__(256 * F, 4) void chain16k_kernel(SegArgs p) {
 }  // namespace
 
 template <int F, bool WINDOW, bool PREFETCH> hipError_t launch_chain16k_f(const SegArgs &a, hipStream_t s) {
-    const dim3 grid(a.wg_per_stream, a.nstreams);
-    constexpr size_t lds = chain16k_lds_bytes<F>();
-    const void *fn = reinterpret_cast<const void *>(chain16k_kernel<F, WINDOW, PREFETCH>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((chain16k_kernel<F, WINDOW, PREFETCH>), grid, dim3(256 * F), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<chain16k_kernel<F, WINDOW, PREFETCH>>(dim3(a.wg_per_stream, a.nstreams), dim3(256 * F), chain16k_lds_bytes<F>(), s, a);
 }
 
 // rect: the chain's window is all ones (a.win is still valid)
@@ -486,13 +481,7 @@ hipError_t launch_chain16k(int nfft, const SegArgs &a, bool rect, hipStream_t s)
 }
 
 template <int DET, int F, bool HALF, bool PAD, bool PILOT, bool PADHALF> hipError_t launch16k_p(const WelchArgs &a, hipStream_t s) {
-    const dim3 grid(a.wg_per_stream, a.nstreams);
-    constexpr size_t lds = lds16_bytes<F>();
-    const void *fn = reinterpret_cast<const void *>(welch16k_kernel<DET, F, HALF, PAD, PILOT, PADHALF>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((welch16k_kernel<DET, F, HALF, PAD, PILOT, PADHALF>), grid, dim3(256 * F), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<welch16k_kernel<DET, F, HALF, PAD, PILOT, PADHALF>>(dim3(a.wg_per_stream, a.nstreams), dim3(256 * F), lds16_bytes<F>(), s, a);
 }
 template <int DET, int F, bool HALF, bool PAD = false, bool PADHALF = false> hipError_t launch16k(const WelchArgs &a, hipStream_t s) {
     if constexpr (DET != 0)

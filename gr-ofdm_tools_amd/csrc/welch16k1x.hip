@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "fft16k.hip.h"
+#include "launch.h"
 
 
 namespace oth {
@@ -689,13 +690,7 @@ __global__ __launch_bounds__(64 * NW, 4) void chain16k1x_kernel(SegArgs p) {
 
 template <int NW, bool WINDOW> static hipError_t launch1x_pipe(const WelchArgs &a, hipStream_t s) {
     if (a.nseg > 0x7fffffffLL) return hipErrorInvalidValue;      // x1_pipe_body counts segments in 32 bits
-    const dim3 grid(a.wg_per_stream, a.nstreams);
-    constexpr size_t lds = x1p_lds_bytes<NW>();
-    const void *fn = reinterpret_cast<const void *>(welch16k1x_pipe_kernel<NW, WINDOW>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((welch16k1x_pipe_kernel<NW, WINDOW>), grid, dim3(64 * NW), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<welch16k1x_pipe_kernel<NW, WINDOW>>(dim3(a.wg_per_stream, a.nstreams), dim3(64 * NW), x1p_lds_bytes<NW>(), s, a);
 }
 
 // 50 % overlap (scipy.signal.welch's default noverlap at nperseg = nfft = 16384, ofdm_cr_tools.py:214,322,342 with
@@ -912,13 +907,7 @@ __global__ __launch_bounds__(64 * NW, 4) void welch16k1x_half_kernel(WelchArgs p
 }
 
 template <int NW, int DET, bool PILOT = false> static hipError_t launch1x_half(const WelchArgs &a, hipStream_t s) {
-    const dim3 grid(a.wg_per_stream, a.nstreams);
-    constexpr size_t lds = x1h_lds_bytes<NW>();
-    const void *fn = reinterpret_cast<const void *>(welch16k1x_half_kernel<NW, DET, PILOT>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((welch16k1x_half_kernel<NW, DET, PILOT>), grid, dim3(64 * NW), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<welch16k1x_half_kernel<NW, DET, PILOT>>(dim3(a.wg_per_stream, a.nstreams), dim3(64 * NW), x1h_lds_bytes<NW>(), s, a);
 }
 template <int NW> static hipError_t launch1x_half_n(const WelchArgs &a, hipStream_t s) {
     if (a.detrend && a.fd) return (a.pilot || a.pilot_inline) ? launch1x_half<NW, 2, true>(a, s) : launch1x_half<NW, 2>(a, s);
@@ -1112,13 +1101,7 @@ __global__ __launch_bounds__(1024, 4) void welch8kws_kernel(WelchArgs p) {
 }
 
 template <int DET, bool PILOT = false> static hipError_t launch8kws(const WelchArgs &a, hipStream_t s) {
-    const dim3 grid(a.wg_per_stream, a.nstreams);
-    constexpr size_t lds = x8ws_lds_bytes();
-    const void *fn = reinterpret_cast<const void *>(welch8kws_kernel<DET, PILOT>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((welch8kws_kernel<DET, PILOT>), grid, dim3(1024), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<welch8kws_kernel<DET, PILOT>>(dim3(a.wg_per_stream, a.nstreams), dim3(1024), x8ws_lds_bytes(), s, a);
 }
 // 8192 points, step = N / 2, contiguous runs; detrend none, or constant through the frequency-domain form (a.fd)
 hipError_t launch_welch_tuned8kws(const WelchArgs &a, hipStream_t s) {
@@ -1128,24 +1111,12 @@ hipError_t launch_welch_tuned8kws(const WelchArgs &a, hipStream_t s) {
 }
 
 template <bool WINDOW> static hipError_t launch1x(const WelchArgs &a, hipStream_t s) {
-    const dim3 grid(a.wg_per_stream, a.nstreams);
-    constexpr size_t lds = x1_lds_bytes();
-    const void *fn = reinterpret_cast<const void *>(welch16k1x_kernel<WINDOW>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((welch16k1x_kernel<WINDOW>), grid, dim3(1024), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<welch16k1x_kernel<WINDOW>>(dim3(a.wg_per_stream, a.nstreams), dim3(1024), x1_lds_bytes(), s, a);
 }
 
 template <int NW, bool WINDOW> static hipError_t launch_chain1x(const SegArgs &a, hipStream_t s) {
     if (a.nseg > 0x7fffffffLL) return hipErrorInvalidValue;      // x1_pipe_body counts segments in 32 bits
-    const dim3 grid(a.wg_per_stream, a.nstreams);
-    constexpr size_t lds = x1p_lds_bytes<NW>();
-    const void *fn = reinterpret_cast<const void *>(chain16k1x_kernel<NW, WINDOW>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((chain16k1x_kernel<NW, WINDOW>), grid, dim3(64 * NW), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<chain16k1x_kernel<NW, WINDOW>>(dim3(a.wg_per_stream, a.nstreams), dim3(64 * NW), x1p_lds_bytes<NW>(), s, a);
 }
 hipError_t launch_chain16k1x(int nfft, const SegArgs &a, bool rect, hipStream_t s) {
     if (nfft == 16384) return rect ? launch_chain1x<16, false>(a, s) : launch_chain1x<16, true>(a, s);

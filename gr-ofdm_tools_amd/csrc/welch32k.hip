@@ -37,6 +37,7 @@
 // (b % 8) (W / 8) + b / 8) - the second reader finds the half in that XCD's L2.
 #include <type_traits>
 #include "fft16k.hip.h"
+#include "launch.h"
 
 namespace oth {
 namespace {
@@ -536,27 +537,15 @@ int welch32k_rows(long long nseg, int cus, bool front) {
     return (int)(nseg < cus ? (nseg < 1 ? 1 : nseg) : cus);
 }
 
+// 153 KiB of dynamic LDS: the opt-in is launch_lds's, once per build and device
 hipError_t launch_welch32k(const W32kArgs &a, int W, hipStream_t s) {
-    static bool armed[64] = {};        // 153 KiB of dynamic LDS needs the opt-in, once per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!armed[dev]) {
-        hipError_t e = hipSuccess;
-        for (const void *fn : {reinterpret_cast<const void *>(welch32k_kernel<true, false>), reinterpret_cast<const void *>(welch32k_kernel<false, false>),
-                               reinterpret_cast<const void *>(welch32k_kernel<true, true>), reinterpret_cast<const void *>(welch32k_kernel<false, true>)})
-            if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W32_LDS_BYTES);
-        if (e != hipSuccess) return e;
-        armed[dev] = true;
+    if (!a.front) {
+        if (a.detrend) return launch_lds<welch32k_kernel<true, false>>(dim3(W), dim3(1024), W32_LDS_BYTES, s, a);
+        return launch_lds<welch32k_kernel<false, false>>(dim3(W), dim3(1024), W32_LDS_BYTES, s, a);
     }
-    if (a.front) {
-        if (!a.wpm && a.detrend) return hipErrorInvalidValue;
-        if (a.detrend) hipLaunchKernelGGL((welch32k_kernel<true, true>), dim3(2 * W), dim3(1024), W32_LDS_BYTES, s, a);
-        else hipLaunchKernelGGL((welch32k_kernel<false, true>), dim3(2 * W), dim3(1024), W32_LDS_BYTES, s, a);
-    } else {
-        if (a.detrend) hipLaunchKernelGGL((welch32k_kernel<true, false>), dim3(W), dim3(1024), W32_LDS_BYTES, s, a);
-        else hipLaunchKernelGGL((welch32k_kernel<false, false>), dim3(W), dim3(1024), W32_LDS_BYTES, s, a);
-    }
-    return hipGetLastError();
+    if (!a.wpm && a.detrend) return hipErrorInvalidValue;
+    if (a.detrend) return launch_lds<welch32k_kernel<true, true>>(dim3(2 * W), dim3(1024), W32_LDS_BYTES, s, a);
+    return launch_lds<welch32k_kernel<false, true>>(dim3(2 * W), dim3(1024), W32_LDS_BYTES, s, a);
 }
 
 }  // namespace oth

@@ -54,6 +54,7 @@
 
 #include <type_traits>
 #include "fft4096.hip.h"
+#include "launch.h"
 
 namespace oth {
 namespace {
@@ -434,45 +435,21 @@ __global__ __launch_bounds__(TWS, 4) void welch4096ws_compl_kernel(WelchArgs p) 
 
 }  // namespace
 
-int tuned4096_blocks_per_cu_ws() {
-    static int cached = 0;
-    if (cached) return cached;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, welch4096ws_kernel<true, false>, TWS, WS_LDS_BYTES) != hipSuccess || n < 1)
-        n = 1;
-    return cached = n;
-}
+int tuned4096_blocks_per_cu_ws() { return resident_blocks<welch4096ws_kernel<true, false>>(TWS, WS_LDS_BYTES); }
 
+// 70 KiB of dynamic LDS: the opt-in is launch_lds's, once per build and device
 hipError_t launch_welch_tuned4096_ws(const WelchArgs &a, hipStream_t s) {
     const dim3 grid(a.wg_per_stream, a.nstreams);
-    static bool armed[64] = {};        // 70 KiB of dynamic LDS needs the opt-in, once per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63, armed[63] = false;
-    bool &big_lds = armed[dev];
-    if (!big_lds) {
-        hipError_t e = hipSuccess;
-        for (const void *fn : {reinterpret_cast<const void *>(welch4096ws_kernel<true, true>),
-                               reinterpret_cast<const void *>(welch4096ws_kernel<true, false>),
-                               reinterpret_cast<const void *>(welch4096ws_kernel<false, false>),
-                               reinterpret_cast<const void *>(welch4096ws_compl_kernel<true, true>),
-                               reinterpret_cast<const void *>(welch4096ws_compl_kernel<true, false>),
-                               reinterpret_cast<const void *>(welch4096ws_compl_kernel<false, false>)})
-            if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WS_LDS_BYTES);
-        if (e != hipSuccess) return e;
-        big_lds = true;
-    }
     const bool pilot = a.detrend && (a.pilot || a.pilot_inline);
-    if (a.compl_win) {      // w[n] + w[n + 2048] = 1 (plan-time check, abi_welch.hip window_is_complementary)
-        if (pilot) hipLaunchKernelGGL((welch4096ws_compl_kernel<true, true>), grid, dim3(TWS), WS_LDS_BYTES, s, a);
-        else if (a.detrend) hipLaunchKernelGGL((welch4096ws_compl_kernel<true, false>), grid, dim3(TWS), WS_LDS_BYTES, s, a);
-        else hipLaunchKernelGGL((welch4096ws_compl_kernel<false, false>), grid, dim3(TWS), WS_LDS_BYTES, s, a);
-    } else if (pilot)
-        hipLaunchKernelGGL((welch4096ws_kernel<true, true>), grid, dim3(TWS), WS_LDS_BYTES, s, a);
-    else if (a.detrend)
-        hipLaunchKernelGGL((welch4096ws_kernel<true, false>), grid, dim3(TWS), WS_LDS_BYTES, s, a);
-    else
-        hipLaunchKernelGGL((welch4096ws_kernel<false, false>), grid, dim3(TWS), WS_LDS_BYTES, s, a);
-    return hipGetLastError();
+    if (!a.compl_win) {
+        if (pilot) return launch_lds<welch4096ws_kernel<true, true>>(grid, dim3(TWS), WS_LDS_BYTES, s, a);
+        if (a.detrend) return launch_lds<welch4096ws_kernel<true, false>>(grid, dim3(TWS), WS_LDS_BYTES, s, a);
+        return launch_lds<welch4096ws_kernel<false, false>>(grid, dim3(TWS), WS_LDS_BYTES, s, a);
+    }
+    // w[n] + w[n + 2048] = 1 (plan-time check, abi_welch.hip window_is_complementary)
+    if (pilot) return launch_lds<welch4096ws_compl_kernel<true, true>>(grid, dim3(TWS), WS_LDS_BYTES, s, a);
+    if (a.detrend) return launch_lds<welch4096ws_compl_kernel<true, false>>(grid, dim3(TWS), WS_LDS_BYTES, s, a);
+    return launch_lds<welch4096ws_compl_kernel<false, false>>(grid, dim3(TWS), WS_LDS_BYTES, s, a);
 }
 
 }  // namespace oth

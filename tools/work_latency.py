@@ -12,6 +12,7 @@ For the five chain blocks and the legacy sensor, pushes of 4096 / 8192 / 32768 i
   Msamples/s         sustained: N pushes back to back, then one synchronisation
   watcher us         from the entry of work() to _on_vector on the watcher thread (threaded=True; median / p95)
 usage (GPU box): python tools/work_latency.py > gpurun_out/work_latency.txt
+       fft sizes other than the default 1024 and 4096: python tools/work_latency.py 8192 16384
 """
 import os
 import statistics
@@ -29,6 +30,7 @@ from oracle import ref_cpu as R  # noqa: E402
 
 ctx = _hip.Context(0)
 REPS = 400
+SIZES = [int(a) for a in sys.argv[1:]] or [1024, 4096]
 
 
 def blocks(N, threaded):
@@ -110,7 +112,7 @@ def watcher_latency(N, items):
 
 print('device: %s' % ctx.device_name())
 print('%-22s %6s %7s | %10s %10s %9s %9s %11s' % ('block', 'fft', 'items', 'work() us', 'enqueue us', 'ops/push', 'dev us', 'Msamples/s'))
-for N in (1024, 4096):
+for N in SIZES:
     for items in (4096, 8192, 32768):
         for name, make in blocks(N, False):
             h, e, om, ox, d, r = measure(name, make, items)
@@ -125,7 +127,7 @@ for items in (4096, 8192, 32768):
         blk.work([x], [])
         host.append((time.perf_counter() - t0) * 1e6)
     print('%-22s %6s %7d | %10.1f %10s %9s %9s %11s' % ('spectrum_sensor (legacy)', '-', items, statistics.median(host), '-', '0', '-', '-'))
-for N in (1024, 4096):
+for N in SIZES:
     for items in (4096, 8192, 32768):
         med, p95, n = watcher_latency(N, items)
         print('watcher latency spectrum_sensor_v2 fft %d items %d: median %.1f us, p95 %.1f us (%d vectors of 200 pushes)' % (N, items, med, p95, n))
