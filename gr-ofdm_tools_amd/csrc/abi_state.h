@@ -132,6 +132,10 @@ struct oth_plan {
     DevBuf<float> d_coef;              // [ntapers] c_k: normalised weight (over the taper's energy with OTH_SCALE_DENSITY)
     bool mtm_csd = false;              // oth_mtm_csd_plan only: the oth_csd_* calls run mtmcsd.hip instead of being refused
     DevBuf<float2> d_mtm_ws;           // mtmcsd.hip's per-workgroup spectrum rows (MtmCsdArgs.ws; 16384 points only)
+    // the harmonic F-test (oth_mtm_ftest*, mtmftest.hip): every multitaper plan carries the tapers' sums
+    DevBuf<float> d_mtm_u;             // [ntapers] U_k = sum_n v_k[n] (summed in double)
+    double mtm_s = 0.0;                // sum_k U_k^2 of the uploaded values
+    DevBuf<float> d_ftest_ws;          // mtmftest.hip's per-workgroup sy / p rows (MtmFtestArgs.ws; 16384 points only)
 };
 
 struct oth_chain {

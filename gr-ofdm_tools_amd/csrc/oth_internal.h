@@ -393,4 +393,27 @@ size_t mtmcsd_ws_points(int nfft);      // 0: the build keeps both spectra in LD
 int mtmcsd_blocks_per_cu(int nfft);
 hipError_t launch_mtmcsd(int nfft, const MtmCsdArgs &a, hipStream_t s);
 
+// ---- mtmftest.hip: Thomson's harmonic F-test on the same taper loop; the work item is a whole segment ------------------
+struct MtmFtestArgs {
+    MtmArgs m;              // x, the tables and the sizes as mtm.hip's (coef unused); wg_per_stream: each workgroup walks a
+                            // contiguous run of the nseg segments; partial: [nstreams][wg_per_stream][2][nfft] sum num, sum den
+    const float *u;         // [ntapers] U_k = sum_n v_k[n]
+    float inv_s;            // 1 / sum_k U_k^2
+    float *ws;              // [nstreams][wg_per_stream][mtm_ftest_ws_floats(nfft)]: a segment's sy / p between its tapers (16384 points)
+};
+struct FtestFinalizeArgs {
+    const float *partial;   // [nstreams][W][2][nfft], natural bin order
+    float *f_out;           // [nstreams][nout]
+    float *line_out;        // or nullptr
+    float *resid_out;       // or nullptr
+    double km1;             // K - 1
+    double line_scale;      // 1 / (S nseg)
+    double resid_scale;     // scale / ((K - 1) nseg)
+    int W, nfft, fftshift, trim, nout;
+};
+size_t mtm_ftest_ws_floats(int nfft);      // 0: the build keeps sy / p in registers
+int mtm_ftest_blocks_per_cu(int nfft);
+hipError_t launch_mtm_ftest(int nfft, const MtmFtestArgs &a, hipStream_t s);
+hipError_t launch_ftest_finalize(const FtestFinalizeArgs &a, int nstreams, hipStream_t s);
+
 }  // namespace oth

@@ -76,6 +76,8 @@ SIGNATURES = {
                                C.c_int, _pp]),
     'oth_mtm_csd_plan': (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, _f, _f, C.c_int, C.c_int, C.c_double, C.c_int,
                                    C.c_int, _pp]),
+    'oth_mtm_ftest_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _p, _u64p]),
+    'oth_mtm_ftest': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _f, _u64p]),
     'oth_plan_set_tuning': (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int, C.c_int]),
     'oth_welch_exec': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _u64p]),
     'oth_welch_exec_async': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _u64p]),
@@ -701,7 +703,8 @@ def mtm_weights(weights, ntapers, slepian=True):
 class MtmPlan(WelchPlan):
     """A WelchPlan whose averaging launch is the multitaper kernel: exec / exec_async / poll / wait / exec_dev /
     partial_dev / scale_dev / accumulate / finalize / reset as WelchPlan's; the median average, the per-segment rows,
-    the cross spectrum, KERNEL_TUNED and build variants raise HipError (OTH_ERR_UNSUPPORTED)."""
+    the cross spectrum, KERNEL_TUNED and build variants raise HipError (OTH_ERR_UNSUPPORTED).  ftest / ftest_dev: Thomson's
+    harmonic F-test on the same tapers."""
 
     _CONSTRUCTOR = 'oth_mtm_plan'
 
@@ -743,6 +746,40 @@ class MtmPlan(WelchPlan):
         self.out_len = n.value
         if db:
             ctx.check(ctx.lib.oth_plan_set_output_db(h, 1), 'oth_plan_set_output_db')
+
+    def ftest(self, x, return_rows=False, nsamples=None):
+        """Thomson's harmonic F-test (oth_mtm_ftest) of one capture: per bin F = (K - 1) sum_s num_s / sum_s den_s, large
+        where a coherent line sits at the bin whatever the background.  x: host complex64 array, or a device pointer when
+        nsamples is given.  -> F (float32, out_len bins, the plan's fftshift and trim; always linear), or with return_rows
+        (F, line, resid): the line's power and the background with the line removed.  Sets last_nseg (see dof)."""
+        rows = [np.empty(self.out_len, np.float32) for _ in range(3 if return_rows else 1)]
+        ptrs = [_fptr(r) for r in rows] + [None] * (3 - len(rows))
+        n = C.c_uint64()
+        if nsamples is None:
+            x = _c64(x)
+            src, count, dev = x.ctypes.data_as(_p), len(x), 0
+        else:
+            src, count, dev = C.c_void_p(x), int(nsamples), 1
+        self.ctx.check(self.ctx.lib.oth_mtm_ftest(self.h, src, count, dev, ptrs[0], ptrs[1], ptrs[2], C.byref(n)), 'oth_mtm_ftest')
+        self.last_nseg = n.value
+        return tuple(rows) if return_rows else rows[0]
+
+    def ftest_dev(self, iq_dev, nsamples, nstreams, stride, f_dev, line_dev=None, resid_dev=None):
+        """Asynchronous: device in, device out - [nstreams][out_len] float32 at f_dev and, where given, line_dev and
+        resid_dev.  -> segments per stream (also last_nseg)."""
+        n = C.c_uint64()
+        vp = lambda v: C.c_void_p(v) if v else None      # noqa: E731
+        self.ctx.check(self.ctx.lib.oth_mtm_ftest_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
+                                                      C.c_void_p(f_dev), vp(line_dev), vp(resid_dev), C.byref(n)),
+                       'oth_mtm_ftest_dev')
+        self.last_nseg = n.value
+        return n.value
+
+    @property
+    def dof(self):
+        """Degrees of freedom (2 nseg, 2 nseg (K - 1)) of the F distribution the last call's bins follow without a line."""
+        nseg = int(getattr(self, 'last_nseg', 0))
+        return 2 * nseg, 2 * nseg * (self.ntapers - 1)
 
 
 class MtmCsdPlan(MtmPlan):

@@ -255,6 +255,61 @@ def mtm_power_estimate(vector, nFFT, Sf, NW=4.0, K=None, ctx=None):
     return float(np.sum(_mtm_plan(ctx, nFFT, Sf, len(vector), NW, K).exec(vector), dtype=np.float64))
 
 
+def _ftest_log_sf(f, a, b, logc):
+    """log P(F > f) for F(2 a, 2 b), a and b integers: with x = a f / (a f + b) the survival function is the binomial sum
+    sum_{i < a} C(a + b - 1, i) x^i (1 - x)^(a + b - 1 - i); logc[i] = log C(a + b - 1, i)."""
+    n = a + b - 1
+    i = np.arange(a, dtype=np.float64)
+    lden = math.log(a * f + b)
+    terms = logc + i * (math.log(a * f) - lden) + (n - i) * (math.log(b) - lden)
+    top = float(np.max(terms))
+    return top + math.log(float(np.sum(np.exp(terms - top))))
+
+
+def ftest_threshold(p_false, nseg, K):
+    """The value the harmonic F-test (MtmPlan.ftest) exceeds with probability p_false in a bin without a line: the upper
+    p_false quantile of F(2 nseg, 2 nseg (K - 1)).  Both half-degrees of freedom are integers, so the survival function is a
+    finite binomial sum (evaluated in log space) and the quantile its inversion by bisection on log f."""
+    nseg, K = int(nseg), int(K)
+    if not 0.0 < p_false < 1.0 or nseg < 1 or K < 2:
+        raise ValueError('need 0 < p_false < 1, nseg >= 1 and K >= 2')
+    a, b = nseg, nseg * (K - 1)
+    n = a + b - 1
+    logc = np.array([math.lgamma(n + 1) - math.lgamma(i + 1) - math.lgamma(n - i + 1) for i in range(a)])
+    want = math.log(p_false)
+    lo, hi = -700.0, 700.0      # log f: the survival function falls from 1 to 0 between
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if not lo < mid < hi:
+            break
+        if _ftest_log_sf(math.exp(mid), a, b, logc) > want:
+            lo = mid
+        else:
+            hi = mid
+    return math.exp(0.5 * (lo + hi))
+
+
+def mtm_line_scan(vector, nFFT, Sf, fc=0.0, NW=4.0, K=None, p_false=None, ctx=None):
+    """Coherent lines (pilots, carriers, narrowband interferers) of one capture by Thomson's harmonic F-test on the plan of
+    the other mtm_* helpers: nperseg = min(nFFT, len), one pass without overlap.  A line is a bin whose F exceeds
+    ftest_threshold(p_false, nseg, K) - p_false = 1e-3 / nFFT by default: one false line in a thousand scans - and is the
+    largest within the main lobe, +-ceil(NW nFFT / nperseg) bins.  -> (F fftshifted, frequency axis, line frequencies)."""
+    ctx = ctx or _hip.default_context()
+    plan = _mtm_plan(ctx, nFFT, Sf, len(vector), NW, K)
+    F = plan.ftest(vector)
+    nseg = plan.last_nseg
+    p_false = 1e-3 / nFFT if p_false is None else p_false
+    thr = ftest_threshold(p_false, nseg, plan.ntapers)
+    axis = np.fft.fftshift(np.fft.fftfreq(nFFT, 1.0 / Sf)) + fc
+    half = int(math.ceil(float(NW) * nFFT / plan.nperseg))
+    lines = []
+    for i in np.flatnonzero(F > thr):
+        lobe = F[np.arange(i - half, i + half + 1) % nFFT]      # (the spectrum is periodic)
+        if int(np.argmax(lobe)) == half:
+            lines.append(float(axis[i]))
+    return F, axis, lines
+
+
 class SpectrumScan(object):
     """The legacy sensor's scan (reference: ofdm_cr_tools.py:471-537; its matplotlib branch is not carried over), split
     where the GPU works: the constructor enqueues the PSD of the chosen method ('welch': flat-top Welch, 'fft': one

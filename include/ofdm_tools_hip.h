@@ -295,6 +295,29 @@ int oth_mtm_plan(oth_ctx *ctx, int nfft, int nperseg, int noverlap, int ntapers,
  * on Welch plans, dB output on any oth_csd_* call. */
 int oth_mtm_csd_plan(oth_ctx *ctx, int nfft, int nperseg, int noverlap, int ntapers, const float *tapers,
                      const float *weights, int detrend, int scaling, double fs, int fftshift, int trim_bins, oth_plan **out);
+/* oth_mtm_ftest_dev / oth_mtm_ftest (additions inside ABI 6; probe by the symbols): Thomson's harmonic F-test - per bin, "is
+ * there a coherent line at this frequency, whatever the background level" - on any plan of oth_mtm_plan or oth_mtm_csd_plan.
+ * With U_k = sum_n v_k[n] (formed in double when the plan is created), S = sum_k U_k^2, and per segment s and bin j
+ * y_k = FFT_nfft((x_s - m_s) v_k)[j] (segmentation, the per-segment mean removal and zero padding as the plan's exec forms):
+ *   mu_s  = sum_k U_k y_k / S                 the complex amplitude of a line at bin j
+ *   num_s = S |mu_s|^2,   den_s = sum_k |y_k|^2 - num_s   ( = sum_k |y_k - mu_s U_k|^2 )
+ *   F     = (K - 1) sum_s num_s / sum_s den_s            F(2 nseg, 2 nseg (K - 1)) distributed where there is no line
+ *   line  = (1 / nseg) sum_s |mu_s|^2                    the power of the sinusoid, input units squared
+ *   resid = scale sum_s den_s / ((K - 1) nseg)           the background with the line removed; scale = the plan's 1 / fs,
+ *                                                        1 / nfft^2 or 1
+ * The plan's weights take no part (the test is unweighted).  The three rows take the plan's fftshift and trim and are always
+ * linear: oth_plan_set_output_db does not apply.  Layout [nstreams][out_len] each; line_out and resid_out may be NULL.
+ * A bin with sum den <= 0 reads F = 0 when sum num = 0 and +INF otherwise, and resid = 0 there: finite input never gives NaN;
+ * all-zero input, and constant input on a detrending plan, give three rows of zeros.
+ * One averaging launch per call (csrc/mtmftest.hip: a workgroup takes whole segments, K transforms each), then a small
+ * finalize launch; sums in a fixed order, bit-identical run to run.  _dev: device in, device out, asynchronous, nstreams
+ * as oth_welch_exec_dev (at most 65535).  oth_mtm_ftest: one stream, host or device source, host outputs, blocking.
+ * Refused with OTH_ERR_UNSUPPORTED and the reason in oth_last_error(): a plan without tapers (oth_welch_plan's), ntapers < 2,
+ * tapers whose sums are all zero (S = 0).  Input shorter than nperseg: OTH_ERR_INVALID, as oth_welch_exec_dev. */
+int oth_mtm_ftest_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride,
+                      float *f_out_dev, float *line_out_dev, float *resid_out_dev, uint64_t *nseg_out);
+int oth_mtm_ftest(oth_plan *plan, const void *iq, size_t nsamples, int src_is_device, float *f_out, float *line_out,
+                  float *resid_out, uint64_t *nseg_out);
 
 /* one-shot: nsamples complex64 -> psd_out[nfft - 2*trim] (host).  Blocking: returns when the PSD is in psd_out.  The
  * last launch writes the row and a completion word into pinned host memory and the call polls that word (no interrupt
