@@ -1,0 +1,118 @@
+// C ABI, host side: spectral kurtosis of a Welch plan (oth_welch_sk / _dev) - the checks, the segment-per-workgroup launch
+// of welchsk.hip and its finalize launch into the SK row and, where asked for, the PSD row.
+#include "abi_state.h"
+
+namespace {
+bool sk_size(int nfft) { return nfft >= 64 && nfft <= 16384 && (nfft & (nfft - 1)) == 0; }
+
+// Every refusal of the two entry points, in the header's order, before anything is allocated, staged or launched.
+int sk_check(oth_plan *p, const void *x, size_t nsamples, int nstreams, size_t stride, const float *sk_out, long long *nseg_out) {
+    oth_ctx *c = p->ctx;
+    if (p->ntapers) return refuse_mtm(p, "the spectral kurtosis", "its segments' periodograms are Welch's (oth_welch_plan)");
+    if (p->average == OTH_AVERAGE_MEDIAN)
+        return fail(c, OTH_ERR_UNSUPPORTED, "the spectral kurtosis is not available with OTH_AVERAGE_MEDIAN: its PSD row is the mean "
+                                            "over segments (oth_plan_set_average(OTH_AVERAGE_MEAN) first)");
+    if (!sk_size(p->nfft))
+        return fail(c, OTH_ERR_UNSUPPORTED, "the spectral kurtosis takes a transform length that is a power of two from 64 to 16384, not " +
+                                                std::to_string(p->nfft));
+    if (!x || !sk_out || nstreams < 1) return fail(c, OTH_ERR_INVALID, "bad argument");
+    if (nstreams > 1 && stride < nsamples) return fail(c, OTH_ERR_INVALID, "stream_stride < nsamples");
+    if (nsamples < (size_t)p->nperseg) return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
+    if (nstreams > 65535) return fail(c, OTH_ERR_UNSUPPORTED, "the spectral kurtosis takes at most 65535 streams per launch");
+    const long long nseg = (long long)((nsamples - (size_t)p->noverlap) / (size_t)p->step);
+    if (nseg < 2) return fail(c, OTH_ERR_INVALID, "the spectral kurtosis needs at least two segments: this input holds one");
+    *nseg_out = nseg;
+    return OTH_OK;
+}
+
+// after sk_check: device in, device out
+int sk_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t stride, float *sk_out, float *psd_out) {
+    oth_ctx *c = p->ctx;
+    if (use_device(c)) return OTH_ERR_HIP;
+    const int N = p->nfft;
+    // whole segments go to W workgroups per stream in contiguous runs: what the device holds at once, a segment at least
+    const int bpc = std::max(1, welch_sk_blocks_per_cu(N));
+    const long long resident = (long long)c->cu_count * bpc;
+    const int W = (int)std::min(nseg, std::max<long long>(1, resident / nstreams));
+    if (int rc = p->d_partial.ensure(c, sizeof(float) * (size_t)nstreams * W * 2 * N)) return rc;
+    WelchSkArgs a{};
+    a.x = x;
+    a.win = p->d_win.get();
+    a.tw = p->d_tw;
+    a.partial = p->d_partial.get();
+    a.nseg = nseg;
+    a.stream_stride = stride;
+    a.nperseg = p->nperseg;
+    a.step = p->step;
+    a.detrend = p->detrend != OTH_DETREND_NONE;
+    a.wg_per_stream = W;
+    a.nstreams = nstreams;
+    a.g = (float)p->sk_g;
+    SkFinalizeArgs f{};
+    f.partial = p->d_partial.get();
+    f.sk_out = sk_out;
+    f.psd_out = psd_out;
+    f.m = (double)nseg;
+    f.mp1_over_mm1 = ((double)nseg + 1.0) / ((double)nseg - 1.0);
+    f.psd_scale = p->scale / ((double)a.g * (double)nseg);      // the float the kernel multiplied by: it cancels
+    f.W = W;
+    f.nfft = N;
+    f.fftshift = p->fftshift;
+    f.trim = p->trim;
+    f.db = p->db;
+    f.nout = N - 2 * p->trim;
+    {
+        Timed tm(c);
+        HIPCHK(c, launch_welch_sk(N, a, c->stream));
+    }
+    {
+        Timed tm(c);
+        HIPCHK(c, launch_sk_finalize(f, nstreams, c->stream));
+    }
+    p->last_recipe = "kernel=welchsk nfft=" + std::to_string(N) + " W=" + std::to_string(W) + " nseg=" + std::to_string(nseg) +
+                     " nstreams=" + std::to_string(nstreams) + " bpc=" + std::to_string(bpc);
+    return OTH_OK;
+}
+}  // namespace
+
+extern "C" {
+int oth_welch_sk_dev(oth_plan *p, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride, float *sk_out_dev,
+                     float *psd_out_dev, uint64_t *nseg_out) {
+    OTH_TRY
+    CtxGuard guard_(p ? p->ctx : nullptr);
+    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    long long nseg = 0;
+    if (int rc = sk_check(p, iq_dev, nsamples, nstreams, stream_stride, sk_out_dev, &nseg)) return rc;
+    if (int rc = sk_run(p, (const float2 *)iq_dev, nseg, nstreams, stream_stride, sk_out_dev, psd_out_dev)) return rc;
+    if (nseg_out) *nseg_out = (uint64_t)nseg;
+    return OTH_OK;
+    OTH_CATCH((p ? p->ctx : nullptr))
+}
+
+int oth_welch_sk(oth_plan *p, const void *iq, size_t nsamples, int src_is_device, float *sk_out, float *psd_out, uint64_t *nseg_out) {
+    OTH_TRY
+    CtxGuard guard_(p ? p->ctx : nullptr);
+    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    oth_ctx *c = p->ctx;
+    long long nseg = 0;
+    if (int rc = sk_check(p, iq, nsamples, 1, nsamples, sk_out, &nseg)) return rc;
+    if (use_device(c)) return OTH_ERR_HIP;
+    const float2 *dx = (const float2 *)iq;
+    int rc;
+    if (!src_is_device) {
+        if ((rc = p->d_stage.ensure(c, nsamples * sizeof(float2)))) return rc;
+        HIPCHK(c, hipMemcpyAsync(p->d_stage.get(), iq, nsamples * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+        dx = p->d_stage.get();
+    }
+    if ((rc = p->d_out.ensure(c, sizeof(float) * 5 * p->nfft))) return rc;
+    const int N = p->nfft, nout = N - 2 * p->trim;
+    float *o = p->d_out.get();
+    if ((rc = sk_run(p, dx, nseg, 1, nsamples, o, psd_out ? o + N : nullptr))) return rc;
+    HIPCHK(c, hipMemcpyAsync(sk_out, o, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
+    if (psd_out) HIPCHK(c, hipMemcpyAsync(psd_out, o + N, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (nseg_out) *nseg_out = (uint64_t)nseg;
+    return OTH_OK;
+    OTH_CATCH((p ? p->ctx : nullptr))
+}
+}  // extern "C"

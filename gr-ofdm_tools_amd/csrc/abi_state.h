@@ -136,6 +136,8 @@ struct oth_plan {
     DevBuf<float> d_mtm_u;             // [ntapers] U_k = sum_n v_k[n] (summed in double)
     double mtm_s = 0.0;                // sum_k U_k^2 of the uploaded values
     DevBuf<float> d_ftest_ws;          // mtmftest.hip's per-workgroup sy / p rows (MtmFtestArgs.ws; 16384 points only)
+    // spectral kurtosis (oth_welch_sk*, abi_sk.hip / welchsk.hip): Welch plans only
+    double sk_g = 1.0;                 // 1 / sum w^2 (1 for an all-zero window): the periodograms' scale inside the kernel
 };
 
 struct oth_chain {

@@ -443,6 +443,7 @@ int oth_welch_plan(oth_ctx *c, int nfft, int nperseg, int noverlap, const float 
         case OTH_SCALE_SPECTRUM: p->scale = 1.0 / (s1 * s1); break;
         default: p->scale = 1.0;
     }
+    p->sk_g = s2 > 0.0 && std::isfinite(1.0 / s2) ? 1.0 / s2 : 1.0;      // oth_welch_sk's periodogram scale
     p->compl_window = nfft == 4096 && nperseg == 4096 && window_is_complementary(w, nfft);      // the welch4096ws route's shape
     // the host tables first, then the uploads: nothing between the first asynchronous copy and the synchronise can throw
     std::vector<float> fd, fd1x, wpm;

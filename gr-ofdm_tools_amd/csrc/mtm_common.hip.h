@@ -1,5 +1,6 @@
-// What the two multitaper kernels (mtm.hip: one channel, mtmcsd.hip: two) share: the fixed-order sums behind a segment's
-// pilot and residual mean, the rule for keeping a segment's samples in registers, and the list of sizes.
+// What the taper-loop kernels (mtm.hip: one channel, mtmcsd.hip: two, mtmftest.hip: the F-test, welchsk.hip: spectral
+// kurtosis with the plan's window as the one taper) share: the fixed-order sums behind a segment's pilot and residual mean,
+// the segment entry built on them, the rule for keeping a segment's samples in registers, and the list of sizes.
 #pragma once
 #include "fft_lds.hip.h"
 
@@ -38,6 +39,39 @@ __device__ __forceinline__ float2 mtm_pilot(const float2 *__restrict__ xs, int n
     }
     __syncthreads();
     return red[0];
+}
+
+// Segment entry of the taper-loop kernels as one call (mtm_kernel's arithmetic, operation for operation): the pilot comes
+// off every sample, then the residual mean - a block sum in a fixed order - comes off.  KEEP: v[q] holds the detrended
+// sample tid + q T (zero behind nperseg); otherwise the caller forms csub(csub(xs[n], pil), mean) again where it needs it,
+// and without detrend nothing is read here.  Without detrend pil = mean = 0.  Every thread of the workgroup calls it.
+template <int N, int T, bool KEEP>
+__device__ __forceinline__ void mtm_segment_entry(const float2 *__restrict__ xs, int nperseg, bool detrend, float2 *red, int tid,
+                                                  float2 (&v)[KEEP ? N / T : 1], float2 &pil, float2 &mean) {
+    constexpr int NQ = N / T;
+    pil = mean = make_float2(0.f, 0.f);
+    if (detrend) pil = mtm_pilot(xs, nperseg, red, tid);
+    if (!KEEP && !detrend) return;
+    float2 sum = make_float2(0.f, 0.f);
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int n = tid + q * T;
+        const float2 r = (n < nperseg) ? csub(xs[n], pil) : make_float2(0.f, 0.f);
+        if constexpr (KEEP) v[q] = r;
+        sum = cadd(sum, r);
+    }
+    if (detrend) {
+        const float2 tot = mtm_block_sum<T>(sum, red, tid);
+        const float inv = 1.0f / (float)nperseg;
+        mean = make_float2(tot.x * inv, tot.y * inv);
+    }
+    if constexpr (KEEP) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int n = tid + q * T;
+            v[q] = (n < nperseg) ? csub(v[q], mean) : make_float2(0.f, 0.f);
+        }
+    }
 }
 
 constexpr bool mtm_keep(int n) { return n < 8192; }      // mtm.hip's header: KEEP

@@ -416,4 +416,32 @@ int mtm_ftest_blocks_per_cu(int nfft);
 hipError_t launch_mtm_ftest(int nfft, const MtmFtestArgs &a, hipStream_t s);
 hipError_t launch_ftest_finalize(const FtestFinalizeArgs &a, int nstreams, hipStream_t s);
 
+// ---- welchsk.hip: spectral kurtosis of a Welch plan - per bin sum_m P_m and sum_m P_m^2, P_m = g |FFT((x_m - mean) w)|^2 ---
+struct WelchSkArgs {
+    const float2 *x;        // device IQ, stream 0
+    const float *win;       // the plan's window, nfft floats (zero-extended behind nperseg)
+    const float2 *tw;       // W_nfft^k, nfft entries
+    float *partial;         // [nstreams][wg_per_stream][2][nfft] S1, S2 of each workgroup's run, natural bin order
+    long long nseg;         // segments per stream
+    size_t stream_stride;   // samples between streams
+    int nperseg;
+    int step;
+    int detrend;            // != 0: each segment's own mean comes off (pilot + residual)
+    int wg_per_stream;      // workgroups of a stream: each walks a contiguous run of the nseg segments
+    int nstreams;
+    float g;                // 1 / sum w^2
+};
+struct SkFinalizeArgs {
+    const float *partial;   // [nstreams][W][2][nfft], natural bin order
+    float *sk_out;          // [nstreams][nout]
+    float *psd_out;         // or nullptr
+    double m;               // the segment count M
+    double mp1_over_mm1;    // (M + 1) / (M - 1)
+    double psd_scale;       // scale / (g M), g as the kernel's float
+    int W, nfft, fftshift, trim, db, nout;
+};
+int welch_sk_blocks_per_cu(int nfft);
+hipError_t launch_welch_sk(int nfft, const WelchSkArgs &a, hipStream_t s);
+hipError_t launch_sk_finalize(const SkFinalizeArgs &a, int nstreams, hipStream_t s);
+
 }  // namespace oth

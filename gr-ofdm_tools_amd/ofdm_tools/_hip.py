@@ -78,6 +78,8 @@ SIGNATURES = {
                                    C.c_int, _pp]),
     'oth_mtm_ftest_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _p, _u64p]),
     'oth_mtm_ftest': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _f, _u64p]),
+    'oth_welch_sk_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
+    'oth_welch_sk': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
     'oth_plan_set_tuning': (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int, C.c_int]),
     'oth_welch_exec': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _u64p]),
     'oth_welch_exec_async': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _u64p]),
@@ -509,6 +511,35 @@ class WelchPlan(object):
         n = C.c_uint64()
         self.ctx.check(self.ctx.lib.oth_welch_segments_dev(self.h, C.c_void_p(dptr), int(nsamples), C.c_void_p(rows_dptr),
                                                            int(capacity), C.byref(n)), 'oth_welch_segments_dev')
+        return n.value
+
+    def sk(self, x, return_psd=False, nsamples=None):
+        """Spectral kurtosis (oth_welch_sk) of one capture: per bin SK = (M + 1) / (M - 1) (M S2 / S1^2 - 1) over the M
+        segments' periodograms - 1 for Gaussian noise at any level, towards 0 for a steady line, well above 1 for a signal
+        present in under half of the segments.  x: host complex64 array, or a device pointer when nsamples is given.
+        -> SK (float32, out_len bins, the plan's fftshift and trim; never dB), or with return_psd (SK, PSD): the row exec()
+        gives for the same input.  Sets last_nseg (M).  Needs at least two segments and a mean-averaging Welch plan of a
+        power-of-two length 64 ... 16384 (HipError otherwise)."""
+        rows = [np.empty(self.out_len, np.float32) for _ in range(2 if return_psd else 1)]
+        n = C.c_uint64()
+        if nsamples is None:
+            x = _c64(x)
+            src, count, dev = x.ctypes.data_as(_p), len(x), 0
+        else:
+            src, count, dev = C.c_void_p(x), int(nsamples), 1
+        self.ctx.check(self.ctx.lib.oth_welch_sk(self.h, src, count, dev, _fptr(rows[0]), _fptr(rows[1]) if return_psd else None,
+                                                 C.byref(n)), 'oth_welch_sk')
+        self.last_nseg = n.value
+        return tuple(rows) if return_psd else rows[0]
+
+    def sk_dev(self, iq_dev, nsamples, nstreams, stride, sk_dev, psd_dev=None):
+        """Asynchronous: device in, device out - [nstreams][out_len] float32 at sk_dev and, where given, psd_dev.
+        -> segments per stream (also last_nseg)."""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_welch_sk_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
+                                                     C.c_void_p(sk_dev), C.c_void_p(psd_dev) if psd_dev else None, C.byref(n)),
+                       'oth_welch_sk_dev')
+        self.last_nseg = n.value
         return n.value
 
     def last_recipe(self):

@@ -310,6 +310,77 @@ def mtm_line_scan(vector, nFFT, Sf, fc=0.0, NW=4.0, K=None, p_false=None, ctx=No
     return F, axis, lines
 
 
+SK_SIZES = tuple(2 ** i for i in range(6, 15))      # the transform lengths WelchPlan.sk takes
+
+
+def sk_null_moments(M):
+    """Exact moments of the spectral kurtosis estimator over M independent segments of Gaussian noise (Nita & Gary): the
+    mean is 1; -> (mu2, beta1, beta2), the variance, the squared skewness and the kurtosis."""
+    M = float(M)
+    mu2 = 4.0 * M * M / ((M - 1.0) * (M + 2.0) * (M + 3.0))
+    beta1 = 4.0 * (M + 2.0) * (M + 3.0) * (5.0 * M - 7.0) ** 2 / ((M - 1.0) * (M + 4.0) ** 2 * (M + 5.0) ** 2)
+    beta2 = (3.0 * (M + 2.0) * (M + 3.0) * (M ** 3 + 98.0 * M * M - 185.0 * M + 78.0) /
+             ((M - 1.0) * (M + 4.0) * (M + 5.0) * (M + 6.0) * (M + 7.0)))
+    return mu2, beta1, beta2
+
+
+def sk_limits(M, p_false):
+    """(lower, upper): the values the spectral kurtosis of a noise-only bin (WelchPlan.sk over M segments) falls below,
+    respectively exceeds, with probability p_false each.  A Pearson type IV density fitted to the exact null moments of the
+    estimator (sk_null_moments), normalised numerically on [0, 1 + 60 sqrt(mu2)] - SK is never negative - and inverted on
+    that grid; no SciPy.  The moments call for type IV from M = 24 on, and a type III fit misses the lower tail by a factor
+    of 40 at M = 16: M < 32 is a ValueError.  The limits assume independent segments, that is no overlap; against a Monte
+    Carlo of the null the fit's rates lie within 0.6 ... 1.1 of p_false down to 1e-3, and below 1e-4 the tails are
+    extrapolated, not checked."""
+    if isinstance(M, bool) or int(M) != M:
+        raise ValueError('M must be an integer segment count, not %r' % (M,))
+    M = int(M)
+    if M < 32:
+        raise ValueError('sk_limits needs M >= 32 segments (the Pearson type IV fit of the null does not hold below), not %d' % M)
+    if not 0.0 < p_false < 1.0:
+        raise ValueError('need 0 < p_false < 1')
+    mu2, beta1, beta2 = sk_null_moments(M)
+    r = 6.0 * (beta2 - beta1 - 1.0) / (2.0 * beta2 - 3.0 * beta1 - 6.0)
+    m = 0.5 * (r + 2.0)
+    d = 16.0 * (r - 1.0) - beta1 * (r - 2.0) ** 2
+    nu = -r * (r - 2.0) * math.sqrt(beta1) / math.sqrt(d)
+    a = math.sqrt(mu2 * d) / 4.0
+    lam = 1.0 - (r - 2.0) * math.sqrt(beta1 * mu2) / 4.0
+    x = np.linspace(0.0, 1.0 + 60.0 * math.sqrt(mu2), (1 << 20) + 1)
+    t = (x - lam) / a
+    logpdf = -m * np.log1p(t * t) - nu * np.arctan(t)
+    pdf = np.exp(logpdf - np.max(logpdf))
+    cell = 0.5 * (pdf[1:] + pdf[:-1])                        # trapezoids (the grid step cancels in the ratios)
+    below = np.concatenate(([0.0], np.cumsum(cell)))           # mass in [0, x]
+    above = np.concatenate((np.cumsum(cell[::-1])[::-1], [0.0]))      # mass in [x, end], summed from the far tail
+    total = below[-1]
+    lower = float(np.interp(p_false * total, below, x))
+    upper = float(np.interp(p_false * total, above[::-1], x[::-1]))
+    return lower, upper
+
+
+def sk_scan(vector, nFFT, Sf, fc=0.0, p_false=None, ctx=None):
+    """What occupies each bin of one capture, by the spectral kurtosis of its nFFT-point periodograms (WelchPlan.sk; Hann
+    window, nperseg = nFFT, no overlap): noise-like - OFDM, the thermal floor - inside sk_limits(M, p_false), steady - a
+    carrier - below the lower limit, intermittent - a burst, a radar, a hopping interferer - above the upper one; none of
+    it depends on the noise floor.  p_false = 1e-3 per side by default.
+    -> (SK fftshifted, frequency axis, steady mask, intermittent mask).
+    The limits assume independent segments, that is no overlap - which is why the scan uses none.  Below p_false = 1e-4
+    the tails of the fitted null density are extrapolated, not checked.  Needs M = len(vector) // nFFT >= 32 segments and
+    nFFT a power of two from 64 to 16384 (ValueError otherwise, before anything runs)."""
+    if nFFT not in SK_SIZES:
+        raise ValueError('sk_scan needs nFFT a power of two from 64 to 16384, not %r' % (nFFT,))
+    p_false = 1e-3 if p_false is None else p_false
+    lower, upper = sk_limits(len(vector) // int(nFFT), p_false)
+    ctx = ctx or _hip.default_context()
+    key = ('sk', nFFT, float(Sf))
+    plan = ctx.cached_plan(key, lambda: ctx.welch_plan(nFFT, nperseg=nFFT, noverlap=0, window=windows.get_window('hann', nFFT),
+                                                       fs=float(Sf), fftshift=True))
+    sk = plan.sk(vector)
+    axis = np.fft.fftshift(np.fft.fftfreq(nFFT, 1.0 / Sf)) + fc
+    return sk, axis, sk < lower, sk > upper
+
+
 class SpectrumScan(object):
     """The legacy sensor's scan (reference: ofdm_cr_tools.py:471-537; its matplotlib branch is not carried over), split
     where the GPU works: the constructor enqueues the PSD of the chosen method ('welch': flat-top Welch, 'fft': one

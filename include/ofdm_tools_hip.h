@@ -319,6 +319,30 @@ int oth_mtm_ftest_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int n
 int oth_mtm_ftest(oth_plan *plan, const void *iq, size_t nsamples, int src_is_device, float *f_out, float *line_out,
                   float *resid_out, uint64_t *nseg_out);
 
+/* oth_welch_sk_dev / oth_welch_sk (additions inside ABI 6; probe by the symbols): the spectral kurtosis estimator of Nita &
+ * Gary on a plan of oth_welch_plan - per bin, "is what sits here noise-like, steady or intermittent", whatever its level.
+ * With M the plan's segment count for the input, g = 1 / sum_n w[n]^2 (formed in double when the plan is created) and per
+ * segment m and bin j  P_m = g |FFT_nfft((x_m - mean_m) w)[j]|^2  (segmentation, window, zero padding and the per-segment
+ * mean removal - only on a detrending plan - as the plan's exec forms):
+ *   S1 = sum_m P_m,   S2 = sum_m P_m^2,   SK = (M + 1) / (M - 1) (M S2 / S1^2 - 1)
+ * SK is 1 in expectation for Gaussian noise at any level, goes towards 0 for a steady line and lies well above 1 for a signal
+ * present in under half of the segments.  The SK row takes the plan's fftshift and trim and is never in dB.  psd_out (may be
+ * NULL): the row oth_welch_exec_dev gives for the same plan and input - S1 scale / (g M), then fftshift, trim and dB.
+ * Layout [nstreams][out_len] each.  A bin with S1 = 0 reads SK = 0 (silence, a constant under detrend, the DC bin of a
+ * noiseless detrended input): finite input never gives NaN; non-finite input may.
+ * One averaging launch per call (csrc/welchsk.hip: a workgroup takes whole segments and carries both sums), then a small
+ * finalize launch that adds the workgroups' rows in double in a fixed order: bit-identical run to run.  _dev: device in,
+ * device out, asynchronous, nstreams as oth_welch_exec_dev (at most 65535).  oth_welch_sk: one stream, host or device
+ * source, host outputs, blocking.
+ * Refused, the reason in oth_last_error(), before anything is staged, and the plan goes on working: OTH_ERR_UNSUPPORTED on a
+ * multitaper plan, on a plan set to OTH_AVERAGE_MEDIAN, and for a transform length that is not a power of two from 64 to
+ * 16384; OTH_ERR_INVALID for fewer than two segments (M - 1 divides), a NULL input or SK pointer, nstreams < 1,
+ * stream_stride < nsamples, input shorter than nperseg. */
+int oth_welch_sk_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride,
+                     float *sk_out_dev, float *psd_out_dev, uint64_t *nseg_out);
+int oth_welch_sk(oth_plan *plan, const void *iq, size_t nsamples, int src_is_device, float *sk_out, float *psd_out,
+                 uint64_t *nseg_out);
+
 /* one-shot: nsamples complex64 -> psd_out[nfft - 2*trim] (host).  Blocking: returns when the PSD is in psd_out.  The
  * last launch writes the row and a completion word into pinned host memory and the call polls that word (no interrupt
  * wake-up; after 20 ms it falls back to a stream synchronisation, which also reports a failed launch;
