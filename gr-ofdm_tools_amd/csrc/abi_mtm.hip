@@ -139,6 +139,24 @@ int mtm_csd_gate(oth_plan *p, const char *what) {
     return refuse_mtm(p, what, "the taper loop holds one channel");
 }
 
+MtmArgs mtm_args(const oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t stride, int W) {
+    MtmArgs a{};
+    a.x = x;
+    a.tapers = p->d_tapers.get();
+    a.coef = p->d_coef.get();
+    a.tw = p->d_tw;
+    a.partial = p->d_partial.get();
+    a.nseg = nseg;
+    a.stream_stride = stride;
+    a.nperseg = p->nperseg;
+    a.step = p->step;
+    a.detrend = p->detrend != OTH_DETREND_NONE;
+    a.ntapers = p->ntapers;
+    a.wg_per_stream = W;
+    a.nstreams = nstreams;
+    return a;
+}
+
 int mtm_run(oth_plan *p, const float2 *x, const float2 *y, long long nseg, int nstreams, size_t stride, int *W_out) {
     oth_ctx *c = p->ctx;
     const int N = p->nfft, K = p->ntapers;
@@ -161,19 +179,7 @@ int mtm_run(oth_plan *p, const float2 *x, const float2 *y, long long nseg, int n
     if (rc) return rc;
     MtmCsdArgs g{};
     MtmArgs &a = g.m;
-    a.x = x;
-    a.tapers = p->d_tapers.get();
-    a.coef = p->d_coef.get();
-    a.tw = p->d_tw;
-    a.partial = p->d_partial.get();
-    a.nseg = nseg;
-    a.stream_stride = stride;
-    a.nperseg = p->nperseg;
-    a.step = p->step;
-    a.detrend = p->detrend != OTH_DETREND_NONE;
-    a.ntapers = K;
-    a.wg_per_stream = W;
-    a.nstreams = nstreams;
+    a = mtm_args(p, x, nseg, nstreams, stride, W);
     g.y = y;
     g.ws = ws_points ? p->d_mtm_ws.get() : nullptr;
     {
@@ -211,20 +217,7 @@ int mtm_ftest_run(oth_plan *p, const float2 *x, size_t nsamples, int nstreams, s
     if (!rc && ws_floats) rc = p->d_ftest_ws.ensure(c, sizeof(float) * (size_t)nstreams * W * ws_floats);
     if (rc) return rc;
     MtmFtestArgs g{};
-    MtmArgs &a = g.m;
-    a.x = x;
-    a.tapers = p->d_tapers.get();
-    a.coef = p->d_coef.get();
-    a.tw = p->d_tw;
-    a.partial = p->d_partial.get();
-    a.nseg = nseg;
-    a.stream_stride = stride;
-    a.nperseg = p->nperseg;
-    a.step = p->step;
-    a.detrend = p->detrend != OTH_DETREND_NONE;
-    a.ntapers = K;
-    a.wg_per_stream = W;
-    a.nstreams = nstreams;
+    g.m = mtm_args(p, x, nseg, nstreams, stride, W);
     g.u = p->d_mtm_u.get();
     g.inv_s = (float)(1.0 / p->mtm_s);
     g.ws = ws_floats ? p->d_ftest_ws.get() : nullptr;
@@ -304,6 +297,7 @@ int mtm_plan_create(oth_ctx *c, int nfft, int nperseg, int noverlap, int ntapers
     }
     p->ntapers = ntapers;
     p->mtm_csd = two_channel;
+    for (int k = 1; weights && k < ntapers; ++k) p->mtm_uniform = p->mtm_uniform && weights[k] == weights[0];
     p->mtm_s = std::isfinite(usq) ? usq : 0.0;
     switch (scaling) {
         case OTH_SCALE_DENSITY: p->scale = 1.0 / fs; break;      // the tapers' energies are in c_k

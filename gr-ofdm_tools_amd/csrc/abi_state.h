@@ -136,6 +136,9 @@ struct oth_plan {
     DevBuf<float> d_mtm_u;             // [ntapers] U_k = sum_n v_k[n] (summed in double)
     double mtm_s = 0.0;                // sum_k U_k^2 of the uploaded values
     DevBuf<float> d_ftest_ws;          // mtmftest.hip's per-workgroup sy / p rows (MtmFtestArgs.ws; 16384 points only)
+    // the jackknife (oth_mtm_jackknife*, oth_mtm_csd_jackknife*: abi_jack.hip / mtmjack.hip)
+    bool mtm_uniform = true;           // every weight a_k is the same: the (segment, taper) items are exchangeable
+    DevBuf<float> d_jack_tot;          // totals of the first pass: [nstreams][nfft], or [4][nfft] + the natural-order Cxy row
     // spectral kurtosis (oth_welch_sk*, abi_sk.hip / welchsk.hip): Welch plans only
     double sk_g = 1.0;                 // 1 / sum w^2 (1 for an all-zero window): the periodograms' scale inside the kernel
 };
@@ -374,6 +377,8 @@ int plan_begin(oth_ctx *c, int nfft, int nperseg, int noverlap, int detrend, int
 // in natural order (finalize layout 0) into p->d_partial
 //   y != nullptr (plans of oth_mtm_csd_plan only): the two-channel launch, four rows per workgroup
 int mtm_run(oth_plan *p, const float2 *x, const float2 *y, long long nseg, int nstreams, size_t stride, int *W_out);
+// the launch description the taper-loop kernels share, from the plan's tables and sizes (partial: p->d_partial as it is now)
+MtmArgs mtm_args(const oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t stride, int W);
 // OTH_ERR_UNSUPPORTED with the reason: `what` is not available on a multitaper plan
 int refuse_mtm(oth_plan *p, const char *what, const char *why);
 // the oth_csd_* entry points: OTH_OK on a plan that holds two channels (every plan but oth_mtm_plan's), else refuse_mtm

@@ -1,6 +1,7 @@
 // What the taper-loop kernels (mtm.hip: one channel, mtmcsd.hip: two, mtmftest.hip: the F-test, welchsk.hip: spectral
-// kurtosis with the plan's window as the one taper) share: the fixed-order sums behind a segment's pilot and residual mean,
-// the segment entry built on them, the rule for keeping a segment's samples in registers, and the list of sizes.
+// kurtosis with the plan's window as the one taper, mtmjack.hip: the jackknife's second pass) share: the fixed-order sums
+// behind a segment's pilot and residual mean, the segment entry built on them, the taper product, the rule for keeping a
+// segment's samples in registers, and the list of sizes.
 #pragma once
 #include "fft_lds.hip.h"
 
@@ -71,6 +72,24 @@ __device__ __forceinline__ void mtm_segment_entry(const float2 *__restrict__ xs,
             const int n = tid + q * T;
             v[q] = (n < nperseg) ? csub(v[q], mean) : make_float2(0.f, 0.f);
         }
+    }
+}
+
+// (x - pilot - mean) v_k of one channel into buf, after mtm_segment_entry; no barrier
+template <int N, int T, bool KEEP>
+__device__ __forceinline__ void mtm_taper_product(const float2 *__restrict__ xs, const float *__restrict__ w, int nperseg, int tid,
+                                                  float2 pil, float2 mean, const float2 (&v)[KEEP ? N / T : 1], float2 *buf) {
+#pragma unroll
+    for (int q = 0; q < N / T; ++q) {
+        const int n = tid + q * T;
+        float2 r;
+        if constexpr (KEEP) {
+            r = v[q];
+        } else {
+            r = (n < nperseg) ? csub(csub(xs[n], pil), mean) : make_float2(0.f, 0.f);      // the same arithmetic as KEEP
+        }
+        const float wn = w[n];
+        buf[n] = make_float2(r.x * wn, r.y * wn);
     }
 }
 

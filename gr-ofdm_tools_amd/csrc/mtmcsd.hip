@@ -74,24 +74,6 @@ __device__ __forceinline__ void mtmcsd_enter(const float2 *__restrict__ xs, int 
     }
 }
 
-// (x - pilot - mean) v_k of one channel into buf; no barrier
-template <int N, int T, bool KEEP>
-__device__ __forceinline__ void mtmcsd_taper(const float2 *__restrict__ xs, const float *__restrict__ w, int nperseg, int tid,
-                                             float2 pil, float2 mean, const float2 (&v)[KEEP ? N / T : 1], float2 *buf) {
-#pragma unroll
-    for (int q = 0; q < N / T; ++q) {
-        const int n = tid + q * T;
-        float2 r;
-        if constexpr (KEEP) {
-            r = v[q];
-        } else {
-            r = (n < nperseg) ? csub(csub(xs[n], pil), mean) : make_float2(0.f, 0.f);      // the same arithmetic as KEEP
-        }
-        const float wn = w[n];
-        buf[n] = make_float2(r.x * wn, r.y * wn);
-    }
-}
-
 template <int N, int T, bool KEEP, bool TWO, bool ACCREG> __global__ __launch_bounds__(T) void mtmcsd_kernel(MtmCsdArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const MtmArgs &p = a.m;
@@ -133,9 +115,9 @@ template <int N, int T, bool KEEP, bool TWO, bool ACCREG> __global__ __launch_bo
             mtmcsd_enter<N, T, KEEP>(ys, p.nperseg, p.detrend, redy, tid, pily, meany, vy);
         }
         const float *__restrict__ w = p.tapers + (size_t)k * N;      // zero-extended to N
-        mtmcsd_taper<N, T, KEEP>(xs, w, p.nperseg, tid, pilx, meanx, vx, bufx);
+        mtm_taper_product<N, T, KEEP>(xs, w, p.nperseg, tid, pilx, meanx, vx, bufx);
         if constexpr (TWO) {
-            mtmcsd_taper<N, T, KEEP>(ys, w, p.nperseg, tid, pily, meany, vy, bufy);
+            mtm_taper_product<N, T, KEEP>(ys, w, p.nperseg, tid, pily, meany, vy, bufy);
             __syncthreads();
             fft_lds<N, T>(bufx, p.tw, tid);
             asm volatile("" : "+v"(tid));      // (nor shared between the two transforms)
@@ -146,7 +128,7 @@ template <int N, int T, bool KEEP, bool TWO, bool ACCREG> __global__ __launch_bo
 #pragma unroll
             for (int q = 0; q < NQ; ++q) ws[tid + q * T] = bufx[tid + q * T];      // this thread's bins, read back below
             __syncthreads();
-            mtmcsd_taper<N, T, KEEP>(ys, w, p.nperseg, tid, pily, meany, vy, bufy);
+            mtm_taper_product<N, T, KEEP>(ys, w, p.nperseg, tid, pily, meany, vy, bufy);
             __syncthreads();
             asm volatile("" : "+v"(tid));
             fft_lds<N, T>(bufy, p.tw, tid);

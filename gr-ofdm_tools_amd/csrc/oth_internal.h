@@ -416,6 +416,32 @@ int mtm_ftest_blocks_per_cu(int nfft);
 hipError_t launch_mtm_ftest(int nfft, const MtmFtestArgs &a, hipStream_t s);
 hipError_t launch_ftest_finalize(const FtestFinalizeArgs &a, int nstreams, hipStream_t s);
 
+// ---- mtmjack.hip: the jackknife over the (segment, taper) items, second pass (the first is the plan's own averaging) ------
+struct MtmJackArgs {
+    MtmArgs m;              // as mtm.hip's; partial: [nstreams][wg_per_stream][2][nfft] sum l, sum l^2
+    const float *totals;    // [nstreams][nfft] S = sum_i p_i of the first pass, natural bin order
+};
+struct MtmCsdJackArgs {
+    MtmCsdArgs c;           // as mtmcsd.hip's; partial: [nstreams][wg_per_stream][6][nfft] sum lx, lx^2, ly, ly^2, d, d^2
+    const float *totals;    // [nstreams][4][nfft] Sxx, Syy, Sxy (re, im interleaved) of the first pass, natural bin order
+};
+struct JackFinalizeArgs {
+    const float *partial;   // [nstreams][W][2 npairs][nfft], natural bin order
+    float *out[3];          // [nstreams][nout] root of the jackknife variance of pair 0 ... npairs - 1, or nullptr
+    const float *cxy_nat;   // [nstreams][nfft] Cxy of the first pass in natural order (two channels), for cxy_out
+    float *cxy_out;         // or nullptr
+    double m;               // the item count M
+    double mm1_over_m;      // (M - 1) / M
+    int npairs;             // 1 (lnsd) or 3 (lnsd x, lnsd y, zsd)
+    int W, nfft, fftshift, trim, nout;
+};
+size_t mtmcsd_jack_ws_points(int nfft);      // 0: the build keeps both spectra in LDS
+int mtm_jack_blocks_per_cu(int nfft);
+int mtmcsd_jack_blocks_per_cu(int nfft);
+hipError_t launch_mtm_jack(int nfft, const MtmJackArgs &a, hipStream_t s);
+hipError_t launch_mtmcsd_jack(int nfft, const MtmCsdJackArgs &a, hipStream_t s);
+hipError_t launch_jack_finalize(const JackFinalizeArgs &a, int nstreams, hipStream_t s);
+
 // ---- welchsk.hip: spectral kurtosis of a Welch plan - per bin sum_m P_m and sum_m P_m^2, P_m = g |FFT((x_m - mean) w)|^2 ---
 struct WelchSkArgs {
     const float2 *x;        // device IQ, stream 0

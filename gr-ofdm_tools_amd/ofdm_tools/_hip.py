@@ -80,6 +80,10 @@ SIGNATURES = {
     'oth_mtm_ftest': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _f, _u64p]),
     'oth_welch_sk_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
     'oth_welch_sk': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
+    'oth_mtm_jackknife_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
+    'oth_mtm_jackknife': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
+    'oth_mtm_csd_jackknife_dev': (C.c_int, [_p, _p, _p, C.c_size_t, _p, _p, _p, _p, _u64p]),
+    'oth_mtm_csd_jackknife': (C.c_int, [_p, _p, _p, C.c_size_t, C.c_int, _f, _f, _f, _f, _u64p]),
     'oth_plan_set_tuning': (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int, C.c_int]),
     'oth_welch_exec': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _u64p]),
     'oth_welch_exec_async': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _u64p]),
@@ -806,6 +810,34 @@ class MtmPlan(WelchPlan):
         self.last_nseg = n.value
         return n.value
 
+    def jackknife(self, x, return_psd=False, nsamples=None):
+        """Jackknife (oth_mtm_jackknife) of one capture over its M = ntapers * nseg (segment, taper) items: per bin the
+        standard deviation of ln PSD, in natural-log units - the interval at Student-t quantile q (M - 1 degrees of freedom)
+        is psd * exp(-+ q * lnsd).  x: host complex64 array, or a device pointer when nsamples is given.  -> lnsd (float32,
+        out_len bins, the plan's fftshift and trim; never dB, never scaled), or with return_psd (lnsd, PSD): the row exec()
+        gives for the same input.  Sets last_nseg.  Needs equal weights and M >= 2 (HipError otherwise)."""
+        rows = [np.empty(self.out_len, np.float32) for _ in range(2 if return_psd else 1)]
+        n = C.c_uint64()
+        if nsamples is None:
+            x = _c64(x)
+            src, count, dev = x.ctypes.data_as(_p), len(x), 0
+        else:
+            src, count, dev = C.c_void_p(x), int(nsamples), 1
+        self.ctx.check(self.ctx.lib.oth_mtm_jackknife(self.h, src, count, dev, _fptr(rows[0]), _fptr(rows[1]) if return_psd else None,
+                                                      C.byref(n)), 'oth_mtm_jackknife')
+        self.last_nseg = n.value
+        return tuple(rows) if return_psd else rows[0]
+
+    def jackknife_dev(self, iq_dev, nsamples, nstreams, stride, lnsd_dev, psd_dev=None):
+        """Asynchronous: device in, device out - [nstreams][out_len] float32 at lnsd_dev and, where given, psd_dev.
+        -> segments per stream (also last_nseg)."""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_mtm_jackknife_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
+                                                          C.c_void_p(lnsd_dev), C.c_void_p(psd_dev) if psd_dev else None,
+                                                          C.byref(n)), 'oth_mtm_jackknife_dev')
+        self.last_nseg = n.value
+        return n.value
+
     @property
     def dof(self):
         """Degrees of freedom (2 nseg, 2 nseg (K - 1)) of the F distribution the last call's bins follow without a line."""
@@ -818,6 +850,37 @@ class MtmCsdPlan(MtmPlan):
     csd_scale_dev - run the two-channel taper loop (oth_mtm_csd_plan) instead of raising."""
 
     _CONSTRUCTOR = 'oth_mtm_csd_plan'
+
+    def csd_jackknife(self, x, y, nsamples=None):
+        """Jackknife (oth_mtm_csd_jackknife) of a pair of captures over their M = ntapers * nseg items -> (cxy, zsd, lnsd_x,
+        lnsd_y), float32 rows of out_len bins with the plan's fftshift and trim: the coherence csd() gives, the standard
+        deviation of z = atanh(sqrt(cxy)) - the interval at Student-t quantile q (M - 1 degrees of freedom) is
+        tanh(max(0, z -+ q * zsd)) ** 2 - and of each channel's ln PSD.  x, y: host complex64 arrays, or device pointers
+        when nsamples is given.  Sets last_nseg.  Needs equal weights and M >= 3 (HipError otherwise)."""
+        rows = [np.empty(self.out_len, np.float32) for _ in range(4)]
+        n = C.c_uint64()
+        if nsamples is None:
+            x, y = _c64(x), _c64(y)
+            if len(x) != len(y):
+                raise ValueError('x and y must have the same length')
+            sx, sy, count, dev = x.ctypes.data_as(_p), y.ctypes.data_as(_p), len(x), 0
+        else:
+            sx, sy, count, dev = C.c_void_p(x), C.c_void_p(y), int(nsamples), 1
+        self.ctx.check(self.ctx.lib.oth_mtm_csd_jackknife(self.h, sx, sy, count, dev, *([_fptr(r) for r in rows] + [C.byref(n)])),
+                       'oth_mtm_csd_jackknife')
+        self.last_nseg = n.value
+        return tuple(rows)
+
+    def csd_jackknife_dev(self, dx, dy, nsamples, zsd_dev, cxy_dev=None, lnsdx_dev=None, lnsdy_dev=None):
+        """Asynchronous: device in, device out - out_len float32 at zsd_dev and, where given, cxy_dev, lnsdx_dev and
+        lnsdy_dev.  -> segments (also last_nseg)."""
+        n = C.c_uint64()
+        vp = lambda v: C.c_void_p(v) if v else None      # noqa: E731
+        self.ctx.check(self.ctx.lib.oth_mtm_csd_jackknife_dev(self.h, C.c_void_p(dx), C.c_void_p(dy), int(nsamples), vp(cxy_dev),
+                                                              C.c_void_p(zsd_dev), vp(lnsdx_dev), vp(lnsdy_dev), C.byref(n)),
+                       'oth_mtm_csd_jackknife_dev')
+        self.last_nseg = n.value
+        return n.value
 
 
 class Chain(object):

@@ -14,6 +14,7 @@ two-channel multitaper estimate instead, whose Pxx / Pyy are the detector's MTM-
 import numpy as np
 
 from . import _hip, windows
+from .ofdm_cr_tools import coherence_bounds, student_t_quantile
 from .gr_compat import sync_block, to_msg
 
 
@@ -93,11 +94,19 @@ class coherence_estimator(sync_block):
     method='mtm': the two-channel multitaper estimate (Context.mtm_csd_plan: K Slepian tapers of time-half-bandwidth NW,
     K=None meaning int(2 NW) - 1, nperseg = N, no overlap) - the estimator for SHORT captures, where a Welch coherence
     of few segments is biased high (one segment: identically 1).  ``block_len`` defaults to N, one segment; pxx and pyy
-    are then the detector's MTM-L and MTM-R inputs."""
+    are then the detector's MTM-L and MTM-R inputs.
+    confidence (method='mtm' only; None: off): every block also sets ``cxy_sd`` - the jackknife standard deviation of
+    z = atanh(sqrt(cxy)) over the block's (segment, taper) items (MtmCsdPlan.csd_jackknife) - and ``cxy_lo``, the one-sided
+    lower bound of the coherence at that confidence, tanh(max(0, z - q cxy_sd))^2: what a detector should compare with its
+    threshold on a short capture.  The published message and the other attributes do not change.  Cost: csd() and
+    csd_jackknife() both run per block, and the jackknife's first pass repeats csd()'s averaging launch - three passes of the
+    taper loop over the block where the point estimate alone takes one."""
 
-    def __init__(self, N, sample_rate, block_len=None, ctx=None, method='welch', NW=4.0, K=None):
+    def __init__(self, N, sample_rate, block_len=None, ctx=None, method='welch', NW=4.0, K=None, confidence=None):
         if method not in ('welch', 'mtm'):
             raise ValueError("method must be 'welch' or 'mtm', not %r" % (method,))
+        if confidence is not None and (method != 'mtm' or not 0.0 < confidence < 1.0):
+            raise ValueError("confidence needs method='mtm' and a value in (0, 1)")
         if method == 'mtm' and block_len is not None and int(block_len) < N:
             raise ValueError('block_len=%d is shorter than one segment of N=%d samples' % (int(block_len), N))
         sync_block.__init__(self, 'coherence_estimator', [np.complex64, np.complex64], None)
@@ -114,6 +123,8 @@ class coherence_estimator(sync_block):
         self._x = np.empty(0, np.complex64)
         self._y = np.empty(0, np.complex64)
         self.pxx = self.pyy = self.pxy = self.cxy = None
+        self.confidence = confidence
+        self.cxy_sd = self.cxy_lo = None
         self.message_port_register_out('coherence')
 
     def work(self, input_items, output_items):
@@ -123,6 +134,10 @@ class coherence_estimator(sync_block):
         while len(self._x) >= self.block_len:
             self.pxx, self.pyy, self.pxy, self.cxy = self._plan.csd(self._x[:self.block_len],
                                                                     self._y[:self.block_len])
+            if self.confidence is not None:
+                cxy, self.cxy_sd = self._plan.csd_jackknife(self._x[:self.block_len], self._y[:self.block_len])[:2]
+                q = student_t_quantile(1.0 - self.confidence, self._plan.last_nseg * self._plan.ntapers - 1)
+                self.cxy_lo = coherence_bounds(cxy, self.cxy_sd, q, q)[0].astype(np.float32)
             self._x = self._x[self.block_len:]
             self._y = self._y[self.block_len:]
             self.message_port_pub('coherence', to_msg('coherence', self.cxy))      # (key . f32vector) pair

@@ -289,6 +289,116 @@ def ftest_threshold(p_false, nseg, K):
     return math.exp(0.5 * (lo + hi))
 
 
+def _betacf(a, b, x):
+    """The continued fraction of the incomplete beta function (modified Lentz), for x < (a + 1) / (a + b + 2)."""
+    tiny = 1e-300
+    c, d = 1.0, 1.0 - (a + b) * x / (a + 1.0)
+    d = 1.0 / (d if abs(d) > tiny else tiny)
+    h = d
+    for m in range(1, 100000):
+        m2 = 2 * m
+        for num in (m * (b - m) * x / ((a + m2 - 1.0) * (a + m2)), -(a + m) * (a + b + m) * x / ((a + m2) * (a + m2 + 1.0))):
+            d = 1.0 + num * d
+            d = 1.0 / (d if abs(d) > tiny else tiny)
+            c = 1.0 + num / c
+            c = c if abs(c) > tiny else tiny
+            h *= d * c
+        if abs(d * c - 1.0) < 1e-16:
+            break
+    return h
+
+
+def _betainc(a, b, x, xc):
+    """Regularised incomplete beta I_x(a, b); xc = 1 - x, handed in so that neither end loses digits."""
+    if x <= 0.0:
+        return 0.0
+    if xc <= 0.0:
+        return 1.0
+    front = math.exp(math.lgamma(a + b) - math.lgamma(a) - math.lgamma(b) + a * math.log(x) + b * math.log(xc))
+    if x < (a + 1.0) / (a + b + 2.0):
+        return front * _betacf(a, b, x) / a
+    return 1.0 - front * _betacf(b, a, xc) / b
+
+
+def _student_t_sf(t, dof):
+    """P(T > t), t >= 0, for Student's t with dof degrees of freedom: I_x(dof / 2, 1 / 2) / 2 at x = dof / (dof + t^2)."""
+    t2 = t * t
+    return 0.5 * _betainc(0.5 * dof, 0.5, dof / (dof + t2), t2 / (dof + t2))
+
+
+def student_t_quantile(p, dof):
+    """The value Student's t with dof degrees of freedom exceeds with probability p (the upper-p quantile,
+    scipy.stats.t.isf): the survival function through the regularised incomplete beta function (continued fraction),
+    inverted by bisection on log t.  The jackknife intervals take it at M - 1 degrees of freedom."""
+    p, dof = float(p), float(dof)
+    if not 0.0 < p < 1.0 or not dof >= 1.0:
+        raise ValueError('need 0 < p < 1 and dof >= 1')
+    if p == 0.5:
+        return 0.0
+    if p > 0.5:
+        return -student_t_quantile(1.0 - p, dof)
+    lo, hi = -100.0, 100.0      # log t: the survival function falls from 1 / 2 to 0 between
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if not lo < mid < hi:
+            break
+        if _student_t_sf(math.exp(mid), dof) > p:
+            lo = mid
+        else:
+            hi = mid
+    return math.exp(0.5 * (lo + hi))
+
+
+def mtm_psd_interval(vector, nFFT, Sf, fc=0.0, NW=4.0, K=None, confidence=0.95, ctx=None):
+    """mtm_plot_dB with a confidence band: the multitaper PSD of one capture on the plan of the other mtm_* helpers and its
+    jackknife interval over the M = K nseg (segment, taper) items (MtmPlan.jackknife) - psd exp(-+ q lnsd) with q the
+    Student-t quantile at (1 - confidence) / 2 and M - 1 degrees of freedom.  -> (axis, lo_dB, psd_dB, hi_dB), arrays."""
+    if not 0.0 < confidence < 1.0:
+        raise ValueError('confidence must lie in (0, 1)')
+    ctx = ctx or _hip.default_context()
+    plan = _mtm_plan(ctx, nFFT, Sf, len(vector), NW, K)
+    lnsd, psd = plan.jackknife(vector, return_psd=True)
+    M = plan.last_nseg * plan.ntapers
+    q = student_t_quantile(0.5 * (1.0 - confidence), M - 1)
+    axis = np.fft.fftshift(np.fft.fftfreq(nFFT, 1.0 / Sf)) + fc
+    psd_dB = 10.0 * np.log10(psd.astype(np.float64) + 1e-20)
+    half = (10.0 / math.log(10.0)) * q * lnsd.astype(np.float64)
+    return axis, psd_dB - half, psd_dB, psd_dB + half
+
+
+def _mtm_csd_plan(ctx, nfft, Sf, npts=None, NW=4.0, K=None):
+    """_mtm_plan's shape with the two-channel calls open."""
+    nperseg = nfft if npts is None else min(int(nfft), int(npts))
+    K = int(2 * NW) - 1 if K is None else int(K)
+    key = ('mtmcsd', 'exec', nfft, nperseg, float(NW), K, float(Sf))
+    return ctx.cached_plan(key, lambda: ctx.mtm_csd_plan(nfft, nperseg=nperseg, noverlap=0, nw=float(NW), ntapers=K,
+                                                         fs=float(Sf), fftshift=True))
+
+
+def coherence_bounds(cxy, zsd, q_lo, q_hi):
+    """tanh(max(0, z - q_lo zsd))^2 and tanh(z + q_hi zsd)^2 at z = atanh(sqrt(cxy)), clamped as the library clamps it."""
+    z = np.arctanh(np.minimum(np.sqrt(np.asarray(cxy, np.float64)), 1.0 - 2.0 ** -24))
+    zsd, c = np.asarray(zsd, np.float64), np.asarray(cxy, np.float64)
+    # (the estimate itself bounds both: tanh(atanh(s))^2 is s^2 to rounding only, and the clamp sits below a coherence of 1)
+    return np.minimum(np.tanh(np.maximum(0.0, z - q_lo * zsd)) ** 2, c), np.maximum(np.tanh(z + q_hi * zsd) ** 2, c)
+
+
+def mtm_coherence_interval(x, y, nFFT, Sf, NW=4.0, K=None, confidence=0.95, ctx=None):
+    """The multitaper magnitude-squared coherence of a capture pair and its jackknife interval (MtmCsdPlan.csd_jackknife):
+    tanh(max(0, z -+ q zsd))^2 around z = atanh(sqrt(cxy)), q the Student-t quantile at (1 - confidence) / 2 and M - 1
+    degrees of freedom.  A true coherence of 0 is not covered at the nominal rate: the estimate is biased upwards there.
+    -> (axis, cxy_lo, cxy, cxy_hi), fftshifted arrays."""
+    if not 0.0 < confidence < 1.0:
+        raise ValueError('confidence must lie in (0, 1)')
+    ctx = ctx or _hip.default_context()
+    plan = _mtm_csd_plan(ctx, nFFT, Sf, min(len(x), len(y)), NW, K)
+    cxy, zsd, _, _ = plan.csd_jackknife(x, y)
+    q = student_t_quantile(0.5 * (1.0 - confidence), plan.last_nseg * plan.ntapers - 1)
+    lo, hi = coherence_bounds(cxy, zsd, q, q)
+    axis = np.fft.fftshift(np.fft.fftfreq(nFFT, 1.0 / Sf))
+    return axis, lo, cxy.astype(np.float64), hi
+
+
 def mtm_line_scan(vector, nFFT, Sf, fc=0.0, NW=4.0, K=None, p_false=None, ctx=None):
     """Coherent lines (pilots, carriers, narrowband interferers) of one capture by Thomson's harmonic F-test on the plan of
     the other mtm_* helpers: nperseg = min(nFFT, len), one pass without overlap.  A line is a bin whose F exceeds

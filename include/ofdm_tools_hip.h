@@ -343,6 +343,47 @@ int oth_welch_sk_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int ns
 int oth_welch_sk(oth_plan *plan, const void *iq, size_t nsamples, int src_is_device, float *sk_out, float *psd_out,
                  uint64_t *nseg_out);
 
+/* oth_mtm_jackknife_dev / oth_mtm_jackknife, oth_mtm_csd_jackknife_dev / oth_mtm_csd_jackknife (additions inside ABI 6; probe
+ * by the symbols): Thomson & Chave's jackknife over the M = K nseg (segment, taper) items of a multitaper estimate - per bin,
+ * "how far can this PSD / this coherence be trusted", with no assumption on the distribution.  Segmentation, per-segment mean
+ * removal, zero padding and tapers as the plan's exec forms; c_k the plan's coefficient (a_k / sum_n v_k[n]^2 under
+ * OTH_SCALE_DENSITY, a_k otherwise); CL = 1 - 2^-24.  Per item i = (s, k) and bin:
+ *   X_i = FFT_nfft((x_s - m_s) v_k), Y_i likewise;   p_i = c_k |X_i|^2,  q_i = c_k |Y_i|^2,  r_i = c_k conj(X_i) Y_i
+ *   Sxx = sum_i p_i,  Syy = sum_i q_i,  Sxy = sum_i r_i      (what oth_welch_partial_dev / oth_csd_partial_dev leave)
+ * ln PSD (one channel, and each channel of a pair):
+ *   t_i = min(p_i / Sxx, CL),  l_i = log1p(-t_i)             the delete-one ln((Sxx - p_i) / (M - 1)) up to a constant
+ *   var = (M - 1) / M (sum l_i^2 - (sum l_i)^2 / M), clamped at 0;   lnsd = sqrt(var)
+ * lnsd is in natural-log units, never dB and never scaled; a bin with Sxx <= 0 reads 0.
+ * Coherence (two channels), with C = |Sxy|^2 / (Sxx Syy) and z(c) = atanh(min(sqrt(c), CL)):
+ *   C_i = |Sxy - r_i|^2 / (Sxx (1 - tx_i) Syy (1 - ty_i)),   d_i = z(C_i) - z(C)
+ *   zvar = (M - 1) / M (sum d_i^2 - (sum d_i)^2 / M), clamped at 0;   zsd = sqrt(zvar)
+ * A bin with Sxx <= 0 or Syy <= 0 reads zsd = 0.  Finite input never gives NaN in lnsd or zsd (cxy_out is the plan's own Cxy:
+ * 0 / 0 = NaN for a silent channel, as oth_csd_exec_dev documents).  A confidence interval is
+ * psd exp(-+ q lnsd) resp. tanh(max(0, z -+ q zsd))^2 with q the Student-t quantile at M - 1 degrees of freedom.  The phase
+ * jackknife is not provided.
+ * Every row takes the plan's fftshift and trim, layout [nstreams][out_len].  psd_out (may be NULL): the row
+ * oth_welch_exec_dev gives for the same plan and input, bit for bit (dB applies to it alone).  cxy_out (may be NULL): the
+ * Cxy row of oth_csd_exec_dev, bit for bit; lnsdx_out / lnsdy_out may be NULL, zsd_out not.
+ * Two passes per call: the plan's own averaging launch and reduction leave the totals in a buffer of the plan, then
+ * csrc/mtmjack.hip walks the items again (mtm.hip's work split) with the running sums and a small finalize launch adds the
+ * workgroups' rows in double in a fixed order: bit-identical run to run.  _dev: device in, device out, asynchronous; the
+ * one-channel form takes nstreams as oth_welch_exec_dev (at most 65535), the two-channel form one stream.  The forms without
+ * _dev: one stream, host or device source, host outputs, blocking.
+ * The one-channel calls work on plans of oth_mtm_plan and oth_mtm_csd_plan, the two-channel calls on oth_mtm_csd_plan's only.
+ * Refused, the reason in oth_last_error(), before anything is staged, and the plan goes on working: OTH_ERR_UNSUPPORTED on a
+ * plan without tapers, on a plan whose weights are not all equal (the items must be exchangeable), for more than 65535
+ * streams, and for the two-channel calls on a plan of oth_mtm_plan; OTH_ERR_INVALID for M < 2 (one channel) or M < 3 (two:
+ * with one item left every delete-one coherence is 1), a NULL input or required output pointer, nstreams < 1,
+ * stream_stride < nsamples, input shorter than nperseg. */
+int oth_mtm_jackknife_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride,
+                          float *lnsd_out_dev, float *psd_out_dev, uint64_t *nseg_out);
+int oth_mtm_jackknife(oth_plan *plan, const void *iq, size_t nsamples, int src_is_device, float *lnsd_out, float *psd_out,
+                      uint64_t *nseg_out);
+int oth_mtm_csd_jackknife_dev(oth_plan *plan, const void *x_dev, const void *y_dev, size_t nsamples, float *cxy_out_dev,
+                              float *zsd_out_dev, float *lnsdx_out_dev, float *lnsdy_out_dev, uint64_t *nseg_out);
+int oth_mtm_csd_jackknife(oth_plan *plan, const void *x, const void *y, size_t nsamples, int src_is_device, float *cxy_out,
+                          float *zsd_out, float *lnsdx_out, float *lnsdy_out, uint64_t *nseg_out);
+
 /* one-shot: nsamples complex64 -> psd_out[nfft - 2*trim] (host).  Blocking: returns when the PSD is in psd_out.  The
  * last launch writes the row and a completion word into pinned host memory and the call polls that word (no interrupt
  * wake-up; after 20 ms it falls back to a stream synchronisation, which also reports a failed launch;
