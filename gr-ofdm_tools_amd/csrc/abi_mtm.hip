@@ -276,6 +276,7 @@ int mtm_plan_create(oth_ctx *c, int nfft, int nperseg, int noverlap, int ntapers
     if (!(wsum > 0.0) || !std::isfinite(wsum)) return fail(c, OTH_ERR_INVALID, "weights must have a positive sum");
     std::vector<float> tab((size_t)ntapers * nfft, 0.f), coef(ntapers);      // zero-extended: the kernel indexes [0, nfft)
     std::vector<float> usum(ntapers);                                        // U_k, the F-test's (oth_mtm_ftest_dev)
+    std::vector<float> inv_g(ntapers);                                       // 1 / g_k, the adaptive weighting's (oth_mtm_adaptive_dev)
     double usq = 0.0;
     for (int k = 0; k < ntapers; ++k) {
         double s2 = 0.0, s1 = 0.0;
@@ -287,6 +288,7 @@ int mtm_plan_create(oth_ctx *c, int nfft, int nperseg, int noverlap, int ntapers
             s1 += (double)t;
         }
         usum[k] = (float)s1;
+        inv_g[k] = s2 > 0.0 ? (float)(1.0 / s2) : 0.f;
         usq += (double)usum[k] * (double)usum[k];
         double ck = (weights ? (double)weights[k] : 1.0) / wsum;
         if (scaling == OTH_SCALE_DENSITY) {
@@ -299,6 +301,7 @@ int mtm_plan_create(oth_ctx *c, int nfft, int nperseg, int noverlap, int ntapers
     p->mtm_csd = two_channel;
     for (int k = 1; weights && k < ntapers; ++k) p->mtm_uniform = p->mtm_uniform && weights[k] == weights[0];
     p->mtm_s = std::isfinite(usq) ? usq : 0.0;
+    p->mtm_inv_g = std::move(inv_g);
     switch (scaling) {
         case OTH_SCALE_DENSITY: p->scale = 1.0 / fs; break;      // the tapers' energies are in c_k
         case OTH_SCALE_OVER_N2: p->scale = 1.0 / ((double)nfft * (double)nfft); break;

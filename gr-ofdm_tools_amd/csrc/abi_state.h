@@ -136,6 +136,11 @@ struct oth_plan {
     DevBuf<float> d_mtm_u;             // [ntapers] U_k = sum_n v_k[n] (summed in double)
     double mtm_s = 0.0;                // sum_k U_k^2 of the uploaded values
     DevBuf<float> d_ftest_ws;          // mtmftest.hip's per-workgroup sy / p rows (MtmFtestArgs.ws; 16384 points only)
+    // adaptive weighting (oth_mtm_set_ratios, oth_mtm_adaptive*: abi_adapt.hip / mtmadapt.hip)
+    std::vector<float> mtm_inv_g;      // [ntapers] 1 / sum_n v_k[n]^2 (summed in double; 0 for an all-zero taper)
+    DevBuf<float> d_mtm_lam;           // [3][ntapers] lambda_k, max(1 - lambda_k, 0) - formed in double - and mtm_inv_g; empty
+                                       // until oth_mtm_set_ratios
+    DevBuf<float> d_adapt_ws;          // mtmadapt.hip's per-workgroup eigenspectra rows (MtmAdaptArgs.ws; from 1024 points on)
     // the jackknife (oth_mtm_jackknife*, oth_mtm_csd_jackknife*: abi_jack.hip / mtmjack.hip)
     bool mtm_uniform = true;           // every weight a_k is the same: the (segment, taper) items are exchangeable
     DevBuf<float> d_jack_tot;          // totals of the first pass: [nstreams][nfft], or [4][nfft] + the natural-order Cxy row

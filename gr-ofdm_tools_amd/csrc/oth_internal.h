@@ -442,6 +442,27 @@ hipError_t launch_mtm_jack(int nfft, const MtmJackArgs &a, hipStream_t s);
 hipError_t launch_mtmcsd_jack(int nfft, const MtmCsdJackArgs &a, hipStream_t s);
 hipError_t launch_jack_finalize(const JackFinalizeArgs &a, int nstreams, hipStream_t s);
 
+// ---- mtmadapt.hip: Thomson's adaptive weighting on the same taper loop; the work item is a whole segment -----------------
+struct MtmAdaptArgs {
+    MtmArgs m;              // as mtmftest.hip's (coef unused); partial: [nstreams][wg_per_stream][2][nfft] sum S_s, sum nu_s
+    const float *lam;       // [3][ntapers] lambda_k, 1 - lambda_k, 1 / g_k (oth_mtm_set_ratios)
+    float *ws;              // [nstreams][wg_per_stream][mtm_adapt_ws_floats(nfft, ntapers)]: a segment's eigenspectra (from 1024 points on)
+    int iters;              // updates of S, 1 ... 64
+};
+struct AdaptFinalizeArgs {
+    const float *partial;   // [nstreams][W][2][nfft], natural bin order
+    float *psd_out;         // [nstreams][nout]
+    float *dof_out;         // or nullptr
+    double psd_scale;       // scale / nseg
+    double inv_nseg;
+    int W, nfft, fftshift, trim, db, nout;
+};
+size_t mtm_adapt_lds_bytes(int nfft, int ntapers);      // dynamic LDS of the launch: up to 512 points it holds the eigenspectra
+size_t mtm_adapt_ws_floats(int nfft, int ntapers);      // 0: the build keeps the eigenspectra in LDS
+int mtm_adapt_blocks_per_cu(int nfft, int ntapers);
+hipError_t launch_mtm_adapt(int nfft, const MtmAdaptArgs &a, hipStream_t s);
+hipError_t launch_adapt_finalize(const AdaptFinalizeArgs &a, int nstreams, hipStream_t s);
+
 // ---- welchsk.hip: spectral kurtosis of a Welch plan - per bin sum_m P_m and sum_m P_m^2, P_m = g |FFT((x_m - mean) w)|^2 ---
 struct WelchSkArgs {
     const float2 *x;        // device IQ, stream 0

@@ -84,6 +84,9 @@ SIGNATURES = {
     'oth_mtm_jackknife': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
     'oth_mtm_csd_jackknife_dev': (C.c_int, [_p, _p, _p, C.c_size_t, _p, _p, _p, _p, _u64p]),
     'oth_mtm_csd_jackknife': (C.c_int, [_p, _p, _p, C.c_size_t, C.c_int, _f, _f, _f, _f, _u64p]),
+    'oth_mtm_set_ratios': (C.c_int, [_p, C.POINTER(C.c_double)]),
+    'oth_mtm_adaptive_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, C.c_int, _p, _p, _u64p]),
+    'oth_mtm_adaptive': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_int, _f, _f, _u64p]),
     'oth_plan_set_tuning': (C.c_int, [_p, C.c_char_p, C.c_int, C.c_int, C.c_int]),
     'oth_welch_exec': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _u64p]),
     'oth_welch_exec_async': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _u64p]),
@@ -739,7 +742,8 @@ class MtmPlan(WelchPlan):
     """A WelchPlan whose averaging launch is the multitaper kernel: exec / exec_async / poll / wait / exec_dev /
     partial_dev / scale_dev / accumulate / finalize / reset as WelchPlan's; the median average, the per-segment rows,
     the cross spectrum, KERNEL_TUNED and build variants raise HipError (OTH_ERR_UNSUPPORTED).  ftest / ftest_dev: Thomson's
-    harmonic F-test on the same tapers."""
+    harmonic F-test on the same tapers.  adaptive / adaptive_dev: Thomson's adaptive weighting and its degrees of freedom
+    (the plan's own Slepian tapers bring their concentration ratios; set_ratios() gives them for user tapers)."""
 
     _CONSTRUCTOR = 'oth_mtm_plan'
 
@@ -781,6 +785,48 @@ class MtmPlan(WelchPlan):
         self.out_len = n.value
         if db:
             ctx.check(ctx.lib.oth_plan_set_output_db(h, 1), 'oth_plan_set_output_db')
+        if slepian:      # (the computed ratio of a taper can come out an ulp past 1, or not above 0 far beyond 2 nw tapers)
+            self.set_ratios(np.clip(ratios, np.finfo(np.float64).tiny, 1.0))
+            self.ratios = ratios
+
+    def set_ratios(self, ratios):
+        """The tapers' concentration ratios lambda_k (oth_mtm_set_ratios), each in (0, 1], as float64 - the adaptive estimate
+        needs 1 - lambda_k, which a float32 lambda_0 does not hold.  Replaces an earlier set; no other call reads them."""
+        r = np.ascontiguousarray(ratios, np.float64)
+        if r.shape != (self.ntapers,):
+            raise ValueError('ratios must have ntapers=%d entries' % self.ntapers)
+        self.ctx.check(self.ctx.lib.oth_mtm_set_ratios(self.h, r.ctypes.data_as(C.POINTER(C.c_double))), 'oth_mtm_set_ratios')
+        self.ratios = r
+
+    def adaptive(self, x, iters=4, return_dof=False, nsamples=None):
+        """Thomson's adaptive-weight estimate (oth_mtm_adaptive) of one capture: per segment and bin the eigenspectra are
+        combined with weights lambda_k b_k^2, b_k = S / (lambda_k S + (1 - lambda_k) sigma^2), S updated `iters` times from
+        (P_0 + P_1) / 2 - a taper leaves a bin as far as its leakage would dominate there, so an empty band next to a strong
+        one is not lifted as it is with fixed weights.  x: host complex64 array, or a device pointer when nsamples is given.
+        -> PSD (float32, out_len bins, the plan's scaling, fftshift, trim and dB), or with return_dof (PSD, dof): the per-bin
+        equivalent degrees of freedom 2 (sum w)^2 / sum w^2, mean over the segments, between 2 and 2 K, always linear.
+        Sets last_nseg.  The plan's weights take no part."""
+        rows = [np.empty(self.out_len, np.float32) for _ in range(2 if return_dof else 1)]
+        n = C.c_uint64()
+        if nsamples is None:
+            x = _c64(x)
+            src, count, dev = x.ctypes.data_as(_p), len(x), 0
+        else:
+            src, count, dev = C.c_void_p(x), int(nsamples), 1
+        self.ctx.check(self.ctx.lib.oth_mtm_adaptive(self.h, src, count, dev, int(iters), _fptr(rows[0]),
+                                                     _fptr(rows[1]) if return_dof else None, C.byref(n)), 'oth_mtm_adaptive')
+        self.last_nseg = n.value
+        return tuple(rows) if return_dof else rows[0]
+
+    def adaptive_dev(self, iq_dev, nsamples, nstreams, stride, psd_dev, dof_dev=None, iters=4):
+        """Asynchronous: device in, device out - [nstreams][out_len] float32 at psd_dev and, where given, dof_dev.
+        -> segments per stream (also last_nseg)."""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_mtm_adaptive_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
+                                                         int(iters), C.c_void_p(psd_dev), C.c_void_p(dof_dev) if dof_dev else None,
+                                                         C.byref(n)), 'oth_mtm_adaptive_dev')
+        self.last_nseg = n.value
+        return n.value
 
     def ftest(self, x, return_rows=False, nsamples=None):
         """Thomson's harmonic F-test (oth_mtm_ftest) of one capture: per bin F = (K - 1) sum_s num_s / sum_s den_s, large

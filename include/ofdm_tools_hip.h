@@ -384,6 +384,47 @@ int oth_mtm_csd_jackknife_dev(oth_plan *plan, const void *x_dev, const void *y_d
 int oth_mtm_csd_jackknife(oth_plan *plan, const void *x, const void *y, size_t nsamples, int src_is_device, float *cxy_out,
                           float *zsd_out, float *lnsdx_out, float *lnsdy_out, uint64_t *nseg_out);
 
+/* oth_mtm_set_ratios, oth_mtm_adaptive_dev / oth_mtm_adaptive (additions inside ABI 6; probe by the symbols): Thomson's
+ * adaptive-weight multitaper PSD and its per-bin equivalent degrees of freedom, on any plan of oth_mtm_plan or
+ * oth_mtm_csd_plan with K = ntapers >= 2.  The fixed weights of a plan let the high-order tapers' leakage (1 - lambda_k of
+ * their energy lies outside the band) lift an empty band next to a strong one; the adaptive weights take a taper out of a
+ * bin as far as its leakage would dominate there.  With the tapers v_k, g_k = sum_n v_k[n]^2 (formed in double when the plan
+ * is created) and the concentration ratios lambda_k of oth_mtm_set_ratios, per stream, segment s and bin j - segmentation,
+ * per-segment mean removal and zero padding as the plan's exec forms:
+ *   P_k     = |FFT_nfft((x_s - m_s) v_k)[j]|^2 / g_k                 the eigenspectra
+ *   sigma^2 = (1 / nperseg) sum_n |x_s[n] - m_s|^2                   so that white noise has E P_k = sigma^2
+ *   S^0     = (P_0 + P_1) / 2
+ *   `iters` times:   b_k = S / (lambda_k S + (1 - lambda_k) sigma^2),   w_k = lambda_k b_k^2,
+ *                    S <- sum_k w_k P_k / sum_k w_k
+ *   then b_k and w_k once more from the final S, and   nu_s = 2 (sum_k w_k)^2 / sum_k w_k^2
+ * A bin where sum_k w_k is not > 0, or a segment with sigma^2 = 0, reads S_s = 0 and nu_s = 0: finite input never gives NaN
+ * or Inf; all-zero input, and constant input on a detrending plan, give two rows of zeros.  The outputs, [nstreams][out_len]
+ * float32 each:
+ *   psd = scale (1 / nseg) sum_s S_s      scale = 1 / fs (OTH_SCALE_DENSITY), 1 (OTH_SCALE_RAW), 1 / nfft^2
+ *                                         (OTH_SCALE_OVER_N2) - for unit-norm tapers the plan's own scaling; the row takes
+ *                                         the plan's fftshift, trim and dB
+ *   dof = (1 / nseg) sum_s nu_s           between 2 and 2 K: what a chi-square threshold or interval on a bin needs; takes
+ *                                         fftshift and trim, always linear; dof_out may be NULL
+ * The plan's weights take no part.  The iteration count is fixed (1 <= iters <= 64, 4 is a good default) and there is no
+ * convergence test: single bins approach the fixed point very slowly while the floor of an empty band settles after three
+ * or four updates, and a fixed count makes the estimate a definite function of its input.
+ * oth_mtm_set_ratios: K host doubles, each in (0, 1] (oth_dpss's `ratios` for Slepian tapers); lambda_k and
+ * max(1 - lambda_k, 0) are formed in double and then rounded to float - 1 - lambda_0 is 3e-10 at NW 4 and cannot be formed
+ * from a float lambda.  It replaces any earlier set, waits for the plan's queued work, and has no effect on any other call.
+ * One averaging launch per call (csrc/mtmadapt.hip: a workgroup takes whole segments, K transforms each, and keeps the
+ * segment's eigenspectra in LDS or in a workspace row of its own), then a small finalize launch that adds the workgroups'
+ * rows in double in a fixed order: bit-identical run to run.  _dev: device in, device out, asynchronous, nstreams as
+ * oth_welch_exec_dev (at most 65535).  oth_mtm_adaptive: one stream, host or device source, host outputs, blocking.
+ * Refused with OTH_ERR_UNSUPPORTED and the reason in oth_last_error(), before anything is staged, and the plan goes on
+ * working: a plan without tapers (oth_welch_plan's), ntapers < 2, a plan on which no ratios were set.  OTH_ERR_INVALID: a
+ * ratio outside (0, 1], iters outside 1 ... 64, a NULL input or psd pointer, nstreams < 1, stream_stride < nsamples, input
+ * shorter than nperseg. */
+int oth_mtm_set_ratios(oth_plan *plan, const double *ratios);
+int oth_mtm_adaptive_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride, int iters,
+                         float *psd_out_dev, float *dof_out_dev, uint64_t *nseg_out);
+int oth_mtm_adaptive(oth_plan *plan, const void *iq, size_t nsamples, int src_is_device, int iters, float *psd_out,
+                     float *dof_out, uint64_t *nseg_out);
+
 /* one-shot: nsamples complex64 -> psd_out[nfft - 2*trim] (host).  Blocking: returns when the PSD is in psd_out.  The
  * last launch writes the row and a completion word into pinned host memory and the call polls that word (no interrupt
  * wake-up; after 20 ms it falls back to a stream synchronisation, which also reports a failed launch;
