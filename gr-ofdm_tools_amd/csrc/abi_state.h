@@ -146,6 +146,14 @@ struct oth_plan {
     DevBuf<float> d_jack_tot;          // totals of the first pass: [nstreams][nfft], or [4][nfft] + the natural-order Cxy row
     // spectral kurtosis (oth_welch_sk*, abi_sk.hip / welchsk.hip): Welch plans only
     double sk_g = 1.0;                 // 1 / sum w^2 (1 for an all-zero window): the periodograms' scale inside the kernel
+    // cyclic spectrum and coherence (oth_welch_set_cycles, oth_welch_cyclic*: abi_cyc.hip / welchcyc.hip): Welch plans only
+    std::vector<float> win_host;       // the window as uploaded (nperseg values): the complex tapers are formed from it in double
+    int ncycles = 0;                   // 0 until oth_welch_set_cycles
+    DevBuf<float2> d_cyc_tap;          // [ncycles][nfft] w[n] e^{-j 2 pi alpha_a n}
+    DevBuf<double> d_cyc_alpha;        // [ncycles]
+    DevBuf<float2> d_cyc_ws;           // welchcyc.hip's per-workgroup spectrum rows (WelchCycArgs.ws; 16384 points only)
+    int tune_cyc_group = 0;            // OTH_CYC_GROUP, read when the plan is created: 1, 2 or 4 forces that build of welchcyc.hip
+                                       // (A/B tools and the parity suite); 0 = the library's choice
 };
 
 struct oth_chain {

@@ -491,4 +491,39 @@ int welch_sk_blocks_per_cu(int nfft);
 hipError_t launch_welch_sk(int nfft, const WelchSkArgs &a, hipStream_t s);
 hipError_t launch_sk_finalize(const SkFinalizeArgs &a, int nstreams, hipStream_t s);
 
+// ---- welchcyc.hip: cyclic spectrum and coherence of a Welch plan - sum_s |X|^2 and, per cycle frequency, sum_s |U|^2 and
+// sum_s U conj(X), U the same segment under the complex taper w[n] e^{-j 2 pi alpha n} and the segment's phase ---------------
+constexpr int kCycMax = 64;      // cycle frequencies of a plan at most
+constexpr int kCycGroup = 4;     // cycle frequencies per workgroup of the widest build (the others take one and two)
+struct WelchCycArgs {
+    const float2 *x;        // device IQ, stream 0
+    const float *win;       // the plan's window, nfft floats (zero-extended behind nperseg)
+    const float2 *ctap;     // [ncyc][nfft] w[n] e^{-j 2 pi alpha_a n}, formed in double (zero-extended behind nperseg)
+    const double *alpha;    // [ncyc] cycles per sample
+    const float2 *tw;       // W_nfft^k, nfft entries
+    float *partial;         // [nstreams][groups][wg_per_stream][1 + 3 GA][nfft]: |X|^2 (group 0 only), then per cycle
+                            // frequency of the group |U|^2, Re and Im sum U conj(X); natural bin order
+    float2 *ws;             // [nstreams][groups][wg_per_stream][welch_cyc_ws_points(nfft)]: X's spectrum (16384 points)
+    long long nseg;         // segments per stream
+    size_t stream_stride;   // samples between streams
+    int nperseg;
+    int step;
+    int detrend;            // != 0: each segment's own mean comes off (pilot + residual)
+    int wg_per_stream;      // workgroups of a stream and group: each walks a contiguous run of the nseg segments
+    int nstreams;
+    int ncyc;
+};
+struct CycFinalizeArgs {
+    const float *partial;   // as WelchCycArgs.partial
+    float *scf_out;         // [nstreams][ncyc][nout] re, im interleaved, or nullptr
+    float *coh_out;         // [nstreams][ncyc][nout]
+    float *psd_out;         // [nstreams][nout], or nullptr
+    double scf_scale;       // scale / M
+    int W, G, ga, ncyc, nfft, fftshift, trim, db, nout;
+};
+size_t welch_cyc_ws_points(int nfft);      // 0: the build keeps both spectra in LDS
+int welch_cyc_blocks_per_cu(int nfft, int ga);      // ga: 1, 2 or kCycGroup
+hipError_t launch_welch_cyc(int nfft, int ga, int groups, const WelchCycArgs &a, hipStream_t s);
+hipError_t launch_cyc_finalize(const CycFinalizeArgs &a, int nstreams, hipStream_t s);
+
 }  // namespace oth

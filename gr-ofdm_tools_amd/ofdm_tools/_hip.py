@@ -80,6 +80,9 @@ SIGNATURES = {
     'oth_mtm_ftest': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _f, _u64p]),
     'oth_welch_sk_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
     'oth_welch_sk': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
+    'oth_welch_set_cycles': (C.c_int, [_p, C.c_int, C.POINTER(C.c_double)]),
+    'oth_welch_cyclic_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _p, _u64p]),
+    'oth_welch_cyclic': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _f, _u64p]),
     'oth_mtm_jackknife_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
     'oth_mtm_jackknife': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
     'oth_mtm_csd_jackknife_dev': (C.c_int, [_p, _p, _p, C.c_size_t, _p, _p, _p, _p, _u64p]),
@@ -546,6 +549,52 @@ class WelchPlan(object):
         self.ctx.check(self.ctx.lib.oth_welch_sk_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
                                                      C.c_void_p(sk_dev), C.c_void_p(psd_dev) if psd_dev else None, C.byref(n)),
                        'oth_welch_sk_dev')
+        self.last_nseg = n.value
+        return n.value
+
+    ncycles = 0      # (class default: no cycle frequencies until set_cycles)
+
+    def set_cycles(self, alphas):
+        """The cycle frequencies of cyclic / cyclic_dev (oth_welch_set_cycles): 1 ... 64 values in cycles per sample, each
+        finite with |alpha| <= 0.5, as float64 - a capture of 2^24 samples resolves alpha to 6e-8, below float32's spacing.
+        Replaces an earlier set; no other call of the plan is affected.  A multitaper plan, a median-averaging plan and a
+        length that is not a power of two 64 ... 16384 raise HipError (OTH_ERR_UNSUPPORTED)."""
+        a = np.ascontiguousarray(np.atleast_1d(alphas), np.float64)
+        if a.ndim != 1:
+            raise ValueError('alphas must be a sequence of cycle frequencies')
+        self.ctx.check(self.ctx.lib.oth_welch_set_cycles(self.h, len(a), a.ctypes.data_as(C.POINTER(C.c_double))), 'oth_welch_set_cycles')
+        self.ncycles = len(a)
+
+    def cyclic(self, x, return_psd=False, nsamples=None):
+        """Cyclic spectrum and cyclic coherence (oth_welch_cyclic) of one capture at the A cycle frequencies of set_cycles:
+        with X_s the plan's windowed transform of segment s and U_s,a the same at frequency f + alpha_a (global time origin),
+        scf_a = scale mean_s U_s,a conj(X_s), an estimate of E[X(f + alpha) X*(f)], and coh_a = |sum U conj(X)|^2 /
+        (sum |U|^2 sum |X|^2) in [0, 1]: 1 / M for stationary noise of any level or colour, well above for a signal
+        that is cyclostationary at alpha_a (CP-OFDM at k / (Tu + Tcp)).  x: host complex64 array, or a device pointer when
+        nsamples is given.  -> (scf complex64 [A, out_len], coh float32 [A, out_len]) with the plan's fftshift and trim, and
+        with return_psd the row exec() gives for the same input (dB applies to it alone).  Sets last_nseg (M)."""
+        A, m = int(self.ncycles), self.out_len
+        scf, coh = np.empty((max(A, 1), m), np.complex64), np.empty((max(A, 1), m), np.float32)
+        psd = np.empty(m, np.float32) if return_psd else None
+        n = C.c_uint64()
+        if nsamples is None:
+            x = _c64(x)
+            src, count, dev = x.ctypes.data_as(_p), len(x), 0
+        else:
+            src, count, dev = C.c_void_p(x), int(nsamples), 1
+        self.ctx.check(self.ctx.lib.oth_welch_cyclic(self.h, src, count, dev, scf.ctypes.data_as(_f), _fptr(coh),
+                                                     _fptr(psd) if return_psd else None, C.byref(n)), 'oth_welch_cyclic')
+        self.last_nseg = n.value
+        return (scf, coh, psd) if return_psd else (scf, coh)
+
+    def cyclic_dev(self, iq_dev, nsamples, nstreams, stride, coh_dev, scf_dev=None, psd_dev=None):
+        """Asynchronous: device in, device out - [nstreams][A][out_len] float32 at coh_dev and, where given,
+        [nstreams][A][out_len] re, im pairs at scf_dev and [nstreams][out_len] at psd_dev.
+        -> segments per stream (also last_nseg)."""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_welch_cyclic_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
+                                                         C.c_void_p(scf_dev) if scf_dev else None, C.c_void_p(coh_dev),
+                                                         C.c_void_p(psd_dev) if psd_dev else None, C.byref(n)), 'oth_welch_cyclic_dev')
         self.last_nseg = n.value
         return n.value
 

@@ -590,6 +590,53 @@ def sk_scan(vector, nFFT, Sf, fc=0.0, p_false=None, ctx=None):
     return sk, axis, sk < lower, sk > upper
 
 
+def ofdm_cycle_frequencies(fft_len, cp_len, Sf, harmonics=2):
+    """The cycle frequencies of a cyclic-prefix OFDM signal of fft_len useful and cp_len prefix samples per symbol at
+    sample rate Sf: +-k Sf / (fft_len + cp_len) in Hz for k = 1 ... harmonics, ordered +1, -1, +2, -2, ...  The prefix
+    repeats the symbol's tail, so the signal is correlated with itself at lag +-fft_len with the symbol period."""
+    fft_len, cp_len, harmonics = int(fft_len), int(cp_len), int(harmonics)
+    if fft_len < 1 or cp_len < 1 or harmonics < 1 or not Sf > 0:
+        raise ValueError('ofdm_cycle_frequencies needs fft_len, cp_len, harmonics >= 1 and Sf > 0')
+    base = float(Sf) / float(fft_len + cp_len)
+    return np.array([sign * k * base for k in range(1, harmonics + 1) for sign in (1.0, -1.0)], np.float64)
+
+
+def cyclic_scan(vector, nFFT, Sf, cycles_hz, fc=0.0, ctx=None):
+    """Is the thing in this band cyclostationary at the given cycle frequencies - a CP-OFDM signal of known symbol period
+    (ofdm_cycle_frequencies) - or just noise of unknown level and colour?  The cyclic coherence of one capture
+    (WelchPlan.cyclic; Hann window, nperseg = nFFT, no overlap) at each of the A cycle frequencies cycles_hz [Hz].
+    -> (profile[A]: the mean over bins of each coherence row, the coherence rows [A, nFFT] fftshifted, frequency axis,
+    null level 1 / M).  Stationary noise reads about 1 / M in every entry of the profile, M = len(vector) // nFFT, whatever
+    its level; that null mean assumes independent segments, that is no overlap - which is why the scan uses none.
+    Row a, bin j compares the spectrum at axis[j] and at axis[j] + cycles_hz[a].  Needs nFFT a power of two from 64 to
+    16384, 1 ... 64 cycle frequencies with |cycle| <= Sf / 2 and at least one segment (ValueError otherwise, before
+    anything runs)."""
+    if nFFT not in SK_SIZES:
+        raise ValueError('cyclic_scan needs nFFT a power of two from 64 to 16384, not %r' % (nFFT,))
+    if not Sf > 0:
+        raise ValueError('cyclic_scan needs a sample rate Sf > 0')
+    cycles = np.atleast_1d(np.asarray(cycles_hz, np.float64))
+    if cycles.ndim != 1 or not 1 <= len(cycles) <= 64:
+        raise ValueError('cyclic_scan needs 1 ... 64 cycle frequencies, not %d' % cycles.size)
+    if not np.all(np.isfinite(cycles)) or np.any(np.abs(cycles) > 0.5 * float(Sf)):
+        raise ValueError('every cycle frequency must be finite with |cycle| <= Sf / 2')
+    M = len(vector) // int(nFFT)
+    if M < 1:
+        raise ValueError('cyclic_scan needs at least nFFT = %d samples' % nFFT)
+    alphas = cycles / float(Sf)
+    ctx = ctx or _hip.default_context()
+    key = ('cyclic', nFFT, float(Sf), alphas.tobytes())
+
+    def make():
+        plan = ctx.welch_plan(nFFT, nperseg=nFFT, noverlap=0, window=windows.get_window('hann', nFFT), fs=float(Sf), fftshift=True)
+        plan.set_cycles(alphas)
+        return plan
+
+    coh = ctx.cached_plan(key, make).cyclic(vector)[1]
+    axis = np.fft.fftshift(np.fft.fftfreq(nFFT, 1.0 / Sf)) + fc
+    return coh.mean(axis=1, dtype=np.float64), coh, axis, 1.0 / M
+
+
 class SpectrumScan(object):
     """The legacy sensor's scan (reference: ofdm_cr_tools.py:471-537; its matplotlib branch is not carried over), split
     where the GPU works: the constructor enqueues the PSD of the chosen method ('welch': flat-top Welch, 'fft': one

@@ -425,6 +425,50 @@ int oth_mtm_adaptive_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, in
 int oth_mtm_adaptive(oth_plan *plan, const void *iq, size_t nsamples, int src_is_device, int iters, float *psd_out,
                      float *dof_out, uint64_t *nseg_out);
 
+/* oth_welch_set_cycles, oth_welch_cyclic_dev / oth_welch_cyclic (additions inside ABI 6; probe by the symbols): the cyclic
+ * spectrum (spectral correlation density) and the cyclic coherence of a plan of oth_welch_plan at a set of A cycle
+ * frequencies alpha_a in cycles per sample - cyclostationary feature detection.  A cyclic-prefix OFDM signal is correlated
+ * with itself at lag +-Tu with period Ts = Tu + Tcp, so E[X(f + alpha) X*(f)] is non-zero at alpha = k / Ts; stationary noise
+ * has none at any alpha != 0, whatever its level or colour - a detector that needs no noise floor.  The estimate is the
+ * time-smoothed cyclic cross periodogram.  With the plan's window w, step = nperseg - noverlap and its M segments
+ * (segmentation, per-segment mean removal m_s and zero padding as the plan's exec forms), per stream, segment s and bin j:
+ *   X_s[j]   = FFT_nfft((x_s[n] - m_s) w[n])[j]
+ *   U_s,a[j] = FFT_nfft((x_s[n] - m_s) w[n] e^{-j 2 pi alpha_a (n + s step)})[j]      X at frequency j / nfft + alpha_a, with
+ *                                                                                    the capture's first sample as time 0
+ *   Sxx = sum_s |X_s|^2,   Suu_a = sum_s |U_s,a|^2,   Sux_a = sum_s U_s,a conj(X_s)
+ *   scf_a = scale Sux_a / M                  the plan's scaling, as Pxy of oth_csd_exec: estimates E[X(f_j + alpha) X*(f_j)],
+ *                                            the spectral correlation density at centre frequency f_j + alpha / 2
+ *   coh_a = |Sux_a|^2 / (Suu_a Sxx)          the cyclic coherence, in [0, 1], independent of level and scaling; 1 / M on
+ *                                            average for stationary noise over independent segments
+ *   psd   = scale Sxx / M                    the plan's own PSD row (dB applies to it alone)
+ * Every row takes the plan's fftshift and trim.  A bin with Suu_a Sxx <= 0 reads scf = 0, coh = 0: finite input never gives
+ * NaN or Inf; all-zero input, and constant input on a detrending plan, give rows of zeros.  alpha = 0 gives coh = 1, a zero
+ * imaginary part and scf = psd in linear units.  One segment is allowed: the coherence is then 1 everywhere, as
+ * oth_csd_exec's.
+ * Phase: e^{-j 2 pi alpha_a n}, n < nperseg, is formed on the host in double and rounded once, multiplied into the window as
+ * a complex taper; the segment's factor e^{-j 2 pi alpha_a s step} comes from the fractional part of alpha_a s step taken
+ * in double - at 2^24 samples a cycle frequency one resolution cell 1 / (M step) off the true one already reads the null
+ * level, and a float32 product of the sample index is useless there.  That is why the cycle frequencies are doubles.
+ * oth_welch_set_cycles: 1 <= ncycles <= 64 host doubles, each finite with |alpha| <= 0.5.  It replaces any earlier set, waits
+ * for the plan's queued work, and has no effect on any other call of the plan.
+ * Outputs: scf [nstreams][A][out_len] interleaved re, im; coh [nstreams][A][out_len]; psd [nstreams][out_len]; scf_out and
+ * psd_out may be NULL, coh_out not.  One averaging launch per call (csrc/welchcyc.hip: a workgroup takes whole segments for
+ * a group of up to 4 consecutive cycle frequencies, transforms X once per segment and every U of the group against it),
+ * then a small finalize launch that adds the workgroups' rows in double in a fixed order: bit-identical run to run.
+ * _dev: device in, device out, asynchronous, nstreams as oth_welch_exec_dev (at most 65535).  oth_welch_cyclic: one stream,
+ * host or device source, host outputs, blocking.
+ * Refused, the reason in oth_last_error(), before anything is staged, and the plan goes on working: OTH_ERR_UNSUPPORTED on a
+ * multitaper plan, a plan set to OTH_AVERAGE_MEDIAN, a transform length that is not a power of two from 64 to 16384, a plan
+ * on which no cycles were set, more than 65535 streams; OTH_ERR_INVALID for ncycles outside 1 ... 64, a non-finite alpha or
+ * |alpha| > 0.5, a NULL alphas, input or coh pointer, nstreams < 1, stream_stride < nsamples, input shorter than nperseg.
+ * Not provided: the conjugate cyclic spectrum E[X(f + alpha) X(-f)], a search over alpha (the caller supplies the cycle
+ * frequencies), multitaper plans, any-length transforms. */
+int oth_welch_set_cycles(oth_plan *plan, int ncycles, const double *alphas);
+int oth_welch_cyclic_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride,
+                         float *scf_out_dev, float *coh_out_dev, float *psd_out_dev, uint64_t *nseg_out);
+int oth_welch_cyclic(oth_plan *plan, const void *iq, size_t nsamples, int src_is_device, float *scf_out, float *coh_out,
+                     float *psd_out, uint64_t *nseg_out);
+
 /* one-shot: nsamples complex64 -> psd_out[nfft - 2*trim] (host).  Blocking: returns when the PSD is in psd_out.  The
  * last launch writes the row and a completion word into pinned host memory and the call polls that word (no interrupt
  * wake-up; after 20 ms it falls back to a stream synchronisation, which also reports a failed launch;
