@@ -1,7 +1,7 @@
 // C ABI, host side: cyclic spectrum and cyclic coherence of a Welch plan (oth_welch_set_cycles, oth_welch_cyclic / _dev) -
 // the cycle set's tables, the checks, the (W, nstreams, groups) launch of welchcyc.hip and its finalize launch into the
 // scf, coh and PSD rows.
-#include "abi_state.h"
+#include "abi_stat.h"
 
 namespace {
 bool cyc_size(int nfft) { return nfft >= 64 && nfft <= 16384 && (nfft & (nfft - 1)) == 0; }
@@ -24,12 +24,7 @@ int cyc_check(oth_plan *p, const void *x, size_t nsamples, int nstreams, size_t 
     oth_ctx *c = p->ctx;
     if (int rc = cyc_plan_check(p)) return rc;
     if (!p->ncycles) return fail(c, OTH_ERR_UNSUPPORTED, "the cyclic spectrum needs its cycle frequencies: call oth_welch_set_cycles on this plan");
-    if (!x || !coh_out || nstreams < 1) return fail(c, OTH_ERR_INVALID, "bad argument");
-    if (nstreams > 1 && stride < nsamples) return fail(c, OTH_ERR_INVALID, "stream_stride < nsamples");
-    if (nsamples < (size_t)p->nperseg) return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
-    if (nstreams > 65535) return fail(c, OTH_ERR_UNSUPPORTED, "the cyclic spectrum takes at most 65535 streams per launch");
-    *nseg_out = (long long)((nsamples - (size_t)p->noverlap) / (size_t)p->step);
-    return OTH_OK;
+    return stream_shape(p, x && coh_out, nsamples, nstreams, stride, "the cyclic spectrum takes at most 65535 streams per launch", nseg_out);
 }
 
 // Cycle frequencies per workgroup: welchcyc.hip's three builds (GA = 1, 2, 4).  A grouped build transforms X once per segment
@@ -59,8 +54,7 @@ int cyc_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t s
     const int ga = cyc_group(p, A), G = (A + ga - 1) / ga, R = 1 + 3 * ga;
     // whole segments go to W workgroups per stream and group in contiguous runs: what the device holds at once, a segment at least
     const int bpc = std::max(1, welch_cyc_blocks_per_cu(N, ga));
-    const long long resident = (long long)c->cu_count * bpc;
-    const int W = (int)std::min(nseg, std::max<long long>(1, resident / ((long long)nstreams * G)));
+    const int W = segment_workgroups(c, nseg, 1, (long long)nstreams * G, bpc);
     const size_t slots = (size_t)nstreams * G * W;
     if (int rc = p->d_partial.ensure(c, sizeof(float) * slots * R * N)) return rc;
     if (const size_t pts = welch_cyc_ws_points(N))
@@ -92,21 +86,10 @@ int cyc_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t s
     f.ga = ga;
     f.ncyc = A;
     f.nfft = N;
-    f.fftshift = p->fftshift;
-    f.trim = p->trim;
-    f.db = p->db;
-    f.nout = N - 2 * p->trim;
-    {
-        Timed tm(c);
-        HIPCHK(c, launch_welch_cyc(N, ga, G, a, c->stream));
-    }
-    {
-        Timed tm(c);
-        HIPCHK(c, launch_cyc_finalize(f, nstreams, c->stream));
-    }
-    p->last_recipe = "kernel=welchcyc nfft=" + std::to_string(N) + " W=" + std::to_string(W) + " nseg=" + std::to_string(nseg) +
-                     " nstreams=" + std::to_string(nstreams) + " ncyc=" + std::to_string(A) + " group=" + std::to_string(ga) +
-                     " bpc=" + std::to_string(bpc);
+    f.out = out_stage(p);
+    TIMED_LAUNCH(c, launch_welch_cyc(N, ga, G, a, c->stream));
+    TIMED_LAUNCH(c, launch_cyc_finalize(f, nstreams, c->stream));
+    p->last_recipe = stat_recipe("welchcyc", p, "", W, nseg, nstreams, " ncyc=" + std::to_string(A) + " group=" + std::to_string(ga), bpc);
     return OTH_OK;
 }
 }  // namespace
@@ -133,16 +116,13 @@ int oth_welch_set_cycles(oth_plan *p, int ncycles, const double *alphas) {
             tab[(size_t)a * N + n] = make_float2((float)(w * std::cos(ang)), (float)(-w * std::sin(ang)));
         }
     }
-    if (use_device(c)) return OTH_ERR_HIP;
-    // fresh tables take the place of earlier ones only when they are complete: launches queued on the old ones drain first
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     DevBuf<float2> taps;
     DevBuf<double> alpha;
-    hipError_t e = taps.upload(c, tab.data(), sizeof(float2) * tab.size());
-    if (e == hipSuccess) e = alpha.upload(c, alphas, sizeof(double) * ncycles);
-    const hipError_t es = hipStreamSynchronize(c->stream);      // also after a failure: the host tables die here
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(c, OTH_ERR_HIP, std::string("oth_welch_set_cycles: ") + hipGetErrorString(e));
+    if (int rc = upload_tables(c, "oth_welch_set_cycles", [&] {
+            const hipError_t e = taps.upload(c, tab.data(), sizeof(float2) * tab.size());
+            return e != hipSuccess ? e : alpha.upload(c, alphas, sizeof(double) * ncycles);
+        }))
+        return rc;
     p->d_cyc_tap = std::move(taps);
     p->d_cyc_alpha = std::move(alpha);
     p->ncycles = ncycles;
@@ -168,29 +148,12 @@ int oth_welch_cyclic(oth_plan *p, const void *iq, size_t nsamples, int src_is_de
     OTH_TRY
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    oth_ctx *c = p->ctx;
     long long nseg = 0;
     if (int rc = cyc_check(p, iq, nsamples, 1, nsamples, coh_out, &nseg)) return rc;
-    if (use_device(c)) return OTH_ERR_HIP;
-    const float2 *dx = (const float2 *)iq;
-    int rc;
-    if (!src_is_device) {
-        if ((rc = p->d_stage.ensure(c, nsamples * sizeof(float2)))) return rc;
-        HIPCHK(c, hipMemcpyAsync(p->d_stage.get(), iq, nsamples * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-        dx = p->d_stage.get();
-    }
-    // [A][nout] coh, [A][nout] scf pairs, the PSD row
-    const int N = p->nfft, A = p->ncycles;
-    const size_t nout = (size_t)(N - 2 * p->trim), rows = (size_t)A * nout;
-    if ((rc = p->d_out.ensure(c, sizeof(float) * (3 * rows + nout + 5 * (size_t)N)))) return rc;      // never below the other calls' 5 N
-    float *coh = p->d_out.get(), *scf = coh + rows, *psd = scf + 2 * rows;
-    if ((rc = cyc_run(p, dx, nseg, 1, nsamples, scf_out ? scf : nullptr, coh, psd_out ? psd : nullptr))) return rc;
-    HIPCHK(c, hipMemcpyAsync(coh_out, coh, sizeof(float) * rows, hipMemcpyDeviceToHost, c->stream));
-    if (scf_out) HIPCHK(c, hipMemcpyAsync(scf_out, scf, sizeof(float) * 2 * rows, hipMemcpyDeviceToHost, c->stream));
-    if (psd_out) HIPCHK(c, hipMemcpyAsync(psd_out, psd, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
-    return OTH_OK;
+    const size_t nout = (size_t)(p->nfft - 2 * p->trim), rows_a = (size_t)p->ncycles * nout;
+    const HostRow rows[] = {{coh_out, rows_a}, {scf_out, 2 * rows_a}, {psd_out, nout}};      // [A][nout] coh, [A][nout] scf pairs, the PSD row
+    return host_form(p, iq, nullptr, nsamples, src_is_device, rows, nseg, nseg_out,
+                     [&](const float2 *dx, const float2 *, float *const *dev) { return cyc_run(p, dx, nseg, 1, nsamples, dev[1], dev[0], dev[2]); });
     OTH_CATCH((p ? p->ctx : nullptr))
 }
 }  // extern "C"

@@ -7,7 +7,7 @@
 // trim and dB: the launch oth_welch_exec_dev makes, on the same partial rows, so the same bits.  From the float32 totals
 // the row would be rounded twice.  The Cxy row does not depend on the scale: the reduction that leaves the totals forms
 // it from its double sums in natural order, and the jackknife's finalize launch moves it to the plan's shift and trim.
-#include "abi_state.h"
+#include "abi_stat.h"
 
 namespace {
 // Every refusal of the entry points, in the header's order, before anything is allocated, staged or launched.  `two`: the
@@ -22,16 +22,12 @@ int jack_check(oth_plan *p, bool two, const void *x, const void *y, size_t nsamp
         if (int rc = mtm_csd_gate(p, "oth_mtm_csd_jackknife")) return rc;
     if (!p->mtm_uniform)
         return fail(c, OTH_ERR_UNSUPPORTED, std::string(what) + " needs exchangeable items: the weights of this plan are not all equal");
-    if (nstreams > 65535) return fail(c, OTH_ERR_UNSUPPORTED, "multitaper plans take at most 65535 streams per launch");
-    if (!x || (two && !y) || !need_out || nstreams < 1) return fail(c, OTH_ERR_INVALID, "bad argument");
-    if (nstreams > 1 && stride < nsamples) return fail(c, OTH_ERR_INVALID, "stream_stride < nsamples");
-    if (nsamples < (size_t)p->nperseg) return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
-    const long long nseg = (long long)((nsamples - (size_t)p->noverlap) / (size_t)p->step);
-    const long long items = nseg * p->ntapers, min_items = two ? 3 : 2;
+    if (nstreams > 65535) return fail(c, OTH_ERR_UNSUPPORTED, kMtmTooMany);      // (in front of "bad argument" here)
+    if (int rc = stream_shape(p, x && (!two || y) && need_out, nsamples, nstreams, stride, nullptr, nseg_out)) return rc;
+    const long long items = *nseg_out * p->ntapers, min_items = two ? 3 : 2;
     if (items < min_items)
         return fail(c, OTH_ERR_INVALID, std::string(what) + " needs at least " + std::to_string(min_items) +
                                             " (segment, taper) items: this input holds " + std::to_string(items));
-    *nseg_out = nseg;
     return OTH_OK;
 }
 
@@ -48,17 +44,6 @@ FinalizeArgs pass1_finalize(const oth_plan *p, int W1, int nch) {
     return f;
 }
 
-// the (segment, taper) items of a stream over W workgroups, as mtm_run splits them
-int jack_workgroups(const oth_plan *p, long long nseg, int nstreams, int bpc) {
-    const long long items = nseg * p->ntapers, resident = (long long)p->ctx->cu_count * bpc;
-    return (int)std::min(items, std::max<long long>(p->ntapers, resident / nstreams));
-}
-
-std::string jack_recipe(const char *kernel, const oth_plan *p, int W, long long nseg, int nstreams, int bpc) {
-    return std::string("kernel=") + kernel + " nfft=" + std::to_string(p->nfft) + " ntapers=" + std::to_string(p->ntapers) +
-           " W=" + std::to_string(W) + " nseg=" + std::to_string(nseg) + " nstreams=" + std::to_string(nstreams) + " bpc=" + std::to_string(bpc);
-}
-
 // after jack_check: device in, device out
 int jack_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t stride, float *lnsd_out, float *psd_out) {
     oth_ctx *c = p->ctx;
@@ -67,7 +52,7 @@ int jack_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t 
     // every buffer of both passes is sized before the first launch: ensure() drains the stream when it has to replace one,
     // and between the passes that would make the asynchronous forms wait
     const int bpc = std::max(1, mtm_jack_blocks_per_cu(N));
-    const int W = jack_workgroups(p, nseg, nstreams, bpc);
+    const int W = segment_workgroups(c, nseg * p->ntapers, p->ntapers, nstreams, bpc);      // the items as mtm_run splits them
     if (int rc = p->d_jack_tot.ensure(c, sizeof(float) * (size_t)nstreams * N)) return rc;
     if (int rc = p->d_partial.ensure(c, sizeof(float) * (size_t)nstreams * W * 2 * N)) return rc;
     int W1 = 0;
@@ -90,24 +75,16 @@ int jack_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t 
     const double m = (double)(nseg * p->ntapers);
     JackFinalizeArgs j{};
     j.partial = p->d_partial.get();
-    j.out[0] = lnsd_out;
+    j.sd_out[0] = lnsd_out;
     j.m = m;
     j.mm1_over_m = (m - 1.0) / m;
     j.npairs = 1;
     j.W = W;
     j.nfft = N;
-    j.fftshift = p->fftshift;
-    j.trim = p->trim;
-    j.nout = N - 2 * p->trim;
-    {
-        Timed tm(c);
-        HIPCHK(c, launch_mtm_jack(N, a, c->stream));
-    }
-    {
-        Timed tm(c);
-        HIPCHK(c, launch_jack_finalize(j, nstreams, c->stream));
-    }
-    p->last_recipe = jack_recipe("mtmjack", p, W, nseg, nstreams, bpc);
+    j.out = out_stage(p);
+    TIMED_LAUNCH(c, launch_mtm_jack(N, a, c->stream));
+    TIMED_LAUNCH(c, launch_jack_finalize(j, nstreams, c->stream));
+    p->last_recipe = stat_recipe("mtmjack", p, " ntapers=" + std::to_string(p->ntapers), W, nseg, nstreams, "", bpc);
     return OTH_OK;
 }
 
@@ -117,7 +94,7 @@ int jackcsd_run(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
     if (use_device(c)) return OTH_ERR_HIP;
     const int N = p->nfft;
     const int bpc = std::max(1, mtmcsd_jack_blocks_per_cu(N));      // (both passes' buffers before the first launch, as jack_run)
-    const int W = jack_workgroups(p, nseg, 1, bpc);
+    const int W = segment_workgroups(c, nseg * p->ntapers, p->ntapers, 1, bpc);
     const size_t ws_points = mtmcsd_jack_ws_points(N);
     if (int rc = p->d_jack_tot.ensure(c, sizeof(float) * 5 * (size_t)N)) return rc;
     if (int rc = p->d_partial.ensure(c, sizeof(float) * (size_t)W * 6 * N)) return rc;
@@ -140,9 +117,9 @@ int jackcsd_run(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
     const double m = (double)(nseg * p->ntapers);
     JackFinalizeArgs j{};
     j.partial = p->d_partial.get();
-    j.out[0] = lnsdx_out;
-    j.out[1] = lnsdy_out;
-    j.out[2] = zsd_out;
+    j.sd_out[0] = lnsdx_out;
+    j.sd_out[1] = lnsdy_out;
+    j.sd_out[2] = zsd_out;
     j.cxy_nat = tot + 4 * N;
     j.cxy_out = cxy_out;
     j.m = m;
@@ -150,18 +127,10 @@ int jackcsd_run(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
     j.npairs = 3;
     j.W = W;
     j.nfft = N;
-    j.fftshift = p->fftshift;
-    j.trim = p->trim;
-    j.nout = N - 2 * p->trim;
-    {
-        Timed tm(c);
-        HIPCHK(c, launch_mtmcsd_jack(N, a, c->stream));
-    }
-    {
-        Timed tm(c);
-        HIPCHK(c, launch_jack_finalize(j, 1, c->stream));
-    }
-    p->last_recipe = jack_recipe("mtmcsdjack", p, W, nseg, 1, bpc);
+    j.out = out_stage(p);
+    TIMED_LAUNCH(c, launch_mtmcsd_jack(N, a, c->stream));
+    TIMED_LAUNCH(c, launch_jack_finalize(j, 1, c->stream));
+    p->last_recipe = stat_recipe("mtmcsdjack", p, " ntapers=" + std::to_string(p->ntapers), W, nseg, 1, "", bpc);
     return OTH_OK;
 }
 }  // namespace
@@ -184,26 +153,12 @@ int oth_mtm_jackknife(oth_plan *p, const void *iq, size_t nsamples, int src_is_d
     OTH_TRY
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    oth_ctx *c = p->ctx;
     long long nseg = 0;
     if (int rc = jack_check(p, false, iq, nullptr, nsamples, 1, nsamples, lnsd_out, &nseg)) return rc;
-    if (use_device(c)) return OTH_ERR_HIP;
-    const float2 *dx = (const float2 *)iq;
-    int rc;
-    if (!src_is_device) {
-        if ((rc = p->d_stage.ensure(c, nsamples * sizeof(float2)))) return rc;
-        HIPCHK(c, hipMemcpyAsync(p->d_stage.get(), iq, nsamples * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-        dx = p->d_stage.get();
-    }
-    if ((rc = p->d_out.ensure(c, sizeof(float) * 5 * p->nfft))) return rc;
-    const int N = p->nfft, nout = N - 2 * p->trim;
-    float *o = p->d_out.get();
-    if ((rc = jack_run(p, dx, nseg, 1, nsamples, o, psd_out ? o + N : nullptr))) return rc;
-    HIPCHK(c, hipMemcpyAsync(lnsd_out, o, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
-    if (psd_out) HIPCHK(c, hipMemcpyAsync(psd_out, o + N, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
-    return OTH_OK;
+    const size_t nout = (size_t)(p->nfft - 2 * p->trim);
+    const HostRow rows[] = {{lnsd_out, nout}, {psd_out, nout}};
+    return host_form(p, iq, nullptr, nsamples, src_is_device, rows, nseg, nseg_out,
+                     [&](const float2 *dx, const float2 *, float *const *dev) { return jack_run(p, dx, nseg, 1, nsamples, dev[0], dev[1]); });
     OTH_CATCH((p ? p->ctx : nullptr))
 }
 
@@ -227,31 +182,13 @@ int oth_mtm_csd_jackknife(oth_plan *p, const void *x, const void *y, size_t nsam
     OTH_TRY
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    oth_ctx *c = p->ctx;
     long long nseg = 0;
     if (int rc = jack_check(p, true, x, y, nsamples, 1, nsamples, zsd_out, &nseg)) return rc;
-    if (use_device(c)) return OTH_ERR_HIP;
-    const float2 *dx = (const float2 *)x, *dy = (const float2 *)y;
-    int rc;
-    if (!src_is_device) {
-        const size_t bytes = nsamples * sizeof(float2);
-        if ((rc = p->d_stage.ensure(c, 2 * bytes))) return rc;
-        HIPCHK(c, hipMemcpyAsync(p->d_stage.get(), x, bytes, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(p->d_stage.get() + nsamples, y, bytes, hipMemcpyHostToDevice, c->stream));
-        dx = p->d_stage.get();
-        dy = p->d_stage.get() + nsamples;
-    }
-    if ((rc = p->d_out.ensure(c, sizeof(float) * 5 * p->nfft))) return rc;
-    const int N = p->nfft, nout = N - 2 * p->trim;
-    float *o = p->d_out.get();
-    float *const host[4] = {cxy_out, zsd_out, lnsdx_out, lnsdy_out};
-    if ((rc = jackcsd_run(p, dx, dy, nsamples, nseg, host[0] ? o : nullptr, o + N, host[2] ? o + 2 * N : nullptr, host[3] ? o + 3 * N : nullptr)))
-        return rc;
-    for (int r = 0; r < 4; ++r)
-        if (host[r]) HIPCHK(c, hipMemcpyAsync(host[r], o + (size_t)r * N, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
-    return OTH_OK;
+    const size_t nout = (size_t)(p->nfft - 2 * p->trim);
+    const HostRow rows[] = {{cxy_out, nout}, {zsd_out, nout}, {lnsdx_out, nout}, {lnsdy_out, nout}};
+    return host_form(p, x, y, nsamples, src_is_device, rows, nseg, nseg_out, [&](const float2 *dx, const float2 *dy, float *const *dev) {
+        return jackcsd_run(p, dx, dy, nsamples, nseg, dev[0], dev[1], dev[2], dev[3]);
+    });
     OTH_CATCH((p ? p->ctx : nullptr))
 }
 }  // extern "C"

@@ -1,8 +1,7 @@
 // C ABI, host side: multitaper (Thomson) PSD plans - the Slepian tapers (oth_dpss: host only, double), the plan
 // (oth_mtm_plan: an ordinary oth_plan whose averaging launch is mtm.hip's taper loop; oth_mtm_csd_plan: the same plan with
-// the two-channel calls open, on mtmcsd.hip), that launch (mtm_run, which run_average branches to before any routing) and
-// Thomson's harmonic F-test on any of these plans (oth_mtm_ftest / _dev: mtm_ftest_run on mtmftest.hip).
-#include "abi_state.h"
+// the two-channel calls open, on mtmcsd.hip) and that launch (mtm_run, which run_average branches to before any routing).
+#include "abi_stat.h"
 
 namespace {
 // ---- Slepian tapers ---------------------------------------------------------------------------------------------------------
@@ -162,13 +161,11 @@ int mtm_run(oth_plan *p, const float2 *x, const float2 *y, long long nseg, int n
     const int N = p->nfft, K = p->ntapers;
     const bool csd = y != nullptr;
     const int nch = csd ? 4 : 1;
-    if (nstreams > 65535) return fail(c, OTH_ERR_UNSUPPORTED, "multitaper plans take at most 65535 streams per launch");
+    if (nstreams > 65535) return fail(c, OTH_ERR_UNSUPPORTED, kMtmTooMany);
     // the (segment, taper) items of a stream go to W workgroups in contiguous runs: one workgroup per taper at least (a
     // single segment spreads over K of them), and for long launches what the device holds at once
-    const long long items = nseg * K;
     const int bpc = std::max(1, csd ? mtmcsd_blocks_per_cu(N) : mtm_blocks_per_cu(N));
-    const long long resident = (long long)c->cu_count * bpc;
-    const int W = (int)std::min(items, std::max<long long>(K, resident / nstreams));
+    const int W = segment_workgroups(c, nseg * K, K, nstreams, bpc);
     int rc = p->d_partial.ensure(c, sizeof(float) * (size_t)nstreams * W * nch * N);
     {
         const int groups = std::max(kReduceGroups, finalize_row_groups(N, W, nch));
@@ -182,69 +179,9 @@ int mtm_run(oth_plan *p, const float2 *x, const float2 *y, long long nseg, int n
     a = mtm_args(p, x, nseg, nstreams, stride, W);
     g.y = y;
     g.ws = ws_points ? p->d_mtm_ws.get() : nullptr;
-    {
-        Timed tm(c);
-        HIPCHK(c, csd ? launch_mtmcsd(N, g, c->stream) : launch_mtm(N, a, c->stream));
-    }
-    p->last_recipe = std::string(csd ? "kernel=mtmcsd" : "kernel=mtm") + " nfft=" + std::to_string(N) + " ntapers=" + std::to_string(K) +
-                     " W=" + std::to_string(W) + " nseg=" + std::to_string(nseg) + " nstreams=" + std::to_string(nstreams) +
-                     " bpc=" + std::to_string(bpc);
+    TIMED_LAUNCH(c, csd ? launch_mtmcsd(N, g, c->stream) : launch_mtm(N, a, c->stream));
+    p->last_recipe = stat_recipe(csd ? "mtmcsd" : "mtm", p, " ntapers=" + std::to_string(K), W, nseg, nstreams, "", bpc);
     *W_out = W;
-    return OTH_OK;
-}
-
-// The harmonic F-test of a multitaper plan: the segment-per-workgroup taper loop of mtmftest.hip, then its finalize launch
-// into the three output rows (device memory; line / resid may be null).
-int mtm_ftest_run(oth_plan *p, const float2 *x, size_t nsamples, int nstreams, size_t stride, float *f_out, float *line_out,
-                  float *resid_out, uint64_t *nseg_out) {
-    oth_ctx *c = p->ctx;
-    if (!p->ntapers) return fail(c, OTH_ERR_UNSUPPORTED, "the harmonic F-test needs a multitaper plan (oth_mtm_plan): this plan has no tapers");
-    if (p->ntapers < 2) return fail(c, OTH_ERR_UNSUPPORTED, "the harmonic F-test needs at least two tapers");
-    if (!(p->mtm_s > 0.0)) return fail(c, OTH_ERR_UNSUPPORTED, "the harmonic F-test needs tapers with a non-zero sum: every U_k of this plan is zero");
-    if (!x || !f_out || nstreams < 1) return fail(c, OTH_ERR_INVALID, "bad argument");
-    if (nstreams > 1 && stride < nsamples) return fail(c, OTH_ERR_INVALID, "stream_stride < nsamples");
-    if (nsamples < (size_t)p->nperseg) return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
-    if (nstreams > 65535) return fail(c, OTH_ERR_UNSUPPORTED, "multitaper plans take at most 65535 streams per launch");
-    if (use_device(c)) return OTH_ERR_HIP;
-    const int N = p->nfft, K = p->ntapers;
-    const long long nseg = (long long)((nsamples - (size_t)p->noverlap) / (size_t)p->step);
-    // whole segments go to W workgroups per stream in contiguous runs: what the device holds at once, a segment at least
-    const int bpc = std::max(1, mtm_ftest_blocks_per_cu(N));
-    const long long resident = (long long)c->cu_count * bpc;
-    const int W = (int)std::min(nseg, std::max<long long>(1, resident / nstreams));
-    int rc = p->d_partial.ensure(c, sizeof(float) * (size_t)nstreams * W * 2 * N);
-    const size_t ws_floats = mtm_ftest_ws_floats(N);
-    if (!rc && ws_floats) rc = p->d_ftest_ws.ensure(c, sizeof(float) * (size_t)nstreams * W * ws_floats);
-    if (rc) return rc;
-    MtmFtestArgs g{};
-    g.m = mtm_args(p, x, nseg, nstreams, stride, W);
-    g.u = p->d_mtm_u.get();
-    g.inv_s = (float)(1.0 / p->mtm_s);
-    g.ws = ws_floats ? p->d_ftest_ws.get() : nullptr;
-    FtestFinalizeArgs f{};
-    f.partial = p->d_partial.get();
-    f.f_out = f_out;
-    f.line_out = line_out;
-    f.resid_out = resid_out;
-    f.km1 = (double)(K - 1);
-    f.line_scale = 1.0 / (p->mtm_s * (double)nseg);
-    f.resid_scale = p->scale / ((double)(K - 1) * (double)nseg);
-    f.W = W;
-    f.nfft = N;
-    f.fftshift = p->fftshift;
-    f.trim = p->trim;
-    f.nout = N - 2 * p->trim;
-    {
-        Timed tm(c);
-        HIPCHK(c, launch_mtm_ftest(N, g, c->stream));
-    }
-    {
-        Timed tm(c);
-        HIPCHK(c, launch_ftest_finalize(f, nstreams, c->stream));
-    }
-    p->last_recipe = "kernel=mtmftest nfft=" + std::to_string(N) + " ntapers=" + std::to_string(K) + " W=" + std::to_string(W) +
-                     " nseg=" + std::to_string(nseg) + " nstreams=" + std::to_string(nstreams) + " bpc=" + std::to_string(bpc);
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
     return OTH_OK;
 }
 }  // namespace oth
@@ -386,44 +323,5 @@ int oth_mtm_csd_plan(oth_ctx *c, int nfft, int nperseg, int noverlap, int ntaper
     CtxGuard guard_(c);
     return mtm_plan_create(c, nfft, nperseg, noverlap, ntapers, tapers, weights, detrend, scaling, fs, fftshift, trim_bins, true, out);
     OTH_CATCH(c)
-}
-
-int oth_mtm_ftest_dev(oth_plan *p, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride, float *f_out_dev,
-                      float *line_out_dev, float *resid_out_dev, uint64_t *nseg_out) {
-    OTH_TRY
-    CtxGuard guard_(p ? p->ctx : nullptr);
-    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    return mtm_ftest_run(p, (const float2 *)iq_dev, nsamples, nstreams, stream_stride, f_out_dev, line_out_dev, resid_out_dev, nseg_out);
-    OTH_CATCH((p ? p->ctx : nullptr))
-}
-
-int oth_mtm_ftest(oth_plan *p, const void *iq, size_t nsamples, int src_is_device, float *f_out, float *line_out, float *resid_out,
-                  uint64_t *nseg_out) {
-    OTH_TRY
-    CtxGuard guard_(p ? p->ctx : nullptr);
-    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    oth_ctx *c = p->ctx;
-    if (!iq || !f_out) return fail(c, OTH_ERR_INVALID, "bad argument");
-    if (p->ntapers < 2 || !(p->mtm_s > 0.0) || nsamples < (size_t)p->nperseg)      // refused before anything is staged
-        return mtm_ftest_run(p, (const float2 *)iq, nsamples, 1, nsamples, f_out, line_out, resid_out, nseg_out);
-    if (use_device(c)) return OTH_ERR_HIP;
-    const float2 *dx = (const float2 *)iq;
-    int rc;
-    if (!src_is_device) {
-        if ((rc = p->d_stage.ensure(c, nsamples * sizeof(float2)))) return rc;
-        HIPCHK(c, hipMemcpyAsync(p->d_stage.get(), iq, nsamples * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-        dx = p->d_stage.get();
-    }
-    if ((rc = p->d_out.ensure(c, sizeof(float) * 5 * p->nfft))) return rc;
-    const int N = p->nfft, nout = N - 2 * p->trim;
-    float *o = p->d_out.get();
-    if ((rc = mtm_ftest_run(p, dx, nsamples, 1, nsamples, o, line_out ? o + N : nullptr, resid_out ? o + 2 * N : nullptr, nseg_out)))
-        return rc;
-    HIPCHK(c, hipMemcpyAsync(f_out, o, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
-    if (line_out) HIPCHK(c, hipMemcpyAsync(line_out, o + N, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
-    if (resid_out) HIPCHK(c, hipMemcpyAsync(resid_out, o + 2 * N, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return OTH_OK;
-    OTH_CATCH((p ? p->ctx : nullptr))
 }
 }  // extern "C"

@@ -1,6 +1,6 @@
 // C ABI, host side: spectral kurtosis of a Welch plan (oth_welch_sk / _dev) - the checks, the segment-per-workgroup launch
 // of welchsk.hip and its finalize launch into the SK row and, where asked for, the PSD row.
-#include "abi_state.h"
+#include "abi_stat.h"
 
 namespace {
 bool sk_size(int nfft) { return nfft >= 64 && nfft <= 16384 && (nfft & (nfft - 1)) == 0; }
@@ -15,13 +15,9 @@ int sk_check(oth_plan *p, const void *x, size_t nsamples, int nstreams, size_t s
     if (!sk_size(p->nfft))
         return fail(c, OTH_ERR_UNSUPPORTED, "the spectral kurtosis takes a transform length that is a power of two from 64 to 16384, not " +
                                                 std::to_string(p->nfft));
-    if (!x || !sk_out || nstreams < 1) return fail(c, OTH_ERR_INVALID, "bad argument");
-    if (nstreams > 1 && stride < nsamples) return fail(c, OTH_ERR_INVALID, "stream_stride < nsamples");
-    if (nsamples < (size_t)p->nperseg) return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
-    if (nstreams > 65535) return fail(c, OTH_ERR_UNSUPPORTED, "the spectral kurtosis takes at most 65535 streams per launch");
-    const long long nseg = (long long)((nsamples - (size_t)p->noverlap) / (size_t)p->step);
-    if (nseg < 2) return fail(c, OTH_ERR_INVALID, "the spectral kurtosis needs at least two segments: this input holds one");
-    *nseg_out = nseg;
+    if (int rc = stream_shape(p, x && sk_out, nsamples, nstreams, stride, "the spectral kurtosis takes at most 65535 streams per launch", nseg_out))
+        return rc;
+    if (*nseg_out < 2) return fail(c, OTH_ERR_INVALID, "the spectral kurtosis needs at least two segments: this input holds one");
     return OTH_OK;
 }
 
@@ -32,8 +28,7 @@ int sk_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t st
     const int N = p->nfft;
     // whole segments go to W workgroups per stream in contiguous runs: what the device holds at once, a segment at least
     const int bpc = std::max(1, welch_sk_blocks_per_cu(N));
-    const long long resident = (long long)c->cu_count * bpc;
-    const int W = (int)std::min(nseg, std::max<long long>(1, resident / nstreams));
+    const int W = segment_workgroups(c, nseg, 1, nstreams, bpc);
     if (int rc = p->d_partial.ensure(c, sizeof(float) * (size_t)nstreams * W * 2 * N)) return rc;
     WelchSkArgs a{};
     a.x = x;
@@ -57,20 +52,10 @@ int sk_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t st
     f.psd_scale = p->scale / ((double)a.g * (double)nseg);      // the float the kernel multiplied by: it cancels
     f.W = W;
     f.nfft = N;
-    f.fftshift = p->fftshift;
-    f.trim = p->trim;
-    f.db = p->db;
-    f.nout = N - 2 * p->trim;
-    {
-        Timed tm(c);
-        HIPCHK(c, launch_welch_sk(N, a, c->stream));
-    }
-    {
-        Timed tm(c);
-        HIPCHK(c, launch_sk_finalize(f, nstreams, c->stream));
-    }
-    p->last_recipe = "kernel=welchsk nfft=" + std::to_string(N) + " W=" + std::to_string(W) + " nseg=" + std::to_string(nseg) +
-                     " nstreams=" + std::to_string(nstreams) + " bpc=" + std::to_string(bpc);
+    f.out = out_stage(p);
+    TIMED_LAUNCH(c, launch_welch_sk(N, a, c->stream));
+    TIMED_LAUNCH(c, launch_sk_finalize(f, nstreams, c->stream));
+    p->last_recipe = stat_recipe("welchsk", p, "", W, nseg, nstreams, "", bpc);
     return OTH_OK;
 }
 }  // namespace
@@ -93,26 +78,12 @@ int oth_welch_sk(oth_plan *p, const void *iq, size_t nsamples, int src_is_device
     OTH_TRY
     CtxGuard guard_(p ? p->ctx : nullptr);
     if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    oth_ctx *c = p->ctx;
     long long nseg = 0;
     if (int rc = sk_check(p, iq, nsamples, 1, nsamples, sk_out, &nseg)) return rc;
-    if (use_device(c)) return OTH_ERR_HIP;
-    const float2 *dx = (const float2 *)iq;
-    int rc;
-    if (!src_is_device) {
-        if ((rc = p->d_stage.ensure(c, nsamples * sizeof(float2)))) return rc;
-        HIPCHK(c, hipMemcpyAsync(p->d_stage.get(), iq, nsamples * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-        dx = p->d_stage.get();
-    }
-    if ((rc = p->d_out.ensure(c, sizeof(float) * 5 * p->nfft))) return rc;
-    const int N = p->nfft, nout = N - 2 * p->trim;
-    float *o = p->d_out.get();
-    if ((rc = sk_run(p, dx, nseg, 1, nsamples, o, psd_out ? o + N : nullptr))) return rc;
-    HIPCHK(c, hipMemcpyAsync(sk_out, o, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
-    if (psd_out) HIPCHK(c, hipMemcpyAsync(psd_out, o + N, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
-    return OTH_OK;
+    const size_t nout = (size_t)(p->nfft - 2 * p->trim);
+    const HostRow rows[] = {{sk_out, nout}, {psd_out, nout}};
+    return host_form(p, iq, nullptr, nsamples, src_is_device, rows, nseg, nseg_out,
+                     [&](const float2 *dx, const float2 *, float *const *dev) { return sk_run(p, dx, nseg, 1, nsamples, dev[0], dev[1]); });
     OTH_CATCH((p ? p->ctx : nullptr))
 }
 }  // extern "C"

@@ -117,24 +117,18 @@ size_t mtm_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedS
 #define OTH_MTM_KERNEL(N) mtm_kernel<N, generic_threads(N), mtm_keep(N)>
 
 int mtm_blocks_per_cu(int nfft) {
-    switch (nfft) {
-#define X(N) \
-    case N: return resident_blocks<OTH_MTM_KERNEL(N)>(generic_threads(N), mtm_lds_bytes(N), 0);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return 0;
-    }
+    return mtm_for_size(nfft, 0, [](auto n) {
+        constexpr int N = decltype(n)::value;
+        return resident_blocks<OTH_MTM_KERNEL(N)>(generic_threads(N), mtm_lds_bytes(N), 0);
+    });
 }
 
 hipError_t launch_mtm(int nfft, const MtmArgs &a, hipStream_t s) {
     const dim3 grid(a.wg_per_stream, a.nstreams);
-    switch (nfft) {
-#define X(N) \
-    case N: return launch_lds<OTH_MTM_KERNEL(N)>(grid, dim3(generic_threads(N)), mtm_lds_bytes(N), s, a);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return hipErrorInvalidValue;
-    }
+    return mtm_for_size(nfft, hipErrorInvalidValue, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        return launch_lds<OTH_MTM_KERNEL(N)>(grid, dim3(generic_threads(N)), mtm_lds_bytes(N), s, a);
+    });
 }
 
 }  // namespace oth

@@ -6,6 +6,8 @@
 #pragma once
 #include "fft_lds.hip.h"
 
+#include <type_traits>
+
 namespace oth {
 
 __device__ __forceinline__ float2 mtm_wave_sum(float2 v) {
@@ -98,5 +100,17 @@ constexpr bool mtm_keep(int n) { return n < 8192; }      // mtm.hip's header: KE
 constexpr int kMtmRedSlots = 32;                         // float2 slots of one `red` array (T / 64 + 1 <= 17 used)
 
 #define OTH_MTM_FOR_EACH_N(X) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192) X(16384)
+
+// f(std::integral_constant<int, N>) of the listed size nfft, `otherwise` for any other: the dispatch behind a kernel file's
+// *_blocks_per_cu(nfft) and launch_*(nfft, ...), whose lambdas name the build of size N = decltype(n)::value.
+template <typename R, typename F> R mtm_for_size(int nfft, R otherwise, F f) {
+    switch (nfft) {
+#define X(N) \
+    case N: return f(std::integral_constant<int, N>{});
+        OTH_MTM_FOR_EACH_N(X)
+#undef X
+        default: return otherwise;
+    }
+}
 
 }  // namespace oth

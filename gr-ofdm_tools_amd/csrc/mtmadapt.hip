@@ -39,7 +39,7 @@
 // a run's segments cannot be registers either (indexed by the loop): they live in the workgroup's own partial rows, as in
 // mtm_ftest_kernel from 4096 points on - the first segment of a run stores, every later one reads, adds and stores.
 #include "mtm_common.hip.h"
-#include "oth_internal.h"
+#include "stat_finalize.hip.h"
 #include "launch.h"
 
 #include <algorithm>
@@ -178,41 +178,17 @@ __global__ __launch_bounds__(T) void mtm_adapt_kernel(MtmAdaptArgs a) {
     }
 }
 
-// 256 threads = 32 consecutive bins x 8 slices of the workgroup axis (ftest_finalize_kernel's shape): slice sums in double,
-// combined in a fixed order; then the two rows with the plan's shift and trim, the PSD row with its dB.
+// The shared finalize stage (stat_finalize.hip.h) on the two rows sum S_s, sum nu_s; then the PSD row with its dB and the dof row.
 __global__ __launch_bounds__(256) void adapt_finalize_kernel(AdaptFinalizeArgs a) {
-    __shared__ double red[2][8][32];
-    const int lane = threadIdx.x & 31, slice = threadIdx.x >> 5;
-    const int k = blockIdx.x * 32 + lane;
-    const int stream = blockIdx.y;
-    int ks = k;
-    if (a.fftshift) {
-        ks = k + a.nfft / 2;
-        if (ks >= a.nfft) ks -= a.nfft;
-    }
-    const int i = ks - a.trim;
-    const bool live = k < a.nfft && i >= 0 && i < a.nout;
+    const int k = blockIdx.x * 32 + (threadIdx.x & 31), stream = blockIdx.y;
+    int i;
+    const bool live = out_slot(a.out, a.nfft, k, i);
     const float *base = a.partial + (size_t)stream * a.W * 2 * a.nfft + k;
-    double t1 = 0.0, t2 = 0.0;
-    if (live) {
-        for (int w = slice; w < a.W; w += 8) {
-            t1 += (double)base[(size_t)w * 2 * a.nfft];
-            t2 += (double)base[((size_t)w * 2 + 1) * a.nfft];
-        }
-    }
-    red[0][slice][lane] = t1;
-    red[1][slice][lane] = t2;
-    __syncthreads();
-    if (slice != 0 || !live) return;
-    t1 = t2 = 0.0;
-    for (int q = 0; q < 8; ++q) {
-        t1 += red[0][q][lane];
-        t2 += red[1][q][lane];
-    }
-    const size_t o = (size_t)stream * a.nout + i;
-    const double v = t1 * a.psd_scale;
-    a.psd_out[o] = a.db ? (float)(10.0 * log10(v)) : (float)v;      // finalize_kernel's output stage
-    if (a.dof_out) a.dof_out[o] = (float)(t2 * a.inv_nseg);
+    double t[2];
+    if (!slice_sums<2>(live, a.W, [&](int w, int r) { return base[((size_t)w * 2 + r) * a.nfft]; }, t)) return;
+    const size_t o = (size_t)stream * a.out.nout + i;
+    a.psd_out[o] = psd_value(a.out, t[0] * a.psd_scale);
+    if (a.dof_out) a.dof_out[o] = (float)(t[1] * a.inv_nseg);
 }
 
 // the transform buffer and the two `red` arrays; the occupancy calculator is asked about this much
@@ -261,9 +237,7 @@ hipError_t launch_mtm_adapt(int nfft, const MtmAdaptArgs &a, hipStream_t s) {
 }
 
 hipError_t launch_adapt_finalize(const AdaptFinalizeArgs &a, int nstreams, hipStream_t s) {
-    const dim3 grid((a.nfft + 31) / 32, nstreams);
-    hipLaunchKernelGGL(adapt_finalize_kernel, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return launch_stat_finalize<adapt_finalize_kernel>(a, nstreams, 1, s);
 }
 
 }  // namespace oth

@@ -188,24 +188,18 @@ constexpr int mtmcsd_threads(int n) { return n == 4096 ? 512 : n == 8192 ? 1024 
 size_t mtmcsd_ws_points(int nfft) { return mtmcsd_two_buffers(nfft) ? 0 : (size_t)nfft; }
 
 int mtmcsd_blocks_per_cu(int nfft) {
-    switch (nfft) {
-#define X(N) \
-    case N: return resident_blocks<OTH_MTMCSD_KERNEL(N)>(mtmcsd_threads(N), mtmcsd_lds_bytes(N), 0);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return 0;
-    }
+    return mtm_for_size(nfft, 0, [](auto n) {
+        constexpr int N = decltype(n)::value;
+        return resident_blocks<OTH_MTMCSD_KERNEL(N)>(mtmcsd_threads(N), mtmcsd_lds_bytes(N), 0);
+    });
 }
 
 hipError_t launch_mtmcsd(int nfft, const MtmCsdArgs &a, hipStream_t s) {
     const dim3 grid(a.m.wg_per_stream, a.m.nstreams);
-    switch (nfft) {
-#define X(N) \
-    case N: return launch_lds<OTH_MTMCSD_KERNEL(N)>(grid, dim3(mtmcsd_threads(N)), mtmcsd_lds_bytes(N), s, a);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return hipErrorInvalidValue;
-    }
+    return mtm_for_size(nfft, hipErrorInvalidValue, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        return launch_lds<OTH_MTMCSD_KERNEL(N)>(grid, dim3(mtmcsd_threads(N)), mtmcsd_lds_bytes(N), s, a);
+    });
 }
 
 }  // namespace oth

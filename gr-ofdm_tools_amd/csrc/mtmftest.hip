@@ -23,7 +23,7 @@
 //                                     read, add and store, the last one reads and closes the segment; again every thread
 //                                     its own addresses, so no barrier, and the rows stay in L2.
 #include "mtm_common.hip.h"
-#include "oth_internal.h"
+#include "stat_finalize.hip.h"
 #include "launch.h"
 
 namespace oth {
@@ -183,43 +183,21 @@ __global__ __launch_bounds__(T) void mtm_ftest_kernel(MtmFtestArgs a) {
     }
 }
 
-// 256 threads = 32 consecutive bins x 8 slices of the workgroup axis (finalize_kernel's shape): slice sums in double,
-// combined in a fixed order; then the three rows with the plan's shift and trim.
+// The shared finalize stage (stat_finalize.hip.h) on the two rows sum num, sum den; then the three rows.
 __global__ __launch_bounds__(256) void ftest_finalize_kernel(FtestFinalizeArgs a) {
-    __shared__ double red[2][8][32];
-    const int lane = threadIdx.x & 31, slice = threadIdx.x >> 5;
-    const int k = blockIdx.x * 32 + lane;
-    const int stream = blockIdx.y;
-    int ks = k;
-    if (a.fftshift) {
-        ks = k + a.nfft / 2;
-        if (ks >= a.nfft) ks -= a.nfft;
-    }
-    const int i = ks - a.trim;
-    const bool live = k < a.nfft && i >= 0 && i < a.nout;
+    const int k = blockIdx.x * 32 + (threadIdx.x & 31), stream = blockIdx.y;
+    int i;
+    const bool live = out_slot(a.out, a.nfft, k, i);
     const float *base = a.partial + (size_t)stream * a.W * 2 * a.nfft + k;
-    double sn = 0.0, sd = 0.0;
-    if (live) {
-        for (int w = slice; w < a.W; w += 8) {
-            sn += (double)base[(size_t)w * 2 * a.nfft];
-            sd += (double)base[((size_t)w * 2 + 1) * a.nfft];
-        }
-    }
-    red[0][slice][lane] = sn;
-    red[1][slice][lane] = sd;
-    __syncthreads();
-    if (slice != 0 || !live) return;
-    sn = sd = 0.0;
-    for (int q = 0; q < 8; ++q) {
-        sn += red[0][q][lane];
-        sd += red[1][q][lane];
-    }
+    double t[2];
+    if (!slice_sums<2>(live, a.W, [&](int w, int r) { return base[((size_t)w * 2 + r) * a.nfft]; }, t)) return;
+    const double sn = t[0], sd = t[1];
     // degenerate bins: nothing left beside the line (or nothing at all) - no 0 / 0, and no negative power
     float f;
     if (sd > 0.0) f = (float)(a.km1 * sn / sd);
     else if (sd <= 0.0) f = sn > 0.0 ? __builtin_inff() : 0.f;
     else f = __builtin_nanf("");      // non-finite input
-    const size_t o = (size_t)stream * a.nout + i;
+    const size_t o = (size_t)stream * a.out.nout + i;
     a.f_out[o] = f;
     if (a.line_out) a.line_out[o] = (float)(sn * a.line_scale);
     if (a.resid_out) a.resid_out[o] = (float)(sd > 0.0 || sd != sd ? sd * a.resid_scale : 0.0);
@@ -234,30 +212,22 @@ size_t ftest_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRe
 size_t mtm_ftest_ws_floats(int nfft) { return ftest_segreg(nfft) ? 0 : 3 * (size_t)nfft; }
 
 int mtm_ftest_blocks_per_cu(int nfft) {
-    switch (nfft) {
-#define X(N) \
-    case N: return resident_blocks<OTH_FTEST_KERNEL(N)>(generic_threads(N), ftest_lds_bytes(N), 0);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return 0;
-    }
+    return mtm_for_size(nfft, 0, [](auto n) {
+        constexpr int N = decltype(n)::value;
+        return resident_blocks<OTH_FTEST_KERNEL(N)>(generic_threads(N), ftest_lds_bytes(N), 0);
+    });
 }
 
 hipError_t launch_mtm_ftest(int nfft, const MtmFtestArgs &a, hipStream_t s) {
     const dim3 grid(a.m.wg_per_stream, a.m.nstreams);
-    switch (nfft) {
-#define X(N) \
-    case N: return launch_lds<OTH_FTEST_KERNEL(N)>(grid, dim3(generic_threads(N)), ftest_lds_bytes(N), s, a);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return hipErrorInvalidValue;
-    }
+    return mtm_for_size(nfft, hipErrorInvalidValue, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        return launch_lds<OTH_FTEST_KERNEL(N)>(grid, dim3(generic_threads(N)), ftest_lds_bytes(N), s, a);
+    });
 }
 
 hipError_t launch_ftest_finalize(const FtestFinalizeArgs &a, int nstreams, hipStream_t s) {
-    const dim3 grid((a.nfft + 31) / 32, nstreams);
-    hipLaunchKernelGGL(ftest_finalize_kernel, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return launch_stat_finalize<ftest_finalize_kernel>(a, nstreams, 1, s);
 }
 
 }  // namespace oth

@@ -26,7 +26,7 @@
 //                  X's spectrum through the workgroup's own global workspace row.
 // The totals are read again per item (L2), never held.
 #include "mtm_common.hip.h"
-#include "oth_internal.h"
+#include "stat_finalize.hip.h"
 #include "launch.h"
 
 #include <type_traits>
@@ -233,42 +233,31 @@ template <int N, int T, bool KEEP, bool TWO, bool ACCREG> __global__ __launch_bo
     }
 }
 
-// 256 threads = 32 consecutive bins x 8 slices of the workgroup axis (ftest_finalize_kernel's shape): slice sums in double,
-// combined in a fixed order; then the variances in double and the rows with the plan's shift and trim.  The Cxy row is
-// the first pass's (its reduction formed it from the double sums, natural order): it only takes the shift and trim here.
-__global__ __launch_bounds__(256) void jack_finalize_kernel(JackFinalizeArgs a) {
-    __shared__ double red[6][8][32];
-    const int lane = threadIdx.x & 31, slice = threadIdx.x >> 5;
-    const int k = blockIdx.x * 32 + lane;
-    const int stream = blockIdx.y;
-    int ks = k;
-    if (a.fftshift) {
-        ks = k + a.nfft / 2;
-        if (ks >= a.nfft) ks -= a.nfft;
-    }
-    const int i = ks - a.trim;
-    const bool live = k < a.nfft && i >= 0 && i < a.nout;
-    const int nrows = 2 * a.npairs;
-    const float *base = a.partial + (size_t)stream * a.W * nrows * a.nfft + k;
-    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (live) {
-        for (int w = slice; w < a.W; w += 8)
-            for (int r = 0; r < nrows; ++r) s[r] += (double)base[((size_t)w * nrows + r) * a.nfft];
-    }
-    for (int r = 0; r < nrows; ++r) red[r][slice][lane] = s[r];
-    __syncthreads();
-    if (slice != 0 || !live) return;
-    const size_t o = (size_t)stream * a.nout + i;
-    for (int pr = 0; pr < a.npairs; ++pr) {
-        double t1 = 0.0, t2 = 0.0;
-        for (int q = 0; q < 8; ++q) {
-            t1 += red[2 * pr][q][lane];
-            t2 += red[2 * pr + 1][q][lane];
-        }
+// The shared finalize stage (stat_finalize.hip.h) on the 2 npairs rows sum l, sum l^2; then the variances in double and
+// their rows.  The Cxy row is the first pass's (its reduction formed it from the double sums, natural order): it only takes
+// the shift and trim here.
+template <int NP> __device__ __forceinline__ void jack_finalize(const JackFinalizeArgs &a) {
+    const int k = blockIdx.x * 32 + (threadIdx.x & 31), stream = blockIdx.y;
+    int i;
+    const bool live = out_slot(a.out, a.nfft, k, i);
+    constexpr int R = 2 * NP;
+    const float *base = a.partial + (size_t)stream * a.W * R * a.nfft + k;
+    double t[R];
+    if (!slice_sums<R>(live, a.W, [&](int w, int r) { return base[((size_t)w * R + r) * a.nfft]; }, t)) return;
+    const size_t o = (size_t)stream * a.out.nout + i;
+#pragma unroll
+    for (int pr = 0; pr < NP; ++pr) {
+        const double t1 = t[2 * pr], t2 = t[2 * pr + 1];
         const double var = a.mm1_over_m * (t2 - t1 * t1 / a.m);
-        if (a.out[pr]) a.out[pr][o] = var > 0.0 ? (float)sqrt(var) : 0.f;      // (a NaN reads 0 as well)
+        if (a.sd_out[pr]) a.sd_out[pr][o] = var > 0.0 ? (float)sqrt(var) : 0.f;      // (a NaN reads 0 as well)
     }
     if (a.cxy_out) a.cxy_out[o] = a.cxy_nat[(size_t)stream * a.nfft + k];
+}
+
+// npairs is 1 (one channel) or 3 (two): the same for every thread of the launch
+__global__ __launch_bounds__(256) void jack_finalize_kernel(JackFinalizeArgs a) {
+    if (a.npairs == 1) jack_finalize<1>(a);
+    else jack_finalize<3>(a);
 }
 
 size_t jack_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedSlots * sizeof(float2); }
@@ -290,51 +279,37 @@ size_t jackcsd_lds_bytes(int nfft) {
 size_t mtmcsd_jack_ws_points(int nfft) { return jackcsd_two_buffers(nfft) ? 0 : (size_t)nfft; }
 
 int mtm_jack_blocks_per_cu(int nfft) {
-    switch (nfft) {
-#define X(N) \
-    case N: return resident_blocks<OTH_JACK_KERNEL(N)>(generic_threads(N), jack_lds_bytes(N), 0);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return 0;
-    }
+    return mtm_for_size(nfft, 0, [](auto n) {
+        constexpr int N = decltype(n)::value;
+        return resident_blocks<OTH_JACK_KERNEL(N)>(generic_threads(N), jack_lds_bytes(N), 0);
+    });
 }
 
 hipError_t launch_mtm_jack(int nfft, const MtmJackArgs &a, hipStream_t s) {
     const dim3 grid(a.m.wg_per_stream, a.m.nstreams);
-    switch (nfft) {
-#define X(N) \
-    case N: return launch_lds<OTH_JACK_KERNEL(N)>(grid, dim3(generic_threads(N)), jack_lds_bytes(N), s, a);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return hipErrorInvalidValue;
-    }
+    return mtm_for_size(nfft, hipErrorInvalidValue, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        return launch_lds<OTH_JACK_KERNEL(N)>(grid, dim3(generic_threads(N)), jack_lds_bytes(N), s, a);
+    });
 }
 
 int mtmcsd_jack_blocks_per_cu(int nfft) {
-    switch (nfft) {
-#define X(N) \
-    case N: return resident_blocks<OTH_JACKCSD_KERNEL(N)>(jackcsd_threads(N), jackcsd_lds_bytes(N), 0);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return 0;
-    }
+    return mtm_for_size(nfft, 0, [](auto n) {
+        constexpr int N = decltype(n)::value;
+        return resident_blocks<OTH_JACKCSD_KERNEL(N)>(jackcsd_threads(N), jackcsd_lds_bytes(N), 0);
+    });
 }
 
 hipError_t launch_mtmcsd_jack(int nfft, const MtmCsdJackArgs &a, hipStream_t s) {
     const dim3 grid(a.c.m.wg_per_stream, a.c.m.nstreams);
-    switch (nfft) {
-#define X(N) \
-    case N: return launch_lds<OTH_JACKCSD_KERNEL(N)>(grid, dim3(jackcsd_threads(N)), jackcsd_lds_bytes(N), s, a);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return hipErrorInvalidValue;
-    }
+    return mtm_for_size(nfft, hipErrorInvalidValue, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        return launch_lds<OTH_JACKCSD_KERNEL(N)>(grid, dim3(jackcsd_threads(N)), jackcsd_lds_bytes(N), s, a);
+    });
 }
 
 hipError_t launch_jack_finalize(const JackFinalizeArgs &a, int nstreams, hipStream_t s) {
-    const dim3 grid((a.nfft + 31) / 32, nstreams);
-    hipLaunchKernelGGL(jack_finalize_kernel, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return launch_stat_finalize<jack_finalize_kernel>(a, nstreams, 1, s);
 }
 
 }  // namespace oth

@@ -393,6 +393,13 @@ size_t mtmcsd_ws_points(int nfft);      // 0: the build keeps both spectra in LD
 int mtmcsd_blocks_per_cu(int nfft);
 hipError_t launch_mtmcsd(int nfft, const MtmCsdArgs &a, hipStream_t s);
 
+// ---- the output stage of a statistic's finalize launch (stat_finalize.hip.h; abi_stat.h fills it from the plan) -------------
+struct OutStage {
+    int fftshift, trim;
+    int db;                 // the PSD rows only (psd_value)
+    int nout;               // nfft - 2 trim
+};
+
 // ---- mtmftest.hip: Thomson's harmonic F-test on the same taper loop; the work item is a whole segment ------------------
 struct MtmFtestArgs {
     MtmArgs m;              // x, the tables and the sizes as mtm.hip's (coef unused); wg_per_stream: each workgroup walks a
@@ -409,7 +416,8 @@ struct FtestFinalizeArgs {
     double km1;             // K - 1
     double line_scale;      // 1 / (S nseg)
     double resid_scale;     // scale / ((K - 1) nseg)
-    int W, nfft, fftshift, trim, nout;
+    int W, nfft;
+    OutStage out;
 };
 size_t mtm_ftest_ws_floats(int nfft);      // 0: the build keeps sy / p in registers
 int mtm_ftest_blocks_per_cu(int nfft);
@@ -427,13 +435,14 @@ struct MtmCsdJackArgs {
 };
 struct JackFinalizeArgs {
     const float *partial;   // [nstreams][W][2 npairs][nfft], natural bin order
-    float *out[3];          // [nstreams][nout] root of the jackknife variance of pair 0 ... npairs - 1, or nullptr
+    float *sd_out[3];       // [nstreams][nout] root of the jackknife variance of pair 0 ... npairs - 1, or nullptr
     const float *cxy_nat;   // [nstreams][nfft] Cxy of the first pass in natural order (two channels), for cxy_out
     float *cxy_out;         // or nullptr
     double m;               // the item count M
     double mm1_over_m;      // (M - 1) / M
     int npairs;             // 1 (lnsd) or 3 (lnsd x, lnsd y, zsd)
-    int W, nfft, fftshift, trim, nout;
+    int W, nfft;
+    OutStage out;
 };
 size_t mtmcsd_jack_ws_points(int nfft);      // 0: the build keeps both spectra in LDS
 int mtm_jack_blocks_per_cu(int nfft);
@@ -455,7 +464,8 @@ struct AdaptFinalizeArgs {
     float *dof_out;         // or nullptr
     double psd_scale;       // scale / nseg
     double inv_nseg;
-    int W, nfft, fftshift, trim, db, nout;
+    int W, nfft;
+    OutStage out;
 };
 size_t mtm_adapt_lds_bytes(int nfft, int ntapers);      // dynamic LDS of the launch: up to 512 points it holds the eigenspectra
 size_t mtm_adapt_ws_floats(int nfft, int ntapers);      // 0: the build keeps the eigenspectra in LDS
@@ -485,7 +495,8 @@ struct SkFinalizeArgs {
     double m;               // the segment count M
     double mp1_over_mm1;    // (M + 1) / (M - 1)
     double psd_scale;       // scale / (g M), g as the kernel's float
-    int W, nfft, fftshift, trim, db, nout;
+    int W, nfft;
+    OutStage out;
 };
 int welch_sk_blocks_per_cu(int nfft);
 hipError_t launch_welch_sk(int nfft, const WelchSkArgs &a, hipStream_t s);
@@ -519,7 +530,8 @@ struct CycFinalizeArgs {
     float *coh_out;         // [nstreams][ncyc][nout]
     float *psd_out;         // [nstreams][nout], or nullptr
     double scf_scale;       // scale / M
-    int W, G, ga, ncyc, nfft, fftshift, trim, db, nout;
+    int W, G, ga, ncyc, nfft;
+    OutStage out;
 };
 size_t welch_cyc_ws_points(int nfft);      // 0: the build keeps both spectra in LDS
 int welch_cyc_blocks_per_cu(int nfft, int ga);      // ga: 1, 2 or kCycGroup

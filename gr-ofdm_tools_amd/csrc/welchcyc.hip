@@ -37,7 +37,7 @@
 // Not here: the conjugate cyclic spectrum E[X(f + alpha) X(-f)], a search over alpha (the caller supplies the cycle
 // frequencies), multitaper plans, transform lengths that are not a power of two.
 #include "mtm_common.hip.h"
-#include "oth_internal.h"
+#include "stat_finalize.hip.h"
 #include "launch.h"
 
 #include <type_traits>
@@ -179,43 +179,19 @@ template <int N, int T, int GA, bool KEEP, bool TWO, bool ACCREG> __global__ __l
     }
 }
 
-// 256 threads = 32 consecutive bins x 8 slices of the workgroup axis (sk_finalize_kernel's shape), one cycle frequency per
-// blockIdx.z: slice sums in double, combined in a fixed order; then scf, coh and (with the first cycle frequency) the PSD row,
-// with the plan's shift and trim.
+// The shared finalize stage (stat_finalize.hip.h), one cycle frequency per blockIdx.z, on the |X|^2 row of group 0 and the
+// frequency's own three rows; then scf, coh and (with the first cycle frequency) the PSD row.
 __global__ __launch_bounds__(256) void cyc_finalize_kernel(CycFinalizeArgs a) {
-    __shared__ double red[4][8][32];
-    const int lane = threadIdx.x & 31, slice = threadIdx.x >> 5;
-    const int k = blockIdx.x * 32 + lane;
-    const int stream = blockIdx.y, cyc = blockIdx.z;
-    int ks = k;
-    if (a.fftshift) {
-        ks = k + a.nfft / 2;
-        if (ks >= a.nfft) ks -= a.nfft;
-    }
-    const int i = ks - a.trim;
-    const bool live = k < a.nfft && i >= 0 && i < a.nout;
+    const int k = blockIdx.x * 32 + (threadIdx.x & 31), stream = blockIdx.y, cyc = blockIdx.z;
+    int i;
+    const bool live = out_slot(a.out, a.nfft, k, i);
     const int R = 1 + 3 * a.ga, grp = cyc / a.ga, g = cyc - grp * a.ga;
     const size_t row = (size_t)a.nfft, wgrows = (size_t)R * row;
     const float *bx = a.partial + (size_t)stream * a.G * a.W * wgrows + k;                       // group 0, row 0
     const float *bu = a.partial + ((size_t)stream * a.G + grp) * a.W * wgrows + (size_t)(1 + 3 * g) * row + k;
-    double t[4] = {0.0, 0.0, 0.0, 0.0};
-    if (live) {
-        for (int w = slice; w < a.W; w += 8) {
-            t[0] += (double)bx[(size_t)w * wgrows];
-            t[1] += (double)bu[(size_t)w * wgrows];
-            t[2] += (double)bu[(size_t)w * wgrows + row];
-            t[3] += (double)bu[(size_t)w * wgrows + 2 * row];
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) red[c][slice][lane] = t[c];
-    __syncthreads();
-    if (slice != 0 || !live) return;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        t[c] = 0.0;
-        for (int q = 0; q < 8; ++q) t[c] += red[c][q][lane];
-    }
+    double t[4];
+    if (!slice_sums<4>(live, a.W, [&](int w, int r) { return r ? bu[(size_t)w * wgrows + (size_t)(r - 1) * row] : bx[(size_t)w * wgrows]; }, t))
+        return;
     // an empty bin (silence, a constant under detrend) reads scf = 0, coh = 0: no 0 / 0; non-finite input stays non-finite
     const double den = t[0] * t[1];
     double coh = 0.0, sr = 0.0, si = 0.0;
@@ -225,16 +201,13 @@ __global__ __launch_bounds__(256) void cyc_finalize_kernel(CycFinalizeArgs a) {
         sr = t[2] * a.scf_scale;
         si = t[3] * a.scf_scale;
     }
-    const size_t o = ((size_t)stream * a.ncyc + cyc) * a.nout + i;
+    const size_t o = ((size_t)stream * a.ncyc + cyc) * a.out.nout + i;
     a.coh_out[o] = (float)coh;
     if (a.scf_out) {
         a.scf_out[2 * o] = (float)sr;
         a.scf_out[2 * o + 1] = (float)si;
     }
-    if (a.psd_out && cyc == 0) {
-        const double v = t[0] * a.scf_scale;
-        a.psd_out[(size_t)stream * a.nout + i] = a.db ? (float)(10.0 * log10(v)) : (float)v;      // finalize_kernel's output stage
-    }
+    if (a.psd_out && cyc == 0) a.psd_out[(size_t)stream * a.out.nout + i] = psd_value(a.out, t[0] * a.scf_scale);
 }
 
 size_t cyc_lds_bytes(int nfft) { return (size_t)(cyc_two_buffers(nfft) ? 2 : 1) * nfft * sizeof(float2) + kMtmRedSlots * sizeof(float2); }
@@ -274,9 +247,7 @@ hipError_t launch_welch_cyc(int nfft, int ga, int groups, const WelchCycArgs &a,
 }
 
 hipError_t launch_cyc_finalize(const CycFinalizeArgs &a, int nstreams, hipStream_t s) {
-    const dim3 grid((a.nfft + 31) / 32, nstreams, a.ncyc);
-    hipLaunchKernelGGL(cyc_finalize_kernel, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return launch_stat_finalize<cyc_finalize_kernel>(a, nstreams, a.ncyc, s);
 }
 
 }  // namespace oth

@@ -20,7 +20,7 @@
 //                         as in mtmftest.hip - the first segment of a run stores them, every later one reads, adds and
 //                         stores, each thread its own addresses, so no barrier.
 #include "mtm_common.hip.h"
-#include "oth_internal.h"
+#include "stat_finalize.hip.h"
 #include "launch.h"
 
 namespace oth {
@@ -55,6 +55,7 @@ template <int N, int T, bool KEEP, bool ACCREG> __global__ __launch_bounds__(T) 
         const float2 *xs = xb + s * p.step;
         float2 pil, mean;
         mtm_segment_entry<N, T, KEEP>(xs, p.nperseg, p.detrend != 0, red, tid, v, pil, mean);
+        // mtm_taper_product spelled out: through the call every build of this kernel comes out scheduled differently
         const float *__restrict__ w = p.win;      // zero-extended to N
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
@@ -105,48 +106,23 @@ template <int N, int T, bool KEEP, bool ACCREG> __global__ __launch_bounds__(T) 
     }
 }
 
-// 256 threads = 32 consecutive bins x 8 slices of the workgroup axis (ftest_finalize_kernel's shape): slice sums in double,
-// combined in a fixed order; then SK in double and the one or two rows with the plan's shift and trim.
+// The shared finalize stage (stat_finalize.hip.h) on the two rows S1, S2; then SK in double and the one or two rows.
 __global__ __launch_bounds__(256) void sk_finalize_kernel(SkFinalizeArgs a) {
-    __shared__ double red[2][8][32];
-    const int lane = threadIdx.x & 31, slice = threadIdx.x >> 5;
-    const int k = blockIdx.x * 32 + lane;
-    const int stream = blockIdx.y;
-    int ks = k;
-    if (a.fftshift) {
-        ks = k + a.nfft / 2;
-        if (ks >= a.nfft) ks -= a.nfft;
-    }
-    const int i = ks - a.trim;
-    const bool live = k < a.nfft && i >= 0 && i < a.nout;
+    const int k = blockIdx.x * 32 + (threadIdx.x & 31), stream = blockIdx.y;
+    int i;
+    const bool live = out_slot(a.out, a.nfft, k, i);
     const float *base = a.partial + (size_t)stream * a.W * 2 * a.nfft + k;
-    double t1 = 0.0, t2 = 0.0;
-    if (live) {
-        for (int w = slice; w < a.W; w += 8) {
-            t1 += (double)base[(size_t)w * 2 * a.nfft];
-            t2 += (double)base[((size_t)w * 2 + 1) * a.nfft];
-        }
-    }
-    red[0][slice][lane] = t1;
-    red[1][slice][lane] = t2;
-    __syncthreads();
-    if (slice != 0 || !live) return;
-    t1 = t2 = 0.0;
-    for (int q = 0; q < 8; ++q) {
-        t1 += red[0][q][lane];
-        t2 += red[1][q][lane];
-    }
+    double t[2];
+    if (!slice_sums<2>(live, a.W, [&](int w, int r) { return base[((size_t)w * 2 + r) * a.nfft]; }, t)) return;
+    const double t1 = t[0], t2 = t[1];
     // an empty bin (silence, a constant under detrend, the DC bin of a noiseless detrended input) reads 0: no 0 / 0
     float sk;
     if (t1 > 0.0) sk = (float)(a.mp1_over_mm1 * (a.m * t2 / (t1 * t1) - 1.0));
     else if (t1 == 0.0) sk = 0.f;
     else sk = __builtin_nanf("");      // non-finite input
-    const size_t o = (size_t)stream * a.nout + i;
+    const size_t o = (size_t)stream * a.out.nout + i;
     a.sk_out[o] = sk;
-    if (a.psd_out) {
-        const double v = t1 * a.psd_scale;
-        a.psd_out[o] = a.db ? (float)(10.0 * log10(v)) : (float)v;      // finalize_kernel's output stage
-    }
+    if (a.psd_out) a.psd_out[o] = psd_value(a.out, t1 * a.psd_scale);
 }
 
 size_t sk_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedSlots * sizeof(float2); }
@@ -156,30 +132,22 @@ size_t sk_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedSl
 #define OTH_SK_KERNEL(N) welch_sk_kernel<N, generic_threads(N), sk_keep(N), sk_accreg(N)>
 
 int welch_sk_blocks_per_cu(int nfft) {
-    switch (nfft) {
-#define X(N) \
-    case N: return resident_blocks<OTH_SK_KERNEL(N)>(generic_threads(N), sk_lds_bytes(N), 0);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return 0;
-    }
+    return mtm_for_size(nfft, 0, [](auto n) {
+        constexpr int N = decltype(n)::value;
+        return resident_blocks<OTH_SK_KERNEL(N)>(generic_threads(N), sk_lds_bytes(N), 0);
+    });
 }
 
 hipError_t launch_welch_sk(int nfft, const WelchSkArgs &a, hipStream_t s) {
     const dim3 grid(a.wg_per_stream, a.nstreams);
-    switch (nfft) {
-#define X(N) \
-    case N: return launch_lds<OTH_SK_KERNEL(N)>(grid, dim3(generic_threads(N)), sk_lds_bytes(N), s, a);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return hipErrorInvalidValue;
-    }
+    return mtm_for_size(nfft, hipErrorInvalidValue, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        return launch_lds<OTH_SK_KERNEL(N)>(grid, dim3(generic_threads(N)), sk_lds_bytes(N), s, a);
+    });
 }
 
 hipError_t launch_sk_finalize(const SkFinalizeArgs &a, int nstreams, hipStream_t s) {
-    const dim3 grid((a.nfft + 31) / 32, nstreams);
-    hipLaunchKernelGGL(sk_finalize_kernel, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return launch_stat_finalize<sk_finalize_kernel>(a, nstreams, 1, s);
 }
 
 }  // namespace oth

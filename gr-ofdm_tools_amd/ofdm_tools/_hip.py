@@ -192,6 +192,28 @@ def _fptr(a):
     return a.ctypes.data_as(_f)
 
 
+def _src(x, nsamples):
+    """The input of a statistic's host form -> (pointer, samples, src_is_device): a host complex64 array, or a device
+    pointer when nsamples is given.  (The pointer holds on to the array it was taken from.)"""
+    if nsamples is None:
+        x = _c64(x)
+        return x.ctypes.data_as(_p), len(x), 0
+    return C.c_void_p(x), int(nsamples), 1
+
+
+def _src2(x, y, nsamples):
+    """_src for a pair of captures -> (pointer, pointer, samples, src_is_device)"""
+    (sx, count, dev), (sy, county, _) = _src(x, nsamples), _src(y, nsamples)
+    if count != county:
+        raise ValueError('x and y must have the same length')
+    return sx, sy, count, dev
+
+
+def _optp(v):
+    """a device pointer, or NULL for a row the caller leaves out"""
+    return C.c_void_p(v) if v else None
+
+
 class Context(object):
     """One device + one HIP stream (oth_ctx).  The library serialises calls per context, so blocks
     running on different scheduler threads may share one."""
@@ -532,11 +554,7 @@ class WelchPlan(object):
         power-of-two length 64 ... 16384 (HipError otherwise)."""
         rows = [np.empty(self.out_len, np.float32) for _ in range(2 if return_psd else 1)]
         n = C.c_uint64()
-        if nsamples is None:
-            x = _c64(x)
-            src, count, dev = x.ctypes.data_as(_p), len(x), 0
-        else:
-            src, count, dev = C.c_void_p(x), int(nsamples), 1
+        src, count, dev = _src(x, nsamples)
         self.ctx.check(self.ctx.lib.oth_welch_sk(self.h, src, count, dev, _fptr(rows[0]), _fptr(rows[1]) if return_psd else None,
                                                  C.byref(n)), 'oth_welch_sk')
         self.last_nseg = n.value
@@ -547,7 +565,7 @@ class WelchPlan(object):
         -> segments per stream (also last_nseg)."""
         n = C.c_uint64()
         self.ctx.check(self.ctx.lib.oth_welch_sk_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
-                                                     C.c_void_p(sk_dev), C.c_void_p(psd_dev) if psd_dev else None, C.byref(n)),
+                                                     C.c_void_p(sk_dev), _optp(psd_dev), C.byref(n)),
                        'oth_welch_sk_dev')
         self.last_nseg = n.value
         return n.value
@@ -577,11 +595,7 @@ class WelchPlan(object):
         scf, coh = np.empty((max(A, 1), m), np.complex64), np.empty((max(A, 1), m), np.float32)
         psd = np.empty(m, np.float32) if return_psd else None
         n = C.c_uint64()
-        if nsamples is None:
-            x = _c64(x)
-            src, count, dev = x.ctypes.data_as(_p), len(x), 0
-        else:
-            src, count, dev = C.c_void_p(x), int(nsamples), 1
+        src, count, dev = _src(x, nsamples)
         self.ctx.check(self.ctx.lib.oth_welch_cyclic(self.h, src, count, dev, scf.ctypes.data_as(_f), _fptr(coh),
                                                      _fptr(psd) if return_psd else None, C.byref(n)), 'oth_welch_cyclic')
         self.last_nseg = n.value
@@ -593,8 +607,8 @@ class WelchPlan(object):
         -> segments per stream (also last_nseg)."""
         n = C.c_uint64()
         self.ctx.check(self.ctx.lib.oth_welch_cyclic_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
-                                                         C.c_void_p(scf_dev) if scf_dev else None, C.c_void_p(coh_dev),
-                                                         C.c_void_p(psd_dev) if psd_dev else None, C.byref(n)), 'oth_welch_cyclic_dev')
+                                                         _optp(scf_dev), C.c_void_p(coh_dev),
+                                                         _optp(psd_dev), C.byref(n)), 'oth_welch_cyclic_dev')
         self.last_nseg = n.value
         return n.value
 
@@ -742,9 +756,8 @@ WelchPlan.csd_device_src = _csd_device_src
 def _csd_exec_dev(self, dx, dy, nsamples, pxx=0, pyy=0, pxy=0, cxy=0):
     """Asynchronous: device in, device out (any output pointer may be 0)."""
     n = C.c_uint64()
-    vp = lambda v: C.c_void_p(v) if v else None      # noqa: E731
-    self.ctx.check(self.ctx.lib.oth_csd_exec_dev(self.h, C.c_void_p(dx), C.c_void_p(dy), nsamples, vp(pxx), vp(pyy),
-                                                 vp(pxy), vp(cxy), C.byref(n)), 'oth_csd_exec_dev')
+    self.ctx.check(self.ctx.lib.oth_csd_exec_dev(self.h, C.c_void_p(dx), C.c_void_p(dy), nsamples, _optp(pxx), _optp(pyy),
+                                                 _optp(pxy), _optp(cxy), C.byref(n)), 'oth_csd_exec_dev')
     return n.value
 
 
@@ -757,9 +770,8 @@ def _csd_partial_dev(self, dx, dy, nsamples, sums_dptr):
 
 
 def _csd_scale_dev(self, sums_dptr, nseg_total, pxx=0, pyy=0, pxy=0, cxy=0):
-    vp = lambda v: C.c_void_p(v) if v else None      # noqa: E731
-    self.ctx.check(self.ctx.lib.oth_csd_scale_dev(self.h, C.c_void_p(sums_dptr), int(nseg_total), vp(pxx), vp(pyy),
-                                                  vp(pxy), vp(cxy)), 'oth_csd_scale_dev')
+    self.ctx.check(self.ctx.lib.oth_csd_scale_dev(self.h, C.c_void_p(sums_dptr), int(nseg_total), _optp(pxx), _optp(pyy),
+                                                  _optp(pxy), _optp(cxy)), 'oth_csd_scale_dev')
 
 
 WelchPlan.csd_exec_dev = _csd_exec_dev
@@ -857,11 +869,7 @@ class MtmPlan(WelchPlan):
         Sets last_nseg.  The plan's weights take no part."""
         rows = [np.empty(self.out_len, np.float32) for _ in range(2 if return_dof else 1)]
         n = C.c_uint64()
-        if nsamples is None:
-            x = _c64(x)
-            src, count, dev = x.ctypes.data_as(_p), len(x), 0
-        else:
-            src, count, dev = C.c_void_p(x), int(nsamples), 1
+        src, count, dev = _src(x, nsamples)
         self.ctx.check(self.ctx.lib.oth_mtm_adaptive(self.h, src, count, dev, int(iters), _fptr(rows[0]),
                                                      _fptr(rows[1]) if return_dof else None, C.byref(n)), 'oth_mtm_adaptive')
         self.last_nseg = n.value
@@ -872,7 +880,7 @@ class MtmPlan(WelchPlan):
         -> segments per stream (also last_nseg)."""
         n = C.c_uint64()
         self.ctx.check(self.ctx.lib.oth_mtm_adaptive_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
-                                                         int(iters), C.c_void_p(psd_dev), C.c_void_p(dof_dev) if dof_dev else None,
+                                                         int(iters), C.c_void_p(psd_dev), _optp(dof_dev),
                                                          C.byref(n)), 'oth_mtm_adaptive_dev')
         self.last_nseg = n.value
         return n.value
@@ -885,11 +893,7 @@ class MtmPlan(WelchPlan):
         rows = [np.empty(self.out_len, np.float32) for _ in range(3 if return_rows else 1)]
         ptrs = [_fptr(r) for r in rows] + [None] * (3 - len(rows))
         n = C.c_uint64()
-        if nsamples is None:
-            x = _c64(x)
-            src, count, dev = x.ctypes.data_as(_p), len(x), 0
-        else:
-            src, count, dev = C.c_void_p(x), int(nsamples), 1
+        src, count, dev = _src(x, nsamples)
         self.ctx.check(self.ctx.lib.oth_mtm_ftest(self.h, src, count, dev, ptrs[0], ptrs[1], ptrs[2], C.byref(n)), 'oth_mtm_ftest')
         self.last_nseg = n.value
         return tuple(rows) if return_rows else rows[0]
@@ -898,9 +902,8 @@ class MtmPlan(WelchPlan):
         """Asynchronous: device in, device out - [nstreams][out_len] float32 at f_dev and, where given, line_dev and
         resid_dev.  -> segments per stream (also last_nseg)."""
         n = C.c_uint64()
-        vp = lambda v: C.c_void_p(v) if v else None      # noqa: E731
         self.ctx.check(self.ctx.lib.oth_mtm_ftest_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
-                                                      C.c_void_p(f_dev), vp(line_dev), vp(resid_dev), C.byref(n)),
+                                                      C.c_void_p(f_dev), _optp(line_dev), _optp(resid_dev), C.byref(n)),
                        'oth_mtm_ftest_dev')
         self.last_nseg = n.value
         return n.value
@@ -913,11 +916,7 @@ class MtmPlan(WelchPlan):
         gives for the same input.  Sets last_nseg.  Needs equal weights and M >= 2 (HipError otherwise)."""
         rows = [np.empty(self.out_len, np.float32) for _ in range(2 if return_psd else 1)]
         n = C.c_uint64()
-        if nsamples is None:
-            x = _c64(x)
-            src, count, dev = x.ctypes.data_as(_p), len(x), 0
-        else:
-            src, count, dev = C.c_void_p(x), int(nsamples), 1
+        src, count, dev = _src(x, nsamples)
         self.ctx.check(self.ctx.lib.oth_mtm_jackknife(self.h, src, count, dev, _fptr(rows[0]), _fptr(rows[1]) if return_psd else None,
                                                       C.byref(n)), 'oth_mtm_jackknife')
         self.last_nseg = n.value
@@ -928,7 +927,7 @@ class MtmPlan(WelchPlan):
         -> segments per stream (also last_nseg)."""
         n = C.c_uint64()
         self.ctx.check(self.ctx.lib.oth_mtm_jackknife_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
-                                                          C.c_void_p(lnsd_dev), C.c_void_p(psd_dev) if psd_dev else None,
+                                                          C.c_void_p(lnsd_dev), _optp(psd_dev),
                                                           C.byref(n)), 'oth_mtm_jackknife_dev')
         self.last_nseg = n.value
         return n.value
@@ -954,13 +953,7 @@ class MtmCsdPlan(MtmPlan):
         when nsamples is given.  Sets last_nseg.  Needs equal weights and M >= 3 (HipError otherwise)."""
         rows = [np.empty(self.out_len, np.float32) for _ in range(4)]
         n = C.c_uint64()
-        if nsamples is None:
-            x, y = _c64(x), _c64(y)
-            if len(x) != len(y):
-                raise ValueError('x and y must have the same length')
-            sx, sy, count, dev = x.ctypes.data_as(_p), y.ctypes.data_as(_p), len(x), 0
-        else:
-            sx, sy, count, dev = C.c_void_p(x), C.c_void_p(y), int(nsamples), 1
+        sx, sy, count, dev = _src2(x, y, nsamples)
         self.ctx.check(self.ctx.lib.oth_mtm_csd_jackknife(self.h, sx, sy, count, dev, *([_fptr(r) for r in rows] + [C.byref(n)])),
                        'oth_mtm_csd_jackknife')
         self.last_nseg = n.value
@@ -970,9 +963,8 @@ class MtmCsdPlan(MtmPlan):
         """Asynchronous: device in, device out - out_len float32 at zsd_dev and, where given, cxy_dev, lnsdx_dev and
         lnsdy_dev.  -> segments (also last_nseg)."""
         n = C.c_uint64()
-        vp = lambda v: C.c_void_p(v) if v else None      # noqa: E731
-        self.ctx.check(self.ctx.lib.oth_mtm_csd_jackknife_dev(self.h, C.c_void_p(dx), C.c_void_p(dy), int(nsamples), vp(cxy_dev),
-                                                              C.c_void_p(zsd_dev), vp(lnsdx_dev), vp(lnsdy_dev), C.byref(n)),
+        self.ctx.check(self.ctx.lib.oth_mtm_csd_jackknife_dev(self.h, C.c_void_p(dx), C.c_void_p(dy), int(nsamples), _optp(cxy_dev),
+                                                              C.c_void_p(zsd_dev), _optp(lnsdx_dev), _optp(lnsdy_dev), C.byref(n)),
                        'oth_mtm_csd_jackknife_dev')
         self.last_nseg = n.value
         return n.value

@@ -31,8 +31,8 @@ def describe(elf):
         m = re.match(r'[0-9a-f]+ <(.+)>:$', line)
         if m:
             sym = m.group(1)
-        if sym:
-            code.setdefault(sym, []).append(line)
+        if sym:      # without the load address: the symbol's line, and the offset in front of each encoding
+            code.setdefault(sym, []).append(re.sub(r'^[0-9a-f]+ <|(?<=// )[0-9A-F]{12}: ', '', line))
     head, *blocks = re.split(r'\n\s*- \.agpr_count:', '\n' + _tool('llvm-readelf', '--notes', elf))
     meta = {}
     for blk in blocks:

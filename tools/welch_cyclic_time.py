@@ -21,45 +21,16 @@ after two warm-up steps each; the median over the repetitions is reported per ca
 usage: welch_cyclic_time.py [reps] [--ab] [--out FILE]
 """
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, 'gr-ofdm_tools_amd'))
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-from ofdm_tools import _hip, windows  # noqa: E402
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from stat_time import Session
 
-ab = '--ab' in sys.argv
-args = [a for a in sys.argv[1:] if not a.startswith('--')]
-out_path = os.path.join(ROOT, 'profiles', 'welch_cyclic_ab.txt' if ab else 'welch_cyclic_time.txt')
-if '--out' in sys.argv:
-    out_path = sys.argv[sys.argv.index('--out') + 1]
-    args = [a for a in args if a != out_path]
-reps = int(args[0]) if args else 20
-INNER = 10
-lines = []
+from ofdm_tools import _hip, windows  # noqa: E402 - stat_time sets the path
 
-
-def say(text):
-    print(text, flush=True)
-    lines.append(text)
-
-
-dev = torch.device('cuda', 0)
-stream = torch.cuda.current_stream(dev)
-ctx = _hip.Context(0, stream=stream.cuda_stream)
-
-
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(stream)
-    for _ in range(INNER):
-        fn()
-    b.record(stream)
-    b.synchronize()
-    return a.elapsed_time(b) / INNER
+s = Session({'--ab': 'welch_cyclic_ab.txt', None: 'welch_cyclic_time.txt'}, reps=20, inner=10, flags=('--ab',))
+ctx, dev, say, reps, INNER = s.ctx, s.dev, s.say, s.reps, s.inner
 
 
 def alphas_for(A):
@@ -81,37 +52,14 @@ def cyclic_plan(nfft, alphas, group=None, detrend=_hip.DETREND_CONSTANT):
     return plan
 
 
-def capture(n):
-    x = torch.empty(2 * n, dtype=torch.float32, device=dev)
-    torch.cuda.synchronize(dev)
-    ctx.synth_iq(x.data_ptr(), n, 2026, ((0.5, 0.1234), (0.05, -0.31), (2.0, 0.4071)), 0j)
-    return x
-
-
-def run_arms(cands):
-    """cands: [(label, fn, plan)] -> {label: median ms}, {label: min ms}, {label: recipe}"""
-    recipes = {}
-    for label, fn, pl in cands:      # warm-up: workspaces, first launches
-        fn()
-        fn()
-        recipes[label] = pl.last_recipe()
-    torch.cuda.synchronize(dev)
-    ms = {label: [] for label, _, _ in cands}
-    for _ in range(reps):
-        for label, fn, _ in cands:
-            ms[label].append(timed(fn))
-    return {k: float(np.median(v)) for k, v in ms.items()}, {k: float(min(v)) for k, v in ms.items()}, recipes
-
-
 def ab_table():
-    say('library %s on %s: the three builds of welch_cyc_kernel, %d repetitions of %d calls per shape, the arms alternating'
-        % (os.path.basename(_hip.LIB_PATH), ctx.device_name(), reps, INNER))
+    say('%s: the three builds of welch_cyc_kernel, %d repetitions of %d calls per shape, the arms alternating' % (s.library, reps, INNER))
     say('ms per call (kernel + finalize launch, scf + coh + psd rows); the ratios are to group 1')
     say('')
     say('%-34s %3s  %9s %9s %9s  %6s %6s   %s' % ('shape', 'A', 'group 1', 'group 2', 'group 4', 'g2/g1', 'g4/g1', 'W and workgroups per CU'))
     for nfft in (256, 4096, 8192, 16384):
         for name, nstreams, per_stream in (('64 streams x 8 segments', 64, 8 * nfft), ('one stream of 2^24 samples', 1, 1 << 24)):
-            x = capture(nstreams * per_stream)
+            x = s.capture(nstreams * per_stream, dc=0j)
             for A in (1, 2, 3, 4, 16):
                 alphas = alphas_for(A)
                 out = torch.empty((3 * A + 1) * nstreams * nfft, dtype=torch.float32, device=dev)
@@ -121,7 +69,7 @@ def ab_table():
                 def arm(g):
                     return lambda: plans[g].cyclic_dev(x.data_ptr(), per_stream, nstreams, per_stream, coh, scf, psd)
 
-                med, low, recipes = run_arms([('g%d' % g, arm(g), plans[g]) for g in (1, 2, 4)])
+                med, low, recipes = s.run_arms([('g%d' % g, arm(g), plans[g]) for g in (1, 2, 4)])
                 shape = ' | '.join('%s %s' % (recipes[k].split(' W=')[1].split()[0], recipes[k].split(' bpc=')[1]) for k in ('g1', 'g2', 'g4'))
                 say('%-34s %3d  %9.4f %9.4f %9.4f  %6.2f %6.2f   %s' % ('%d: %s' % (nfft, name), A, med['g1'], med['g2'], med['g4'], med['g2'] / med['g1'],
                                                                          med['g4'] / med['g1'], shape))
@@ -132,13 +80,13 @@ def ab_table():
 
 
 def time_table():
-    say('library %s on %s, %d repetitions of %d calls per shape, the arms alternating' % (os.path.basename(_hip.LIB_PATH), ctx.device_name(), reps, INNER))
+    say('%s, %d repetitions of %d calls per shape, the arms alternating' % (s.library, reps, INNER))
     nfft, A = 4096, 4
     alphas = alphas_for(A)
     for name, nstreams, per_stream in (('2^24 samples at 4096 points, no overlap, A = 4', 1, 1 << 24),
                                        ('64 streams of 8 x 4096 points, A = 4', 64, 8 * 4096)):
         n = nstreams * per_stream
-        x = capture(n)
+        x = s.capture(n, dc=0j)
         xc = torch.view_as_complex(x.view(n, 2))
         t = torch.arange(per_stream, dtype=torch.float64, device=dev)
         # the phasors in double, once: [A][n], every stream's time starting at 0
@@ -157,19 +105,14 @@ def time_table():
         def run_composition():
             for a in range(A):
                 torch.mul(xc, ph[a], out=y)
-                for s in range(nstreams):
-                    r = rows[a, s].data_ptr()
-                    welch.csd_exec_dev(x.data_ptr() + 8 * s * per_stream, y.data_ptr() + 8 * s * per_stream, per_stream,
+                for i in range(nstreams):
+                    r = rows[a, i].data_ptr()
+                    welch.csd_exec_dev(x.data_ptr() + 8 * i * per_stream, y.data_ptr() + 8 * i * per_stream, per_stream,
                                        r, r + 4 * nfft, r + 8 * nfft, r + 16 * nfft)
 
         cands = [('composition (A x (torch mix + csd_exec_dev per stream))', run_composition, welch), ('fused (cyclic_dev: scf, coh, psd)', run_fused, fused)]
-        med, low, recipes = run_arms(cands)
-        say('')
-        say(name)
+        med = s.report(name, cands, 56, 'composition')
         base = med[cands[0][0]]
-        for label, _, _ in cands:
-            say('  %-56s %9.3f ms per call (median of %d, min %.3f)  x%.2f of the composition   [%s]'
-                % (label, med[label], reps, low[label], med[label] / base, recipes[label]))
         # the arms agree (no detrend: file header)
         c_f = out[:A * nstreams * nfft].view(nstreams, A, nfft).permute(1, 0, 2).double()
         c_c = rows[:, :, 4, :].double()
@@ -180,20 +123,9 @@ def time_table():
         del x, xc, ph, y, out, rows
 
 
-if ab:
+if '--ab' in s.flags:
     ab_table()
 else:
     time_table()
-ctx.close()
-
-say('')
-import kernel_resources  # noqa: E402
-ks = {n: v for n, v in kernel_resources.kernels(_hip.LIB_PATH).items() if 'welch_cyc_kernel<' in n or 'cyc_finalize_kernel' in n}
-say('%-64s %5s %5s %6s %9s' % ('kernel <N, T, GA, KEEP, two LDS buffers, sums in registers>', 'VGPR', 'SGPR', 'spills', 'scratch B'))
-for n in sorted(ks, key=lambda q: (int(q.split('<')[1].split(',')[0]) if '<' in q else 0, q)):
-    k = ks[n]
-    say('%-64s %5d %5d %6d %9d' % (n.split('(')[0], k['vgpr'] + k['agpr'], k['sgpr'], k['spill_vgpr'], k['scratch']))
-
-os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-with open(out_path, 'w') as f:
-    f.write('\n'.join(lines) + '\n')
+s.finish('kernel <N, T, GA, KEEP, two LDS buffers, sums in registers>', ('welch_cyc_kernel<', 'cyc_finalize_kernel'),
+         key=lambda name, length: (length, name))
