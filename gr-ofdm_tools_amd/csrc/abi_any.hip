@@ -129,7 +129,7 @@ int any_partial_rows(const AnyShape &sh, long long nseg, int cu_count) {
 }
 
 // nseg segments starting at x[first + s seg_step] (nperseg samples, window win, optional constant detrend) -> either the
-// W x nch partial rows of |X|^2 (cross) sums (rows == nullptr; layout 0, or 6 = [k1][k2] for the two-level route), or one
+// W x nch partial rows of |X|^2 (cross) sums (rows == nullptr; ROW_NATURAL, or ROW_TWOLEVEL = [k1][k2] for the two-level route), or one
 // periodogram row per segment (rows != nullptr: epilogue / scale / fftshift as PgramArgs).  nbins = t.sh.nfft.
 int any_run(oth_ctx *c, AnyTables &t, const float2 *x, const float2 *y, long long first, long long seg_step, int nperseg,
             const float *win, bool detrend, long long nseg, float *partial, int W, float *rows, int epilogue, float scale,
@@ -232,7 +232,7 @@ int any_run(oth_ctx *c, AnyTables &t, const float2 *x, const float2 *y, long lon
         k2.load_op = 0;
         k2.nat_i = sh.L1, k2.nat_t = kAnyRowTile, k2.nat_c = 1;
         if (!blu) {
-            k2.pp_i = 1, k2.pp_t = kAnyRowTile * sh.L2, k2.pp_c = sh.L2;      // partial rows in [k1][k2] order (finalize layout 6)
+            k2.pp_i = 1, k2.pp_t = kAnyRowTile * sh.L2, k2.pp_c = sh.L2;      // partial rows in [k1][k2] order (ROW_TWOLEVEL)
             HIPCHK(c, launch_any_fft(k2, sh.L1 / kAnyRowTile, rows ? gy_rows : W, 1, rows ? 3 : acc_store, c->stream));
             continue;
         }

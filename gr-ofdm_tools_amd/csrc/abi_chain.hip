@@ -200,8 +200,8 @@ static int chain_launch_fused(oth_chain *h, const float2 *x, long long first_vec
         h->ops += 1;
         if (a.acc_mode != 3) h->ops += (groups ? 2 : 1) + ((a.acc_mode == 1 && give > 8) ? 1 : 0);      // [reduce +] state [+ rows]
         if (a.acc_mode != 3)
-            HIPCHK(c, launch_chain_tail(h->d_partial.get(), groups ? h->d_tail.get() : nullptr, (int)W, N, big ? (x1 ? (N == 16384 ? 4 : 5) : (N == 16384 ? 2 : 3)) : 0,
-                                        h->fftshift, a.acc_mode, a.acc_end,
+            HIPCHK(c, launch_chain_tail(h->d_partial.get(), groups ? h->d_tail.get() : nullptr, (int)W, N,
+                                        big ? (x1 ? x1_layout(N) : w16k_layout(N)) : ROW_NATURAL, h->fftshift, a.acc_mode, a.acc_end,
                                         h->alpha, h->kdb, h->d_iir.get(), h->d_peak.get(), h->d_rows.get(), h->do_iir ? give : 0, rows_last,
                                         c->stream));
     }

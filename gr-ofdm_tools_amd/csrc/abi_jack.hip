@@ -31,16 +31,10 @@ int jack_check(oth_plan *p, bool two, const void *x, const void *y, size_t nsamp
     return OTH_OK;
 }
 
-// the reduction of the first pass: W1 natural-order partial rows per stream (mtm_run) through launch_finalize
+// the reduction of the first pass: W1 natural-order partial rows per stream (mtm_run) through launch_finalize, raw sums
 FinalizeArgs pass1_finalize(const oth_plan *p, int W1, int nch) {
-    FinalizeArgs f{};
-    f.partial = p->d_partial.get();
-    f.scratch = p->d_reduce.get();
-    f.W = W1;
-    f.nfft = p->nfft;
-    f.nch = nch;
+    FinalizeArgs f = finalize_args(p, W1, ROW_NATURAL, nch, raw_stage(p));
     f.scale = 1.0;
-    f.nout = p->nfft;
     return f;
 }
 
@@ -63,10 +57,7 @@ int jack_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t 
     if (psd_out) {      // oth_welch_exec_dev's finalize launch
         f.out0 = psd_out;
         f.scale = p->scale / (double)nseg;
-        f.fftshift = p->fftshift;
-        f.trim = p->trim;
-        f.db = p->db;
-        f.nout = N - 2 * p->trim;
+        f.out = out_stage(p);
         HIPCHK(c, launch_finalize(f, nstreams, c->stream));
     }
     MtmJackArgs a{};

@@ -99,7 +99,7 @@ int resolve_recipe(const PlanShape &p, bool csd, long long nseg, int nstreams, i
     r.nch = csd ? 4 : 1;
     if (p.any.kind != ANY_NONE) {
         // lengths outside the power-of-two kernels: detrend in the time domain from each segment's own mean (no pilot),
-        // contiguous strided rows of segments, partial rows in natural order (two-level: [k1][k2], finalize layout 6)
+        // contiguous strided rows of segments, partial rows in natural order (two-level: [k1][k2], ROW_TWOLEVEL)
         if (p.kernel == OTH_KERNEL_TUNED) {
             if (why) *why = "tuned kernel does not cover this plan";
             return OTH_ERR_UNSUPPORTED;
@@ -111,7 +111,7 @@ int resolve_recipe(const PlanShape &p, bool csd, long long nseg, int nstreams, i
         r.any_r16 = !r.any_onewg && p.any.kind == ANY_TWOLEVEL && tl_supported(p.any.L) && p.tune_variant != "anycov";      // fft_tl.hip
         r.form = p.detrend ? 1 : 0;
         r.W = r.any_onewg ? welch32k_rows(nseg, cu_count, p.any.L == 65536) : any_partial_rows(p.any, nseg, cu_count);
-        r.layout = r.any_onewg ? (p.any.L == 65536 ? 8 : 7) : (p.any.kind == ANY_TWOLEVEL ? 6 : 0);
+        r.layout = r.any_onewg ? w32k_layout(p.any.L) : (p.any.kind == ANY_TWOLEVEL ? ROW_TWOLEVEL : ROW_NATURAL);
         *out = r;
         return OTH_OK;
     }
@@ -202,9 +202,9 @@ int resolve_recipe(const PlanShape &p, bool csd, long long nseg, int nstreams, i
         const long long w = ((long long)cu_count * r.bpc + nstreams - 1) / nstreams;
         r.W = (int)(w > nseg ? nseg : (w < 1 ? 1 : w));
     }
-    r.layout = (r.kern == RK_W4096 || r.kern == RK_CSD4096 || r.kern == RK_CSD4096WS) ? 1
-               : (r.kern == RK_W16K1X || r.kern == RK_W16K1X_HALF) ? (p.nfft == 16384 ? 4 : 5)
-               : (r.kern == RK_W16K ? (p.nfft == 16384 ? 2 : 3) : 0);
+    r.layout = (r.kern == RK_W4096 || r.kern == RK_CSD4096 || r.kern == RK_CSD4096WS) ? ROW_W4096
+               : (r.kern == RK_W16K1X || r.kern == RK_W16K1X_HALF) ? x1_layout(p.nfft)
+               : (r.kern == RK_W16K ? w16k_layout(p.nfft) : ROW_NATURAL);
     // ---- schedule and chunks (tuned kernels only; the coverage kernel walks contiguous runs)
     if (r.kern != RK_GENERIC) {
         const bool auto_sched = p.tune_sched < 0 && p.sched == OTH_SCHED_DYNAMIC;      // "the library's choice"
@@ -299,7 +299,7 @@ std::string recipe_text(const LaunchRecipe &r, int nfft) {
     // rows=1: every kernel leaves one partial row per workgroup; the field stays because the text is compared byte for byte
     snprintf(buf, sizeof buf, "kernel=%s nfft=%d form=%s pilot=%s sched=%s chunk=%d tail=%d nbig=%lld bpc=%d W=%d rows=1 nch=%d layout=%d",
              k.c_str(), nfft, kForm[r.form], kPilot[r.pilot], kSched[r.sched], r.chunk, r.tail_chunk, r.nbig, r.bpc, r.W,
-             r.nch, r.layout);
+             r.nch, (int)r.layout);
     return buf;
 }
 

@@ -1,6 +1,6 @@
 // What the host files of the per-bin statistics (abi_ftest, abi_sk, abi_jack, abi_adapt, abi_cyc; mtm_run for the work split
-// and the recipe) share: the stream-shape refusals, the work split over resident workgroups, the finalize launch's output
-// stage, the recipe text, the timed launch, the host form around a device run, and the replacement of a plan's tables.
+// and the recipe) share: the stream-shape refusals, the work split over resident workgroups, the recipe text, the timed
+// launch, the host form around a device run, and the replacement of a plan's tables.
 #pragma once
 #include "abi_state.h"
 
@@ -26,8 +26,6 @@ inline int segment_workgroups(const oth_ctx *c, long long items, long long min_p
     const long long resident = (long long)c->cu_count * bpc;
     return (int)std::min(items, std::max(min_per_stream, resident / launch_streams));
 }
-
-inline OutStage out_stage(const oth_plan *p) { return OutStage{p->fftshift, p->trim, p->db, p->nfft - 2 * p->trim}; }
 
 // last_recipe of a taper-loop launch: `front` (" ntapers=7 iters=4") follows nfft, `back` (" ncyc=3 group=2") the work split
 inline std::string stat_recipe(const char *kernel, const oth_plan *p, const std::string &front, int W, long long nseg, int nstreams,

@@ -353,7 +353,8 @@ struct LaunchRecipe {
     bool x1_window = false, x1_plain = false;      // RK_W16K1X: windowed build / the un-pipelined loop
     bool half_ws = false;                          // RK_W16K1X_HALF, 8192 points: welch8kws_kernel
     int bpc = 0;                 // resident workgroups (teams) per CU (0: generic grid rule)
-    int W = 1, nch = 1, layout = 0;
+    int W = 1, nch = 1;
+    RowLayout layout = ROW_NATURAL;
     int sched = 0, chunk = 1, tail_chunk = 1;
     long long nbig = 0;
     bool tickets = false;        // draws chunk tickets from the context's queue
@@ -379,6 +380,26 @@ inline size_t any_fft_nat_scratch(const AnyShape &sh) { return 2 * (size_t)sh.L;
 int any_fft_nat(oth_ctx *c, const AnyTables &t, float2 *data, float2 *scratch);
 void host_fft_pow2(std::vector<double> &re, std::vector<double> &im);
 
+// ---- the finalize launch of a plan ---------------------------------------------------------------------------------------------
+// the plan's output stage, and the one of the raw forms (partial, accumulate, the time-sharded sums): natural order, no dB
+inline OutStage out_stage(const oth_plan *p) { return OutStage{p->fftshift, p->trim, p->db, p->nfft - 2 * p->trim}; }
+inline OutStage raw_stage(const oth_plan *p) { return OutStage{0, 0, 0, p->nfft}; }
+
+// finalize_kernel's view of W partial rows of nch channels per stream in `layout`, as the plan's averaging launch leaves them
+// in d_partial (reduced through d_reduce), leaving through `stage`.  The caller adds the outputs, scale and accumulate.
+inline FinalizeArgs finalize_args(const oth_plan *p, int W, RowLayout layout, int nch, const OutStage &stage) {
+    FinalizeArgs f{};
+    f.partial = p->d_partial.get();
+    f.scratch = p->d_reduce.get();
+    f.W = W;
+    f.nfft = p->nfft;
+    f.nch = nch;
+    f.layout = layout;
+    f.l1 = p->any.sh.L1, f.l2 = p->any.sh.L2;
+    f.out = stage;
+    return f;
+}
+
 // ---- abi_welch.hip -----------------------------------------------------------------------------------------------------------
 // What oth_welch_plan and oth_mtm_plan share: the checks of the arguments both take, then a fresh plan on the context's
 // device with the common fields set (the detrend code normalised, OTH_HOSTWAIT read).  The caller adds its tables.
@@ -387,7 +408,7 @@ int plan_begin(oth_ctx *c, int nfft, int nperseg, int noverlap, int detrend, int
 
 // ---- abi_mtm.hip: multitaper plans ------------------------------------------------------------------------------------------
 // the averaging launch of a multitaper plan (run_average branches here before resolve_recipe): W partial rows per stream
-// in natural order (finalize layout 0) into p->d_partial
+// in natural order (ROW_NATURAL) into p->d_partial
 //   y != nullptr (plans of oth_mtm_csd_plan only): the two-channel launch, four rows per workgroup
 int mtm_run(oth_plan *p, const float2 *x, const float2 *y, long long nseg, int nstreams, size_t stride, int *W_out);
 // the launch description the taper-loop kernels share, from the plan's tables and sizes (partial: p->d_partial as it is now)

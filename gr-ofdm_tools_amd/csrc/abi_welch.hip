@@ -117,21 +117,29 @@ int segments(const oth_plan *p, size_t nsamples, long long *nseg) {
     return OTH_OK;
 }
 
-// Launch the averaging kernel: partial sums land in plan->d_partial.
-int run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, int nstreams, size_t stride,
-                long long *nseg_out, int *W_out, int *layout_out) {
-    oth_ctx *c = p->ctx;
+// What an averaging launch leaves in plan->d_partial: W rows in `layout` per stream (and channel), sums over nseg segments.
+struct Averaged {
+    int rc = OTH_OK;      // or the refusal / error (run_average's `return fail(...)` and HIPCHK): nothing was left
     long long nseg = 0;
+    int W = 0;
+    RowLayout layout = ROW_NATURAL;
+    Averaged() = default;
+    Averaged(int code) : rc(code) {}
+};
+
+// Launch the averaging kernel: partial sums land in plan->d_partial.
+Averaged run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, int nstreams, size_t stride) {
+    oth_ctx *c = p->ctx;
+    Averaged av;
+    long long &nseg = av.nseg;
     if (segments(p, nsamples, &nseg) != OTH_OK)
         return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
     const bool csd = (y != nullptr);
     if (p->ntapers) {      // multitaper plans: mtm.hip, before any routing
         if (csd)      // (the oth_csd_* entry points have asked already)
             if (int rc = mtm_csd_gate(p, "the cross spectrum")) return rc;
-        if (int rc = mtm_run(p, x, y, nseg, nstreams, stride, W_out)) return rc;
-        *nseg_out = nseg;
-        *layout_out = 0;
-        return OTH_OK;
+        if (int rc = mtm_run(p, x, y, nseg, nstreams, stride, &av.W)) return rc;
+        return av;
     }
     LaunchRecipe r;
     const char *why = "";
@@ -244,10 +252,9 @@ int run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamples, 
             default: HIPCHK(c, launch_welch_generic(p->nfft, a, c->stream)); break;
         }
     }
-    *nseg_out = nseg;
-    *W_out = r.W;
-    *layout_out = r.layout;
-    return OTH_OK;
+    av.W = r.W;
+    av.layout = r.layout;
+    return av;
 }
 
 // finalize_kernel zeroes the ticket counters the averaging launch before it used (saves a memset per call)
@@ -264,20 +271,6 @@ int finalize_and_rearm(oth_ctx *c, FinalizeArgs &f, int nstreams) {
         c->queue_used = 0;
     }
     return OTH_OK;
-}
-
-// finalize_kernel's view of the plan's last averaging launch: W partial rows of nch channels per stream in `layout`,
-// reduced through d_reduce.  The caller adds the outputs, scale, shift, trim and accumulate.
-FinalizeArgs finalize_args(const oth_plan *p, int W, int layout, int nch) {
-    FinalizeArgs f{};
-    f.partial = p->d_partial.get();
-    f.scratch = p->d_reduce.get();
-    f.W = W;
-    f.nfft = p->nfft;
-    f.nch = nch;
-    f.layout = layout;
-    f.l1 = p->any.sh.L1, f.l2 = p->any.sh.L2;
-    return f;
 }
 
 // ---- median average (OTH_AVERAGE_MEDIAN) --------------------------------------------------------------------------------
@@ -598,20 +591,13 @@ int oth_welch_segments_dev(oth_plan *p, const void *iq_dev, size_t nsamples, flo
     const char *route = "";
     if (int rc = median_rows(p, (const float2 *)iq_dev, 1, nsamples, nseg, &route)) return rc;
     // the plan's scaling, fftshift, trim and dB per row: finalize_kernel with one "stream" per segment (grid.y <= 65535)
-    const int nout = p->nfft - 2 * p->trim;
+    FinalizeArgs f = finalize_args(p, 1, ROW_NATURAL, 1, out_stage(p));
+    f.scratch = nullptr;
+    f.scale = p->scale;
     for (long long s0 = 0; s0 < nseg; s0 += 65535) {
         const long long nb = std::min(65535LL, nseg - s0);
-        FinalizeArgs f{};
         f.partial = p->d_rows.get() + (size_t)s0 * p->nfft;
-        f.out0 = rows_dev + (size_t)s0 * nout;
-        f.scale = p->scale;
-        f.W = 1;
-        f.nfft = p->nfft;
-        f.nch = 1;
-        f.fftshift = p->fftshift;
-        f.trim = p->trim;
-        f.db = p->db;
-        f.nout = nout;
+        f.out0 = rows_dev + (size_t)s0 * f.out.nout;
         HIPCHK(c, launch_finalize(f, (int)nb, c->stream));
     }
     if (nseg_out) *nseg_out = (uint64_t)nseg;
@@ -632,22 +618,18 @@ static int welch_exec_dev_impl(oth_plan *p, const void *iq_dev, size_t nsamples,
     if (p->average == OTH_AVERAGE_MEDIAN) {
         // one row of medians per stream: finalize_kernel applies scale / bias, fftshift, trim and dB
         if (int rc = median_run(p, (const float2 *)iq_dev, nsamples, nstreams, stream_stride, &nseg)) return rc;
-        f = finalize_args(p, 1, 0, 1);
+        f = finalize_args(p, 1, ROW_NATURAL, 1, out_stage(p));
         f.partial = p->d_med.get();
         f.scratch = nullptr;
         f.scale = p->scale / p->bias;
     } else {
-        int W = 0, layout = 0;
-        int rc = run_average(p, (const float2 *)iq_dev, nullptr, nsamples, nstreams, stream_stride, &nseg, &W, &layout);
-        if (rc) return rc;
-        f = finalize_args(p, W, layout, 1);
+        const Averaged av = run_average(p, (const float2 *)iq_dev, nullptr, nsamples, nstreams, stream_stride);
+        if (av.rc) return av.rc;
+        nseg = av.nseg;
+        f = finalize_args(p, av.W, av.layout, 1, out_stage(p));
         f.scale = p->scale / (double)nseg;
     }
     f.out0 = psd_out_dev;
-    f.fftshift = p->fftshift;
-    f.trim = p->trim;
-    f.db = p->db;
-    f.nout = p->nfft - 2 * p->trim;
     if (host_seq) {
         f.done_count = c->done_count;
         f.host_seq = host_seq;
@@ -892,16 +874,13 @@ int oth_welch_partial_dev(oth_plan *p, const void *iq_dev, size_t nsamples, floa
     oth_ctx *c = p->ctx;
     if (!iq_dev || !sum_out_dev) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (use_device(c)) return OTH_ERR_HIP;
-    long long nseg = 0;
-    int W = 0, layout = 0;
-    int rc = run_average(p, (const float2 *)iq_dev, nullptr, nsamples, 1, nsamples, &nseg, &W, &layout);
-    if (rc) return rc;
-    FinalizeArgs f = finalize_args(p, W, layout, 1);
+    const Averaged av = run_average(p, (const float2 *)iq_dev, nullptr, nsamples, 1, nsamples);
+    if (av.rc) return av.rc;
+    FinalizeArgs f = finalize_args(p, av.W, av.layout, 1, raw_stage(p));
     f.out0 = sum_out_dev;
     f.scale = 1.0;
-    f.nout = p->nfft;
     if (int frc = finalize_and_rearm(c, f, 1)) return frc;
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
+    if (nseg_out) *nseg_out = (uint64_t)av.nseg;
     return OTH_OK;
     OTH_CATCH((p ? p->ctx : nullptr))
 }
@@ -914,8 +893,7 @@ int oth_welch_scale_dev(oth_plan *p, const float *sum_dev, uint64_t nseg_total, 
     oth_ctx *c = p->ctx;
     if (!sum_dev || !psd_out_dev || !nseg_total) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (use_device(c)) return OTH_ERR_HIP;
-    HIPCHK(c, launch_scale(sum_dev, psd_out_dev, p->nfft, p->scale / (double)nseg_total, p->fftshift, p->trim, p->db,
-                           c->stream));
+    HIPCHK(c, launch_scale(sum_dev, psd_out_dev, p->nfft, p->scale / (double)nseg_total, out_stage(p), c->stream));
     return OTH_OK;
     OTH_CATCH((p ? p->ctx : nullptr))
 }
@@ -962,18 +940,16 @@ int oth_welch_accumulate(oth_plan *p, const void *iq_host, size_t nsamples) {
         p->carry = total;
         return OTH_OK;
     }
-    long long nseg = 0;
-    int W = 0, layout = 0;
-    if ((rc = run_average(p, p->d_stream.get(), nullptr, total, 1, total, &nseg, &W, &layout))) return rc;
-    FinalizeArgs f = finalize_args(p, W, layout, 1);
+    const Averaged av = run_average(p, p->d_stream.get(), nullptr, total, 1, total);
+    if (av.rc) return av.rc;
+    FinalizeArgs f = finalize_args(p, av.W, av.layout, 1, raw_stage(p));
     f.out0 = p->d_sum.get();
     f.scale = 1.0;
-    f.nout = p->nfft;
     f.accumulate = 1;
     if (int frc = finalize_and_rearm(c, f, 1)) return frc;
-    p->nseg_total += (uint64_t)nseg;
+    p->nseg_total += (uint64_t)av.nseg;
     // keep the samples the next segment still needs
-    const size_t consumed = (size_t)nseg * (size_t)p->step;
+    const size_t consumed = (size_t)av.nseg * (size_t)p->step;
     const size_t keep = total - consumed;
     if (keep) {
         // regions may overlap when keep > consumed: bounce through the partial-free tail of d_stage
@@ -1004,10 +980,9 @@ int oth_welch_finalize(oth_plan *p, float *psd_out, uint64_t *nseg_out) {
     if (use_device(c)) return OTH_ERR_HIP;
     int rc = p->d_out.ensure(c, sizeof(float) * 5 * p->nfft);
     if (rc) return rc;
-    const int nout = p->nfft - 2 * p->trim;
-    HIPCHK(c, launch_scale(p->d_sum.get(), p->d_out.get(), p->nfft, p->scale / (double)p->nseg_total, p->fftshift, p->trim,
-                           p->db, c->stream));
-    HIPCHK(c, hipMemcpyAsync(psd_out, p->d_out.get(), sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
+    const OutStage stage = out_stage(p);
+    HIPCHK(c, launch_scale(p->d_sum.get(), p->d_out.get(), p->nfft, p->scale / (double)p->nseg_total, stage, c->stream));
+    HIPCHK(c, hipMemcpyAsync(psd_out, p->d_out.get(), sizeof(float) * stage.nout, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (nseg_out) *nseg_out = p->nseg_total;
     return oth_welch_reset(p);
@@ -1019,21 +994,16 @@ int oth_welch_finalize(oth_plan *p, float *psd_out, uint64_t *nseg_out) {
 static int csd_run(oth_plan *p, const float2 *dx, const float2 *dy, size_t nsamples, bool raw, float *o_xx,
                    float *o_yy, float *o_xy, float *o_c, uint64_t *nseg_out) {
     oth_ctx *c = p->ctx;
-    long long nseg = 0;
-    int W = 0, layout = 0;
-    int rc = run_average(p, dx, dy, nsamples, 1, nsamples, &nseg, &W, &layout);
-    if (rc) return rc;
-    FinalizeArgs f = finalize_args(p, W, layout, 4);
+    const Averaged av = run_average(p, dx, dy, nsamples, 1, nsamples);
+    if (av.rc) return av.rc;
+    FinalizeArgs f = finalize_args(p, av.W, av.layout, 4, raw ? raw_stage(p) : out_stage(p));      // (dB: refused by every caller)
     f.out0 = o_xx;
     f.out1 = o_yy;
     f.out2 = o_xy;
     f.out3 = o_c;
-    f.scale = raw ? 1.0 : p->scale / (double)nseg;
-    f.fftshift = raw ? 0 : p->fftshift;
-    f.trim = raw ? 0 : p->trim;
-    f.nout = raw ? p->nfft : p->nfft - 2 * p->trim;
+    f.scale = raw ? 1.0 : p->scale / (double)av.nseg;
     if (int frc = finalize_and_rearm(c, f, 1)) return frc;
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
+    if (nseg_out) *nseg_out = (uint64_t)av.nseg;
     return OTH_OK;
 }
 
@@ -1083,8 +1053,8 @@ int oth_csd_scale_dev(oth_plan *p, const float *sums_dev, uint64_t nseg_total, f
     if (!sums_dev || !nseg_total) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (p->db) return fail(c, OTH_ERR_UNSUPPORTED, "dB output is not defined for the cross spectrum");
     if (use_device(c)) return OTH_ERR_HIP;
-    HIPCHK(c, launch_csd_scale(sums_dev, p->nfft, p->scale / (double)nseg_total, p->fftshift, p->trim, pxx_dev,
-                               pyy_dev, pxy_dev, cxy_dev, c->stream));
+    HIPCHK(c, launch_csd_scale(sums_dev, p->nfft, p->scale / (double)nseg_total, out_stage(p), pxx_dev, pyy_dev, pxy_dev, cxy_dev,
+                               c->stream));
     return OTH_OK;
     OTH_CATCH((p ? p->ctx : nullptr))
 }

@@ -5,51 +5,9 @@
 // 232-249), the synthetic IQ generator and the measurement probes.
 #include <cstdint>
 
-#include "oth_internal.h"
+#include "out_stage.hip.h"
 
 namespace oth {
-
-// bin held at position `pos` of a partial-sum row
-//   layout 0: natural order (generic kernels)
-//   layout 1: welch4096 / csd4096 leave bin k0 + 16 k1 + 256 k2 at 16 k0 + k1 + 256 k2
-//   layout 2: welch16k leaves bin k' + 4 q at 4096 k' + (layout-1 position of q); layout 3 (8192 points): k' + 2 q
-//   layout 4: welch16k1x leaves bin k0 + 16 k1 + 256 k2 + 4096 bitrev2(q) at 1024 k2 + 64 k0 + 4 k1 + q
-//   layout 5: its 8-wave form (8192 points) leaves bin k0 + 16 k1 + 128 k2 + 2048 bitrev2(q) at 512 k2 + 64 (k0 >> 1) + 4 (8 (k0 & 1) + k1) + q
-//   layout 6: the two-level any-length route (fft_any.hip) leaves bin k1 + l1 k2 at k1 l2 + k2
-__device__ __forceinline__ int bin_pos(int pos, int layout, int l1 = 0, int l2 = 0) {
-    if (layout == 0) return pos;
-    if (layout == 6) {
-        const int k1 = pos / l2;
-        return k1 + l1 * (pos - k1 * l2);
-    }
-    if (layout == 4 || layout == 7 || layout == 8) {
-        // 7 (welch32k.hip): halves A | B of 16384 positions in layout 4 each; A holds bin 2 k, B bin 2 k + 1
-        // 8 (its 65536-point form): halves of 32768 positions in layout 7 each, the first the even bins, the second the odd ones
-        const int h8 = layout == 8 ? pos >> 15 : 0;
-        if (layout == 8) pos &= 32767;
-        const int h7 = layout != 4 ? pos >> 14 : 0;
-        if (layout != 4) pos &= 16383;
-        int k = ((pos >> 6) & 15) + 16 * ((pos >> 2) & 15) + 256 * (pos >> 10) + 4096 * (((pos & 1) << 1) | ((pos >> 1) & 1));
-        if (layout != 4) k = 2 * k + h7;
-        return layout == 8 ? 2 * k + h8 : k;
-    }
-    if (layout == 5)      // 8192 points: pos = 512 k2 + 64 k0' + 4 (8 h + k1) + q holds bin (2 k0' + h) + 16 k1 + 128 k2 + 2048 bitrev2(q)
-        return 2 * ((pos >> 6) & 7) + ((pos >> 5) & 1) + 16 * ((pos >> 2) & 7) + 128 * (pos >> 9) + 2048 * (((pos & 1) << 1) | ((pos >> 1) & 1));
-    const int r = pos & 4095;
-    const int q = ((r & 15) << 4) | ((r >> 4) & 15) | (r & ~255);
-    return layout == 1 ? q : (pos >> 12) + (layout == 2 ? 4 : 2) * q;
-}
-
-// np.fft.fftshift for any length: bin k lands at (k + n / 2) mod n (integer division: n odd included)
-__device__ __forceinline__ int shifted(int k, int n) {
-    const int p = k + n / 2;
-    return p >= n ? p - n : p;
-}
-// ... and its inverse: the bin at shifted position ks
-__device__ __forceinline__ int unshifted(int ks, int n) {
-    const int p = ks + n - n / 2;
-    return p >= n ? p - n : p;
-}
 
 // Output stage of the two-channel path, shared by the finalize kernels and csd_scale_kernel.  An inf sample leaves NaN in
 // every bin of SciPy's result (its transform multiplies the inf by twiddle zeros); here the register butterflies of the
@@ -97,44 +55,22 @@ __device__ __forceinline__ void finalize_signal(const FinalizeArgs &a) {
     }
 }
 
-// 256 threads = 32 consecutive bins x 8 slices of the workgroup axis; the 8 slice sums are
-// combined in a fixed order, so the result does not depend on scheduling.
+// 256 threads = 32 consecutive bins x 8 slices of the workgroup axis: slice_sums on the NCH rows of every workgroup, so the
+// result does not depend on scheduling.
+template <int NCH>
 __global__ __launch_bounds__(256) void finalize_kernel(FinalizeArgs a) {
-    __shared__ double red[4][8][32];
     if (a.queue_reset && blockIdx.x == 0 && blockIdx.y == 0 && (int)threadIdx.x < a.queue_n) a.queue_reset[threadIdx.x] = 0u;
-    const int lane = threadIdx.x & 31, slice = threadIdx.x >> 5;
     // threads walk partial-sum POSITIONS (coalesced reads); the bin and output slot follow
-    const int pos = blockIdx.x * 32 + lane;
-    const int stream = blockIdx.y;
-    const int k = bin_pos(pos, a.layout, a.l1, a.l2);     // (layouts 1-3: the digit swap is its own inverse)
-    const int ks = a.fftshift ? shifted(k, a.nfft) : k;
-    const int i = ks - a.trim;
-    const bool live = pos < a.nfft && i >= 0 && i < a.nout;
-    const float *base = a.partial + (size_t)stream * a.W * a.nch * a.nfft + pos;
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    if (live) {
-        for (int w = slice; w < a.W; w += 8)
-            for (int c = 0; c < a.nch; ++c) s[c] += (double)base[((size_t)w * a.nch + c) * a.nfft];
-    }
-    for (int c = 0; c < a.nch; ++c) red[c][slice][lane] = s[c];
-    __syncthreads();
-    if (slice == 0 && live) {
-        for (int c = 0; c < a.nch; ++c) {
-            double t = 0.0;
-            for (int q = 0; q < 8; ++q) t += red[c][q][lane];
-            s[c] = t;
-        }
-        const size_t o = (size_t)stream * a.nout + i;
-        if (a.nch == 1) {
-            if (a.accumulate) {
-                a.out0[o] += (float)s[0];
-            } else {
-                const double v = s[0] * a.scale;
-                a.out0[o] = a.db ? (float)(10.0 * log10(v)) : (float)v;
-            }
-        } else {
-            csd_store(s[0], s[1], s[2], s[3], a.scale, o, a.out0, a.out1, a.out2, a.out3);
-        }
+    const int pos = blockIdx.x * 32 + (threadIdx.x & 31), stream = blockIdx.y;
+    const int k = bin_pos(pos, a.layout, a.l1, a.l2);
+    int i;
+    const bool live = out_slot(a.out, a.nfft, k, i) && pos < a.nfft;
+    const float *base = a.partial + (size_t)stream * a.W * NCH * a.nfft + pos;
+    double s[NCH];
+    if (slice_sums<NCH>(live, a.W, [&](int w, int c) { return base[((size_t)w * NCH + c) * a.nfft]; }, s)) {
+        const size_t o = (size_t)stream * a.out.nout + i;
+        if constexpr (NCH == 1) store_psd(a.out0, o, s[0], a.scale, a.accumulate, a.out);
+        else csd_store(s[0], s[1], s[2], s[3], a.scale, o, a.out0, a.out1, a.out2, a.out3);
     }
     finalize_signal<false>(a);      // the stores above are wave 0's (slice 0)
 }
@@ -191,9 +127,8 @@ __global__ __launch_bounds__(256) void finalize_wide_kernel(FinalizeArgs a) {
     __syncthreads();
     const int pos = blockIdx.x * POS + threadIdx.x;
     const int k = bin_pos(pos, a.layout, a.l1, a.l2);
-    const int ks = a.fftshift ? shifted(k, a.nfft) : k;
-    const int i = ks - a.trim;
-    if (threadIdx.x < POS && i >= 0 && i < a.nout) {
+    int i;
+    if (out_slot(a.out, a.nfft, k, i) && threadIdx.x < POS) {
         double t[NCH];
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
@@ -201,14 +136,9 @@ __global__ __launch_bounds__(256) void finalize_wide_kernel(FinalizeArgs a) {
 #pragma unroll 4
             for (int q = 0; q < GROUPS; ++q) t[c] += red2[c][q][threadIdx.x];
         }
-        const size_t o = (size_t)stream * a.nout + i;
+        const size_t o = (size_t)stream * a.out.nout + i;
         if constexpr (NCH == 1) {
-            if (a.accumulate) {
-                a.out0[o] += (float)t[0];
-            } else {
-                const double v = t[0] * a.scale;
-                a.out0[o] = a.db ? (float)(10.0 * log10(v)) : (float)v;
-            }
+            store_psd(a.out0, o, t[0], a.scale, a.accumulate, a.out);
         } else {      // as finalize_kernel: Pxx, Pyy, Pxy, Cxy
             csd_store(t[0], t[1], t[2], t[3], a.scale, o, a.out0, a.out1, a.out2, a.out3);
         }
@@ -254,7 +184,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float *parti
     *reinterpret_cast<float4 *>(scratch + ((((size_t)stream * G) + g) * nch + ch) * nfft + col) = o;
 }
 
-// Layout 4 (welch16k1x, 16384 points, one channel): position 1024 k2 + 4 (16 k0 + k1) + q holds bin
+// ROW_X1_16K (welch16k1x, 16384 points, one channel): position 1024 k2 + 4 (16 k0 + k1) + q holds bin
 // k0 + 16 k1 + 256 k2 + 4096 bitrev2(q), so ONE float4 at position 1024 k2 + 4 t (t = 16 k0 + k1) carries the four k3 of
 // (k0, k1, k2).  A block takes one k2: 256 threads read W rows of 4 KiB each as float4 (coalesced), sum in double (fixed
 // order), turn t = 16 k0 + k1 into k0 + 16 k1 through LDS and write four runs of 256 consecutive bins (1 KiB each) -
@@ -294,25 +224,16 @@ __global__ __launch_bounds__(256) void finalize_l4_kernel(FinalizeArgs a) {
     __syncthreads();
 #pragma unroll
     for (int k3 = 0; k3 < 4; ++k3) {
-        const int k = t + 256 * k2 + 4096 * k3;
-        const int ks = a.fftshift ? shifted(k, a.nfft) : k;
-        const int i = ks - a.trim;
-        if (i < 0 || i >= a.nout) continue;
-        const size_t o = (size_t)stream * a.nout + i;
-        const double sum = red[k3][t];
-        if (a.accumulate) {
-            a.out0[o] += (float)sum;
-        } else {
-            const double v = sum * a.scale;
-            a.out0[o] = a.db ? (float)(10.0 * log10(v)) : (float)v;
-        }
+        int i;
+        if (!out_slot(a.out, a.nfft, t + 256 * k2 + 4096 * k3, i)) continue;
+        store_psd(a.out0, (size_t)stream * a.out.nout + i, red[k3][t], a.scale, a.accumulate, a.out);
     }
     finalize_signal<true>(a);
 }
 
 hipError_t launch_finalize(const FinalizeArgs &a_in, int nstreams, hipStream_t s) {
     FinalizeArgs a = a_in;
-    if (a.layout == 4 && a.nch == 1 && a.nfft == 16384 && a.W <= 64) {
+    if (a.layout == ROW_X1_16K && a.nch == 1 && a.nfft == 16384 && a.W <= 64) {
         hipLaunchKernelGGL(finalize_l4_kernel, dim3(16, nstreams), dim3(256), 0, s, a);
         return hipGetLastError();
     }
@@ -329,7 +250,7 @@ hipError_t launch_finalize(const FinalizeArgs &a_in, int nstreams, hipStream_t s
         hipLaunchKernelGGL((finalize_wide_kernel<16, 1>), dim3(a.nfft / 16, nstreams), dim3(256), 0, s, a);
         return hipGetLastError();
     }
-    if (a.nch == 4 && a.W >= 64 && (a.nfft % 16) == 0 && !a.accumulate && !a.db) {
+    if (a.nch == 4 && a.W >= 64 && (a.nfft % 16) == 0 && !a.accumulate && !a.out.db) {
         hipLaunchKernelGGL((finalize_wide_kernel<16, 4>), dim3(a.nfft / 16, nstreams), dim3(256), 0, s, a);
         return hipGetLastError();
     }
@@ -342,45 +263,36 @@ hipError_t launch_finalize(const FinalizeArgs &a_in, int nstreams, hipStream_t s
         a.W = kReduceGroups;
     }
     const dim3 grid((a.nfft + 31) / 32, nstreams);
-    hipLaunchKernelGGL(finalize_kernel, grid, dim3(256), 0, s, a);
+    if (a.nch == 1) hipLaunchKernelGGL(finalize_kernel<1>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(finalize_kernel<4>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
-__global__ void scale_kernel(const float *sum, float *out, int nfft, double scale, int fftshift, int trim, int db,
-                             int nout) {
+__global__ void scale_kernel(const float *sum, float *out, int nfft, double scale, OutStage stage) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nout) return;
-    const int ks = i + trim;
-    const int k = fftshift ? unshifted(ks, nfft) : ks;
-    const double v = (double)sum[k] * scale;
-    out[i] = db ? (float)(10.0 * log10(v)) : (float)v;
+    if (i >= stage.nout) return;
+    out[i] = psd_value(stage, (double)sum[in_bin(stage, nfft, i)] * scale);
 }
 
-hipError_t launch_scale(const float *sum, float *out, int nfft, double scale, int fftshift, int trim, int db,
-                        hipStream_t s) {
-    const int nout = nfft - 2 * trim;
-    hipLaunchKernelGGL(scale_kernel, dim3((nout + 255) / 256), dim3(256), 0, s, sum, out, nfft, scale, fftshift,
-                       trim, db, nout);
+hipError_t launch_scale(const float *sum, float *out, int nfft, double scale, const OutStage &stage, hipStream_t s) {
+    hipLaunchKernelGGL(scale_kernel, dim3((stage.nout + 255) / 256), dim3(256), 0, s, sum, out, nfft, scale, stage);
     return hipGetLastError();
 }
 
 // Summed partials of the two-channel path (time-sharded form): sums = [sum|X|^2][sum|Y|^2][sum conj(X)Y re,im]
 // in natural bin order -> scaled Pxx, Pyy, Pxy, Cxy with the plan's shift / trim.
-__global__ void csd_scale_kernel(const float *sums, int nfft, double scale, int fftshift, int trim, int nout,
-                                 float *pxx, float *pyy, float *pxy, float *cxy) {
+__global__ void csd_scale_kernel(const float *sums, int nfft, double scale, OutStage stage, float *pxx, float *pyy, float *pxy,
+                                 float *cxy) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nout) return;
-    const int ks = i + trim;
-    const int k = fftshift ? unshifted(ks, nfft) : ks;
+    if (i >= stage.nout) return;
+    const int k = in_bin(stage, nfft, i);
     const double xx = sums[k], yy = sums[nfft + k], re = sums[2 * nfft + 2 * k], im = sums[2 * nfft + 2 * k + 1];
     csd_store(xx, yy, re, im, scale, (size_t)i, pxx, pyy, pxy, cxy);
 }
 
-hipError_t launch_csd_scale(const float *sums, int nfft, double scale, int fftshift, int trim, float *pxx, float *pyy,
-                            float *pxy, float *cxy, hipStream_t s) {
-    const int nout = nfft - 2 * trim;
-    hipLaunchKernelGGL(csd_scale_kernel, dim3((nout + 255) / 256), dim3(256), 0, s, sums, nfft, scale, fftshift, trim,
-                       nout, pxx, pyy, pxy, cxy);
+hipError_t launch_csd_scale(const float *sums, int nfft, double scale, const OutStage &stage, float *pxx, float *pyy, float *pxy,
+                            float *cxy, hipStream_t s) {
+    hipLaunchKernelGGL(csd_scale_kernel, dim3((stage.nout + 255) / 256), dim3(256), 0, s, sums, nfft, scale, stage, pxx, pyy, pxy, cxy);
     return hipGetLastError();
 }
 
@@ -461,7 +373,8 @@ __global__ __launch_bounds__(256) void chain_reduce_kernel(const float *partial,
 
 struct ChainStateArgs {
     const float *rows;      // [nrows][nfft] group rows (or the team rows); bin order by `layout` (bin_pos)
-    int nrows, nfft, fftshift, acc_mode, layout;
+    int nrows, nfft, fftshift, acc_mode;
+    RowLayout layout;
     long long nbase;
     double decay;           // (1 - alpha)^nbase, computed on the host (a device pow() in double is a long routine)
     float alpha, kdb;
@@ -537,7 +450,7 @@ int chain_tail_groups(int W, int nfft) {
     return g < 1 ? 1 : g;
 }
 
-hipError_t launch_chain_tail(const float *partial, float *scratch, int W, int nfft, int layout, int fftshift, int acc_mode, long long nbase,
+hipError_t launch_chain_tail(const float *partial, float *scratch, int W, int nfft, RowLayout layout, int fftshift, int acc_mode, long long nbase,
                              float alpha, float kdb, float *iir_state, float *peak_state, const float *raw_rows,
                              long long nraw, float *rows_out, hipStream_t s) {
     ChainStateArgs a;

@@ -39,7 +39,7 @@
 // a run's segments cannot be registers either (indexed by the loop): they live in the workgroup's own partial rows, as in
 // mtm_ftest_kernel from 4096 points on - the first segment of a run stores, every later one reads, adds and stores.
 #include "mtm_common.hip.h"
-#include "stat_finalize.hip.h"
+#include "out_stage.hip.h"
 #include "launch.h"
 
 #include <algorithm>
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(T) void mtm_adapt_kernel(MtmAdaptArgs a) {
     }
 }
 
-// The shared finalize stage (stat_finalize.hip.h) on the two rows sum S_s, sum nu_s; then the PSD row with its dB and the dof row.
+// The shared finalize stage (out_stage.hip.h) on the two rows sum S_s, sum nu_s; then the PSD row with its dB and the dof row.
 __global__ __launch_bounds__(256) void adapt_finalize_kernel(AdaptFinalizeArgs a) {
     const int k = blockIdx.x * 32 + (threadIdx.x & 31), stream = blockIdx.y;
     int i;

@@ -23,7 +23,7 @@
 //                                     read, add and store, the last one reads and closes the segment; again every thread
 //                                     its own addresses, so no barrier, and the rows stay in L2.
 #include "mtm_common.hip.h"
-#include "stat_finalize.hip.h"
+#include "out_stage.hip.h"
 #include "launch.h"
 
 namespace oth {
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(T) void mtm_ftest_kernel(MtmFtestArgs a) {
     }
 }
 
-// The shared finalize stage (stat_finalize.hip.h) on the two rows sum num, sum den; then the three rows.
+// The shared finalize stage (out_stage.hip.h) on the two rows sum num, sum den; then the three rows.
 __global__ __launch_bounds__(256) void ftest_finalize_kernel(FtestFinalizeArgs a) {
     const int k = blockIdx.x * 32 + (threadIdx.x & 31), stream = blockIdx.y;
     int i;

@@ -26,7 +26,7 @@
 //                  X's spectrum through the workgroup's own global workspace row.
 // The totals are read again per item (L2), never held.
 #include "mtm_common.hip.h"
-#include "stat_finalize.hip.h"
+#include "out_stage.hip.h"
 #include "launch.h"
 
 #include <type_traits>
@@ -233,7 +233,7 @@ template <int N, int T, bool KEEP, bool TWO, bool ACCREG> __global__ __launch_bo
     }
 }
 
-// The shared finalize stage (stat_finalize.hip.h) on the 2 npairs rows sum l, sum l^2; then the variances in double and
+// The shared finalize stage (out_stage.hip.h) on the 2 npairs rows sum l, sum l^2; then the variances in double and
 // their rows.  The Cxy row is the first pass's (its reduction formed it from the double sums, natural order): it only takes
 // the shift and trim here.
 template <int NP> __device__ __forceinline__ void jack_finalize(const JackFinalizeArgs &a) {

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include "row_layout.h"
+
 namespace oth {
 
 // Launch description of the segment-averaging (Welch / CSD) kernels.
@@ -109,6 +111,13 @@ inline int finalize_row_groups(int nfft, int W, int nch) {
     return 65536 / nfft;      // (nfft / 256) x groups = 256 workgroups: 256 / 128 / 64 groups
 }
 
+// ---- the output stage of a finalize launch (out_stage.hip.h; abi_state.h fills it from the plan) ---------------------------
+struct OutStage {
+    int fftshift, trim;
+    int db;                 // the PSD rows only (psd_value)
+    int nout;               // nfft - 2 trim
+};
+
 struct FinalizeArgs {
     const float *partial;   // [nstreams][W][nch][nfft]
     float *scratch;         // [nstreams][kReduceGroups][nch][nfft] or nullptr (single-stage)
@@ -120,13 +129,9 @@ struct FinalizeArgs {
     int W;
     int nfft;
     int nch;                // 1 or 4
-    int layout;             // 0 natural, 1 welch4096 digit order, 2 / 3 welch16k order at 16384 / 8192, 4 / 5 welch16k1x order at 16384 / 8192,
-                            // 6 the two-level any-length route: position k1 l2 + k2 holds bin k1 + l1 k2 (kernels_misc.hip bin_pos)
-    int l1, l2;             // layout 6 only
-    int fftshift;
-    int trim;
-    int db;
-    int nout;
+    RowLayout layout;       // bin order of the partial rows (row_layout.h)
+    int l1, l2;             // ROW_TWOLEVEL only
+    OutStage out;
     int accumulate;         // out0 += (raw sums; streaming form)
     unsigned *queue_reset;  // chunk-ticket counters of the averaging kernel, zeroed here for the next launch (or null)
     int queue_n;
@@ -158,14 +163,14 @@ int csd4096ws_blocks_per_cu();
 // welch16k.hip: nfft = nperseg = 16384 (one 1024-thread workgroup per CU) or 8192 (two 512-thread workgroups)
 hipError_t launch_welch_tuned16k(int nfft, const WelchArgs &a, hipStream_t s);
 // welch16k1x.hip: nfft = nperseg = 16384, no detrend, whole-segment loads (the scanner's non-overlapping vectors): one
-// cross-wave exchange, two workgroup barriers per segment; partial rows in finalize layout 4
+// cross-wave exchange, two workgroup barriers per segment; partial rows in x1_layout(nfft)
 hipError_t launch_welch_tuned16k1x(int nfft, const WelchArgs &a, bool window, bool plain, hipStream_t s);
 // the same transform at step = 8192 (50 % overlap, the kept half in registers); WelchArgs.fd = window_spectrum_table_16k1x
 hipError_t launch_welch_tuned16k1x_half(int nfft, const WelchArgs &a, hipStream_t s);
 hipError_t launch_welch_tuned8kws(const WelchArgs &a, hipStream_t s);      // 8192 points, 50 % overlap, role-split (contiguous runs only)
 // the fused periodogram chain at 8192 / 16384 points (one workgroup per segment; workgroups per CU: 2 / 1)
 hipError_t launch_chain16k(int nfft, const SegArgs &a, bool rect, hipStream_t s);
-// the same chain at 16384 points on the one-exchange pipelined loop (welch16k1x.hip); partial rows in layout 4; needs
+// the same chain at 16384 points on the one-exchange pipelined loop (welch16k1x.hip); partial rows in ROW_X1_16K; needs
 // chunks of at least two segments
 hipError_t launch_chain16k1x(int nfft, const SegArgs &a, bool rect, hipStream_t s);
 hipError_t launch_pgram(int nfft, const PgramArgs &a, hipStream_t s);
@@ -183,16 +188,15 @@ hipError_t launch_segws(int nfft, const SegArgs &a, int det, hipStream_t s);
 // partial rows of a chain launch + the stored raw rows -> IIR / peak state and the rows handed back; `scratch` holds
 // chain_tail_groups(W, nfft) rows of nfft floats (0 rows: not needed)
 int chain_tail_groups(int W, int nfft);
-// layout: bin order of the partial rows (kernels_misc.hip bin_pos: 0 natural, 2 / 3 welch16k order at 16384 / 8192)
-hipError_t launch_chain_tail(const float *partial, float *scratch, int W, int nfft, int layout, int fftshift, int acc_mode, long long nbase,
+// layout: bin order of the partial rows (row_layout.h)
+hipError_t launch_chain_tail(const float *partial, float *scratch, int W, int nfft, RowLayout layout, int fftshift, int acc_mode, long long nbase,
                              float alpha, float kdb, float *iir_state, float *peak_state, const float *raw_rows,
                              long long nraw, float *rows_out, hipStream_t s);
 hipError_t launch_set_flag(int *flag, int v, hipStream_t s);
 hipError_t launch_finalize(const FinalizeArgs &a, int nstreams, hipStream_t s);
-hipError_t launch_scale(const float *sum, float *out, int nfft, double scale, int fftshift, int trim, int db,
-                        hipStream_t s);
-hipError_t launch_csd_scale(const float *sums, int nfft, double scale, int fftshift, int trim, float *pxx, float *pyy,
-                            float *pxy, float *cxy, hipStream_t s);
+hipError_t launch_scale(const float *sum, float *out, int nfft, double scale, const OutStage &stage, hipStream_t s);
+hipError_t launch_csd_scale(const float *sums, int nfft, double scale, const OutStage &stage, float *pxx, float *pyy, float *pxy,
+                            float *cxy, hipStream_t s);
 hipError_t launch_rows_epilogue(float *rows, long long nrows, int nfft, float alpha, float kdb, float *iir_state,
                                 float *peak_state, int *peak_init, int do_iir, int do_peak, hipStream_t s);
 hipError_t launch_group_mean(const float *rows, long long ngroups, int nfft, int group, float *out, hipStream_t s);
@@ -313,7 +317,7 @@ struct TlArgs {
     size_t ws_seg_stride;
     long long nseg;
     const float2 *tw;          // W_L^k
-    float *partial;            // [W][channels 1 | 4][L] sums, position k1 L2 + k2 (finalize layout 6)
+    float *partial;            // [W][channels 1 | 4][L] sums in ROW_TWOLEVEL
     int first_chunk;
 };
 constexpr int kTlSub = 4096;
@@ -325,7 +329,7 @@ struct W32kArgs {
     long long nseg;
     const float *win;          // 32768 window values
     const float2 *tw;          // W_32768^k, k < 32768
-    float *partial;            // [W][32768] sums, finalize layout 7 (front: [W][65536], layout 8)
+    float *partial;            // [W][32768] sums in ROW_W32K (front: [W][65536] in ROW_W64K)
     int detrend;
     int front;                 // 1: 65536-point segments, a pair of workgroups each (win: 65536 values, tw: W_65536^k)
     const float *wpm;          // front + detrend: w[n] + w[n + 32768] (n < 32768), then w[n] - w[n + 32768]
@@ -392,13 +396,6 @@ struct MtmCsdArgs {
 size_t mtmcsd_ws_points(int nfft);      // 0: the build keeps both spectra in LDS
 int mtmcsd_blocks_per_cu(int nfft);
 hipError_t launch_mtmcsd(int nfft, const MtmCsdArgs &a, hipStream_t s);
-
-// ---- the output stage of a statistic's finalize launch (stat_finalize.hip.h; abi_stat.h fills it from the plan) -------------
-struct OutStage {
-    int fftshift, trim;
-    int db;                 // the PSD rows only (psd_value)
-    int nout;               // nfft - 2 trim
-};
 
 // ---- mtmftest.hip: Thomson's harmonic F-test on the same taper loop; the work item is a whole segment ------------------
 struct MtmFtestArgs {

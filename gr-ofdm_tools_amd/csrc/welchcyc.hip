@@ -37,7 +37,7 @@
 // Not here: the conjugate cyclic spectrum E[X(f + alpha) X(-f)], a search over alpha (the caller supplies the cycle
 // frequencies), multitaper plans, transform lengths that are not a power of two.
 #include "mtm_common.hip.h"
-#include "stat_finalize.hip.h"
+#include "out_stage.hip.h"
 #include "launch.h"
 
 #include <type_traits>
@@ -179,7 +179,7 @@ template <int N, int T, int GA, bool KEEP, bool TWO, bool ACCREG> __global__ __l
     }
 }
 
-// The shared finalize stage (stat_finalize.hip.h), one cycle frequency per blockIdx.z, on the |X|^2 row of group 0 and the
+// The shared finalize stage (out_stage.hip.h), one cycle frequency per blockIdx.z, on the |X|^2 row of group 0 and the
 // frequency's own three rows; then scf, coh and (with the first cycle frequency) the PSD row.
 __global__ __launch_bounds__(256) void cyc_finalize_kernel(CycFinalizeArgs a) {
     const int k = blockIdx.x * 32 + (threadIdx.x & 31), stream = blockIdx.y, cyc = blockIdx.z;

@@ -20,7 +20,7 @@
 //                         as in mtmftest.hip - the first segment of a run stores them, every later one reads, adds and
 //                         stores, each thread its own addresses, so no barrier.
 #include "mtm_common.hip.h"
-#include "stat_finalize.hip.h"
+#include "out_stage.hip.h"
 #include "launch.h"
 
 namespace oth {
@@ -106,7 +106,7 @@ template <int N, int T, bool KEEP, bool ACCREG> __global__ __launch_bounds__(T) 
     }
 }
 
-// The shared finalize stage (stat_finalize.hip.h) on the two rows S1, S2; then SK in double and the one or two rows.
+// The shared finalize stage (out_stage.hip.h) on the two rows S1, S2; then SK in double and the one or two rows.
 __global__ __launch_bounds__(256) void sk_finalize_kernel(SkFinalizeArgs a) {
     const int k = blockIdx.x * 32 + (threadIdx.x & 31), stream = blockIdx.y;
     int i;

@@ -128,6 +128,64 @@ def test_exception_barrier_of_the_abi_host_files(tmp_path):
         {name: defined.count(name) for name in _hip.SIGNATURES if defined.count(name) != 1}
 
 
+def test_row_layouts_are_permutations(tmp_path):
+    """csrc/row_layout.h is the one place that knows where a bin sits in a partial-sum row; bin_pos is what the finalize
+    kernels call, here built for the host with g++ (csrc/row_layout_probe.cpp).  For every layout at the size or sizes its
+    writer runs it is a bijection of [0, nfft); the digit swap of layouts 1 - 3 is its own inverse; and three positions per layout hold the bin the header's formula gives, worked out by hand.  The writers themselves are
+    checked by the GPU parity tests only."""
+    import subprocess
+    import numpy as np
+    csrc = os.path.join(ROOT, 'gr-ofdm_tools_amd', 'csrc')
+    so = str(tmp_path / 'row_layout_probe.so')
+    subprocess.check_call(['g++', '-std=c++17', '-O1', '-shared', '-fPIC', os.path.join(csrc, 'row_layout_probe.cpp'), '-o', so])
+    probe = ctypes.CDLL(so)
+
+    def bins(layout, nfft, l1=0, l2=0):
+        return np.array([probe.oth_probe_bin_pos(pos, layout, l1, l2) for pos in range(nfft)])
+
+    assert [probe.oth_probe_w16k_layout(n) for n in (16384, 8192)] == [2, 3]
+    assert [probe.oth_probe_x1_layout(n) for n in (16384, 8192)] == [4, 5]
+    assert [probe.oth_probe_w32k_layout(n) for n in (32768, 65536)] == [7, 8]
+    # (layout, nfft, l1, l2): 6 at the split any_describe (fft_any.hip) gives 32768 points, L1 = 256 rows of L2 = 128
+    cases = [(0, 64, 0, 0), (0, 999, 0, 0), (1, 4096, 0, 0), (2, 16384, 0, 0), (4, 16384, 0, 0), (3, 8192, 0, 0), (5, 8192, 0, 0),
+             (6, 32768, 256, 128), (7, 32768, 0, 0), (8, 65536, 0, 0)]
+    table = {}
+    for layout, nfft, l1, l2 in cases:
+        k = table[layout, nfft] = bins(layout, nfft, l1, l2)
+        assert np.array_equal(np.sort(k), np.arange(nfft)), (layout, nfft)
+    # the digit swap k0 <-> k1 is its own inverse: layout 1 as a whole; in layouts 2 / 3 the swap inside each block of 4096
+    # positions (block k' holds the bins k' + F q, F = 4 / 2, at the layout-1 position of q - as a whole permutation they
+    # are no involution: k' moves from the top of the position to the bottom of the bin)
+    swap = table[1, 4096]
+    assert np.array_equal(swap[swap], np.arange(4096))
+    for layout, nfft, F in ((2, 16384, 4), (3, 8192, 2)):
+        pos, k = np.arange(nfft), table[layout, nfft]
+        assert np.array_equal(k % F, pos >> 12) and np.array_equal(swap[k // F], pos & 4095), layout
+    # position -> bin, from the formulas in row_layout.h
+    literal = {
+        (0, 999): {0: 0, 500: 500, 998: 998},
+        # 16 k0 + k1 + 256 k2 holds k0 + 16 k1 + 256 k2
+        (1, 4096): {1: 16, 16 * 3 + 5 + 256 * 7: 3 + 16 * 5 + 256 * 7, 4095: 4095},
+        # 4096 k' + (layout-1 position of q) holds k' + 4 q; 8192 points: k' + 2 q
+        (2, 16384): {1: 4 * 16, 4096 * 3 + 16 * 2 + 9 + 256 * 5: 3 + 4 * (2 + 16 * 9 + 256 * 5), 16383: 16383},
+        (3, 8192): {1: 2 * 16, 4096 + 16 * 2 + 9 + 256 * 5: 1 + 2 * (2 + 16 * 9 + 256 * 5), 8191: 8191},
+        # 1024 k2 + 64 k0 + 4 k1 + q holds k0 + 16 k1 + 256 k2 + 4096 bitrev2(q)
+        (4, 16384): {1: 8192, 2: 4096, 1024 * 6 + 64 * 11 + 4 * 13 + 3: 11 + 16 * 13 + 256 * 6 + 4096 * 3},
+        # 512 k2 + 64 (k0 >> 1) + 4 (8 (k0 & 1) + k1) + q holds k0 + 16 k1 + 128 k2 + 2048 bitrev2(q)
+        (5, 8192): {1: 4096, 32: 1, 512 * 9 + 64 * 6 + 4 * (8 + 5) + 2: 13 + 16 * 5 + 128 * 9 + 2048 * 1},
+        # k1 l2 + k2 holds k1 + l1 k2
+        (6, 32768): {1: 256, 128: 1, 200 * 128 + 77: 200 + 256 * 77},
+        # halves of 16384 positions in layout 4: A holds bin 2 k, B bin 2 k + 1
+        (7, 32768): {1: 2 * 8192, 16384: 1, 16384 + 1024 * 6 + 64 * 11 + 4 * 13 + 3: 2 * (11 + 16 * 13 + 256 * 6 + 4096 * 3) + 1},
+        # halves of 32768 positions in layout 7: the first the even bins, the second the odd
+        (8, 65536): {1: 4 * 8192, 32768: 1, 32768 + 16384 + 2: 2 * (2 * 4096 + 1) + 1},
+        (0, 64): {0: 0, 31: 31, 63: 63},
+    }
+    assert sorted(literal) == sorted(table)
+    for key, want in literal.items():
+        assert len(want) == 3 and {pos: int(table[key][pos]) for pos in want} == want, key
+
+
 def test_bench_gpus_n_without_a_gpu_exits_with_the_clear_message():
     """`python bench.py --gpus N` is the driver's command shape: without a launcher it must decide BEFORE touching the
     GPU whether it can spawn its ranks, and say why not."""
