@@ -10,22 +10,9 @@ namespace {
 constexpr int XROW = 68;                       // float2 per exchange-B row (64 + 4 pad)
 constexpr int XREG = 16 * XROW;                // float2 per wave region (1088: exchange A uses [0, 1024))
 
-// v[r16(k)] *= W^k, k = 1..15, W^k rebuilt from p1 = W and p4 = W^4 as in scatter_pow16
+// v[r16(k)] *= W^k, k = 1..15, W^k rebuilt from p1 = W and p4 = W^4
 __device__ __forceinline__ void twiddle_pow16_inplace(float2 (&v)[16], float2 p1, float2 p4) {
-    float2 wj[4], wi[4];
-    wj[1] = p1;
-    wi[1] = p4;
-    asm volatile("" : "+v"(wj[1].x), "+v"(wj[1].y), "+v"(wi[1].x), "+v"(wi[1].y));
-    wj[2] = cmul(wj[1], wj[1]);
-    wj[3] = cmul(wj[2], wj[1]);
-    wi[2] = cmul(wi[1], wi[1]);
-    wi[3] = cmul(wi[2], wi[1]);
-#pragma unroll
-    for (int k = 1; k < 16; ++k) {
-        const int i = k >> 2, j = k & 3;
-        const float2 w = (i == 0) ? wj[j] : ((j == 0) ? wi[i] : cmul(wi[i], wj[j]));
-        v[r16(k)] = cmul(v[r16(k)], w);
-    }
+    twiddle16(v, Tw16(p1, p4), [&](int k, float2 val) { v[r16(k)] = val; });
 }
 
 // Radix-4 butterfly over the four lanes of a quad (lane q holds input q of every one of its sixteen registers), in

@@ -4,6 +4,8 @@
 #pragma once
 #include "fft_lds.hip.h"
 #include "oth_internal.h"
+#include "pinned_load.hip.h"
+#include "twiddle16.hip.h"
 
 static_assert(oth::kPilotProbes == 8, "load_pilot() (fft_lds.hip.h) adds eight probe means");
 
@@ -26,9 +28,6 @@ __device__ __forceinline__ float2 mul_w3(float2 a) { return make_float2(fmaf(a.x
 __device__ __forceinline__ float2 mul_w4(float2 a) { return make_float2(a.y, -a.x); }
 __device__ __forceinline__ float2 mul_w6(float2 a) { return make_float2((a.y - a.x) * RH, -(a.x + a.y) * RH); }
 __device__ __forceinline__ float2 mul_w9(float2 a) { return make_float2(-fmaf(a.x, C1, a.y * S1), fmaf(a.x, S1, -a.y * C1)); }
-
-// position of output k of dft16() inside v[]
-__host__ __device__ constexpr int r16(int k) { return 4 * (k & 3) + (k >> 2); }
 
 constexpr float T1 = 0.41421356237309503f;   // tan(pi/8)
 
@@ -211,12 +210,6 @@ __device__ __forceinline__ float2 load_once(const float2 *p) {
 
 // Chunk c of the segment schedule: the first `nbig` chunks have `chunk` segments, the rest `tail_chunk`
 // (smaller chunks for the last round even out the finish of the dynamic schedule).
-// 4-byte non-temporal-free load of a window value at (uniform row base) + (lane offset), pinned like load_row_nt: the
-// compiler would hoist sixteen loop-invariant window loads into sixteen registers the two segments in flight need
-__device__ __forceinline__ void load_win(float &dst, unsigned lane_off, const char *row) {
-    asm volatile("global_load_dword %0, %1, %2" : "=v"(dst) : "v"(lane_off), "s"(row) : "memory");
-}
-
 __device__ __forceinline__ long long chunk_count(const WelchArgs &p) {
     const long long rest = p.nseg - p.nbig * p.chunk;
     return p.nbig + (rest + p.tail_chunk - 1) / p.tail_chunk;
@@ -259,51 +252,10 @@ __device__ __forceinline__ void prio_compute() { __builtin_amdgcn_s_setprio(0); 
 // global loads stay in flight across the barrier (the compiler still waits for them at first use).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// out[STRIDE * k] = v[r16(k)] * W^k for k = 0..15, where W^k is rebuilt from p1 = W and p4 = W^4 as
-// (W^4)^i * W^j, k = 4i + j: 13 complex products per call instead of 15 stored (30 VGPRs) or loaded
-// values.  Loading them from an LDS table costs more than the arithmetic: hipcc issues one table read,
-// waits lgkmcnt(0), multiplies and writes, fifteen exposed LDS round trips per exchange.  The empty asm
-// keeps the loop-invariant powers from being hoisted back into registers.
-template <int STRIDE>
-__device__ __forceinline__ void scatter_pow16(const float2 (&v)[16], float2 *out, float2 p1, float2 p4) {
-    float2 wj[4], wi[4];
-    wj[1] = p1;
-    wi[1] = p4;
-    asm volatile("" : "+v"(wj[1].x), "+v"(wj[1].y), "+v"(wi[1].x), "+v"(wi[1].y));
-    wj[2] = cmul(wj[1], wj[1]);
-    wj[3] = cmul(wj[2], wj[1]);
-    wi[2] = cmul(wi[1], wi[1]);
-    wi[3] = cmul(wi[2], wi[1]);
-    out[0] = v[0];                              // r16(0) == 0
-#pragma unroll
-    for (int k = 1; k < 16; ++k) {
-        const int i = k >> 2, j = k & 3;
-        const float2 w = (i == 0) ? wj[j] : ((j == 0) ? wi[i] : cmul(wi[i], wj[j]));
-        out[STRIDE * k] = cmul(v[r16(k)], w);
-    }
-}
-
-// The same scatter with six stored powers W, W^2, W^3, W^4, W^8, W^12: nine products instead of thirteen (the four
-// squarings / cubings of scatter_pow16 are gone), at eight more registers for the caller.
-template <int STRIDE>
-__device__ __forceinline__ void scatter_pow16_six(const float2 (&v)[16], float2 *out, float2 p1, float2 p2, float2 p3, float2 p4,
-                                                  float2 p8, float2 p12) {
-    float2 wj[4], wi[4];
-    wj[1] = p1, wj[2] = p2, wj[3] = p3;
-    wi[1] = p4, wi[2] = p8, wi[3] = p12;
-    asm volatile("" : "+v"(wj[1].x), "+v"(wj[1].y), "+v"(wj[2].x), "+v"(wj[2].y), "+v"(wj[3].x), "+v"(wj[3].y));
-    out[0] = v[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) {
-        const int i = k >> 2, j = k & 3;
-        const float2 w = (i == 0) ? wj[j] : ((j == 0) ? wi[i] : cmul(wi[i], wj[j]));
-        out[STRIDE * k] = cmul(v[r16(k)], w);
-    }
-}
-
-// The same scatter with 6 + NM stored powers: pm = W^5, W^6, W^7, W^9, W^10, W^11, ... in that order (NM = 3: nine stored,
-// six products; NM = 4: ten, five).  Each remaining product is formed at the store that uses it (formed ahead of the
-// stores they cost 14-18 spilled registers).
+// scatter_pow16_six (twiddle16.hip.h) with 6 + NM stored powers: pm = W^5, W^6, W^7, W^9, W^10, W^11, ... in that order
+// (NM = 3: nine stored, six products; NM = 4: ten, five).  Each remaining product is formed at the store that uses it (formed
+// ahead of the stores they cost 14-18 spilled registers).  Not a twiddle16() call site: which factors are opaque depends on
+// NM (below), and welch4096ws.hip's code object is not to move.
 __host__ __device__ constexpr int pow16_slot(int k) { return k - 5 - (k >> 2) + 1; }      // k = 5, 6, 7, 9, 10, 11, 13, ... -> 0, 1, 2, ...
 template <int STRIDE, int NM>
 __device__ __forceinline__ void scatter_pow16_stored(const float2 (&v)[16], float2 *out, float2 p1, float2 p2, float2 p3, float2 p4,

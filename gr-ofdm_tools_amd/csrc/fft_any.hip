@@ -390,6 +390,7 @@ __global__ __launch_bounds__(64) void any_mean_kernel(const float2 *x, const flo
         sr += (double)v.x;
         si += (double)v.y;
     }
+    // (spelled out: through wave_sum() of fft_lds.hip.h this kernel comes out with other registers)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         sr += __shfl_xor(sr, off, 64);

@@ -20,6 +20,35 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
 }
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+
+// Reduction over the 64 lanes of a wave by xor-shuffle: every lane ends with op over all lanes.
+template <class V, class Op> __device__ __forceinline__ V wave_reduce(V v, Op op) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
+    return v;
+}
+template <class V> __device__ __forceinline__ V wave_sum(V v) {
+    return wave_reduce(v, [](V a, V b) { return a + b; });
+}
+__device__ __forceinline__ float2 wave_sum(float2 v) {      // both components ride the same six steps
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        v.x += __shfl_xor(v.x, off, 64);
+        v.y += __shfl_xor(v.y, off, 64);
+    }
+    return v;
+}
+// Sum of v over the T threads of the workgroup in a fixed order; ends with every thread holding it.  red[base .. base + T / 64)
+// are its slots, free for reuse after the caller's next barrier.
+template <int T> __device__ __forceinline__ float2 block_sum(float2 v, float2 *red, int tid, int base = 0) {
+    v = wave_sum(v);
+    if ((tid & 63) == 0) red[base + (tid >> 6)] = v;
+    __syncthreads();
+    float2 s = make_float2(0.f, 0.f);
+#pragma unroll
+    for (int w = 0; w < T / 64; ++w) s = cadd(s, red[base + w]);
+    return s;
+}
 // Im(conj(X) Y) = X.x Y.y - X.y Y.x for the two-channel sums, with BOTH products rounded before they are subtracted (no
 // contraction into an fma): the form is antisymmetric in X and Y bit for bit, so a channel against itself gives exactly 0 in
 // every segment and Im Pxy = 0 - as numpy's complex product does.  fmaf(X.x, Y.y, fmaf(-X.y, Y.x, acc)) left the rounding

@@ -210,6 +210,7 @@ __global__ __launch_bounds__(256) void tl_mean_kernel(const float2 *x, long long
         sr += (double)v.x;
         si += (double)v.y;
     }
+    // (spelled out: through wave_sum() of fft_lds.hip.h this kernel comes out with other registers)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         sr += __shfl_xor(sr, off, 64);
@@ -243,6 +244,7 @@ __global__ __launch_bounds__(256) void tl_blocksum_kernel(const float2 *x, long 
         sr += (double)v[q].x;
         si += (double)v[q].y;
     }
+    // (spelled out: through wave_sum() of fft_lds.hip.h this kernel comes out with other registers)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         sr += __shfl_xor(sr, off, 64);

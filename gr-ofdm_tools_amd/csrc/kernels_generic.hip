@@ -12,27 +12,6 @@
 
 namespace oth {
 
-__device__ __forceinline__ float2 wave_sum(float2 v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        v.x += __shfl_xor(v.x, off, 64);
-        v.y += __shfl_xor(v.y, off, 64);
-    }
-    return v;
-}
-
-// Sum of v over the workgroup; `red` has T/64 slots and is free for reuse after
-// the caller's next barrier.
-template <int T> __device__ __forceinline__ float2 block_sum(float2 v, float2 *red, int tid) {
-    v = wave_sum(v);
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    float2 s = make_float2(0.f, 0.f);
-#pragma unroll
-    for (int w = 0; w < T / 64; ++w) s = cadd(s, red[w]);
-    return s;
-}
-
 // Load one segment (zero-padded past nperseg), remove its mean if asked,
 // apply the window and leave it in buf.  Ends with a barrier.
 template <int N, int T>

@@ -5,6 +5,7 @@
 // 232-249), the synthetic IQ generator and the measurement probes.
 #include <cstdint>
 
+#include "fft_lds.hip.h"
 #include "out_stage.hip.h"
 
 namespace oth {
@@ -542,8 +543,7 @@ __global__ void channel_sum_kernel(const double *movavg, int nfft, int nch, cons
     const double *row = movavg + (size_t)blockIdx.y * nfft;
     double s = 0.0;
     for (int i = lo[c] + threadIdx.x; i < hi[c]; i += 64) s += row[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = wave_sum(s);
     if (threadIdx.x == 0) power[(size_t)blockIdx.y * nch + c] = (float)s;
 }
 
@@ -571,6 +571,7 @@ __global__ __launch_bounds__(256) void bin_threshold_kernel(const float *psd, in
         }
         mn = nan_min(mn, (float)fabs(s / srch_bins));
     }
+    // (spelled out: through wave_reduce() of fft_lds.hip.h this kernel comes out with other registers)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mn = nan_min(mn, __shfl_xor(mn, off, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
@@ -590,6 +591,7 @@ __global__ __launch_bounds__(256) void bin_threshold_ma_kernel(const float *psd,
     const double *ma = movavg + (size_t)blockIdx.x * nfft;
     float mn = INFINITY;
     for (int i = threadIdx.x; i < nfft; i += 256) mn = nan_min(mn, (float)ma[i]);
+    // (spelled out: through wave_reduce() of fft_lds.hip.h this kernel comes out with other registers)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mn = nan_min(mn, __shfl_xor(mn, off, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
@@ -737,6 +739,7 @@ __global__ __launch_bounds__(kMaThreads) void movavg_run_kernel(const float *psd
     }
     __syncthreads();
     for (int k = threadIdx.x; k < kMaTile && base + k < nfft; k += kMaThreads) out[base + k] = ys[ma_pad(k)];
+    // (spelled out: through wave_reduce() of fft_lds.hip.h this kernel comes out with other registers)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mn = nan_min(mn, __shfl_xor(mn, off, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
@@ -782,8 +785,7 @@ __global__ __launch_bounds__(256) void scan_post_kernel(const float *psd, const 
     const double *row = movavg + (size_t)blockIdx.y * nfft;
     double s = 0.0;
     for (int i = lo[c] + (threadIdx.x & 63); i < hi[c]; i += 64) s += row[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) power[(size_t)blockIdx.y * nch + c] = (float)s;
 }
 
@@ -930,6 +932,7 @@ __global__ void iq_power_kernel(const float2 *iq, size_t n, double *acc4) {
         si += v.y;
         sp += (double)v.x * v.x + (double)v.y * v.y;
     }
+    // (spelled out: through wave_sum() of fft_lds.hip.h this kernel comes out with other registers)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         sr += __shfl_xor(sr, off, 64);
@@ -962,6 +965,7 @@ __global__ __launch_bounds__(1024) void pilot_mean_kernel(const float2 *x, const
         sr += ((double)v[0].x + v[1].x) + ((double)v[2].x + v[3].x);
         si += ((double)v[0].y + v[1].y) + ((double)v[2].y + v[3].y);
     }
+    // (spelled out: through wave_sum() of fft_lds.hip.h this kernel comes out with other registers)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         sr += __shfl_xor(sr, off, 64);

@@ -13,6 +13,7 @@
 // Counts are integers, so the result is the same bits under any schedule and any workgroup order.  Even nseg needs ranks k
 // and k + 1: only k is carried through the passes; the last pass also records the smallest key above k's 24-bit bucket,
 // and rank k + 1 is then k's own value (the bucket's count allows it), the next digit of the last histogram, or that key.
+#include "fft_lds.hip.h"
 #include "oth_internal.h"
 
 namespace oth {
@@ -79,15 +80,6 @@ __global__ __launch_bounds__(kMedBlock) void median_hist_kernel(MedianArgs a, in
     }
 }
 
-__device__ __forceinline__ unsigned wave_min(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned w = __shfl_xor(v, o, 64);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-
 // one wave per (stream, bin); LAST: the pass of the lowest digit - writes the median
 template <bool LAST>
 __global__ __launch_bounds__(256) void median_scan_kernel(MedianArgs a, int shift) {
@@ -137,7 +129,7 @@ __global__ __launch_bounds__(256) void median_scan_kernel(MedianArgs a, int shif
 #pragma unroll
     for (int j = 3; j >= 0; --j)
         if (4u * lane + j > d && cnt[j]) nxt = 4u * lane + j;
-    nxt = wave_min(nxt);
+    nxt = wave_reduce(nxt, [](unsigned v, unsigned w) { return w < v ? w : v; });
     if (lane == 0) {
         const unsigned klo = prefix | d;
         const unsigned khi = r + 1 < cd ? klo : (nxt < 256u ? (prefix | nxt) : a.above[sb]);

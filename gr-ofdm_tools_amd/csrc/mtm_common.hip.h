@@ -10,26 +10,7 @@
 
 namespace oth {
 
-__device__ __forceinline__ float2 mtm_wave_sum(float2 v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        v.x += __shfl_xor(v.x, off, 64);
-        v.y += __shfl_xor(v.y, off, 64);
-    }
-    return v;
-}
-
-// Sum of v over the workgroup in a fixed order; ends with every thread holding it.  `red` has T / 64 + 1 slots.
-template <int T> __device__ __forceinline__ float2 mtm_block_sum(float2 v, float2 *red, int tid) {
-    v = mtm_wave_sum(v);
-    if ((tid & 63) == 0) red[1 + (tid >> 6)] = v;
-    __syncthreads();
-    float2 s = make_float2(0.f, 0.f);
-#pragma unroll
-    for (int w = 0; w < T / 64; ++w) s = cadd(s, red[1 + w]);
-    return s;
-}
-
+// `red` of the taper-loop kernels: red[0] holds the pilot, red[1 ..] are block_sum's T / 64 slots (base 1)
 constexpr int kMtmPilot = 64;      // samples behind the pilot (the first wave's lanes)
 
 // the mean of the segment's first min(64, nperseg) samples, the same bits in every thread (red[0])
@@ -37,7 +18,7 @@ __device__ __forceinline__ float2 mtm_pilot(const float2 *__restrict__ xs, int n
     if (tid < kMtmPilot) {
         const int np = nperseg < kMtmPilot ? nperseg : kMtmPilot;
         float2 t = tid < np ? xs[tid] : make_float2(0.f, 0.f);
-        t = mtm_wave_sum(t);
+        t = wave_sum(t);
         const float inv = 1.0f / (float)np;
         if (tid == 0) red[0] = make_float2(t.x * inv, t.y * inv);
     }
@@ -65,7 +46,7 @@ __device__ __forceinline__ void mtm_segment_entry(const float2 *__restrict__ xs,
         sum = cadd(sum, r);
     }
     if (detrend) {
-        const float2 tot = mtm_block_sum<T>(sum, red, tid);
+        const float2 tot = block_sum<T>(sum, red, tid, 1);
         const float inv = 1.0f / (float)nperseg;
         mean = make_float2(tot.x * inv, tot.y * inv);
     }

@@ -92,7 +92,7 @@ __global__ __launch_bounds__(T) void mtm_adapt_kernel(MtmAdaptArgs a) {
                 sq.x = fmaf(r.x, r.x, sq.x);
                 sq.y = fmaf(r.y, r.y, sq.y);
             }
-            const float2 tot = mtm_block_sum<T>(sq, red2, tid);
+            const float2 tot = block_sum<T>(sq, red2, tid, 1);
             sig2 = (tot.x + tot.y) * inv_n;
         }
         for (int k = 0; k < K; ++k) {

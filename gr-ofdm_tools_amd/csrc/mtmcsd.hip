@@ -61,7 +61,7 @@ __device__ __forceinline__ void mtmcsd_enter(const float2 *__restrict__ xs, int 
         sum = cadd(sum, r);
     }
     if (detrend) {
-        const float2 tot = mtm_block_sum<T>(sum, red, tid);
+        const float2 tot = block_sum<T>(sum, red, tid, 1);
         const float inv = 1.0f / (float)nperseg;
         mean = make_float2(tot.x * inv, tot.y * inv);
     }

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(T) void mtm_ftest_kernel(MtmFtestArgs a) {
                 sum = cadd(sum, r);
             }
             if (p.detrend) {
-                const float2 tot = mtm_block_sum<T>(sum, red, tid);
+                const float2 tot = block_sum<T>(sum, red, tid, 1);
                 const float inv = 1.0f / (float)p.nperseg;
                 mean = make_float2(tot.x * inv, tot.y * inv);
             }

@@ -86,41 +86,6 @@ template <int IMM, class PT> __device__ __forceinline__ void lds_read_imm(PT &ds
 template <int IMM, bool VEC = false> __device__ __forceinline__ void lds_write_imm(unsigned addr, float2 val) {
     asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(Pair<VEC>::from_f2(val)), "n"(IMM) : "memory");
 }
-template <int I, int N, class F> __device__ __forceinline__ void static_for(F f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// v[r16(k)] * W^k for k = 0..15 handed to put(k, value).  W^k = W^(4i) W^j (k = 4i + j) from the six stored
-// powers W, W^2, W^3, W^4, W^8, W^12 (correctly rounded table values): at most ONE complex product per twiddle.
-// Rebuilding all fifteen from W and W^4 (scatter_pow16 of the 4096 kernels) chains up to three products; with a
-// strong off-bin tone in a rectangular-window periodogram that rounding shows in every bin (the tone's bins carry
-// 2 sqrt(N) times the noise amplitude), enough to break 1e-4 on single rows.
-struct Pow6 {
-    float2 j1, j2, j3, i1, i2, i3;      // W^1, W^2, W^3, W^4, W^8, W^12
-};
-template <class F> __device__ __forceinline__ void twiddle_pow16(const float2 (&v)[16], const Pow6 &w6, F put) {
-    float2 wj[4], wi[4];
-    wj[1] = w6.j1;
-    wj[2] = w6.j2;
-    wj[3] = w6.j3;
-    wi[1] = w6.i1;
-    wi[2] = w6.i2;
-    wi[3] = w6.i3;
-    // the products below are loop-invariant: without this the compiler hoists all nine out of the segment loop
-    // and keeps them in registers (+36 VGPRs per pass)
-    // (every product has a wj factor: making those three opaque is enough, and costs six copies instead of twelve)
-    asm volatile("" : "+v"(wj[1].x), "+v"(wj[1].y), "+v"(wj[2].x), "+v"(wj[2].y), "+v"(wj[3].x), "+v"(wj[3].y));
-    put(std::integral_constant<int, 0>{}, v[0]);
-    static_for<1, 16>([&](auto kc) {
-        constexpr int k = decltype(kc)::value, i = k >> 2, j = k & 3;
-        const float2 w = (i == 0) ? wj[j] : ((j == 0) ? wi[i] : cmul(wi[i], wj[j]));
-        put(kc, cmul(v[r16(k)], w));
-    });
-}
-
 // Sum over the T lanes of a team that is a wave or part of one; every lane of the team gets the total.
 template <int T> __device__ __forceinline__ float team_total(float v) {
     if constexpr (T >= 64) {
@@ -218,7 +183,8 @@ __global__ __launch_bounds__(Geo<R>::BLOCK, WPS) void seg_kernel(SegArgs p) {
 #pragma unroll
         for (int a = 0; a < NA; ++a) win[a] = p.win[T * a + t];
     }
-    // W_N^(k t) for pass 1 and W_N^(16 k c) for pass 2, k = 1, 2, 3, 4, 8, 12 (table index mod N)
+    // W_N^(k t) for pass 1 and W_N^(16 k c) for pass 2, k = 1, 2, 3, 4, 8, 12 (table index mod N): six stored powers, not two
+    // seeds - the chain compares single rows to 1e-4 (twiddle16.hip.h)
     const Pow6 tw1 = {p.tw[t], p.tw[(2 * t) & (N - 1)], p.tw[(3 * t) & (N - 1)], p.tw[(4 * t) & (N - 1)],
                       p.tw[(8 * t) & (N - 1)], p.tw[(12 * t) & (N - 1)]};
     const Pow6 tw2 = {p.tw[16 * lo], p.tw[(32 * lo) & (N - 1)], p.tw[(48 * lo) & (N - 1)], p.tw[(64 * lo) & (N - 1)],
@@ -370,7 +336,7 @@ __global__ __launch_bounds__(Geo<R>::BLOCK, WPS) void seg_kernel(SegArgs p) {
             prio_compute();
             dft16<PL1>(v);
             prio_latency();
-            twiddle_pow16(v, w1, [&](auto kc, float2 val) {
+            twiddle16<true>(v, Tw16::stored(w1), [&](auto kc, float2 val) {
                 constexpr int k0 = decltype(kc)::value;
                 lds_write_imm<8 * (512 * (k0 >> P) + R * (k0 & KP & ~KM)), kPairVec>(a_w1 ^ (8u * R * (k0 & KM)), val);
             });
@@ -408,7 +374,7 @@ __global__ __launch_bounds__(Geo<R>::BLOCK, WPS) void seg_kernel(SegArgs p) {
                 // traffic, no extra instruction; lane c ends up with k2 = c for all sixteen k1.
                 prio_compute();
                 float2 y[16];
-                twiddle_pow16(v, w2, [&](auto kc, float2 val) { y[decltype(kc)::value] = val; });
+                twiddle16<true>(v, Tw16::stored(w2), [&](auto kc, float2 val) { y[decltype(kc)::value] = val; });
                 const float sgn = lo ? -1.0f : 1.0f;
                 asm volatile("s_nop 1");      // VALU write -> DPP read of the same register needs two wait states
 #pragma unroll
@@ -421,7 +387,7 @@ __global__ __launch_bounds__(Geo<R>::BLOCK, WPS) void seg_kernel(SegArgs p) {
             } else if constexpr (R > 1) {
                 prio_latency();
                 // in place: the R lanes that share k0 sit in one wave and have issued their reads of region k0 above
-                twiddle_pow16(v, w2, [&](auto kc, float2 val) {
+                twiddle16<true>(v, Tw16::stored(w2), [&](auto kc, float2 val) {
                     constexpr int k1 = decltype(kc)::value;
                     lds_write_imm<256 * k1, kPairVec>(a_rw ^ (8u * (R * (k1 & KM) + (k1 & (R - 1)))), val);
                 });

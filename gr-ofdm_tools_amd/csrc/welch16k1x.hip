@@ -34,7 +34,6 @@
 #include "fft16k.hip.h"
 #include "launch.h"
 
-
 namespace oth {
 namespace {
 
@@ -59,106 +58,10 @@ template <int NW = 16> constexpr size_t x1p_lds_bytes() {
 template <int NW> __host__ __device__ constexpr int exa_off(int k) { return NW == 16 ? XREG * k : XREG * (k >> 1) + 512 * (k & 1); }
 template <int NW> __host__ __device__ constexpr int p2reg(int k) { return NW == 16 ? r16(k) : k; }
 
-// Non-temporal 8-byte load at (uniform row base in scalar registers) + (lane offset): one lane-offset register serves
-// all sixteen rows of a segment, and the compiler can neither move the load nor gather it with its neighbours - the
-// next segment's loads are spread over the step on purpose.  The caller waits (s_waitcnt vmcnt) before the first use.
-typedef float f2v __attribute__((ext_vector_type(2)));      // a register pair the inline asm below can name as one operand
-__device__ __forceinline__ void load_row_nt(f2v &dst, unsigned lane_off, const char *row) {
-    asm volatile("global_load_dwordx2 %0, %1, %2 nt" : "=v"(dst) : "v"(lane_off), "s"(row) : "memory");
-}
-
-// ---- waiting for pinned loads ------------------------------------------------------------------------------------------
-// A register written by an inline-asm load is NOT valid until the s_waitcnt that covers it, and the compiler does not
-// know: to it the value exists from the asm on.  Two things follow (tools/isa_async_hazard.py checks the shipped code
-// objects for both, tests/test_abi_cpu.py runs it):
-//   * a wait has to NAME the registers it makes valid, or nothing keeps an instruction that reads them behind it (the
-//     bare `s_waitcnt lgkmcnt(0)` in front of the last segment's tail was overtaken by the sixty instructions of its
-//     first butterfly layer - late round 5; it only worked because a vmcnt wait happened to stand in between);
-//   * naming them as in-out operands ("+v") is not enough when the value has to end up somewhere else (the kept half of
-//     the 50 %-overlap builds): the compiler then copies the INPUT of the wait into the register it wants, i.e. reads
-//     the loading register in front of the wait.  arrive8 / arrive16 take the loading registers as inputs only and hand
-//     out fresh ones, wait and copies in one statement.
-#define OTH_IO8(r) "+v"((r)[0]), "+v"((r)[1]), "+v"((r)[2]), "+v"((r)[3]), "+v"((r)[4]), "+v"((r)[5]), "+v"((r)[6]), "+v"((r)[7])
-#define OTH_IO16(r) OTH_IO8(r), "+v"((r)[8]), "+v"((r)[9]), "+v"((r)[10]), "+v"((r)[11]), "+v"((r)[12]), "+v"((r)[13]), "+v"((r)[14]), "+v"((r)[15])
-// every vector-memory load of this wave has landed; r[0..15] are valid behind this statement (in place)
-__device__ __forceinline__ void vm_arrived16(f2v (&r)[16]) { asm volatile("s_waitcnt vmcnt(0)" : OTH_IO16(r) : : "memory"); }
-// every LDS read of this wave has landed (with the workgroup barrier: lds_barrier() for a wave that holds reads in flight)
-__device__ __forceinline__ void lds_arrived16(f2v (&r)[16]) { asm volatile("s_waitcnt lgkmcnt(0)" : OTH_IO16(r) : : "memory"); }
-__device__ __forceinline__ void lds_barrier_arrived16(f2v (&r)[16]) {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : OTH_IO16(r) : : "memory");
-}
-// wait, then out[i] = in[i] in fresh registers (eight pairs)
-__device__ __forceinline__ void vm_arrive8(float2 (&out)[8], const f2v (&in)[8]) {
-    f2v o[8];
-    asm volatile("s_waitcnt vmcnt(0)\n\t"
-                 "v_mov_b64 %0, %8\n\tv_mov_b64 %1, %9\n\tv_mov_b64 %2, %10\n\tv_mov_b64 %3, %11\n\t"
-                 "v_mov_b64 %4, %12\n\tv_mov_b64 %5, %13\n\tv_mov_b64 %6, %14\n\tv_mov_b64 %7, %15"
-                 : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(o[6]), "=&v"(o[7])
-                 : "v"(in[0]), "v"(in[1]), "v"(in[2]), "v"(in[3]), "v"(in[4]), "v"(in[5]), "v"(in[6]), "v"(in[7])
-                 : "memory");
-#pragma unroll
-    for (int i = 0; i < 8; ++i) out[i] = make_float2(o[i].x, o[i].y);
-}
-// the sixteen window values of a step (load_win): valid in place behind this statement; they are used up inside the step,
-// nothing of them lives across a loop edge
-__device__ __forceinline__ void vm_arrived_win16(float (&w)[16]) { asm volatile("s_waitcnt vmcnt(0)" : OTH_IO16(w) : : "memory"); }
-
-// The same two operations with six stored powers W, W^2, W^3, W^4, W^8, W^12 (nine products instead of thirteen)
-struct Pow6x {
-    float2 j1, j2, j3, i1, i2, i3;
-};
-__device__ __forceinline__ Pow6x pow6_load(const float2 *tw, int e) {
-    return Pow6x{tw[e], tw[2 * e], tw[3 * e], tw[4 * e], tw[8 * e], tw[12 * e]};
-}
-template <int STRIDE, bool STORE>
-__device__ __forceinline__ void twiddle6(float2 (&v)[16], float2 *out, const Pow6x &w) {
-    float2 wj[4], wi[4];
-    wj[1] = w.j1, wj[2] = w.j2, wj[3] = w.j3;
-    wi[1] = w.i1, wi[2] = w.i2, wi[3] = w.i3;
-    // every product below has a wj factor: making those opaque keeps the nine products out of loop-invariant registers
-    asm volatile("" : "+v"(wj[1].x), "+v"(wj[1].y), "+v"(wj[2].x), "+v"(wj[2].y), "+v"(wj[3].x), "+v"(wj[3].y));
-    if (STORE) out[0] = v[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) {
-        const int i = k >> 2, j = k & 3;
-        const float2 tw = (i == 0) ? wj[j] : ((j == 0) ? wi[i] : cmul(wi[i], wj[j]));
-        const float2 r = cmul(v[r16(k)], tw);
-        if (STORE) out[STRIDE * k] = r;
-        else v[r16(k)] = r;
-    }
-}
-
-// exchange-A writes of either form: out[exa_off<NW>(k)] = v[r16(k)] W^k from the six stored powers
-template <int NW> __device__ __forceinline__ void twiddle6_exa(float2 (&v)[16], float2 *out, const Pow6x &w) {
-    float2 wj[4], wi[4];
-    wj[1] = w.j1, wj[2] = w.j2, wj[3] = w.j3;
-    wi[1] = w.i1, wi[2] = w.i2, wi[3] = w.i3;
-    asm volatile("" : "+v"(wj[1].x), "+v"(wj[1].y), "+v"(wj[2].x), "+v"(wj[2].y), "+v"(wj[3].x), "+v"(wj[3].y));
-    out[0] = v[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) {
-        const int i = k >> 2, j = k & 3;
-        const float2 tw = (i == 0) ? wj[j] : ((j == 0) ? wi[i] : cmul(wi[i], wj[j]));
-        out[exa_off<NW>(k)] = cmul(v[r16(k)], tw);
-    }
-}
-// the same from two seeds (the 50 %-overlap kernel: no room for six)
-template <int NW> __device__ __forceinline__ void scatter_pow16_exa(const float2 (&v)[16], float2 *out, float2 p1, float2 p4) {
-    float2 wj[4], wi[4];
-    wj[1] = p1;
-    wi[1] = p4;
-    asm volatile("" : "+v"(wj[1].x), "+v"(wj[1].y), "+v"(wi[1].x), "+v"(wi[1].y));
-    wj[2] = cmul(wj[1], wj[1]);
-    wj[3] = cmul(wj[2], wj[1]);
-    wi[2] = cmul(wi[1], wi[1]);
-    wi[3] = cmul(wi[2], wi[1]);
-    out[0] = v[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) {
-        const int i = k >> 2, j = k & 3;
-        const float2 w = (i == 0) ? wj[j] : ((j == 0) ? wi[i] : cmul(wi[i], wj[j]));
-        out[exa_off<NW>(k)] = cmul(v[r16(k)], w);
-    }
+// exchange-A writes of either form: out[exa_off<NW>(k)] = v[r16(k)] W^k; w = Tw16::stored(six powers), nine products per
+// segment instead of thirteen, or Tw16(W, W^4) (the 50 %-overlap kernel: no room for six)
+template <int NW> __device__ __forceinline__ void twiddle_exa(const float2 (&v)[16], float2 *out, const Tw16 &w) {
+    twiddle16(v, w, [&](int k, float2 val) { out[exa_off<NW>(k)] = val; });
 }
 
 // The plain loop: every phase of a segment in program order, its sixteen loads at the top.  The pipelined kernel below
@@ -396,7 +299,7 @@ __device__ __forceinline__ void x1_pipe_body(const float2 *xb, long long step, c
             quadK[tid] = make_float4(tid < 2 ? 1.0f : -1.0f, tid == 0 ? 1.0f : (tid == 1 ? -1.0f : 0.0f), be, -be);
         }
     }
-    const Pow6x a6 = pow6_load(tw, tid);
+    const Pow6 a6 = pow6_load(tw, tid);
     __syncthreads();
 
     float2 *wa = lds + tid;
@@ -419,7 +322,7 @@ __device__ __forceinline__ void x1_pipe_body(const float2 *xb, long long step, c
     if (live) {
         const char *x0 = reinterpret_cast<const char *>(xb + (long long)s * step);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) load_row_nt(pfr[r], 8u * tid, x0 + 512 * NW * r);
+        for (int r = 0; r < 16; ++r) load_row8_nt(pfr[r], 8u * tid, x0 + 512 * NW * r);
         vm_arrived16(pfr);
     }
     auto tail = [&](auto hook1, auto hook2) {      // pass 3, twiddles, pass 4 of the segment whose exchange-B values sit in rB
@@ -441,12 +344,12 @@ __device__ __forceinline__ void x1_pipe_body(const float2 *xb, long long step, c
         float2 pf[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) pf[r] = make_float2(pfr[r].x, pfr[r].y);
-        if constexpr (WINDOW) {      // sixteen L2-resident window values, loaded where they are used (see load_win)
+        if constexpr (WINDOW) {      // sixteen L2-resident window values, loaded where they are used (pinned_load.hip.h)
             float wv16[16];
             const char *wbase = reinterpret_cast<const char *>(win);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) load_win(wv16[r], 4u * tid, wbase + 256 * NW * r);
-            vm_arrived_win16(wv16);
+            for (int r = 0; r < 16; ++r) load_row4(wv16[r], 4u * tid, wbase + 256 * NW * r);
+            vm_arrived16(wv16);
 #pragma unroll
             for (int r = 0; r < 16; ++r) pf[r] = make_float2(pf[r].x * wv16[r], pf[r].y * wv16[r]);
         }
@@ -456,7 +359,7 @@ __device__ __forceinline__ void x1_pipe_body(const float2 *xb, long long step, c
         lds_barrier_arrived16(rB);      // 1 (also waits for this wave's exchange-B reads of the segment before: rB valid)
         const bool first_of_chunk = s == sb;
         if (sched == 2 && first_of_chunk && tid == 0) lnext[par] = (int)atomicAdd(sc.queue, 1u);
-        twiddle6_exa<NW>(pf, wa, a6);                          // WA
+        twiddle_exa<NW>(pf, wa, Tw16::stored(a6));             // WA
         // The segment after this one: its loads go out two at a time over the whole step.  A ticket (dynamic schedule)
         // is drawn with a chunk's FIRST segment and published before barrier 2 of that segment, so at the chunk's last
         // segment it is known here - the launcher never makes one-segment chunks except the very last one of a stream,
@@ -497,7 +400,7 @@ __device__ __forceinline__ void x1_pipe_body(const float2 *xb, long long step, c
             if constexpr (cnt > 0) {
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int r = first; r < first + cnt; ++r) load_row_nt(pfr[r], voff, xn + 512 * NW * r);
+                for (int r = first; r < first + cnt; ++r) load_row8_nt(pfr[r], voff, xn + 512 * NW * r);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -757,7 +660,7 @@ __global__ __launch_bounds__(64 * NW, 4) void welch16k1x_half_kernel(WelchArgs p
     //   keep[8]  the raw second half of the segment before (= this segment's first half), pilot already off
     //   nxt[8]   this segment's new half, PREFETCHED during the step before (pinned non-temporal loads, two at each of
     //            four places of the step as in the scanner kernel: a burst stalls the issuing wave at its loads)
-    //   the sixteen window values come from L2 where they are used (pinned loads, see load_win): 64 KiB shared by every
+    //   the sixteen window values come from L2 where they are used (pinned loads, pinned_load.hip.h): 64 KiB shared by every
     //   workgroup of the XCD, against 64 KiB of new samples per step
     float2 keep[8];
     f2v nxt[8];
@@ -784,9 +687,9 @@ __global__ __launch_bounds__(64 * NW, 4) void welch16k1x_half_kernel(WelchArgs p
             const char *x0 = reinterpret_cast<const char *>(xb + sb * p.step);
             f2v first[8];
 #pragma unroll
-            for (int r = 0; r < 8; ++r) load_row_nt(first[r], voff, x0 + 512 * NW * r);
+            for (int r = 0; r < 8; ++r) load_row8_nt(first[r], voff, x0 + 512 * NW * r);
 #pragma unroll
-            for (int r = 0; r < 8; ++r) load_row_nt(nxt[r], voff, x0 + 512 * NW * (8 + r));
+            for (int r = 0; r < 8; ++r) load_row8_nt(nxt[r], voff, x0 + 512 * NW * (8 + r));
             vm_arrive8(keep, first);      // (nxt has landed as well; the step below says so where it takes it)
         }
         for (long long s = sb; s < se; ++s) {
@@ -798,14 +701,14 @@ __global__ __launch_bounds__(64 * NW, 4) void welch16k1x_half_kernel(WelchArgs p
             {
                 const char *wbase = reinterpret_cast<const char *>(p.win);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) load_win(wv16[r], 4u * tid, wbase + 256 * NW * r);
+                for (int r = 0; r < 16; ++r) load_row4(wv16[r], 4u * tid, wbase + 256 * NW * r);
             }
             // the new half (requested during the step before, or above) and the window values: the new half comes out of
             // its loading registers in the same statement that waits for it (vm_arrive8: it outlives the next loads into
             // them as the kept half, and a copy the compiler makes for that may not stand in front of the wait)
             float2 fresh[8];
             vm_arrive8(fresh, nxt);
-            vm_arrived_win16(wv16);
+            vm_arrived16(wv16);
             float2 sum = make_float2(0.f, 0.f), sumf = make_float2(0.f, 0.f);
             if (s == sb) {      // the chunk's first half arrives raw
 #pragma unroll
@@ -828,8 +731,8 @@ __global__ __launch_bounds__(64 * NW, 4) void welch16k1x_half_kernel(WelchArgs p
             const char *xn = reinterpret_cast<const char *>(xb + (s + 1 < se ? s + 1 : s) * p.step) + 512 * NW * 8;
             auto prefetch = [&](int r0) {
                 __builtin_amdgcn_sched_barrier(0);
-                load_row_nt(nxt[r0], voff, xn + 512 * NW * r0);
-                load_row_nt(nxt[r0 + 1], voff, xn + 512 * NW * (r0 + 1));
+                load_row8_nt(nxt[r0], voff, xn + 512 * NW * r0);
+                load_row8_nt(nxt[r0 + 1], voff, xn + 512 * NW * (r0 + 1));
                 __builtin_amdgcn_sched_barrier(0);
             };
             const int par = (int)(s & 1);
@@ -859,7 +762,7 @@ __global__ __launch_bounds__(64 * NW, 4) void welch16k1x_half_kernel(WelchArgs p
                 part.y = wave_total_lane63(part.y);
                 if (tid == 63) red[40 + par] = part;      // read behind barrier 2, at the end of the step
             }
-            scatter_pow16_exa<NW>(v, wa, a1, a4);                  // x W_N^(k0 tid) -> [k0][w][l]
+            twiddle_exa<NW>(v, wa, Tw16(a1, a4));                   // x W_N^(k0 tid) -> [k0][w][l]
             prefetch(0);
             lds_barrier();      // 2
             TwBatch ta;
@@ -964,7 +867,7 @@ __global__ __launch_bounds__(1024, 4) void welch8kws_kernel(WelchArgs p) {
 
     if (role == 0) {
         // ---------------------------------------------------------------------------------------------- producer
-        const Pow6x a6 = pow6_load(p.tw, t);      // W^1,2,3,4,8,12 of this thread: nine products per segment instead of thirteen
+        const Pow6 a6 = pow6_load(p.tw, t);      // W^1,2,3,4,8,12 of this thread: nine products per segment instead of thirteen
         float2 keep[8];
         f2v nxt[8];
         const unsigned voff = 8u * t;
@@ -989,9 +892,9 @@ __global__ __launch_bounds__(1024, 4) void welch8kws_kernel(WelchArgs p) {
             const char *x0 = reinterpret_cast<const char *>(xb + (long long)s0 * p.step);
             f2v first[8];
 #pragma unroll
-            for (int r = 0; r < 8; ++r) load_row_nt(first[r], voff, x0 + 512 * NW * r);
+            for (int r = 0; r < 8; ++r) load_row8_nt(first[r], voff, x0 + 512 * NW * r);
 #pragma unroll
-            for (int r = 0; r < 8; ++r) load_row_nt(nxt[r], voff, x0 + 512 * NW * (8 + r));
+            for (int r = 0; r < 8; ++r) load_row8_nt(nxt[r], voff, x0 + 512 * NW * (8 + r));
             vm_arrive8(keep, first);
         }
         for (int s = s0; s < s1; ++s) {
@@ -1021,8 +924,8 @@ __global__ __launch_bounds__(1024, 4) void welch8kws_kernel(WelchArgs p) {
             const char *xn = reinterpret_cast<const char *>(xb + (long long)(s + 1 < s1 ? s + 1 : s) * p.step) + 512 * NW * 8;
             auto prefetch = [&](int r0) {
                 __builtin_amdgcn_sched_barrier(0);
-                load_row_nt(nxt[r0], voff, xn + 512 * NW * r0);
-                load_row_nt(nxt[r0 + 1], voff, xn + 512 * NW * (r0 + 1));
+                load_row8_nt(nxt[r0], voff, xn + 512 * NW * r0);
+                load_row8_nt(nxt[r0 + 1], voff, xn + 512 * NW * (r0 + 1));
                 __builtin_amdgcn_sched_barrier(0);
             };
             prefetch(0);
@@ -1039,7 +942,7 @@ __global__ __launch_bounds__(1024, 4) void welch8kws_kernel(WelchArgs p) {
             dft16(v);                                              // pass 1: r -> k0
             prio_latency();
             prefetch(4);
-            twiddle6_exa<NW>(v, wa, a6);                           // x W_N^(k0 t) -> [k0][w][l] of this image
+            twiddle_exa<NW>(v, wa, Tw16::stored(a6));              // x W_N^(k0 t) -> [k0][w][l] of this image
             prefetch(6);
             lds_barrier();
         }

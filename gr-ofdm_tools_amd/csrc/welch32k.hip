@@ -82,32 +82,13 @@ constexpr float W64_IM[32] = {-0.0f, -0.09801714032956060f, -0.19509032201612827
                               -0.55557023301960222f, -0.47139673682599764f, -0.38268343236508977f, -0.29028467725446233f,
                               -0.19509032201612827f, -0.09801714032956060f};
 
-// Loads at (uniform row base in scalar registers) + (the lane's 32-bit byte offset): one offset register serves every row
-// of a segment.  Written as inline asm because the compiler, left to itself, forms thirty-two 64-bit row addresses per
-// lane, keeps them across the loop and spills them.  A register written here is NOT valid until the s_waitcnt that
-// covers it (the waits below name the registers they make valid; tools/isa_async_hazard.py checks the code object).
-typedef float f2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void load_row8(f2v &dst, unsigned lane_off, const void *row) {
-    asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(dst) : "v"(lane_off), "s"(row) : "memory");
-}
-__device__ __forceinline__ void load_row4(float &dst, unsigned lane_off, const void *row) {
-    asm volatile("global_load_dword %0, %1, %2" : "=v"(dst) : "v"(lane_off), "s"(row) : "memory");
-}
-#define W32_IO8(r) "+v"((r)[0]), "+v"((r)[1]), "+v"((r)[2]), "+v"((r)[3]), "+v"((r)[4]), "+v"((r)[5]), "+v"((r)[6]), "+v"((r)[7])
-#define W32_IO16(r) W32_IO8(r), "+v"((r)[8]), "+v"((r)[9]), "+v"((r)[10]), "+v"((r)[11]), "+v"((r)[12]), "+v"((r)[13]), "+v"((r)[14]), "+v"((r)[15])
-// every vector-memory load of this wave has landed: r[0..15] valid behind this statement
-__device__ __forceinline__ void vm_arrived16(f2v (&r)[16]) { asm volatile("s_waitcnt vmcnt(0)" : W32_IO16(r) : : "memory"); }
-// all but the youngest eight loads have landed (the caller has issued the NEXT batch of eight behind this one)
-__device__ __forceinline__ void vm_arrived8_keep8(float (&w)[8]) { asm volatile("s_waitcnt vmcnt(8)" : W32_IO8(w) : : "memory"); }
-__device__ __forceinline__ void vm_arrived8(float (&w)[8]) { asm volatile("s_waitcnt vmcnt(0)" : W32_IO8(w) : : "memory"); }
 // the front step's batch of four rows: x[n] (in place in z), x[n + 32768], w[n], w[n + 32768] - sixteen loads; KEEP = the loads
 // of the next batch already issued behind it (16) or none
 template <int KEEP>
 __device__ __forceinline__ void vm_arrived_front(f2v &z0, f2v &z1, f2v &z2, f2v &z3, f2v (&x2)[4], float (&w1)[4], float (&w2)[4]) {
     static_assert(KEEP == 0 || KEEP == 16 || KEEP == 32 || KEEP == 48, "whole batches of sixteen loads");
-#define W32_FRONT_WAIT(n)                                                                                                                  \
-    asm volatile("s_waitcnt vmcnt(" #n ")" : "+v"(z0), "+v"(z1), "+v"(z2), "+v"(z3), "+v"(x2[0]), "+v"(x2[1]), "+v"(x2[2]), "+v"(x2[3]), \
-                 "+v"(w1[0]), "+v"(w1[1]), "+v"(w1[2]), "+v"(w1[3]), "+v"(w2[0]), "+v"(w2[1]), "+v"(w2[2]), "+v"(w2[3]) : : "memory")
+#define W32_FRONT_WAIT(n) \
+    asm volatile("s_waitcnt vmcnt(" #n ")" : "+v"(z0), "+v"(z1), "+v"(z2), "+v"(z3), OTH_IO4(x2), OTH_IO4(w1), OTH_IO4(w2) : : "memory")
     if (KEEP == 48) W32_FRONT_WAIT(48);
     else if (KEEP == 32) W32_FRONT_WAIT(32);
     else if (KEEP == 16) W32_FRONT_WAIT(16);
@@ -115,24 +96,10 @@ __device__ __forceinline__ void vm_arrived_front(f2v &z0, f2v &z1, f2v &z2, f2v 
 #undef W32_FRONT_WAIT
 }
 
-// scatter_pow16 (fft4096.hip.h) with the rows k >= 8 addressed from a second base: 8 XREG float2 is past the 64 KiB a
+// scatter_pow16 (twiddle16.hip.h) with the rows k >= 8 addressed from a second base: 8 XREG float2 is past the 64 KiB a
 // ds_write offset reaches, and the compiler otherwise keeps eight more address registers across the loop
 __device__ __forceinline__ void scatter_pow16_exa(const float2 (&v)[16], float2 *lo, float2 *hi, float2 p1, float2 p4) {
-    float2 wj[4], wi[4];
-    wj[1] = p1;
-    wi[1] = p4;
-    asm volatile("" : "+v"(wj[1].x), "+v"(wj[1].y), "+v"(wi[1].x), "+v"(wi[1].y));
-    wj[2] = cmul(wj[1], wj[1]);
-    wj[3] = cmul(wj[2], wj[1]);
-    wi[2] = cmul(wi[1], wi[1]);
-    wi[3] = cmul(wi[2], wi[1]);
-    lo[0] = v[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) {
-        const int i = k >> 2, j = k & 3;
-        const float2 w = (i == 0) ? wj[j] : ((j == 0) ? wi[i] : cmul(wi[i], wj[j]));
-        (k < 8 ? lo : hi)[XREG * (k & 7)] = cmul(v[r16(k)], w);
-    }
+    twiddle16(v, Tw16(p1, p4), [&](int k, float2 val) { (k < 8 ? lo : hi)[XREG * (k & 7)] = val; });
 }
 
 // Sum over the 64 lanes of a wave, the same value in every lane: DPP row operations on the two halves of the double +

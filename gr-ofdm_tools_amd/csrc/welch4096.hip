@@ -73,7 +73,7 @@ __global__ __launch_bounds__(T4, OTH_W4096_PIPE ? 4 : 1) void welch4096_kernel(W
 
     // thread-constant tables
 #if OTH_W4096_PIPE
-    // window rows 0..7 live in registers; rows 8..15 come from L2 with every segment (pinned loads, see load_win):
+    // window rows 0..7 live in registers; rows 8..15 come from L2 with every segment (pinned loads, pinned_load.hip.h):
     // with the kept half and the prefetch next to the data the sixteen values did not fit into 128 VGPRs (round 4's
     // build spilled 6-12 registers inside the segment loop)
     float win[8];
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(T4, OTH_W4096_PIPE ? 4 : 1) void welch4096_kernel(W
         }
         float wu[8];        // window rows 8..15: issued in front of the prefetch, awaited where they are used
 #pragma unroll
-        for (int a = 0; a < 8; ++a) load_win(wu[a], 4u * t, win_hi + 1024 * a);
+        for (int a = 0; a < 8; ++a) load_row4(wu[a], 4u * t, win_hi + 1024 * a);
         {   // the half the NEXT segment adds; lands while this segment is transformed.  Behind the chunk's last segment
             // the same loads run once more on the half just taken: always eight loads younger than the window's, so
             // ONE counted wait serves every step (two waits in two branches made the compiler merge their operands

@@ -233,7 +233,7 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
             dft16(v);
             __builtin_amdgcn_s_setprio(WS_PAS);
             if constexpr (COMPL) scatter_pow16_stored<RS>(v, lx + w1, b1, b2, b3, b4, b8, b12, bm);
-            else scatter_pow16_six<RS>(v, lx + w1, b1, b2, b3, b4, b8, b12);
+            else scatter_pow16_six<RS>(v, lx + w1, Pow6{b1, b2, b3, b4, b8, b12});
             step_end(ITEM_DATA);
         };
 
