@@ -35,6 +35,7 @@ int jack_check(oth_plan *p, bool two, const void *x, const void *y, size_t nsamp
 FinalizeArgs pass1_finalize(const oth_plan *p, int W1, int nch) {
     FinalizeArgs f = finalize_args(p, W1, ROW_NATURAL, nch, raw_stage(p));
     f.scale = 1.0;
+    if (nch == 1) f.accumulate = 2;      // raw totals as they are (the two-channel form has its own store, csd_store)
     return f;
 }
 
@@ -58,6 +59,7 @@ int jack_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t 
         f.out0 = psd_out;
         f.scale = p->scale / (double)nseg;
         f.out = out_stage(p);
+        f.accumulate = 0;      // the plan's scaled output
         HIPCHK(c, launch_finalize(f, nstreams, c->stream));
     }
     MtmJackArgs a{};

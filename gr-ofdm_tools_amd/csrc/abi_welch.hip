@@ -879,6 +879,7 @@ int oth_welch_partial_dev(oth_plan *p, const void *iq_dev, size_t nsamples, floa
     FinalizeArgs f = finalize_args(p, av.W, av.layout, 1, raw_stage(p));
     f.out0 = sum_out_dev;
     f.scale = 1.0;
+    f.accumulate = 2;      // raw sums, non-finite or not: the rule for them applies where sums are scaled (oth_welch_scale_dev)
     if (int frc = finalize_and_rearm(c, f, 1)) return frc;
     if (nseg_out) *nseg_out = (uint64_t)av.nseg;
     return OTH_OK;

@@ -49,6 +49,17 @@ template <int T> __device__ __forceinline__ float2 block_sum(float2 v, float2 *r
     for (int w = 0; w < T / 64; ++w) s = cadd(s, red[base + w]);
     return s;
 }
+// Peak hold (oth_chain_set_peak_hold) is the reference's np.maximum: a NaN stays in the peak until oth_chain_reset.  fmaxf
+// and v_max_f32 are IEEE maxNum and drop a NaN operand.  |X| and |X|^2 are >= +0 or NaN, and on such values the bit
+// patterns order as the values do, with every NaN above +inf: one unsigned maximum (v_max_u32) where v_max_f32 stood.
+// (Spelled as the instruction: from a C++ max of the bit patterns the compiler makes a compare and a select.)
+__device__ __forceinline__ float peak_max(float a, float b) {
+    float r;
+    asm("v_max_u32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// ... and on the bit patterns themselves (the cross-team reductions of kernels_misc.hip)
+__device__ __forceinline__ unsigned peak_max(unsigned a, unsigned b) { return a > b ? a : b; }
 // Im(conj(X) Y) = X.x Y.y - X.y Y.x for the two-channel sums, with BOTH products rounded before they are subtracted (no
 // contraction into an fma): the form is antisymmetric in X and Y bit for bit, so a channel against itself gives exactly 0 in
 // every segment and Im Pxy = 0 - as numpy's complex product does.  fmaf(X.x, Y.y, fmaf(-X.y, Y.x, acc)) left the rounding

@@ -272,7 +272,7 @@ hipError_t launch_finalize(const FinalizeArgs &a_in, int nstreams, hipStream_t s
 __global__ void scale_kernel(const float *sum, float *out, int nfft, double scale, OutStage stage) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= stage.nout) return;
-    out[i] = psd_value(stage, (double)sum[in_bin(stage, nfft, i)] * scale);
+    out[i] = psd_value(stage, finite_power((double)sum[in_bin(stage, nfft, i)] * scale));      // (the rule of store_psd)
 }
 
 hipError_t launch_scale(const float *sum, float *out, int nfft, double scale, const OutStage &stage, hipStream_t s) {
@@ -307,7 +307,7 @@ __global__ void rows_epilogue_kernel(float *rows, long long nrows, int nfft, flo
     float pk = have_peak ? peak_state[k] : 0.f;
     for (long long r = 0; r < nrows; ++r) {
         float v = rows[(size_t)r * nfft + k];
-        if (do_peak) pk = (have_peak || r > 0) ? fmaxf(pk, v) : v;
+        if (do_peak) pk = (have_peak || r > 0) ? peak_max(pk, v) : v;
         if (do_iir) {
             y = fmaf(alpha, v, (1.0f - alpha) * y);
             rows[(size_t)r * nfft + k] = 10.0f * log10f(y) + kdb;
@@ -343,15 +343,28 @@ __global__ __launch_bounds__(256) void chain_reduce_kernel(const float *partial,
     const int col = (blockIdx.x * 64 + q) * 4;
     const int g = blockIdx.y;
     const int w0 = g * rows_per_group, w1 = min(W, w0 + rows_per_group);
-    double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
     const float *base = partial + col;
+    if constexpr (MAX) {      // peak hold: the maximum of the bit patterns (peak_max, fft_lds.hip.h: a NaN stays)
+        unsigned(*redu)[64][4] = reinterpret_cast<unsigned(*)[64][4]>(red);
+        uint4 m = make_uint4(0u, 0u, 0u, 0u);
+        for (int w = w0 + j; w < w1; w += 4) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(base + (size_t)w * nfft);
+            m.x = peak_max(m.x, v.x), m.y = peak_max(m.y, v.y), m.z = peak_max(m.z, v.z), m.w = peak_max(m.w, v.w);
+        }
+        if (j) redu[j - 1][q][0] = m.x, redu[j - 1][q][1] = m.y, redu[j - 1][q][2] = m.z, redu[j - 1][q][3] = m.w;
+        __syncthreads();
+        if (j) return;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            m.x = peak_max(m.x, redu[r][q][0]), m.y = peak_max(m.y, redu[r][q][1]), m.z = peak_max(m.z, redu[r][q][2]),
+            m.w = peak_max(m.w, redu[r][q][3]);
+        *reinterpret_cast<uint4 *>(scratch + (size_t)g * nfft + col) = m;
+        return;
+    }
+    double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
     for (int w = w0 + j; w < w1; w += 4) {
         const float4 v = *reinterpret_cast<const float4 *>(base + (size_t)w * nfft);
-        if (MAX) {
-            s0 = fmax(s0, (double)v.x), s1 = fmax(s1, (double)v.y), s2 = fmax(s2, (double)v.z), s3 = fmax(s3, (double)v.w);
-        } else {
-            s0 += v.x, s1 += v.y, s2 += v.z, s3 += v.w;
-        }
+        s0 += v.x, s1 += v.y, s2 += v.z, s3 += v.w;
     }
     if (j) {
         red[j - 1][q][0] = s0;
@@ -362,13 +375,7 @@ __global__ __launch_bounds__(256) void chain_reduce_kernel(const float *partial,
     __syncthreads();
     if (j) return;
 #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        if (MAX) {
-            s0 = fmax(s0, red[r][q][0]), s1 = fmax(s1, red[r][q][1]), s2 = fmax(s2, red[r][q][2]), s3 = fmax(s3, red[r][q][3]);
-        } else {
-            s0 += red[r][q][0], s1 += red[r][q][1], s2 += red[r][q][2], s3 += red[r][q][3];
-        }
-    }
+    for (int r = 0; r < 3; ++r) s0 += red[r][q][0], s1 += red[r][q][1], s2 += red[r][q][2], s3 += red[r][q][3];
     *reinterpret_cast<float4 *>(scratch + (size_t)g * nfft + col) = make_float4((float)s0, (float)s1, (float)s2, (float)s3);
 }
 
@@ -390,15 +397,31 @@ __global__ __launch_bounds__(256) void chain_state_kernel(ChainStateArgs a) {
     __shared__ double red[SLICES][POS + 1];
     const int col = threadIdx.x % COLS, slice = threadIdx.x / COLS;
     const float *base = a.rows + blockIdx.x * POS + col * 4;
-    const bool mx = a.acc_mode == 2;
+    if (a.acc_mode == 2) {      // peak hold (launch-uniform): the maximum of the bit patterns, a NaN stays (peak_max)
+        unsigned(*redu)[POS + 1] = reinterpret_cast<unsigned(*)[POS + 1]>(red);
+        uint4 m = make_uint4(0u, 0u, 0u, 0u);
+        for (int w = slice; w < a.nrows; w += SLICES) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(base + (size_t)w * a.nfft);
+            m.x = peak_max(m.x, v.x), m.y = peak_max(m.y, v.y), m.z = peak_max(m.z, v.z), m.w = peak_max(m.w, v.w);
+        }
+        redu[slice][col * 4] = m.x;
+        redu[slice][col * 4 + 1] = m.y;
+        redu[slice][col * 4 + 2] = m.z;
+        redu[slice][col * 4 + 3] = m.w;
+        __syncthreads();
+        if (threadIdx.x >= POS) return;
+        const int k = bin_pos(blockIdx.x * POS + threadIdx.x, a.layout);
+        const int i = a.fftshift ? shifted(k, a.nfft) : k;
+        unsigned t = 0u;
+        for (int q = 0; q < SLICES; ++q) t = peak_max(t, redu[q][threadIdx.x]);
+        // |X| and |X|^2 are >= 0 or NaN and the state starts at 0: no "initialised" flag needed
+        a.peak_state[i] = peak_max(__builtin_bit_cast(float, t), a.peak_state[i]);
+        return;
+    }
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     for (int w = slice; w < a.nrows; w += SLICES) {
         const float4 v = *reinterpret_cast<const float4 *>(base + (size_t)w * a.nfft);
-        if (mx) {
-            s0 = fmax(s0, (double)v.x), s1 = fmax(s1, (double)v.y), s2 = fmax(s2, (double)v.z), s3 = fmax(s3, (double)v.w);
-        } else {
-            s0 += v.x, s1 += v.y, s2 += v.z, s3 += v.w;
-        }
+        s0 += v.x, s1 += v.y, s2 += v.z, s3 += v.w;
     }
     red[slice][col * 4] = s0;
     red[slice][col * 4 + 1] = s1;
@@ -409,12 +432,7 @@ __global__ __launch_bounds__(256) void chain_state_kernel(ChainStateArgs a) {
     const int k = bin_pos(blockIdx.x * POS + threadIdx.x, a.layout);                // bin held at this position of a row
     const int i = a.fftshift ? shifted(k, a.nfft) : k;                              // row position
     double t = 0.0;
-    for (int q = 0; q < SLICES; ++q) t = mx ? fmax(t, red[q][threadIdx.x]) : t + red[q][threadIdx.x];
-    if (mx) {
-        // |X| and |X|^2 are >= 0 and the state starts at 0: no "initialised" flag needed
-        a.peak_state[i] = fmaxf((float)t, a.peak_state[i]);
-        return;
-    }
+    for (int q = 0; q < SLICES; ++q) t += red[q][threadIdx.x];
     float y = a.iir_state[i];
     if (a.nbase > 0) y = (float)((double)y * a.decay + (double)a.alpha * t);
     for (long long r = 0; r < a.nraw; ++r) {

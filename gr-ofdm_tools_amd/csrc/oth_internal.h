@@ -132,7 +132,8 @@ struct FinalizeArgs {
     RowLayout layout;       // bin order of the partial rows (row_layout.h)
     int l1, l2;             // ROW_TWOLEVEL only
     OutStage out;
-    int accumulate;         // out0 += (raw sums; streaming form)
+    int accumulate;         // one channel (store_psd): 0 out0 = scaled output; 1 out0 += raw sums (streaming form);
+                            // 2 out0 = raw sums as they are (oth_welch_partial_dev, first pass of the jackknife)
     unsigned *queue_reset;  // chunk-ticket counters of the averaging kernel, zeroed here for the next launch (or null)
     int queue_n;
     // Completion word for a host that polls instead of sleeping in hipStreamSynchronize (oth_welch_exec / _poll / _wait,

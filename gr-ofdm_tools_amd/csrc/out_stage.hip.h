@@ -32,10 +32,19 @@ __device__ __forceinline__ int in_bin(const OutStage &o, int nfft, int i) { retu
 // a PSD value leaves linear, or as dB
 __device__ __forceinline__ float psd_value(const OutStage &o, double v) { return o.db ? (float)(10.0 * log10(v)) : (float)v; }
 
-// a summed bin into slot o of `out`: added raw to the running sums there (the streaming form), else scaled and through psd_value
+// The one-channel rule for sums that are not finite (include/ofdm_tools_hip.h, oth_welch_exec; csd_store in kernels_misc.hip
+// is its two-channel twin): a scaled power that float32 cannot hold - an inf or NaN sum, or one that overflows on the way
+// out - leaves as NaN, linear or dB, never as inf.  An inf sample leaves NaN in every bin of SciPy's transform but inf in
+// some bins of the register-butterfly kernels, and a float32 sum of |X|^2 that overflowed reads inf in every kernel.  It is
+// applied here and not in psd_value, which the per-bin statistics share.  Zero stays zero (-inf in dB, numpy's 10 log10(0)).
+__device__ __forceinline__ double finite_power(double v) { return isfinite((float)v) ? v : __builtin_nan(""); }
+
+// a summed bin into slot o of `out` by FinalizeArgs.accumulate: 0 scaled, through finite_power and psd_value; 1 added raw to
+// the running sums there (the streaming form); 2 stored raw, non-finite or not (the time-sharded sums)
 __device__ __forceinline__ void store_psd(float *out, size_t o, double sum, double scale, int accumulate, const OutStage &stage) {
-    if (accumulate) out[o] += (float)sum;
-    else out[o] = psd_value(stage, sum * scale);
+    if (accumulate == 1) out[o] += (float)sum;
+    else if (accumulate) out[o] = (float)sum;
+    else out[o] = psd_value(stage, finite_power(sum * scale));
 }
 
 // t[r] = sum over the W workgroups of load(w, r), r < R: slice `slice` adds w = slice, slice + 8, ... in double, then the

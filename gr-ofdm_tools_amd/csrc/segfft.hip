@@ -487,8 +487,7 @@ __global__ __launch_bounds__(Geo<R>::BLOCK, WPS) void seg_kernel(SegArgs p) {
                         for (int k = 0; k < 16; ++k) acc[k] = fmaf(w, val[k], acc[k]);
                     } else if (p.acc_mode == ACC_MAX) {
 #pragma unroll
-                        for (int k = 0; k < 16; ++k)      // plain v_max_f32: no NaN canonicalisation (finite by construction)
-                            asm("v_max_f32 %0, %1, %2" : "=v"(acc[k]) : "v"(acc[k]), "v"(val[k]));
+                        for (int k = 0; k < 16; ++k) acc[k] = peak_max(acc[k], val[k]);      // val >= +0 or NaN; a NaN stays
                     }
                 }
             }

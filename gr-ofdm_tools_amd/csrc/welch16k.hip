@@ -450,7 +450,7 @@ __global__ __launch_bounds__(256 * F, 4) void chain16k_kernel(SegArgs p) {
                     for (int k = 0; k < 16; ++k) acc[k] = fmaf(w, val[k], acc[k]);
                 } else if (p.acc_mode == C16_MAX) {
 #pragma unroll
-                    for (int k = 0; k < 16; ++k) asm("v_max_f32 %0, %1, %2" : "=v"(acc[k]) : "v"(acc[k]), "v"(val[k]));
+                    for (int k = 0; k < 16; ++k) acc[k] = peak_max(acc[k], val[k]);
                 }
             }
         }

@@ -520,7 +520,7 @@ struct X1ChainEpi {
                     for (int k = 0; k < 8; ++k) acc[h + k] = fmaf(w, val[k], acc[h + k]);
                 } else if (a.acc_mode == 2) {
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) acc[h + k] = fmaxf(acc[h + k], val[k]);
+                    for (int k = 0; k < 8; ++k) acc[h + k] = peak_max(acc[h + k], val[k]);
                 }
             }
         }
@@ -558,7 +558,7 @@ struct X1ChainEpi {
                 for (int k = 0; k < 16; ++k) acc[k] = fmaf(w, val[k], acc[k]);
             } else if (a.acc_mode == 2) {
 #pragma unroll
-                for (int k = 0; k < 16; ++k) acc[k] = fmaxf(acc[k], val[k]);
+                for (int k = 0; k < 16; ++k) acc[k] = peak_max(acc[k], val[k]);
             }
         }
     }

@@ -469,6 +469,19 @@ int oth_welch_cyclic_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, in
 int oth_welch_cyclic(oth_plan *plan, const void *iq, size_t nsamples, int src_is_device, float *scf_out, float *coh_out,
                      float *psd_out, uint64_t *nseg_out);
 
+/* Degenerate inputs of the one-channel average - oth_welch_exec, _exec_async, _exec_dev, _scale_dev and _finalize, plans
+ * of oth_welch_plan and oth_mtm_plan, every kernel route and detrend mode (tests/test_degenerate_gpu.py): the rule is the
+ * two-channel path's, and SciPy's result is the specification.  A sample with a NaN or +-inf part makes every bin of that
+ * stream's output NaN, linear or dB, never inf (an inf sample leaves NaN in all bins of SciPy's transform, inf in some of
+ * this one's: the output stage writes NaN for every scaled sum that float32 does not hold), so a bin whose float32 sum of
+ * |X|^2 overflowed reads NaN too, never inf, while the other bins of the row stay right.  The other streams of the launch
+ * are untouched, bit for bit under the static schedules, and so is the next call on the plan: nothing of a poisoned launch
+ * stays in a workspace, and oth_welch_reset clears the streaming form.  oth_welch_partial_dev hands back the raw sums as
+ * they are, non-finite or not: the rule applies where sums are scaled.  oth_welch_segments_dev: exactly the rows of the
+ * segments that hold the sample are non-finite (NaN) in every bin.  Silence gives exact zeros, -inf under
+ * oth_plan_set_output_db (numpy's 10 log10(0)); a constant gives exact zeros under OTH_DETREND_CONSTANT and at most
+ * (4 ulp)^2 of the undetrended line under OTH_DETREND_CONSTANT_FAST.  A gain that is a power of two scales the output by
+ * its square bit for bit while no value leaves float32's normal range. */
 /* one-shot: nsamples complex64 -> psd_out[nfft - 2*trim] (host).  Blocking: returns when the PSD is in psd_out.  The
  * last launch writes the row and a completion word into pinned host memory and the call polls that word (no interrupt
  * wake-up; after 20 ms it falls back to a stream synchronisation, which also reports a failed launch;
@@ -550,6 +563,13 @@ int oth_csd_scale_dev(oth_plan *plan, const float *sums_dev, uint64_t nseg_total
  * front of the vector that is still incomplete.  That vector is kept if the new count says so even when
  * oth_chain_push_async skipped its first samples as dropped: such samples wait in host memory (a plain copy, no
  * stream operation) and go to the device with the next push that enqueues work.
+ *
+ * Degenerate inputs (tests/test_degenerate_gpu.py): a NaN or +-inf sample makes the row of its vector non-finite in every
+ * bin - NaN or inf: which of the two is not pinned, GNU Radio's own blocks differ there - and leaves every other raw row
+ * untouched bit for bit.  From that vector on every bin of the IIR memory, of the dB rows and of the peak-hold vector is
+ * non-finite and stays so across pushes until oth_chain_reset: the peak is the reference's np.maximum, which keeps a NaN
+ * (a NaN ranks above +inf above every finite value), not IEEE maxNum, which drops it.  A bad sample inside a vector that
+ * keep_one_in_n drops changes nothing.  After oth_chain_reset the chain gives what a new one gives, bit for bit.
  */
 int oth_chain_create(oth_ctx *ctx, int nfft, const float *window, int fftshift, int epilogue,
                      int keep_one_in_n, oth_chain **out);
