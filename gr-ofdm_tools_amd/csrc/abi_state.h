@@ -154,6 +154,13 @@ struct oth_plan {
     DevBuf<float2> d_cyc_ws;           // welchcyc.hip's per-workgroup spectrum rows (WelchCycArgs.ws; 16384 points only)
     int tune_cyc_group = 0;            // OTH_CYC_GROUP, read when the plan is created: 1, 2 or 4 forces that build of welchcyc.hip
                                        // (A/B tools and the parity suite); 0 = the library's choice
+    // cyclic autocorrelation (oth_welch_set_lags, oth_welch_caf*: abi_lag.hip / welchlag.hip): Welch plans only
+    int nlags = 0;                     // 0 until oth_welch_set_lags
+    int lag_max = 0;                   // the largest lag of the set: the segments are counted on nsamples - lag_max
+    DevBuf<int> d_lags;                // [nlags] tau_l in samples
+    DevBuf<double> d_lag_means;        // welchlag.hip's per-workgroup sums of the products' means (WelchLagArgs.means)
+    int tune_lag_group = 0;            // OTH_LAG_GROUP, read when the plan is created: 1 or 2 forces that build of welchlag.hip
+                                       // (A/B tools and the parity suite); 0 = the library's choice
 };
 
 struct oth_chain {

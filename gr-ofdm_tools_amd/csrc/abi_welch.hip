@@ -439,6 +439,7 @@ int oth_welch_plan(oth_ctx *c, int nfft, int nperseg, int noverlap, const float 
     p->sk_g = s2 > 0.0 && std::isfinite(1.0 / s2) ? 1.0 / s2 : 1.0;      // oth_welch_sk's periodogram scale
     p->win_host.assign(w.begin(), w.begin() + nperseg);                   // oth_welch_set_cycles' complex tapers
     if (const char *e = getenv("OTH_CYC_GROUP")) p->tune_cyc_group = atoi(e);
+    if (const char *e = getenv("OTH_LAG_GROUP")) p->tune_lag_group = atoi(e);
     p->compl_window = nfft == 4096 && nperseg == 4096 && window_is_complementary(w, nfft);      // the welch4096ws route's shape
     // the host tables first, then the uploads: nothing between the first asynchronous copy and the synchronise can throw
     std::vector<float> fd, fd1x, wpm;

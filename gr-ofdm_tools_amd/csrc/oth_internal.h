@@ -536,4 +536,39 @@ int welch_cyc_blocks_per_cu(int nfft, int ga);      // ga: 1, 2 or kCycGroup
 hipError_t launch_welch_cyc(int nfft, int ga, int groups, const WelchCycArgs &a, hipStream_t s);
 hipError_t launch_cyc_finalize(const CycFinalizeArgs &a, int nstreams, hipStream_t s);
 
+// ---- welchlag.hip: cyclic autocorrelation of a Welch plan - per lag sum_s |FFT((z_s - m) w)|^2 of the lag product
+// z_s[n] = x[s step + n + tau] conj(x[s step + n]), and sum_s of the products' segment means -------------------------------
+constexpr int kLagMax = 64;      // lags of a plan at most
+constexpr int kLagTauMax = 65535;
+constexpr int kLagGroup = 2;     // lags per workgroup of the grouped build (the other takes one)
+struct WelchLagArgs {
+    const float2 *x;        // device IQ, stream 0
+    const float *win;       // the plan's window, nfft floats (zero-extended behind nperseg)
+    const float2 *tw;       // W_nfft^k, nfft entries
+    const int *lags;        // [nlags] tau_l in samples
+    float *partial;         // [nstreams][groups][wg_per_stream][GL][nfft]: per lag of the group sum |Z|^2; natural bin order
+    double *means;          // [nstreams][groups][wg_per_stream][GL] re, im: per lag of the group the run's sum of mbar
+    long long nseg;         // segments per stream, counted on nsamples - max tau: no lagged read leaves the stream
+    size_t stream_stride;   // samples between streams
+    int nperseg;
+    int step;
+    int detrend;            // != 0: each product segment's own mean comes off (pilot + residual)
+    int wg_per_stream;      // workgroups of a stream and group: each walks a contiguous run of the nseg segments
+    int nstreams;
+    int nlags;
+};
+struct LagFinalizeArgs {
+    const float *partial;   // as WelchLagArgs.partial
+    const double *means;    // as WelchLagArgs.means
+    float *caf_out;         // [nstreams][nlags][nout]
+    float *r_out;           // [nstreams][nlags] re, im interleaved, or nullptr
+    double scale;           // scale / M
+    double inv_m;           // 1 / M
+    int W, G, gl, nlags, nfft;
+    OutStage out;
+};
+int welch_lag_blocks_per_cu(int nfft, int gl);      // gl: 1 or kLagGroup
+hipError_t launch_welch_lag(int nfft, int gl, int groups, const WelchLagArgs &a, hipStream_t s);
+hipError_t launch_lag_finalize(const LagFinalizeArgs &a, int nstreams, hipStream_t s);
+
 }  // namespace oth

@@ -83,6 +83,9 @@ SIGNATURES = {
     'oth_welch_set_cycles': (C.c_int, [_p, C.c_int, C.POINTER(C.c_double)]),
     'oth_welch_cyclic_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _p, _u64p]),
     'oth_welch_cyclic': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _f, _u64p]),
+    'oth_welch_set_lags': (C.c_int, [_p, C.c_int, C.POINTER(C.c_int)]),
+    'oth_welch_caf_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
+    'oth_welch_caf': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
     'oth_mtm_jackknife_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
     'oth_mtm_jackknife': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
     'oth_mtm_csd_jackknife_dev': (C.c_int, [_p, _p, _p, C.c_size_t, _p, _p, _p, _p, _u64p]),
@@ -609,6 +612,46 @@ class WelchPlan(object):
         self.ctx.check(self.ctx.lib.oth_welch_cyclic_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
                                                          _optp(scf_dev), C.c_void_p(coh_dev),
                                                          _optp(psd_dev), C.byref(n)), 'oth_welch_cyclic_dev')
+        self.last_nseg = n.value
+        return n.value
+
+    nlags = 0      # (class default: no lags until set_lags)
+
+    def set_lags(self, lags):
+        """The lags of caf / caf_dev (oth_welch_set_lags): 1 ... 64 integers in samples, each 0 ... 65535.  Replaces an
+        earlier set; no other call of the plan is affected.  A multitaper plan, a median-averaging plan and a length that is
+        not a power of two 64 ... 16384 raise HipError (OTH_ERR_UNSUPPORTED)."""
+        a = np.atleast_1d(np.asarray(lags))
+        if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError('lags must be a sequence of integer lags in samples')
+        a = np.ascontiguousarray(np.clip(a.astype(np.int64), -1, 1 << 30), np.intc)      # (out of range stays out of range)
+        self.ctx.check(self.ctx.lib.oth_welch_set_lags(self.h, len(a), a.ctypes.data_as(C.POINTER(C.c_int))), 'oth_welch_set_lags')
+        self.nlags = len(a)
+
+    def caf(self, x, return_r=False, nsamples=None):
+        """Cyclic autocorrelation (oth_welch_caf) of one capture at the L lags of set_lags, as the plan's Welch PSD of the
+        lag product z_l[n] = x[n + tau_l] conj(x[n]): row l, bin q is the power of z_l at cycle frequency alpha = q / nfft
+        cycles per sample (the upper half of a row holds negative alpha, as for a PSD).  A CP-OFDM signal shows lines at
+        k / (Tu + Tcp) in the row of tau = Tu; stationary noise shows a flat floor at every lag.  The segments are counted
+        on nsamples - max(lags) samples.  x: host complex64 array, or a device pointer when nsamples is given.
+        -> caf float32 [L, out_len] with the plan's scaling, fftshift, trim and dB, and with return_r also r complex64 [L]:
+        the mean of z_l over all segments, the autocorrelation estimate R(tau_l), never scaled.  Sets last_nseg (M)."""
+        L, m = int(self.nlags), self.out_len
+        caf = np.empty((max(L, 1), m), np.float32)
+        r = np.empty(max(L, 1), np.complex64) if return_r else None
+        n = C.c_uint64()
+        src, count, dev = _src(x, nsamples)
+        self.ctx.check(self.ctx.lib.oth_welch_caf(self.h, src, count, dev, _fptr(caf), r.ctypes.data_as(_f) if return_r else None,
+                                                  C.byref(n)), 'oth_welch_caf')
+        self.last_nseg = n.value
+        return (caf, r) if return_r else caf
+
+    def caf_dev(self, iq_dev, nsamples, nstreams, stride, caf_dev, r_dev=None):
+        """Asynchronous: device in, device out - [nstreams][L][out_len] float32 at caf_dev and, where given, [nstreams][L]
+        re, im pairs at r_dev.  -> segments per stream (also last_nseg)."""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_welch_caf_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
+                                                      C.c_void_p(caf_dev), _optp(r_dev), C.byref(n)), 'oth_welch_caf_dev')
         self.last_nseg = n.value
         return n.value
 

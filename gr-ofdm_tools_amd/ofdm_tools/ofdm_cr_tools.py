@@ -637,6 +637,110 @@ def cyclic_scan(vector, nFFT, Sf, cycles_hz, fc=0.0, ctx=None):
     return coh.mean(axis=1, dtype=np.float64), coh, axis, 1.0 / M
 
 
+def caf_scan(vector, nFFT, Sf, lags, fc=0.0, ctx=None):
+    """Which lags of this capture carry a cyclic autocorrelation, with no prior knowledge of the signal: the Welch PSD of the
+    lag product x[n + tau] conj(x[n]) (WelchPlan.caf; Hann window, nperseg = nFFT, no overlap, the segment mean taken off,
+    density scaling) at each of the L lags [samples].
+    -> (alpha axis [Hz] fftshifted, caf rows [L, nFFT] fftshifted, r [L] complex - the mean lag product R(tau) - and the
+    segment count M = (len(vector) - max(lags)) // nFFT).  A CP-OFDM signal shows lines at k Sf / (Tu + Tcp) in the row of
+    tau = Tu and |r| well above the other lags'; stationary noise shows a flat row at every lag.  The lag product of a
+    signal does not move with the tuner, so fc does not enter the alpha axis; it is accepted as the other scans do.
+    Needs nFFT a power of two from 64 to 16384, 1 ... 64 integer lags in 0 ... 65535 and at least max(lags) + nFFT samples
+    (ValueError otherwise, before anything runs)."""
+    if nFFT not in SK_SIZES:
+        raise ValueError('caf_scan needs nFFT a power of two from 64 to 16384, not %r' % (nFFT,))
+    if not Sf > 0:
+        raise ValueError('caf_scan needs a sample rate Sf > 0')
+    taus = np.atleast_1d(np.asarray(lags))
+    if taus.ndim != 1 or not 1 <= len(taus) <= 64:
+        raise ValueError('caf_scan needs 1 ... 64 lags, not %d' % taus.size)
+    if not np.issubdtype(taus.dtype, np.integer) or np.any(taus < 0) or np.any(taus > 65535):
+        raise ValueError('every lag must be an integer in 0 ... 65535 samples')
+    taus = taus.astype(np.intc)
+    if len(vector) < int(taus.max()) + int(nFFT):
+        raise ValueError('caf_scan needs at least max(lags) + nFFT = %d samples' % (int(taus.max()) + int(nFFT)))
+    ctx = ctx or _hip.default_context()
+    key = ('caf', nFFT, float(Sf), taus.tobytes())
+
+    def make():
+        plan = ctx.welch_plan(nFFT, nperseg=nFFT, noverlap=0, window=windows.get_window('hann', nFFT), fs=float(Sf), fftshift=True)
+        plan.set_lags(taus)
+        return plan
+
+    plan = ctx.cached_plan(key, make)
+    caf, r = plan.caf(vector, return_r=True)
+    axis = np.fft.fftshift(np.fft.fftfreq(nFFT, 1.0 / Sf))
+    return axis, caf, r, int(plan.last_nseg)
+
+
+def ofdm_blind_hypotheses(fft_lens, cp_fractions, nFFT):
+    """The (Tu, cp = Tu // f, bin) triples ofdm_blind_parameters tests, bin = round(nFFT / (Tu + cp)): where the symbol
+    rate of the hypothesis falls in a caf row of nFFT points.  ValueError when two of them fall on the same bin or one on a
+    bin below 4 - nFFT is too small to tell these candidates apart, or from the row's DC."""
+    hyp = []
+    for tu in fft_lens:
+        for f in cp_fractions:
+            tu, f = int(tu), int(f)
+            if tu < 1 or f < 1 or tu // f < 1:
+                raise ValueError('ofdm_blind_parameters needs fft_lens >= 1 and cp_fractions that leave a prefix of a sample at least')
+            cp = tu // f
+            hyp.append((tu, cp, int(round(float(nFFT) / float(tu + cp)))))
+    bins = [q for _, _, q in hyp]
+    if not hyp or len(set(bins)) != len(bins) or min(bins) < 4:
+        raise ValueError('nFFT = %d is too small for these candidates: their symbol rates fall on bins %s, which must differ and '
+                         'be 4 at least' % (nFFT, bins))
+    return hyp
+
+
+def ofdm_blind_threshold(nseg, nhyp, p_false=1e-3):
+    """What the statistic of ofdm_blind_decision exceeds with probability p_false over all nhyp hypotheses on a flat floor:
+    the mean of two bins of an M-segment average is chi-square with 4 M degrees of freedom over 4 M, the row's median that of
+    2 M over 2 M; Bonferroni over the hypotheses."""
+    M = float(nseg)
+    return (chi2_quantile(1.0 - float(p_false) / float(nhyp), 4.0 * M) / (4.0 * M)) / (chi2_quantile(0.5, 2.0 * M) / (2.0 * M))
+
+
+def ofdm_blind_decision(rows, r, nseg, Sf, fft_lens, cp_fractions=(4, 8, 16, 32), p_false=1e-3):
+    """The decision of ofdm_blind_parameters on caf rows in natural bin order: rows [1 + len(fft_lens), nFFT] and r for the
+    lags (0,) + fft_lens, nseg the segment count behind them.  -> the dict ofdm_blind_parameters returns."""
+    rows = np.asarray(rows, np.float64)
+    nFFT = rows.shape[-1]
+    fft_lens = [int(t) for t in fft_lens]
+    if rows.shape[0] != 1 + len(fft_lens) or len(r) != rows.shape[0]:
+        raise ValueError('rows and r must hold lag 0 and one lag per entry of fft_lens')
+    hyp = ofdm_blind_hypotheses(fft_lens, cp_fractions, nFFT)
+    floors = {tu: float(np.median(rows[1 + i, 1:])) for i, tu in enumerate(fft_lens)}
+    best = None
+    for tu, cp, q in hyp:
+        row = rows[1 + fft_lens.index(tu)]
+        stat = float(row[q] + row[nFFT - q]) / (2.0 * floors[tu]) if floors[tu] > 0.0 else 0.0
+        if best is None or stat > best[0]:
+            best = (stat, tu, cp)
+    stat, tu, cp = best
+    threshold = float(ofdm_blind_threshold(nseg, len(hyp), p_false))
+    r0 = float(np.real(r[0]))
+    rho = float(abs(r[1 + fft_lens.index(tu)]) / r0) if r0 > 0.0 else 0.0
+    return {'detected': bool(stat >= threshold), 'fft_len': tu, 'cp_len': cp, 'rho': rho, 'stat': stat, 'threshold': threshold,
+            'nseg': int(nseg), 'cycles_hz': ofdm_cycle_frequencies(tu, cp, Sf)}
+
+
+def ofdm_blind_parameters(vector, Sf, fft_lens=(64, 128, 256, 512), cp_fractions=(4, 8, 16, 32), nFFT=4096, p_false=1e-3, ctx=None):
+    """The useful length and the prefix length of an unknown CP-OFDM signal in this capture, by its cyclic autocorrelation:
+    one WelchPlan.caf call (caf_scan) with the lags (0,) + fft_lens.  For every hypothesis (Tu, cp = Tu // f) the statistic
+    is (row_Tu[q] + row_Tu[nFFT - q]) / (2 median(row_Tu[1:])) at q = round(nFFT / (Tu + cp)) - the line at the symbol rate
+    over the row's floor; the largest wins, and `detected` says that it reaches ofdm_blind_threshold (p_false over all
+    hypotheses).  -> dict: detected, fft_len, cp_len, rho = |r_Tu| / r_0 (the correlation coefficient at lag Tu, about
+    cp / (Tu + cp) times the signal's share of the power), stat, threshold, nseg, cycles_hz =
+    ofdm_cycle_frequencies(fft_len, cp_len, Sf) - what cyclic_scan takes.
+    Assumes that the floor of the lag product is flat over the row, which holds for receiver noise that is white over the
+    capture band.  ValueError when two hypotheses fall on the same bin or one on a bin below 4: nFFT is too small for
+    these candidates (fft_lens up to 512 with a prefix of 1/32 need nFFT = 8192)."""
+    fft_lens = tuple(int(t) for t in fft_lens)
+    ofdm_blind_hypotheses(fft_lens, cp_fractions, nFFT)      # the refusals, before anything runs
+    _, caf, r, nseg = caf_scan(vector, nFFT, Sf, (0,) + fft_lens, ctx=ctx)
+    return ofdm_blind_decision(np.fft.ifftshift(caf, axes=-1), r, nseg, Sf, fft_lens, cp_fractions, p_false)
+
+
 class SpectrumScan(object):
     """The legacy sensor's scan (reference: ofdm_cr_tools.py:471-537; its matplotlib branch is not carried over), split
     where the GPU works: the constructor enqueues the PSD of the chosen method ('welch': flat-top Welch, 'fft': one

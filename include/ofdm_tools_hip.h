@@ -462,12 +462,57 @@ int oth_mtm_adaptive(oth_plan *plan, const void *iq, size_t nsamples, int src_is
  * on which no cycles were set, more than 65535 streams; OTH_ERR_INVALID for ncycles outside 1 ... 64, a non-finite alpha or
  * |alpha| > 0.5, a NULL alphas, input or coh pointer, nstreams < 1, stream_stride < nsamples, input shorter than nperseg.
  * Not provided: the conjugate cyclic spectrum E[X(f + alpha) X(-f)], a search over alpha (the caller supplies the cycle
- * frequencies), multitaper plans, any-length transforms. */
+ * frequencies; oth_welch_caf below finds those of a CP-OFDM signal), multitaper plans, any-length transforms. */
 int oth_welch_set_cycles(oth_plan *plan, int ncycles, const double *alphas);
 int oth_welch_cyclic_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride,
                          float *scf_out_dev, float *coh_out_dev, float *psd_out_dev, uint64_t *nseg_out);
 int oth_welch_cyclic(oth_plan *plan, const void *iq, size_t nsamples, int src_is_device, float *scf_out, float *coh_out,
                      float *psd_out, uint64_t *nseg_out);
+
+/* oth_welch_set_lags, oth_welch_caf_dev / oth_welch_caf (additions inside ABI 6; probe by the symbols): the cyclic
+ * autocorrelation function of a plan of oth_welch_plan at a set of L lags tau_l >= 0 in samples, as the plan's Welch PSD of
+ * the lag product - the blind counterpart of oth_welch_cyclic, which needs the cycle frequencies beforehand.  For a
+ * cyclic-prefix OFDM signal with useful length Tu and symbol period Ts = Tu + Tcp the lag product at tau = Tu has a non-zero
+ * mean and periodic components at alpha = k / Ts; at any other lag, and for stationary noise at every lag but 0, it has
+ * neither.  A handful of candidate lags therefore finds Tu and Tcp with no prior knowledge - the input of
+ * oth_welch_set_cycles.  With the plan's window w, nperseg, step = nperseg - noverlap, nfft, detrend mode and scaling, and
+ * T = max_l tau_l: M is the plan's segment count for an input of nsamples - T samples, so that every lagged sample a segment
+ * reads lies inside the stream's own nsamples.  Per stream, segment s and lag l, for n < nperseg:
+ *   z_s,l[n] = x[s step + n + tau_l] conj(x[s step + n])     float32: re = fma(ar, br, ai bi), im = ai br - ar bi
+ *   mbar_s,l = (1 / nperseg) sum_n z_s,l[n]                  always formed (it feeds r)
+ *   Z_s,l[q] = FFT_nfft((z_s,l[n] - m) w[n])[q]              m = mbar_s,l on a detrending plan, 0 otherwise; zero-padded when
+ *                                                            nperseg < nfft
+ *   caf_l[q] = scale (1 / M) sum_s |Z_s,l[q]|^2              the plan's scaling, then its fftshift, trim and dB
+ *   r_l      = (1 / M) sum_s mbar_s,l                        complex: the ordinary autocorrelation estimate R(tau_l)
+ * Bin q of caf is the cycle frequency alpha = q / nfft cycles per sample; the upper half of a row holds negative alpha, as
+ * for a PSD.  The segments are averaged incoherently: the resolution in alpha is one bin of the transform, and a cycle
+ * frequency off the grid is not nulled.  The mean comes off as in the multitaper kernels - a pilot (the mean of the first
+ * min(64, nperseg) products), then the residual mean as a fixed-order block sum: lag 0 and a DC offset in x both give z a
+ * mean far above its fluctuation.
+ * Outputs: caf [nstreams][L][out_len] float32; r [nstreams][L] interleaved re, im, never scaled and never in dB; r_out may
+ * be NULL, caf_out not.  tau = 0 is allowed: its r is the mean power with an imaginary part of exactly 0, so |r_l| / r_0 is
+ * the correlation coefficient of lag l when lag 0 is in the list.  All-zero input gives rows of exact zeros and r = 0; a
+ * constant input on a detrending plan gives exact-zero caf rows (-inf under dB).  A sample with a NaN or +-inf part: every
+ * caf row of that stream whose lag products include the sample reads NaN in every bin, never inf; other streams of the
+ * launch are untouched bit for bit.
+ * One averaging launch per call (csrc/welchlag.hip: a workgroup takes whole segments of one stream for one lag, or for
+ * two consecutive lags that share one load of the base segment), then a small finalize launch that adds the workgroups' rows, and
+ * the mbar sums, in double in a fixed order: bit-identical run to run.
+ * oth_welch_set_lags: 1 <= nlags <= 64 host ints, each 0 <= tau <= 65535.  It replaces any earlier set, waits for the plan's
+ * queued work, and has no effect on any other call of the plan.
+ * _dev: device in, device out, asynchronous, nstreams as oth_welch_exec_dev (at most 65535).  oth_welch_caf: one stream,
+ * host or device source, host outputs, blocking.
+ * Refused, the reason in oth_last_error(), before anything is staged, and the plan goes on working: OTH_ERR_UNSUPPORTED on a
+ * multitaper plan, a plan set to OTH_AVERAGE_MEDIAN, a transform length that is not a power of two from 64 to 16384, a plan
+ * on which no lags were set, more than 65535 streams; OTH_ERR_INVALID for nlags outside 1 ... 64, a lag outside 0 ... 65535,
+ * a NULL lags, input or caf pointer, nstreams < 1, stream_stride < nsamples, nsamples < T + nperseg.
+ * Not provided: the conjugate cyclic autocorrelation x[n + tau] x[n], negative lags (R(-tau; alpha) follows from
+ * R(tau; alpha)), coherent averaging across segments, multitaper plans, any-length transforms. */
+int oth_welch_set_lags(oth_plan *plan, int nlags, const int *lags);
+int oth_welch_caf_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride,
+                      float *caf_out_dev, float *r_out_dev, uint64_t *nseg_out);
+int oth_welch_caf(oth_plan *plan, const void *iq, size_t nsamples, int src_is_device, float *caf_out, float *r_out,
+                  uint64_t *nseg_out);
 
 /* Degenerate inputs of the one-channel average - oth_welch_exec, _exec_async, _exec_dev, _scale_dev and _finalize, plans
  * of oth_welch_plan and oth_mtm_plan, every kernel route and detrend mode (tests/test_degenerate_gpu.py): the rule is the
