@@ -1,0 +1,99 @@
+// C ABI, host side: spectral matrix and generalized coherence of C coherent channels on a Welch plan (oth_welch_matrix /
+// _dev) - the checks, the segment-per-workgroup launch of welchmat.hip at the channel capacity that takes nchan, and its two
+// finalize launches into the packed matrix rows and the gcoh row.
+#include "abi_stat.h"
+
+namespace {
+bool mat_size(int nfft) { return nfft >= 64 && nfft <= 16384 && (nfft & (nfft - 1)) == 0; }
+
+// Every refusal of the two entry points, in the header's order, before anything is allocated, staged or launched.
+int mat_check(oth_plan *p, const void *x, size_t nsamples, int nchan, size_t stride, const float *s_out, const float *gcoh_out,
+              long long *nseg_out) {
+    oth_ctx *c = p->ctx;
+    if (p->ntapers) return refuse_mtm(p, "the spectral matrix", "its segments' transforms are Welch's (oth_welch_plan)");
+    if (p->average == OTH_AVERAGE_MEDIAN)
+        return fail(c, OTH_ERR_UNSUPPORTED, "the spectral matrix is not available with OTH_AVERAGE_MEDIAN: its rows are means over "
+                                            "segments (oth_plan_set_average(OTH_AVERAGE_MEAN) first)");
+    if (!mat_size(p->nfft))
+        return fail(c, OTH_ERR_UNSUPPORTED, "the spectral matrix takes a transform length that is a power of two from 64 to 16384, not " +
+                                                std::to_string(p->nfft));
+    if (nchan < 2 || nchan > kMatChanMax) return fail(c, OTH_ERR_INVALID, "nchan must lie in 2 ... " + std::to_string(kMatChanMax));
+    if (!x) return fail(c, OTH_ERR_INVALID, "the input is NULL");
+    if (!s_out && !gcoh_out) return fail(c, OTH_ERR_INVALID, "s_out and gcoh_out are both NULL");
+    if (stride < nsamples) return fail(c, OTH_ERR_INVALID, "chan_stride < nsamples");
+    return stream_shape(p, true, nsamples, nchan, stride, nullptr, nseg_out);
+}
+
+// after mat_check: device in, device out
+int mat_run(oth_plan *p, const float2 *x, long long nseg, int nchan, size_t stride, float *s_out, float *gcoh_out) {
+    oth_ctx *c = p->ctx;
+    if (use_device(c)) return OTH_ERR_HIP;
+    const int N = p->nfft, C = nchan, cc = welch_mat_capacity(C);
+    // whole segments (all channels of each) go to W workgroups in contiguous runs: what the device holds at once, a segment at least
+    const int bpc = std::max(1, welch_mat_blocks_per_cu(N, cc));
+    const int W = segment_workgroups(c, nseg, 1, 1, bpc);
+    if (int rc = p->d_partial.ensure(c, sizeof(float) * (size_t)W * C * C * N)) return rc;
+    if (int rc = p->d_mat_totals.ensure(c, sizeof(double) * (size_t)C * C * N)) return rc;
+    const size_t pts = welch_mat_ws_points(N, cc);
+    if (pts)
+        if (int rc = p->d_mat_ws.ensure(c, sizeof(float2) * (size_t)W * C * pts)) return rc;
+    WelchMatArgs a{};
+    a.x = x;
+    a.win = p->d_win.get();
+    a.tw = p->d_tw;
+    a.partial = p->d_partial.get();
+    a.ws = p->d_mat_ws.get();
+    a.nseg = nseg;
+    a.chan_stride = stride;
+    a.nperseg = p->nperseg;
+    a.step = p->step;
+    a.detrend = p->detrend != OTH_DETREND_NONE;
+    a.wg_count = W;
+    a.nchan = C;
+    MatFinalizeArgs f{};
+    f.partial = p->d_partial.get();
+    f.totals = p->d_mat_totals.get();
+    f.s_out = s_out;
+    f.gcoh_out = gcoh_out;
+    f.s_scale = p->scale / (double)nseg;
+    f.W = W;
+    f.nchan = C;
+    f.nfft = N;
+    f.out = out_stage(p);
+    TIMED_LAUNCH(c, launch_welch_mat(N, cc, a, c->stream));
+    TIMED_LAUNCH(c, launch_mat_finalize(f, c->stream));
+    p->last_recipe = stat_recipe("welchmat", p, "", W, nseg, 1,
+                                 " nchan=" + std::to_string(C) + " cap=" + std::to_string(cc) + (pts ? " state=rows" : " state=regs"), bpc);
+    return OTH_OK;
+}
+}  // namespace
+
+extern "C" {
+int oth_welch_matrix_dev(oth_plan *p, const void *iq_dev, size_t nsamples, int nchan, size_t chan_stride, float *s_out_dev,
+                         float *gcoh_out_dev, uint64_t *nseg_out) {
+    OTH_TRY
+    CtxGuard guard_(p ? p->ctx : nullptr);
+    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    long long nseg = 0;
+    if (int rc = mat_check(p, iq_dev, nsamples, nchan, chan_stride, s_out_dev, gcoh_out_dev, &nseg)) return rc;
+    if (int rc = mat_run(p, (const float2 *)iq_dev, nseg, nchan, chan_stride, s_out_dev, gcoh_out_dev)) return rc;
+    if (nseg_out) *nseg_out = (uint64_t)nseg;
+    return OTH_OK;
+    OTH_CATCH((p ? p->ctx : nullptr))
+}
+
+int oth_welch_matrix(oth_plan *p, const void *iq, size_t nsamples, int nchan, int src_is_device, float *s_out, float *gcoh_out,
+                     uint64_t *nseg_out) {
+    OTH_TRY
+    CtxGuard guard_(p ? p->ctx : nullptr);
+    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    long long nseg = 0;
+    if (int rc = mat_check(p, iq, nsamples, nchan, nsamples, s_out, gcoh_out, &nseg)) return rc;
+    const size_t nout = (size_t)(p->nfft - 2 * p->trim), pairs = (size_t)nchan * (nchan + 1) / 2;
+    const HostRow rows[] = {{s_out, 2 * pairs * nout}, {gcoh_out, nout}};
+    // the channels lie one behind the other: staged as one block of nchan nsamples
+    return host_form(p, iq, nullptr, (size_t)nchan * nsamples, src_is_device, rows, nseg, nseg_out,
+                     [&](const float2 *dx, const float2 *, float *const *dev) { return mat_run(p, dx, nseg, nchan, nsamples, dev[0], dev[1]); });
+    OTH_CATCH((p ? p->ctx : nullptr))
+}
+}  // extern "C"

@@ -1,4 +1,4 @@
-// What the host files of the per-bin statistics (abi_ftest, abi_sk, abi_jack, abi_adapt, abi_cyc, abi_lag; mtm_run for the work split
+// What the host files of the per-bin statistics (abi_ftest, abi_sk, abi_jack, abi_adapt, abi_cyc, abi_lag, abi_mat; mtm_run for the work split
 // and the recipe) share: the stream-shape refusals, the work split over resident workgroups, the recipe text, the timed
 // launch, the host form around a device run, and the replacement of a plan's tables.
 #pragma once

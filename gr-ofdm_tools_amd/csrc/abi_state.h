@@ -161,6 +161,9 @@ struct oth_plan {
     DevBuf<double> d_lag_means;        // welchlag.hip's per-workgroup sums of the products' means (WelchLagArgs.means)
     int tune_lag_group = 0;            // OTH_LAG_GROUP, read when the plan is created: 1 or 2 forces that build of welchlag.hip
                                        // (A/B tools and the parity suite); 0 = the library's choice
+    // spectral matrix of C channels (oth_welch_matrix*: abi_mat.hip / welchmat.hip): Welch plans only
+    DevBuf<float2> d_mat_ws;           // welchmat.hip's per-workgroup spectrum rows (WelchMatArgs.ws; the builds that keep them in memory)
+    DevBuf<double> d_mat_totals;       // [nchan][nchan][nfft]: the summed rows between its two finalize launches
 };
 
 struct oth_chain {

@@ -571,4 +571,36 @@ int welch_lag_blocks_per_cu(int nfft, int gl);      // gl: 1 or kLagGroup
 hipError_t launch_welch_lag(int nfft, int gl, int groups, const WelchLagArgs &a, hipStream_t s);
 hipError_t launch_lag_finalize(const LagFinalizeArgs &a, int nstreams, hipStream_t s);
 
+// ---- welchmat.hip: spectral matrix of C coherent channels on a Welch plan - sum_s conj(X_s,a) X_s,b for a <= b, then
+// S = scale T / M and the generalized coherence 1 - det G, G_ab = T_ab / sqrt(T_aa T_bb) ---------------------------------------
+constexpr int kMatChanMax = 8;      // channels at most; the kernels are built for a capacity of 2, 4 and 8
+struct WelchMatArgs {
+    const float2 *x;        // device IQ, channel 0
+    const float *win;       // the plan's window, nfft floats (zero-extended behind nperseg)
+    const float2 *tw;       // W_nfft^k, nfft entries
+    float *partial;         // [wg_count][nchan][nchan][nfft]: [a][b] is Re T_ab for a <= b and Im T_ba for a > b; natural bin order
+    float2 *ws;             // [wg_count][nchan][welch_mat_ws_points]: the channels' spectra where they do not stay in registers
+    long long nseg;         // segments per channel
+    size_t chan_stride;     // samples between channels
+    int nperseg;
+    int step;
+    int detrend;            // != 0: each segment's own mean comes off per channel (pilot + residual)
+    int wg_count;           // workgroups: each walks a contiguous run of the nseg segments
+    int nchan;              // 2 ... the build's capacity
+};
+struct MatFinalizeArgs {
+    const float *partial;   // as WelchMatArgs.partial
+    double *totals;         // [nchan][nchan][nfft]: the workgroups' rows added up (live bins), mat_det_kernel's input
+    float *s_out;           // [nchan (nchan + 1) / 2][nout] re, im interleaved, the upper triangle row by row; or nullptr
+    float *gcoh_out;        // [nout], or nullptr
+    double s_scale;         // scale / M
+    int W, nchan, nfft;
+    OutStage out;
+};
+int welch_mat_capacity(int nchan);                   // the build that takes nchan channels: 2, 4 or kMatChanMax
+size_t welch_mat_ws_points(int nfft, int cc);        // 0: the build keeps the spectra in registers
+int welch_mat_blocks_per_cu(int nfft, int cc);
+hipError_t launch_welch_mat(int nfft, int cc, const WelchMatArgs &a, hipStream_t s);
+hipError_t launch_mat_finalize(const MatFinalizeArgs &a, hipStream_t s);      // two launches: the totals, then S and gcoh
+
 }  // namespace oth

@@ -1,6 +1,6 @@
 // The output stage every finalize kernel shares - natural bin -> fftshift -> trim -> output slot (out_slot; in_bin the other
 // way round), then sum * scale -> optional 10 log10 -> store or accumulate (psd_value, store_psd) - and the finalize stage of
-// the per-bin statistics (ftest_, sk_, jack_, adapt_, cyc_ and lag_finalize_kernel): 256 threads = 32 consecutive bins x 8 slices
+// the per-bin statistics (ftest_, sk_, jack_, adapt_, cyc_, lag_ and mat_finalize_kernel): 256 threads = 32 consecutive bins x 8 slices
 // of the workgroup axis.  Such a kernel maps its bin to the output slot, adds its R rows of the W workgroups' partial sums
 // in double in a fixed order (slice_sums: a result depends on the launch shape only), and keeps for itself the statistic's
 // own formula and its degenerate-bin rules.

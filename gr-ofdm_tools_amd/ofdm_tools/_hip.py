@@ -86,6 +86,8 @@ SIGNATURES = {
     'oth_welch_set_lags': (C.c_int, [_p, C.c_int, C.POINTER(C.c_int)]),
     'oth_welch_caf_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
     'oth_welch_caf': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
+    'oth_welch_matrix_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
+    'oth_welch_matrix': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_int, _f, _f, _u64p]),
     'oth_mtm_jackknife_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
     'oth_mtm_jackknife': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
     'oth_mtm_csd_jackknife_dev': (C.c_int, [_p, _p, _p, C.c_size_t, _p, _p, _p, _p, _u64p]),
@@ -215,6 +217,19 @@ def _src2(x, y, nsamples):
 def _optp(v):
     """a device pointer, or NULL for a row the caller leaves out"""
     return C.c_void_p(v) if v else None
+
+
+def unpack_matrix(packed, nchan):
+    """The packed upper triangle of oth_welch_matrix, complex [C (C + 1) / 2, m] row by row -> the Hermitian [C, C, m]"""
+    S = np.empty((nchan, nchan, packed.shape[-1]), packed.dtype)
+    k = 0
+    for a in range(nchan):
+        for b in range(a, nchan):
+            S[a, b] = packed[k]
+            if b != a:
+                S[b, a] = np.conj(packed[k])
+            k += 1
+    return S
 
 
 class Context(object):
@@ -652,6 +667,47 @@ class WelchPlan(object):
         n = C.c_uint64()
         self.ctx.check(self.ctx.lib.oth_welch_caf_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
                                                       C.c_void_p(caf_dev), _optp(r_dev), C.byref(n)), 'oth_welch_caf_dev')
+        self.last_nseg = n.value
+        return n.value
+
+    def matrix(self, x, return_gcoh=True, nsamples=None):
+        """Spectral matrix and generalized coherence (oth_welch_matrix) of C coherent channels, 2 <= C <= 8: with X_s,a the
+        plan's windowed transform of segment s of channel a, S[a][b] = scale mean_s conj(X_s,a) X_s,b - scipy.signal.csd(x_a,
+        x_b) with the plan's parameters, the diagonal scipy.signal.welch - and gcoh = 1 - det G, G_ab = S_ab / sqrt(S_aa S_bb),
+        in [0, 1]: the Hadamard ratio, independent of every channel's gain and noise floor, near 1 - prod_k (M - k) / M for
+        independent noise and near 1 where the channels share a signal.  x: host complex64 array (C, n), or a device pointer
+        to [C][nsamples] when nsamples is given as (C, nsamples).  -> (S complex64 [C, C, out_len], always linear, with
+        S[b][a] = conj(S[a][b]) and the plan's fftshift and trim, gcoh float32 [out_len]), or S alone with
+        return_gcoh=False.  A bin where a channel holds no power reads 0 in that channel's rows and in gcoh.  Sets
+        last_nseg (M); with M < C the matrix is singular and gcoh reads 1."""
+        if nsamples is None:
+            x = np.asarray(x)
+            if x.ndim != 2:
+                raise ValueError('x must be a (C, n) array of C channels')
+            x = np.ascontiguousarray(x, np.complex64)
+            nchan, count, src, dev = x.shape[0], x.shape[1], x.ctypes.data_as(_p), 0
+        else:
+            nchan, count = (int(v) for v in nsamples)
+            src, dev = C.c_void_p(x), 1
+        if not 2 <= nchan <= 8:
+            raise ValueError('the spectral matrix takes 2 ... 8 channels, not %d' % nchan)
+        m, pairs = self.out_len, nchan * (nchan + 1) // 2
+        packed = np.empty((pairs, m), np.complex64)
+        gcoh = np.empty(m, np.float32) if return_gcoh else None
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_welch_matrix(self.h, src, count, nchan, dev, packed.ctypes.data_as(_f),
+                                                     _fptr(gcoh) if return_gcoh else None, C.byref(n)), 'oth_welch_matrix')
+        self.last_nseg = n.value
+        S = unpack_matrix(packed, nchan)
+        return (S, gcoh) if return_gcoh else S
+
+    def matrix_dev(self, iq_dev, nsamples, nchan, stride, s_dev=None, gcoh_dev=None):
+        """Asynchronous: device in, device out - the packed upper triangle [C (C + 1) / 2][out_len] re, im pairs at s_dev
+        (pairs (0,0), (0,1), ..., (0,C-1), (1,1), ...: unpack_matrix) and [out_len] float32 at gcoh_dev; either may be left
+        out, not both.  stride: samples between channels.  -> segments per channel (also last_nseg)."""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_welch_matrix_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nchan), int(stride),
+                                                         _optp(s_dev), _optp(gcoh_dev), C.byref(n)), 'oth_welch_matrix_dev')
         self.last_nseg = n.value
         return n.value
 

@@ -673,6 +673,48 @@ def caf_scan(vector, nFFT, Sf, lags, fc=0.0, ctx=None):
     return axis, caf, r, int(plan.last_nseg)
 
 
+def multiantenna_null_mean(nchan, M):
+    """E[1 - det G] of nchan channels of independent noise over M independent segments: 1 - prod_{k=1}^{C-1} (M - k) / M
+    (the determinant of a complex Wishart sample coherence matrix; 1 / M at two channels).  1 where M < nchan."""
+    prod = 1.0
+    for k in range(1, int(nchan)):
+        prod *= max(M - k, 0) / float(M)
+    return 1.0 - prod
+
+
+def multiantenna_scan(vectors, nFFT, Sf, fc=0.0, ctx=None):
+    """Do these C coherent channels (antennas of one receiver, 2 <= C <= 8) share a signal, with no knowledge of any
+    channel's gain or noise floor?  The spectral matrix of one capture (WelchPlan.matrix; Hann window, nperseg = nFFT, no
+    overlap, density scaling) and its generalized coherence 1 - det G per bin, the GLRT for a common signal in uncalibrated
+    receivers.  vectors: (C, n) complex array.
+    -> (frequency axis [Hz] fftshifted, psd [C, nFFT]: each channel's Welch PSD fftshifted, gcoh [nFFT] fftshifted in [0, 1],
+    null_mean).  Independent noise reads about null_mean = 1 - prod_{k=1}^{C-1} (M - k) / M in every bin, M = n // nFFT,
+    whatever its level per channel; that expectation assumes independent segments, that is no overlap - which is why the scan
+    uses none.  A bin where the channels share a signal reads near 1.  With M < C every bin reads 1: the matrix is singular.
+    Needs nFFT a power of two from 64 to 16384, 2 ... 8 channels and at least one segment (ValueError otherwise, before
+    anything runs)."""
+    if nFFT not in SK_SIZES:
+        raise ValueError('multiantenna_scan needs nFFT a power of two from 64 to 16384, not %r' % (nFFT,))
+    if not Sf > 0:
+        raise ValueError('multiantenna_scan needs a sample rate Sf > 0')
+    x = np.asarray(vectors)
+    if x.ndim != 2 or not 2 <= x.shape[0] <= 8:
+        raise ValueError('multiantenna_scan needs a (C, n) array of 2 ... 8 channels, not shape %r' % (x.shape,))
+    M = x.shape[1] // int(nFFT)
+    if M < 1:
+        raise ValueError('multiantenna_scan needs at least nFFT = %d samples per channel' % nFFT)
+    ctx = ctx or _hip.default_context()
+    key = ('matrix', nFFT, float(Sf))
+
+    def make():
+        return ctx.welch_plan(nFFT, nperseg=nFFT, noverlap=0, window=windows.get_window('hann', nFFT), fs=float(Sf), fftshift=True)
+
+    S, gcoh = ctx.cached_plan(key, make).matrix(x)
+    psd = np.ascontiguousarray(S[np.arange(x.shape[0]), np.arange(x.shape[0])].real)
+    axis = np.fft.fftshift(np.fft.fftfreq(nFFT, 1.0 / Sf)) + fc
+    return axis, psd, gcoh, multiantenna_null_mean(x.shape[0], M)
+
+
 def ofdm_blind_hypotheses(fft_lens, cp_fractions, nFFT):
     """The (Tu, cp = Tu // f, bin) triples ofdm_blind_parameters tests, bin = round(nFFT / (Tu + cp)): where the symbol
     rate of the hypothesis falls in a caf row of nFFT points.  ValueError when two of them fall on the same bin or one on a

@@ -514,6 +514,53 @@ int oth_welch_caf_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int n
 int oth_welch_caf(oth_plan *plan, const void *iq, size_t nsamples, int src_is_device, float *caf_out, float *r_out,
                   uint64_t *nseg_out);
 
+/* oth_welch_matrix_dev / oth_welch_matrix (additions inside ABI 6; probe by the symbols): the spectral matrix of C coherent
+ * channels, 2 <= C <= 8 (the ports of one receiver), on a plan of oth_welch_plan, and the generalized coherence that follows
+ * from it - a detector that needs no noise floor and no calibration of the channels' gains.  oth_csd_exec takes one pair;
+ * C channels pair by pair cost C (C - 1) / 2 launches and transform every channel C - 1 times.  Here a channel of a segment
+ * is transformed once.  With the plan's window w, nperseg, step = nperseg - noverlap, nfft, detrend mode and scaling; channel
+ * a is nsamples long and begins a chan_stride samples behind channel 0; M is the plan's segment count for nsamples, common to
+ * all channels.  Per segment s, channel a and bin j:
+ *   X_s,a[j] = FFT_nfft((x_a,s[n] - m_s,a) w[n])[j]     m_s,a: the segment's mean on a detrending plan, else 0
+ *   T_ab[j]  = sum_s conj(X_s,a[j]) X_s,b[j]             a <= b; T_aa is real.  float32: |X|^2 = fma(Xr, Xr, Xi Xi),
+ *                                                        Re = fma(Ar, Br, Ai Bi), Im = Ar Bi - Ai Br (two rounded products)
+ *   S_ab     = scale T_ab / M                            scipy.signal.csd(x_a, x_b) with the plan's parameters;
+ *                                                        S_aa = scipy.signal.welch(x_a)
+ *   G_ab     = T_ab / sqrt(T_aa T_bb)                    the coherence matrix, in double
+ *   gcoh[j]  = 1 - det G[j]                              in [0, 1] (Hadamard's inequality); the Hadamard ratio
+ *                                                        det S / prod_a S_aa taken from 1, the GLRT statistic for a common
+ *                                                        signal in uncalibrated receivers.  For C = 2 it is
+ *                                                        |S_01|^2 / (S_00 S_11), the coherence of oth_csd_exec.
+ * gcoh does not change under a complex gain per channel.  On independent noise over M independent segments (no overlap) its
+ * expectation is 1 - prod_{k=1}^{C-1} (M - k) / M, whatever the channels' levels.
+ * Outputs: s_out [C (C + 1) / 2][out_len] interleaved re, im - the upper triangle row by row, (0,0), (0,1), ..., (0,C-1),
+ * (1,1), ...; S_ba = conj(S_ab); the imaginary part of a diagonal row is exactly 0.  The matrix is always linear: on a plan
+ * set to dB (oth_plan_set_output_db) it is the linear twin's bit for bit, as scf is in oth_welch_cyclic.  gcoh_out
+ * [out_len].  Both take the plan's fftshift and trim.  Either pointer may be NULL, not both.
+ * Degenerate input (the cyclic family's rules, not SciPy's 0 / 0): a bin in which a channel holds no power (T_aa <= 0:
+ * silence, a constant under detrend) reads 0 in every S_ab that involves the channel and gcoh = 0; finite input never gives
+ * NaN or inf.  A sample with a NaN or +-inf part in channel a makes every S_ab that involves a NaN in every bin, never inf,
+ * and gcoh NaN in every bin; every other entry of the matrix stays bit for bit what it is without the bad sample.  M = 1 is
+ * allowed, as in oth_csd_exec: the matrix has rank one and gcoh = 1.  With M < C the matrix is singular and gcoh reads 1 up
+ * to rounding in every bin - nothing is refused, the caller sees M in nseg_out.  Two identical channels give bit-identical
+ * rows S_aa, S_bb and Re S_ab, Im S_ab = 0 exactly and gcoh = 1 up to rounding; exchanging two channels exchanges their rows
+ * and conjugates S_ab exactly.  gcoh is clamped to [0, 1], as coh is.
+ * One averaging launch per call (csrc/welchmat.hip: a workgroup takes whole segments and transforms the C channels of each
+ * one behind the other; built for a channel capacity of 2, 4 and 8), then two small finalize launches: the workgroups' rows
+ * added in double in a fixed order, then per bin S, G and det G by LDL^H in double.  Bit-identical run to run.
+ * _dev: device in, device out, asynchronous.  oth_welch_matrix: iq is [nchan][nsamples] contiguous, host or device source,
+ * host outputs, blocking.
+ * Refused, the reason in oth_last_error(), before anything is staged, and the plan goes on working: OTH_ERR_UNSUPPORTED on a
+ * multitaper plan, a plan set to OTH_AVERAGE_MEDIAN, a transform length that is not a power of two from 64 to 16384;
+ * OTH_ERR_INVALID for nchan outside 2 ... 8, a NULL input, both outputs NULL, chan_stride < nsamples, input shorter than
+ * nperseg.
+ * Not provided: partial sums for time-sharded multi-GPU runs, multitaper plans, any-length transforms, more than 8 channels,
+ * eigenvalues. */
+int oth_welch_matrix_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nchan, size_t chan_stride,
+                         float *s_out_dev, float *gcoh_out_dev, uint64_t *nseg_out);
+int oth_welch_matrix(oth_plan *plan, const void *iq, size_t nsamples, int nchan, int src_is_device,
+                     float *s_out, float *gcoh_out, uint64_t *nseg_out);      /* iq: [nchan][nsamples], blocking */
+
 /* Degenerate inputs of the one-channel average - oth_welch_exec, _exec_async, _exec_dev, _scale_dev and _finalize, plans
  * of oth_welch_plan and oth_mtm_plan, every kernel route and detrend mode (tests/test_degenerate_gpu.py): the rule is the
  * two-channel path's, and SciPy's result is the specification.  A sample with a NaN or +-inf part makes every bin of that
