@@ -78,13 +78,9 @@ int oth_mtm_set_ratios(oth_plan *p, const double *ratios) {
 int oth_mtm_adaptive_dev(oth_plan *p, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride, int iters,
                          float *psd_out_dev, float *dof_out_dev, uint64_t *nseg_out) {
     OTH_TRY
-    CtxGuard guard_(p ? p->ctx : nullptr);
-    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    long long nseg = 0;
-    if (int rc = adapt_check(p, iq_dev, nsamples, nstreams, stream_stride, iters, psd_out_dev, &nseg)) return rc;
-    if (int rc = adapt_run(p, (const float2 *)iq_dev, nseg, nstreams, stream_stride, iters, psd_out_dev, dof_out_dev)) return rc;
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
-    return OTH_OK;
+    return dev_form(
+        p, nseg_out, [&](long long *nseg) { return adapt_check(p, iq_dev, nsamples, nstreams, stream_stride, iters, psd_out_dev, nseg); },
+        [&](long long nseg) { return adapt_run(p, (const float2 *)iq_dev, nseg, nstreams, stream_stride, iters, psd_out_dev, dof_out_dev); });
     OTH_CATCH((p ? p->ctx : nullptr))
 }
 

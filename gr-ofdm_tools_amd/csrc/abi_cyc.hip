@@ -4,20 +4,8 @@
 #include "abi_stat.h"
 
 namespace {
-bool cyc_size(int nfft) { return nfft >= 64 && nfft <= 16384 && (nfft & (nfft - 1)) == 0; }
-
 // What kind of plan takes cycle frequencies: shared by set_cycles and the exec entry points, in the header's order.
-int cyc_plan_check(oth_plan *p) {
-    oth_ctx *c = p->ctx;
-    if (p->ntapers) return refuse_mtm(p, "the cyclic spectrum", "its segments' transforms are Welch's (oth_welch_plan)");
-    if (p->average == OTH_AVERAGE_MEDIAN)
-        return fail(c, OTH_ERR_UNSUPPORTED, "the cyclic spectrum is not available with OTH_AVERAGE_MEDIAN: its rows are means over "
-                                            "segments (oth_plan_set_average(OTH_AVERAGE_MEAN) first)");
-    if (!cyc_size(p->nfft))
-        return fail(c, OTH_ERR_UNSUPPORTED, "the cyclic spectrum takes a transform length that is a power of two from 64 to 16384, not " +
-                                                std::to_string(p->nfft));
-    return OTH_OK;
-}
+int cyc_plan_check(oth_plan *p) { return welch_stat_plan(p, "the cyclic spectrum"); }
 
 // Every refusal of the two exec entry points, before anything is allocated, staged or launched.
 int cyc_check(oth_plan *p, const void *x, size_t nsamples, int nstreams, size_t stride, const float *coh_out, long long *nseg_out) {
@@ -59,21 +47,10 @@ int cyc_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t s
     if (int rc = p->d_partial.ensure(c, sizeof(float) * slots * R * N)) return rc;
     if (const size_t pts = welch_cyc_ws_points(N))
         if (int rc = p->d_cyc_ws.ensure(c, sizeof(float2) * slots * pts)) return rc;
-    WelchCycArgs a{};
-    a.x = x;
-    a.win = p->d_win.get();
+    WelchCycArgs a = welch_stat_args<WelchCycArgs>(p, x, nseg, nstreams, stride, W);
     a.ctap = p->d_cyc_tap.get();
     a.alpha = p->d_cyc_alpha.get();
-    a.tw = p->d_tw;
-    a.partial = p->d_partial.get();
     a.ws = p->d_cyc_ws.get();
-    a.nseg = nseg;
-    a.stream_stride = stride;
-    a.nperseg = p->nperseg;
-    a.step = p->step;
-    a.detrend = p->detrend != OTH_DETREND_NONE;
-    a.wg_per_stream = W;
-    a.nstreams = nstreams;
     a.ncyc = A;
     CycFinalizeArgs f{};
     f.partial = p->d_partial.get();
@@ -133,13 +110,10 @@ int oth_welch_set_cycles(oth_plan *p, int ncycles, const double *alphas) {
 int oth_welch_cyclic_dev(oth_plan *p, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride, float *scf_out_dev,
                          float *coh_out_dev, float *psd_out_dev, uint64_t *nseg_out) {
     OTH_TRY
-    CtxGuard guard_(p ? p->ctx : nullptr);
-    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    long long nseg = 0;
-    if (int rc = cyc_check(p, iq_dev, nsamples, nstreams, stream_stride, coh_out_dev, &nseg)) return rc;
-    if (int rc = cyc_run(p, (const float2 *)iq_dev, nseg, nstreams, stream_stride, scf_out_dev, coh_out_dev, psd_out_dev)) return rc;
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
-    return OTH_OK;
+    return dev_form(p, nseg_out, [&](long long *nseg) { return cyc_check(p, iq_dev, nsamples, nstreams, stream_stride, coh_out_dev, nseg); },
+                    [&](long long nseg) {
+                        return cyc_run(p, (const float2 *)iq_dev, nseg, nstreams, stream_stride, scf_out_dev, coh_out_dev, psd_out_dev);
+                    });
     OTH_CATCH((p ? p->ctx : nullptr))
 }
 

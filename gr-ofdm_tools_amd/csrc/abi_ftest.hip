@@ -51,13 +51,10 @@ extern "C" {
 int oth_mtm_ftest_dev(oth_plan *p, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride, float *f_out_dev,
                       float *line_out_dev, float *resid_out_dev, uint64_t *nseg_out) {
     OTH_TRY
-    CtxGuard guard_(p ? p->ctx : nullptr);
-    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    long long nseg = 0;
-    if (int rc = ftest_check(p, iq_dev, nsamples, nstreams, stream_stride, f_out_dev, &nseg)) return rc;
-    if (int rc = ftest_run(p, (const float2 *)iq_dev, nseg, nstreams, stream_stride, f_out_dev, line_out_dev, resid_out_dev)) return rc;
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
-    return OTH_OK;
+    return dev_form(p, nseg_out, [&](long long *nseg) { return ftest_check(p, iq_dev, nsamples, nstreams, stream_stride, f_out_dev, nseg); },
+                    [&](long long nseg) {
+                        return ftest_run(p, (const float2 *)iq_dev, nseg, nstreams, stream_stride, f_out_dev, line_out_dev, resid_out_dev);
+                    });
     OTH_CATCH((p ? p->ctx : nullptr))
 }
 

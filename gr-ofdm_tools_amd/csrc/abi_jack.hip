@@ -132,13 +132,9 @@ extern "C" {
 int oth_mtm_jackknife_dev(oth_plan *p, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride, float *lnsd_out_dev,
                           float *psd_out_dev, uint64_t *nseg_out) {
     OTH_TRY
-    CtxGuard guard_(p ? p->ctx : nullptr);
-    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    long long nseg = 0;
-    if (int rc = jack_check(p, false, iq_dev, nullptr, nsamples, nstreams, stream_stride, lnsd_out_dev, &nseg)) return rc;
-    if (int rc = jack_run(p, (const float2 *)iq_dev, nseg, nstreams, stream_stride, lnsd_out_dev, psd_out_dev)) return rc;
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
-    return OTH_OK;
+    return dev_form(
+        p, nseg_out, [&](long long *nseg) { return jack_check(p, false, iq_dev, nullptr, nsamples, nstreams, stream_stride, lnsd_out_dev, nseg); },
+        [&](long long nseg) { return jack_run(p, (const float2 *)iq_dev, nseg, nstreams, stream_stride, lnsd_out_dev, psd_out_dev); });
     OTH_CATCH((p ? p->ctx : nullptr))
 }
 
@@ -158,15 +154,11 @@ int oth_mtm_jackknife(oth_plan *p, const void *iq, size_t nsamples, int src_is_d
 int oth_mtm_csd_jackknife_dev(oth_plan *p, const void *x_dev, const void *y_dev, size_t nsamples, float *cxy_out_dev, float *zsd_out_dev,
                               float *lnsdx_out_dev, float *lnsdy_out_dev, uint64_t *nseg_out) {
     OTH_TRY
-    CtxGuard guard_(p ? p->ctx : nullptr);
-    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    long long nseg = 0;
-    if (int rc = jack_check(p, true, x_dev, y_dev, nsamples, 1, nsamples, zsd_out_dev, &nseg)) return rc;
-    if (int rc = jackcsd_run(p, (const float2 *)x_dev, (const float2 *)y_dev, nsamples, nseg, cxy_out_dev, zsd_out_dev, lnsdx_out_dev,
-                             lnsdy_out_dev))
-        return rc;
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
-    return OTH_OK;
+    return dev_form(p, nseg_out, [&](long long *nseg) { return jack_check(p, true, x_dev, y_dev, nsamples, 1, nsamples, zsd_out_dev, nseg); },
+                    [&](long long nseg) {
+                        return jackcsd_run(p, (const float2 *)x_dev, (const float2 *)y_dev, nsamples, nseg, cxy_out_dev, zsd_out_dev,
+                                           lnsdx_out_dev, lnsdy_out_dev);
+                    });
     OTH_CATCH((p ? p->ctx : nullptr))
 }
 

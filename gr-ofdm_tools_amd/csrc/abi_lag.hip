@@ -3,20 +3,8 @@
 #include "abi_stat.h"
 
 namespace {
-bool lag_size(int nfft) { return nfft >= 64 && nfft <= 16384 && (nfft & (nfft - 1)) == 0; }
-
 // What kind of plan takes lags: shared by set_lags and the exec entry points, in the header's order.
-int lag_plan_check(oth_plan *p) {
-    oth_ctx *c = p->ctx;
-    if (p->ntapers) return refuse_mtm(p, "the cyclic autocorrelation", "its segments' transforms are Welch's (oth_welch_plan)");
-    if (p->average == OTH_AVERAGE_MEDIAN)
-        return fail(c, OTH_ERR_UNSUPPORTED, "the cyclic autocorrelation is not available with OTH_AVERAGE_MEDIAN: its rows are means over "
-                                            "segments (oth_plan_set_average(OTH_AVERAGE_MEAN) first)");
-    if (!lag_size(p->nfft))
-        return fail(c, OTH_ERR_UNSUPPORTED, "the cyclic autocorrelation takes a transform length that is a power of two from 64 to 16384, not " +
-                                                std::to_string(p->nfft));
-    return OTH_OK;
-}
+int lag_plan_check(oth_plan *p) { return welch_stat_plan(p, "the cyclic autocorrelation"); }
 
 // Every refusal of the two exec entry points, before anything is allocated, staged or launched.  The segments are counted on
 // nsamples - T, T the largest lag: every lagged sample a segment reads then lies inside the stream's own nsamples.
@@ -24,14 +12,10 @@ int lag_check(oth_plan *p, const void *x, size_t nsamples, int nstreams, size_t 
     oth_ctx *c = p->ctx;
     if (int rc = lag_plan_check(p)) return rc;
     if (!p->nlags) return fail(c, OTH_ERR_UNSUPPORTED, "the cyclic autocorrelation needs its lags: call oth_welch_set_lags on this plan");
-    if (!x || !caf_out || nstreams < 1) return fail(c, OTH_ERR_INVALID, "bad argument");
-    if (nstreams > 1 && stride < nsamples) return fail(c, OTH_ERR_INVALID, "stream_stride < nsamples");
-    if (nsamples < (size_t)p->lag_max + (size_t)p->nperseg)
-        return fail(c, OTH_ERR_INVALID, "input shorter than the largest lag + nperseg (" + std::to_string(p->lag_max) + " + " +
-                                            std::to_string(p->nperseg) + " samples)");
-    if (nstreams > 65535) return fail(c, OTH_ERR_UNSUPPORTED, "the cyclic autocorrelation takes at most 65535 streams per launch");
-    *nseg_out = (long long)((nsamples - (size_t)p->lag_max - (size_t)p->noverlap) / (size_t)p->step);
-    return OTH_OK;
+    const std::string too_short =
+        "input shorter than the largest lag + nperseg (" + std::to_string(p->lag_max) + " + " + std::to_string(p->nperseg) + " samples)";
+    return stream_shape(p, x && caf_out, nsamples, nstreams, stride, "the cyclic autocorrelation takes at most 65535 streams per launch", nseg_out,
+                        (size_t)p->lag_max, too_short.c_str());
 }
 
 // Lags per workgroup: welchlag.hip's two builds (GL = 1, 2).  The grouped build loads the base segment once for two lags; the
@@ -62,20 +46,9 @@ int lag_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t s
     const size_t slots = (size_t)nstreams * G * W;
     if (int rc = p->d_partial.ensure(c, sizeof(float) * slots * gl * N)) return rc;
     if (int rc = p->d_lag_means.ensure(c, sizeof(double) * slots * gl * 2)) return rc;
-    WelchLagArgs a{};
-    a.x = x;
-    a.win = p->d_win.get();
-    a.tw = p->d_tw;
+    WelchLagArgs a = welch_stat_args<WelchLagArgs>(p, x, nseg, nstreams, stride, W);
     a.lags = p->d_lags.get();
-    a.partial = p->d_partial.get();
     a.means = p->d_lag_means.get();
-    a.nseg = nseg;
-    a.stream_stride = stride;
-    a.nperseg = p->nperseg;
-    a.step = p->step;
-    a.detrend = p->detrend != OTH_DETREND_NONE;
-    a.wg_per_stream = W;
-    a.nstreams = nstreams;
     a.nlags = L;
     LagFinalizeArgs f{};
     f.partial = p->d_partial.get();
@@ -123,13 +96,9 @@ int oth_welch_set_lags(oth_plan *p, int nlags, const int *lags) {
 int oth_welch_caf_dev(oth_plan *p, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride, float *caf_out_dev,
                       float *r_out_dev, uint64_t *nseg_out) {
     OTH_TRY
-    CtxGuard guard_(p ? p->ctx : nullptr);
-    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    long long nseg = 0;
-    if (int rc = lag_check(p, iq_dev, nsamples, nstreams, stream_stride, caf_out_dev, &nseg)) return rc;
-    if (int rc = lag_run(p, (const float2 *)iq_dev, nseg, nstreams, stream_stride, caf_out_dev, r_out_dev)) return rc;
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
-    return OTH_OK;
+    return dev_form(
+        p, nseg_out, [&](long long *nseg) { return lag_check(p, iq_dev, nsamples, nstreams, stream_stride, caf_out_dev, nseg); },
+        [&](long long nseg) { return lag_run(p, (const float2 *)iq_dev, nseg, nstreams, stream_stride, caf_out_dev, r_out_dev); });
     OTH_CATCH((p ? p->ctx : nullptr))
 }
 

@@ -4,19 +4,11 @@
 #include "abi_stat.h"
 
 namespace {
-bool mat_size(int nfft) { return nfft >= 64 && nfft <= 16384 && (nfft & (nfft - 1)) == 0; }
-
 // Every refusal of the two entry points, in the header's order, before anything is allocated, staged or launched.
 int mat_check(oth_plan *p, const void *x, size_t nsamples, int nchan, size_t stride, const float *s_out, const float *gcoh_out,
               long long *nseg_out) {
     oth_ctx *c = p->ctx;
-    if (p->ntapers) return refuse_mtm(p, "the spectral matrix", "its segments' transforms are Welch's (oth_welch_plan)");
-    if (p->average == OTH_AVERAGE_MEDIAN)
-        return fail(c, OTH_ERR_UNSUPPORTED, "the spectral matrix is not available with OTH_AVERAGE_MEDIAN: its rows are means over "
-                                            "segments (oth_plan_set_average(OTH_AVERAGE_MEAN) first)");
-    if (!mat_size(p->nfft))
-        return fail(c, OTH_ERR_UNSUPPORTED, "the spectral matrix takes a transform length that is a power of two from 64 to 16384, not " +
-                                                std::to_string(p->nfft));
+    if (int rc = welch_stat_plan(p, "the spectral matrix")) return rc;
     if (nchan < 2 || nchan > kMatChanMax) return fail(c, OTH_ERR_INVALID, "nchan must lie in 2 ... " + std::to_string(kMatChanMax));
     if (!x) return fail(c, OTH_ERR_INVALID, "the input is NULL");
     if (!s_out && !gcoh_out) return fail(c, OTH_ERR_INVALID, "s_out and gcoh_out are both NULL");
@@ -72,13 +64,9 @@ extern "C" {
 int oth_welch_matrix_dev(oth_plan *p, const void *iq_dev, size_t nsamples, int nchan, size_t chan_stride, float *s_out_dev,
                          float *gcoh_out_dev, uint64_t *nseg_out) {
     OTH_TRY
-    CtxGuard guard_(p ? p->ctx : nullptr);
-    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    long long nseg = 0;
-    if (int rc = mat_check(p, iq_dev, nsamples, nchan, chan_stride, s_out_dev, gcoh_out_dev, &nseg)) return rc;
-    if (int rc = mat_run(p, (const float2 *)iq_dev, nseg, nchan, chan_stride, s_out_dev, gcoh_out_dev)) return rc;
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
-    return OTH_OK;
+    return dev_form(
+        p, nseg_out, [&](long long *nseg) { return mat_check(p, iq_dev, nsamples, nchan, chan_stride, s_out_dev, gcoh_out_dev, nseg); },
+        [&](long long nseg) { return mat_run(p, (const float2 *)iq_dev, nseg, nchan, chan_stride, s_out_dev, gcoh_out_dev); });
     OTH_CATCH((p ? p->ctx : nullptr))
 }
 

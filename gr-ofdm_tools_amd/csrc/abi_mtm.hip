@@ -125,7 +125,6 @@ double concentration(const std::vector<double> &v, double W) {
     return 2.0 * W * (re[0] / (double)M) + 2.0 * acc;
 }
 
-bool mtm_size(int nfft) { return nfft >= 64 && nfft <= 16384 && (nfft & (nfft - 1)) == 0; }
 }  // namespace
 
 namespace oth {
@@ -194,7 +193,7 @@ int mtm_plan_create(oth_ctx *c, int nfft, int nperseg, int noverlap, int ntapers
     if (!c || !out) return fail(c, OTH_ERR_INVALID, "ctx/out is NULL");
     *out = nullptr;
     // the refusals of its own in front of the shared checks (OTH_SCALE_SPECTRUM before the range check of plan_begin)
-    if (nfft >= 1 && !mtm_size(nfft))
+    if (nfft >= 1 && !stat_size(nfft))
         return fail(c, OTH_ERR_UNSUPPORTED, "multitaper plans take a transform length that is a power of two from 64 to 16384, not " +
                                                 std::to_string(nfft));
     if (scaling == OTH_SCALE_SPECTRUM)

@@ -3,18 +3,10 @@
 #include "abi_stat.h"
 
 namespace {
-bool sk_size(int nfft) { return nfft >= 64 && nfft <= 16384 && (nfft & (nfft - 1)) == 0; }
-
 // Every refusal of the two entry points, in the header's order, before anything is allocated, staged or launched.
 int sk_check(oth_plan *p, const void *x, size_t nsamples, int nstreams, size_t stride, const float *sk_out, long long *nseg_out) {
     oth_ctx *c = p->ctx;
-    if (p->ntapers) return refuse_mtm(p, "the spectral kurtosis", "its segments' periodograms are Welch's (oth_welch_plan)");
-    if (p->average == OTH_AVERAGE_MEDIAN)
-        return fail(c, OTH_ERR_UNSUPPORTED, "the spectral kurtosis is not available with OTH_AVERAGE_MEDIAN: its PSD row is the mean "
-                                            "over segments (oth_plan_set_average(OTH_AVERAGE_MEAN) first)");
-    if (!sk_size(p->nfft))
-        return fail(c, OTH_ERR_UNSUPPORTED, "the spectral kurtosis takes a transform length that is a power of two from 64 to 16384, not " +
-                                                std::to_string(p->nfft));
+    if (int rc = welch_stat_plan(p, "the spectral kurtosis", "periodograms", "its PSD row is the mean")) return rc;
     if (int rc = stream_shape(p, x && sk_out, nsamples, nstreams, stride, "the spectral kurtosis takes at most 65535 streams per launch", nseg_out))
         return rc;
     if (*nseg_out < 2) return fail(c, OTH_ERR_INVALID, "the spectral kurtosis needs at least two segments: this input holds one");
@@ -30,18 +22,7 @@ int sk_run(oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t st
     const int bpc = std::max(1, welch_sk_blocks_per_cu(N));
     const int W = segment_workgroups(c, nseg, 1, nstreams, bpc);
     if (int rc = p->d_partial.ensure(c, sizeof(float) * (size_t)nstreams * W * 2 * N)) return rc;
-    WelchSkArgs a{};
-    a.x = x;
-    a.win = p->d_win.get();
-    a.tw = p->d_tw;
-    a.partial = p->d_partial.get();
-    a.nseg = nseg;
-    a.stream_stride = stride;
-    a.nperseg = p->nperseg;
-    a.step = p->step;
-    a.detrend = p->detrend != OTH_DETREND_NONE;
-    a.wg_per_stream = W;
-    a.nstreams = nstreams;
+    WelchSkArgs a = welch_stat_args<WelchSkArgs>(p, x, nseg, nstreams, stride, W);
     a.g = (float)p->sk_g;
     SkFinalizeArgs f{};
     f.partial = p->d_partial.get();
@@ -64,13 +45,9 @@ extern "C" {
 int oth_welch_sk_dev(oth_plan *p, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride, float *sk_out_dev,
                      float *psd_out_dev, uint64_t *nseg_out) {
     OTH_TRY
-    CtxGuard guard_(p ? p->ctx : nullptr);
-    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
-    long long nseg = 0;
-    if (int rc = sk_check(p, iq_dev, nsamples, nstreams, stream_stride, sk_out_dev, &nseg)) return rc;
-    if (int rc = sk_run(p, (const float2 *)iq_dev, nseg, nstreams, stream_stride, sk_out_dev, psd_out_dev)) return rc;
-    if (nseg_out) *nseg_out = (uint64_t)nseg;
-    return OTH_OK;
+    return dev_form(
+        p, nseg_out, [&](long long *nseg) { return sk_check(p, iq_dev, nsamples, nstreams, stream_stride, sk_out_dev, nseg); },
+        [&](long long nseg) { return sk_run(p, (const float2 *)iq_dev, nseg, nstreams, stream_stride, sk_out_dev, psd_out_dev); });
     OTH_CATCH((p ? p->ctx : nullptr))
 }
 

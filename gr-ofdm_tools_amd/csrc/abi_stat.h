@@ -1,23 +1,62 @@
 // What the host files of the per-bin statistics (abi_ftest, abi_sk, abi_jack, abi_adapt, abi_cyc, abi_lag, abi_mat; mtm_run for the work split
-// and the recipe) share: the stream-shape refusals, the work split over resident workgroups, the recipe text, the timed
-// launch, the host form around a device run, and the replacement of a plan's tables.
+// and the recipe) share: the size rule, the plan and stream-shape refusals, the kernel arguments a Welch statistic takes from
+// its plan, the work split over resident workgroups, the recipe text, the timed launch, the host and device forms around a
+// device run, and the replacement of a plan's tables.
 #pragma once
 #include "abi_state.h"
 
 namespace oth {
+// the transform lengths the taper-loop kernels are built for (OTH_MTM_FOR_EACH_N)
+inline bool stat_size(int nfft) { return nfft >= 64 && nfft <= 16384 && (nfft & (nfft - 1)) == 0; }
+
+// What kind of plan a statistic of Welch segments (`what`: "the cyclic spectrum") takes, in the header's order: no
+// multitaper plan - its segments' `segments` ("transforms") are Welch's -, no median - `rows` ("its rows are means") over
+// segments -, a size the kernels are built for.
+inline int welch_stat_plan(oth_plan *p, const std::string &what, const char *segments = "transforms", const char *rows = "its rows are means") {
+    oth_ctx *c = p->ctx;
+    if (p->ntapers) return refuse_mtm(p, what.c_str(), ("its segments' " + std::string(segments) + " are Welch's (oth_welch_plan)").c_str());
+    if (p->average == OTH_AVERAGE_MEDIAN)
+        return fail(c, OTH_ERR_UNSUPPORTED, what + " is not available with OTH_AVERAGE_MEDIAN: " + rows +
+                                                " over segments (oth_plan_set_average(OTH_AVERAGE_MEAN) first)");
+    if (!stat_size(p->nfft))
+        return fail(c, OTH_ERR_UNSUPPORTED, what + " takes a transform length that is a power of two from 64 to 16384, not " + std::to_string(p->nfft));
+    return OTH_OK;
+}
+
 // The refusals of a statistic's stream shape in their common order - "bad argument" (args_ok: the caller's pointers), the
-// stride, the input's length, the stream limit (too_many: its text; nullptr where the caller has tested it in front) - and
-// the segment count.  A family's check calls it where that keeps the family's precedence.
-inline int stream_shape(oth_plan *p, bool args_ok, size_t nsamples, int nstreams, size_t stride, const char *too_many, long long *nseg) {
+// stride, the input's length (a segment reaches `reach` samples past its nperseg - the caf's largest lag -, and too_short is
+// the refusal's text where that is not 0), the stream limit (too_many: its text; nullptr where the caller has tested it in
+// front) - and the segment count.  A family's check calls it where that keeps the family's precedence.
+inline int stream_shape(oth_plan *p, bool args_ok, size_t nsamples, int nstreams, size_t stride, const char *too_many, long long *nseg,
+                        size_t reach = 0, const char *too_short = "input shorter than nperseg") {
     oth_ctx *c = p->ctx;
     if (!args_ok || nstreams < 1) return fail(c, OTH_ERR_INVALID, "bad argument");
     if (nstreams > 1 && stride < nsamples) return fail(c, OTH_ERR_INVALID, "stream_stride < nsamples");
-    if (nsamples < (size_t)p->nperseg) return fail(c, OTH_ERR_INVALID, "input shorter than nperseg");
+    if (nsamples < reach + (size_t)p->nperseg) return fail(c, OTH_ERR_INVALID, too_short);
     if (too_many && nstreams > 65535) return fail(c, OTH_ERR_UNSUPPORTED, too_many);
-    *nseg = (long long)((nsamples - (size_t)p->noverlap) / (size_t)p->step);
+    *nseg = (long long)((nsamples - reach - (size_t)p->noverlap) / (size_t)p->step);
     return OTH_OK;
 }
 constexpr const char *kMtmTooMany = "multitaper plans take at most 65535 streams per launch";
+
+// The fields the kernel arguments of the Welch statistics share (Args: WelchSkArgs, WelchCycArgs, WelchLagArgs), from the plan
+// and the launch's shape, as mtm_args does for the taper loop; the rest of Args stays zero for the caller.  WelchMatArgs
+// names three of them after its channels (chan_stride, wg_count, nchan) and fills its own.
+template <typename Args> Args welch_stat_args(const oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t stride, int W) {
+    Args a{};
+    a.x = x;
+    a.win = p->d_win.get();
+    a.tw = p->d_tw;
+    a.partial = p->d_partial.get();
+    a.nseg = nseg;
+    a.stream_stride = stride;
+    a.nperseg = p->nperseg;
+    a.step = p->step;
+    a.detrend = p->detrend != OTH_DETREND_NONE;
+    a.wg_per_stream = W;
+    a.nstreams = nstreams;
+    return a;
+}
 
 // Workgroups per stream of a launch whose streams' work items (segments, or (segment, taper) pairs) go to workgroups in
 // contiguous runs: what the device holds at once (bpc per CU over launch_streams streams and groups), min_per_stream at
@@ -79,6 +118,17 @@ int host_form(oth_plan *p, const void *x, const void *y, size_t nsamples, int sr
     for (size_t r = 0; r < R; ++r)
         if (dev[r]) HIPCHK(c, hipMemcpyAsync(rows[r].host, dev[r], sizeof(float) * rows[r].floats, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (nseg_out) *nseg_out = (uint64_t)nseg;
+    return OTH_OK;
+}
+
+// The _dev form of a statistic between its OTH_TRY and OTH_CATCH: the plan, check(&nseg) - every refusal -, run(nseg), nseg_out.
+template <typename Check, typename Run> int dev_form(oth_plan *p, uint64_t *nseg_out, Check check, Run run) {
+    CtxGuard guard_(p ? p->ctx : nullptr);
+    if (!p) return fail(nullptr, OTH_ERR_INVALID, "plan is NULL");
+    long long nseg = 0;
+    if (int rc = check(&nseg)) return rc;
+    if (int rc = run(nseg)) return rc;
     if (nseg_out) *nseg_out = (uint64_t)nseg;
     return OTH_OK;
 }

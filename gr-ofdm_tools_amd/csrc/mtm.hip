@@ -110,8 +110,6 @@ template <int N, int T, bool KEEP> __global__ __launch_bounds__(T) void mtm_kern
     for (int q = 0; q < NQ; ++q) dst[tid0 + q * T] = acc[q];
 }
 
-size_t mtm_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedSlots * sizeof(float2); }
-
 }  // namespace
 
 #define OTH_MTM_KERNEL(N) mtm_kernel<N, generic_threads(N), mtm_keep(N)>
@@ -119,7 +117,7 @@ size_t mtm_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedS
 int mtm_blocks_per_cu(int nfft) {
     return mtm_for_size(nfft, 0, [](auto n) {
         constexpr int N = decltype(n)::value;
-        return resident_blocks<OTH_MTM_KERNEL(N)>(generic_threads(N), mtm_lds_bytes(N), 0);
+        return resident_blocks<OTH_MTM_KERNEL(N)>(generic_threads(N), stat_lds_bytes(N), 0);
     });
 }
 
@@ -127,7 +125,7 @@ hipError_t launch_mtm(int nfft, const MtmArgs &a, hipStream_t s) {
     const dim3 grid(a.wg_per_stream, a.nstreams);
     return mtm_for_size(nfft, hipErrorInvalidValue, [&](auto n) {
         constexpr int N = decltype(n)::value;
-        return launch_lds<OTH_MTM_KERNEL(N)>(grid, dim3(generic_threads(N)), mtm_lds_bytes(N), s, a);
+        return launch_lds<OTH_MTM_KERNEL(N)>(grid, dim3(generic_threads(N)), stat_lds_bytes(N), s, a);
     });
 }
 

@@ -2,7 +2,7 @@
 // kurtosis with the plan's window as the one taper, mtmjack.hip: the jackknife's second pass, mtmadapt.hip: the adaptive
 // weighting) share: the fixed-order sums
 // behind a segment's pilot and residual mean, the segment entry built on them, the taper product, the rule for keeping a
-// segment's samples in registers, and the list of sizes.
+// segment's samples in registers, the list of sizes with its dispatch over (size, build), and the launchers' thread and LDS rules.
 #pragma once
 #include "fft_lds.hip.h"
 
@@ -79,6 +79,14 @@ __device__ __forceinline__ void mtm_taper_product(const float2 *__restrict__ xs,
 
 constexpr bool mtm_keep(int n) { return n < 8192; }      // mtm.hip's header: KEEP
 constexpr int kMtmRedSlots = 32;                         // float2 slots of one `red` array (T / 64 + 1 <= 17 used)
+// Threads of the kernels that keep several spectra or rows of sums next to the butterflies (mtmcsd, the two-channel jackknife,
+// welchcyc, welchlag, welchmat): twice the coverage kernels' at 4096 and 8192 points, N / T = 8 there.  The others run
+// generic_threads.
+constexpr int stat_threads(int n) { return n == 4096 ? 512 : n == 8192 ? 1024 : generic_threads(n); }
+// dynamic LDS of a launch: `buffers` transform buffers of nfft points and `reds` red arrays behind them
+inline size_t stat_lds_bytes(int nfft, int buffers = 1, int reds = 1) {
+    return (size_t)buffers * nfft * sizeof(float2) + (size_t)reds * kMtmRedSlots * sizeof(float2);
+}
 
 #define OTH_MTM_FOR_EACH_N(X) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192) X(16384)
 
@@ -92,6 +100,16 @@ template <typename R, typename F> R mtm_for_size(int nfft, R otherwise, F f) {
 #undef X
         default: return otherwise;
     }
+}
+
+// f(std::integral_constant<int, N>, std::integral_constant<int, B>) of the listed size nfft and the build `build` out of B...
+// (welchcyc's 1, 2, 4 cycle frequencies per workgroup; welchmat's capacities), `otherwise` for any other size or build.
+template <int... B, typename R, typename F> R mtm_for_build(int nfft, int build, R otherwise, F f) {
+    return mtm_for_size(nfft, otherwise, [&](auto n) {
+        R r = otherwise;
+        (void)((build == B && (r = f(n, std::integral_constant<int, B>{}), true)) || ...);
+        return r;
+    });
 }
 
 }  // namespace oth

@@ -175,13 +175,10 @@ template <int N, int T, bool KEEP, bool TWO, bool ACCREG> __global__ __launch_bo
     }
 }
 
-size_t mtmcsd_lds_bytes(int nfft) {
-    return (size_t)(mtmcsd_two_buffers(nfft) ? 2 : 1) * nfft * sizeof(float2) + 2 * kMtmRedSlots * sizeof(float2);
-}
+size_t mtmcsd_lds_bytes(int nfft) { return stat_lds_bytes(nfft, mtmcsd_two_buffers(nfft) ? 2 : 1, 2); }
 
 // (file header: twice the coverage kernels' threads at 4096 and 8192 points)
-constexpr int mtmcsd_threads(int n) { return n == 4096 ? 512 : n == 8192 ? 1024 : generic_threads(n); }
-#define OTH_MTMCSD_KERNEL(N) mtmcsd_kernel<N, mtmcsd_threads(N), mtm_keep(N), mtmcsd_two_buffers(N), mtmcsd_two_buffers(N)>
+#define OTH_MTMCSD_KERNEL(N) mtmcsd_kernel<N, stat_threads(N), mtm_keep(N), mtmcsd_two_buffers(N), mtmcsd_two_buffers(N)>
 
 }  // namespace
 
@@ -190,7 +187,7 @@ size_t mtmcsd_ws_points(int nfft) { return mtmcsd_two_buffers(nfft) ? 0 : (size_
 int mtmcsd_blocks_per_cu(int nfft) {
     return mtm_for_size(nfft, 0, [](auto n) {
         constexpr int N = decltype(n)::value;
-        return resident_blocks<OTH_MTMCSD_KERNEL(N)>(mtmcsd_threads(N), mtmcsd_lds_bytes(N), 0);
+        return resident_blocks<OTH_MTMCSD_KERNEL(N)>(stat_threads(N), mtmcsd_lds_bytes(N), 0);
     });
 }
 
@@ -198,7 +195,7 @@ hipError_t launch_mtmcsd(int nfft, const MtmCsdArgs &a, hipStream_t s) {
     const dim3 grid(a.m.wg_per_stream, a.m.nstreams);
     return mtm_for_size(nfft, hipErrorInvalidValue, [&](auto n) {
         constexpr int N = decltype(n)::value;
-        return launch_lds<OTH_MTMCSD_KERNEL(N)>(grid, dim3(mtmcsd_threads(N)), mtmcsd_lds_bytes(N), s, a);
+        return launch_lds<OTH_MTMCSD_KERNEL(N)>(grid, dim3(stat_threads(N)), mtmcsd_lds_bytes(N), s, a);
     });
 }
 

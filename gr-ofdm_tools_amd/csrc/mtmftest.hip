@@ -203,8 +203,6 @@ __global__ __launch_bounds__(256) void ftest_finalize_kernel(FtestFinalizeArgs a
     if (a.resid_out) a.resid_out[o] = (float)(sd > 0.0 || sd != sd ? sd * a.resid_scale : 0.0);
 }
 
-size_t ftest_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedSlots * sizeof(float2); }
-
 }  // namespace
 
 #define OTH_FTEST_KERNEL(N) mtm_ftest_kernel<N, generic_threads(N), ftest_keep(N), ftest_segreg(N), ftest_accreg(N)>
@@ -214,7 +212,7 @@ size_t mtm_ftest_ws_floats(int nfft) { return ftest_segreg(nfft) ? 0 : 3 * (size
 int mtm_ftest_blocks_per_cu(int nfft) {
     return mtm_for_size(nfft, 0, [](auto n) {
         constexpr int N = decltype(n)::value;
-        return resident_blocks<OTH_FTEST_KERNEL(N)>(generic_threads(N), ftest_lds_bytes(N), 0);
+        return resident_blocks<OTH_FTEST_KERNEL(N)>(generic_threads(N), stat_lds_bytes(N), 0);
     });
 }
 
@@ -222,7 +220,7 @@ hipError_t launch_mtm_ftest(int nfft, const MtmFtestArgs &a, hipStream_t s) {
     const dim3 grid(a.m.wg_per_stream, a.m.nstreams);
     return mtm_for_size(nfft, hipErrorInvalidValue, [&](auto n) {
         constexpr int N = decltype(n)::value;
-        return launch_lds<OTH_FTEST_KERNEL(N)>(grid, dim3(generic_threads(N)), ftest_lds_bytes(N), s, a);
+        return launch_lds<OTH_FTEST_KERNEL(N)>(grid, dim3(generic_threads(N)), stat_lds_bytes(N), s, a);
     });
 }
 

@@ -260,28 +260,24 @@ __global__ __launch_bounds__(256) void jack_finalize_kernel(JackFinalizeArgs a) 
     else jack_finalize<3>(a);
 }
 
-size_t jack_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedSlots * sizeof(float2); }
 constexpr bool jack_accreg(int n) { return n < 16384; }
 
 // mtmcsd.hip's threads, buffers and workspace
 constexpr bool jackcsd_two_buffers(int n) { return n <= 8192; }
-constexpr int jackcsd_threads(int n) { return n == 4096 ? 512 : n == 8192 ? 1024 : generic_threads(n); }
 constexpr bool jackcsd_accreg(int n) { return n <= 2048; }
-size_t jackcsd_lds_bytes(int nfft) {
-    return (size_t)(jackcsd_two_buffers(nfft) ? 2 : 1) * nfft * sizeof(float2) + 2 * kMtmRedSlots * sizeof(float2);
-}
+size_t jackcsd_lds_bytes(int nfft) { return stat_lds_bytes(nfft, jackcsd_two_buffers(nfft) ? 2 : 1, 2); }
 
 }  // namespace
 
 #define OTH_JACK_KERNEL(N) mtm_jack_kernel<N, generic_threads(N), mtm_keep(N), jack_accreg(N)>
-#define OTH_JACKCSD_KERNEL(N) mtmcsd_jack_kernel<N, jackcsd_threads(N), mtm_keep(N), jackcsd_two_buffers(N), jackcsd_accreg(N)>
+#define OTH_JACKCSD_KERNEL(N) mtmcsd_jack_kernel<N, stat_threads(N), mtm_keep(N), jackcsd_two_buffers(N), jackcsd_accreg(N)>
 
 size_t mtmcsd_jack_ws_points(int nfft) { return jackcsd_two_buffers(nfft) ? 0 : (size_t)nfft; }
 
 int mtm_jack_blocks_per_cu(int nfft) {
     return mtm_for_size(nfft, 0, [](auto n) {
         constexpr int N = decltype(n)::value;
-        return resident_blocks<OTH_JACK_KERNEL(N)>(generic_threads(N), jack_lds_bytes(N), 0);
+        return resident_blocks<OTH_JACK_KERNEL(N)>(generic_threads(N), stat_lds_bytes(N), 0);
     });
 }
 
@@ -289,14 +285,14 @@ hipError_t launch_mtm_jack(int nfft, const MtmJackArgs &a, hipStream_t s) {
     const dim3 grid(a.m.wg_per_stream, a.m.nstreams);
     return mtm_for_size(nfft, hipErrorInvalidValue, [&](auto n) {
         constexpr int N = decltype(n)::value;
-        return launch_lds<OTH_JACK_KERNEL(N)>(grid, dim3(generic_threads(N)), jack_lds_bytes(N), s, a);
+        return launch_lds<OTH_JACK_KERNEL(N)>(grid, dim3(generic_threads(N)), stat_lds_bytes(N), s, a);
     });
 }
 
 int mtmcsd_jack_blocks_per_cu(int nfft) {
     return mtm_for_size(nfft, 0, [](auto n) {
         constexpr int N = decltype(n)::value;
-        return resident_blocks<OTH_JACKCSD_KERNEL(N)>(jackcsd_threads(N), jackcsd_lds_bytes(N), 0);
+        return resident_blocks<OTH_JACKCSD_KERNEL(N)>(stat_threads(N), jackcsd_lds_bytes(N), 0);
     });
 }
 
@@ -304,7 +300,7 @@ hipError_t launch_mtmcsd_jack(int nfft, const MtmCsdJackArgs &a, hipStream_t s) 
     const dim3 grid(a.c.m.wg_per_stream, a.c.m.nstreams);
     return mtm_for_size(nfft, hipErrorInvalidValue, [&](auto n) {
         constexpr int N = decltype(n)::value;
-        return launch_lds<OTH_JACKCSD_KERNEL(N)>(grid, dim3(jackcsd_threads(N)), jackcsd_lds_bytes(N), s, a);
+        return launch_lds<OTH_JACKCSD_KERNEL(N)>(grid, dim3(stat_threads(N)), jackcsd_lds_bytes(N), s, a);
     });
 }
 

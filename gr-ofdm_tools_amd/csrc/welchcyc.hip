@@ -48,8 +48,6 @@ namespace {
 constexpr bool cyc_two_buffers(int n) { return n <= 8192; }
 // the sums in registers: what builds without scratch (tests/test_welch_cyclic_cpu.py reads the code objects)
 constexpr bool cyc_accreg(int n, int ga) { return ga <= 2 ? n <= 8192 : n <= 4096; }
-// mtmcsd.hip's threads: twice the coverage kernels' at 4096 and 8192 points, N / T = 8 next to the sums
-constexpr int cyc_threads(int n) { return n == 4096 ? 512 : n == 8192 ? 1024 : generic_threads(n); }
 
 // (x - pilot - mean) c_a of the segment into buf, after mtm_segment_entry; no barrier.  mtm_taper_product with a complex taper.
 template <int N, int T, bool KEEP>
@@ -210,40 +208,28 @@ __global__ __launch_bounds__(256) void cyc_finalize_kernel(CycFinalizeArgs a) {
     if (a.psd_out && cyc == 0) a.psd_out[(size_t)stream * a.out.nout + i] = psd_value(a.out, t[0] * a.scf_scale);
 }
 
-size_t cyc_lds_bytes(int nfft) { return (size_t)(cyc_two_buffers(nfft) ? 2 : 1) * nfft * sizeof(float2) + kMtmRedSlots * sizeof(float2); }
+size_t cyc_lds_bytes(int nfft) { return stat_lds_bytes(nfft, cyc_two_buffers(nfft) ? 2 : 1); }
 
 }  // namespace
 
-#define OTH_CYC_KERNEL(N, GA) welch_cyc_kernel<N, cyc_threads(N), GA, mtm_keep(N), cyc_two_buffers(N), cyc_accreg(N, GA)>
+#define OTH_CYC_KERNEL(N, GA) welch_cyc_kernel<N, stat_threads(N), GA, mtm_keep(N), cyc_two_buffers(N), cyc_accreg(N, GA)>
 
 size_t welch_cyc_ws_points(int nfft) { return cyc_two_buffers(nfft) ? 0 : (size_t)nfft; }
 
 int welch_cyc_blocks_per_cu(int nfft, int ga) {
-    switch (nfft) {
-#define X(N)                                                                                                             \
-    case N:                                                                                                              \
-        return ga == 1   ? resident_blocks<OTH_CYC_KERNEL(N, 1)>(cyc_threads(N), cyc_lds_bytes(N), 0)                    \
-               : ga == 2 ? resident_blocks<OTH_CYC_KERNEL(N, 2)>(cyc_threads(N), cyc_lds_bytes(N), 0)                    \
-                         : resident_blocks<OTH_CYC_KERNEL(N, kCycGroup)>(cyc_threads(N), cyc_lds_bytes(N), 0);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return 0;
-    }
+    return mtm_for_build<1, 2, kCycGroup>(nfft, ga, 0, [](auto n, auto g) {
+        constexpr int N = decltype(n)::value, GA = decltype(g)::value;
+        return resident_blocks<OTH_CYC_KERNEL(N, GA)>(stat_threads(N), cyc_lds_bytes(N), 0);
+    });
 }
 
 hipError_t launch_welch_cyc(int nfft, int ga, int groups, const WelchCycArgs &a, hipStream_t s) {
     if (ga != 1 && ga != 2 && ga != kCycGroup) return hipErrorInvalidValue;
     const dim3 grid(a.wg_per_stream, a.nstreams, groups);
-    switch (nfft) {
-#define X(N)                                                                                                             \
-    case N:                                                                                                              \
-        return ga == 1   ? launch_lds<OTH_CYC_KERNEL(N, 1)>(grid, dim3(cyc_threads(N)), cyc_lds_bytes(N), s, a)          \
-               : ga == 2 ? launch_lds<OTH_CYC_KERNEL(N, 2)>(grid, dim3(cyc_threads(N)), cyc_lds_bytes(N), s, a)          \
-                         : launch_lds<OTH_CYC_KERNEL(N, kCycGroup)>(grid, dim3(cyc_threads(N)), cyc_lds_bytes(N), s, a);
-        OTH_MTM_FOR_EACH_N(X)
-#undef X
-        default: return hipErrorInvalidValue;
-    }
+    return mtm_for_build<1, 2, kCycGroup>(nfft, ga, hipErrorInvalidValue, [&](auto n, auto g) {
+        constexpr int N = decltype(n)::value, GA = decltype(g)::value;
+        return launch_lds<OTH_CYC_KERNEL(N, GA)>(grid, dim3(stat_threads(N)), cyc_lds_bytes(N), s, a);
+    });
 }
 
 hipError_t launch_cyc_finalize(const CycFinalizeArgs &a, int nstreams, hipStream_t s) {

@@ -49,8 +49,6 @@ namespace {
 
 // the sums in registers: what builds without scratch (tests/test_welch_caf_cpu.py reads the code objects)
 constexpr bool lag_accreg(int n, int gl) { return gl == 1 || n <= 8192; }
-// welchcyc.hip's threads: N / T = 8 next to the sums at 4096 and 8192 points
-constexpr int lag_threads(int n) { return n == 4096 ? 512 : n == 8192 ? 1024 : generic_threads(n); }
 
 // x[n + tau] conj(x[n]): a the lagged sample, b the base one
 __device__ __forceinline__ float2 lag_product(float2 a, float2 b) { return make_float2(fmaf(a.x, b.x, a.y * b.y), cross_im(b, a)); }
@@ -224,27 +222,23 @@ __global__ __launch_bounds__(256) void lag_finalize_kernel(LagFinalizeArgs a) {
     store_psd(a.caf_out, ((size_t)stream * a.nlags + lag) * a.out.nout + i, t[0], a.scale, 0, a.out);
 }
 
-size_t lag_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedSlots * sizeof(float2); }
-
 }  // namespace
 
-#define OTH_LAG_KERNEL(N, GL) welch_lag_kernel<N, lag_threads(N), GL, mtm_keep(N), lag_accreg(N, GL)>
+#define OTH_LAG_KERNEL(N, GL) welch_lag_kernel<N, stat_threads(N), GL, mtm_keep(N), lag_accreg(N, GL)>
 
 int welch_lag_blocks_per_cu(int nfft, int gl) {
-    return mtm_for_size<int>(nfft, 0, [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        return gl == 1 ? resident_blocks<OTH_LAG_KERNEL(N, 1)>(lag_threads(N), lag_lds_bytes(N), 0)
-                       : resident_blocks<OTH_LAG_KERNEL(N, kLagGroup)>(lag_threads(N), lag_lds_bytes(N), 0);
+    return mtm_for_build<1, kLagGroup>(nfft, gl, 0, [](auto n, auto g) {
+        constexpr int N = decltype(n)::value, GL = decltype(g)::value;
+        return resident_blocks<OTH_LAG_KERNEL(N, GL)>(stat_threads(N), stat_lds_bytes(N), 0);
     });
 }
 
 hipError_t launch_welch_lag(int nfft, int gl, int groups, const WelchLagArgs &a, hipStream_t s) {
     if (gl != 1 && gl != kLagGroup) return hipErrorInvalidValue;
     const dim3 grid(a.wg_per_stream, a.nstreams, groups);
-    return mtm_for_size<hipError_t>(nfft, hipErrorInvalidValue, [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        return gl == 1 ? launch_lds<OTH_LAG_KERNEL(N, 1)>(grid, dim3(lag_threads(N)), lag_lds_bytes(N), s, a)
-                       : launch_lds<OTH_LAG_KERNEL(N, kLagGroup)>(grid, dim3(lag_threads(N)), lag_lds_bytes(N), s, a);
+    return mtm_for_build<1, kLagGroup>(nfft, gl, hipErrorInvalidValue, [&](auto n, auto g) {
+        constexpr int N = decltype(n)::value, GL = decltype(g)::value;
+        return launch_lds<OTH_LAG_KERNEL(N, GL)>(grid, dim3(stat_threads(N)), stat_lds_bytes(N), s, a);
     });
 }
 

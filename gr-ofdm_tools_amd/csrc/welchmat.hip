@@ -41,12 +41,11 @@
 namespace oth {
 namespace {
 
-// mtmcsd.hip's threads: N / T <= 8 up to 8192 points
-constexpr int mat_threads(int n) { return n == 4096 ? 512 : n == 8192 ? 1024 : generic_threads(n); }
-// registers a lane may hold at this workgroup size, and what the transform, the samples and the addresses take of them
-constexpr int mat_regs(int n) { return mat_threads(n) <= 256 ? 512 : mat_threads(n) == 512 ? 256 : 128; }
+// registers a lane may hold at this workgroup size (stat_threads: N / T <= 8 up to 8192 points), and what the transform, the
+// samples and the addresses take of them
+constexpr int mat_regs(int n) { return stat_threads(n) <= 256 ? 512 : stat_threads(n) == 512 ? 256 : 128; }
 constexpr int kMatReserve = 64;
-constexpr int mat_nq(int n) { return n / mat_threads(n); }
+constexpr int mat_nq(int n) { return n / stat_threads(n); }
 // the owned bins of the C spectra (2 C N / T registers) and the C^2 running rows (C^2 N / T) in registers
 constexpr bool mat_reg(int n, int cc) { return n < 16384 && (2 * cc + cc * cc) * mat_nq(n) + kMatReserve <= mat_regs(n); }
 
@@ -251,27 +250,20 @@ __global__ __launch_bounds__(kMatDetThreads) void mat_det_kernel(MatFinalizeArgs
     a.gcoh_out[i] = g;
 }
 
-size_t mat_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedSlots * sizeof(float2); }
-
 }  // namespace
 
-#define OTH_MAT_KERNEL(N, CC) welch_mat_kernel<N, mat_threads(N), CC, mtm_keep(N), mat_reg(N, CC)>
+#define OTH_MAT_KERNEL(N, CC) welch_mat_kernel<N, stat_threads(N), CC, mtm_keep(N), mat_reg(N, CC)>
 
 int welch_mat_capacity(int nchan) { return nchan <= 2 ? 2 : nchan <= 4 ? 4 : kMatChanMax; }
 
 size_t welch_mat_ws_points(int nfft, int cc) {
-    return mtm_for_size(nfft, (size_t)0, [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        return (cc == 2 ? mat_reg(N, 2) : cc == 4 ? mat_reg(N, 4) : mat_reg(N, kMatChanMax)) ? (size_t)0 : (size_t)N;
-    });
+    return mtm_for_build<2, 4, kMatChanMax>(nfft, cc, (size_t)0, [](auto n, auto c) { return mat_reg(n(), c()) ? (size_t)0 : (size_t)n(); });
 }
 
 int welch_mat_blocks_per_cu(int nfft, int cc) {
-    return mtm_for_size(nfft, 0, [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        return cc == 2   ? resident_blocks<OTH_MAT_KERNEL(N, 2)>(mat_threads(N), mat_lds_bytes(N), 0)
-               : cc == 4 ? resident_blocks<OTH_MAT_KERNEL(N, 4)>(mat_threads(N), mat_lds_bytes(N), 0)
-                         : resident_blocks<OTH_MAT_KERNEL(N, kMatChanMax)>(mat_threads(N), mat_lds_bytes(N), 0);
+    return mtm_for_build<2, 4, kMatChanMax>(nfft, cc, 0, [](auto n, auto c) {
+        constexpr int N = decltype(n)::value, CC = decltype(c)::value;
+        return resident_blocks<OTH_MAT_KERNEL(N, CC)>(stat_threads(N), stat_lds_bytes(N), 0);
     });
 }
 
@@ -279,11 +271,9 @@ hipError_t launch_welch_mat(int nfft, int cc, const WelchMatArgs &a, hipStream_t
     if (cc != 2 && cc != 4 && cc != kMatChanMax) return hipErrorInvalidValue;
     if (a.nchan < 2 || a.nchan > cc) return hipErrorInvalidValue;
     const dim3 grid(a.wg_count);
-    return mtm_for_size(nfft, hipErrorInvalidValue, [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        return cc == 2   ? launch_lds<OTH_MAT_KERNEL(N, 2)>(grid, dim3(mat_threads(N)), mat_lds_bytes(N), s, a)
-               : cc == 4 ? launch_lds<OTH_MAT_KERNEL(N, 4)>(grid, dim3(mat_threads(N)), mat_lds_bytes(N), s, a)
-                         : launch_lds<OTH_MAT_KERNEL(N, kMatChanMax)>(grid, dim3(mat_threads(N)), mat_lds_bytes(N), s, a);
+    return mtm_for_build<2, 4, kMatChanMax>(nfft, cc, hipErrorInvalidValue, [&](auto n, auto c) {
+        constexpr int N = decltype(n)::value, CC = decltype(c)::value;
+        return launch_lds<OTH_MAT_KERNEL(N, CC)>(grid, dim3(stat_threads(N)), stat_lds_bytes(N), s, a);
     });
 }
 

@@ -125,8 +125,6 @@ __global__ __launch_bounds__(256) void sk_finalize_kernel(SkFinalizeArgs a) {
     if (a.psd_out) a.psd_out[o] = psd_value(a.out, t1 * a.psd_scale);
 }
 
-size_t sk_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedSlots * sizeof(float2); }
-
 }  // namespace
 
 #define OTH_SK_KERNEL(N) welch_sk_kernel<N, generic_threads(N), sk_keep(N), sk_accreg(N)>
@@ -134,7 +132,7 @@ size_t sk_lds_bytes(int nfft) { return (size_t)nfft * sizeof(float2) + kMtmRedSl
 int welch_sk_blocks_per_cu(int nfft) {
     return mtm_for_size(nfft, 0, [](auto n) {
         constexpr int N = decltype(n)::value;
-        return resident_blocks<OTH_SK_KERNEL(N)>(generic_threads(N), sk_lds_bytes(N), 0);
+        return resident_blocks<OTH_SK_KERNEL(N)>(generic_threads(N), stat_lds_bytes(N), 0);
     });
 }
 
@@ -142,7 +140,7 @@ hipError_t launch_welch_sk(int nfft, const WelchSkArgs &a, hipStream_t s) {
     const dim3 grid(a.wg_per_stream, a.nstreams);
     return mtm_for_size(nfft, hipErrorInvalidValue, [&](auto n) {
         constexpr int N = decltype(n)::value;
-        return launch_lds<OTH_SK_KERNEL(N)>(grid, dim3(generic_threads(N)), sk_lds_bytes(N), s, a);
+        return launch_lds<OTH_SK_KERNEL(N)>(grid, dim3(generic_threads(N)), stat_lds_bytes(N), s, a);
     });
 }
 

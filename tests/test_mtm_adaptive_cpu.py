@@ -4,15 +4,14 @@ interval's coverage, the float32 emulation that sets the GPU gate, the ABI surfa
 mtm_adapt_kernel build read from the code objects of the built library."""
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
 import mtm_adaptive_oracle as AO
+from stat_support import POWERS, check_builds
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
 SYMBOLS = ('oth_mtm_set_ratios', 'oth_mtm_adaptive_dev', 'oth_mtm_adaptive')
 
@@ -135,17 +134,4 @@ def test_every_mtm_adaptive_kernel_build_has_no_scratch():
     in a workspace row from 1024 on, and the iteration's sums are twelve to sixteen floats.  Read from the code objects
     inside the built library: one build per power of two 64 ... 16384, each with a private segment of 0 bytes and no
     spilled register; the 1024-thread build at 16384 points inside its 128 registers."""
-    import kernel_resources
-    from ofdm_tools import _hip
-    if not os.path.exists(_hip.LIB_PATH):
-        pytest.skip('library not built yet')
-    ks = {n: v for n, v in kernel_resources.kernels(_hip.LIB_PATH).items() if 'mtm_adapt_kernel<' in n}
-    sizes = sorted(int(n.split('mtm_adapt_kernel<')[1].split(',')[0]) for n in ks)
-    assert sizes == [64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384], sorted(ks)
-    for n, v in sorted(ks.items()):
-        print('%s: vgpr %d agpr %d sgpr %d scratch %d' % (n.split('(')[0], v['vgpr'], v['agpr'], v['sgpr'], v['scratch']))
-    bad = {n: (v['scratch'], v['spill_vgpr'], v['spill_sgpr']) for n, v in ks.items()
-           if v['scratch'] or v['spill_vgpr'] or v['spill_sgpr']}
-    assert not bad, bad
-    big = [v for n, v in ks.items() if 'mtm_adapt_kernel<16384' in n][0]
-    assert big['vgpr'] + big['agpr'] <= 128, big
+    check_builds('mtm_adapt_kernel', POWERS, {1024: 128})

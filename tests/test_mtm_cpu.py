@@ -7,6 +7,8 @@ import sys
 import numpy as np
 import pytest
 
+from stat_support import POWERS, check_builds
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
@@ -127,15 +129,4 @@ def test_every_mtm_kernel_build_has_no_scratch():
     """The taper loop keeps its accumulators (and, below 16384 points, the detrended samples) in registers across the
     transforms of a run: a spilled register would come back at memory latency K times per segment.  Read from the code
     objects inside the built library: one build per power of two 64 ... 16384, each with a private segment of 0 bytes."""
-    import kernel_resources
-    from ofdm_tools import _hip
-    if not os.path.exists(_hip.LIB_PATH):
-        pytest.skip('library not built yet')
-    ks = {n: v for n, v in kernel_resources.kernels(_hip.LIB_PATH).items() if 'mtm_kernel<' in n}
-    sizes = sorted(int(n.split('mtm_kernel<')[1].split(',')[0]) for n in ks)
-    assert sizes == [64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384], sorted(ks)
-    bad = {n: (v['scratch'], v['spill_vgpr'], v['spill_sgpr']) for n, v in ks.items()
-           if v['scratch'] or v['spill_vgpr'] or v['spill_sgpr']}
-    assert not bad, bad
-    big = [v for n, v in ks.items() if 'mtm_kernel<16384' in n][0]
-    assert big['vgpr'] + big['agpr'] <= 128      # 1024 threads: four waves per SIMD
+    check_builds('mtm_kernel', POWERS, {1024: 128})      # 1024 threads: four waves per SIMD

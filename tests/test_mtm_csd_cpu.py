@@ -3,17 +3,16 @@ SciPy and against the one-channel oracle, the declared surface, the Python argum
 every mtmcsd_kernel build read from the code objects of the built library."""
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
 import mtm_csd_oracle as MC
 import mtm_oracle as O
+from stat_support import POWERS, check_builds
 from oracle import ref_cpu as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
 HEADER = os.path.join(ROOT, 'include', 'ofdm_tools_hip.h')
 
 
@@ -110,24 +109,6 @@ def test_every_mtmcsd_kernel_build_has_no_scratch():
     library: one build per power of two 64 ... 16384, each with a private segment of 0 bytes and no spilled register;
     the 1024-thread build inside its 128 registers; dynamic LDS (not in the code object) at most 160 KiB by the launcher's
     own arithmetic - 2 N float2 up to 8192 points, N float2 at 16384, and 64 float2 of reduction slots."""
-    import kernel_resources
-    from ofdm_tools import _hip
-    if not os.path.exists(_hip.LIB_PATH):
-        pytest.skip('library not built yet')
-    ks = {n: v for n, v in kernel_resources.kernels(_hip.LIB_PATH).items() if 'mtmcsd_kernel<' in n}
-    sizes = sorted(int(n.split('mtmcsd_kernel<')[1].split(',')[0]) for n in ks)
-    assert sizes == [64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384], sorted(ks)
-    assert not [n for n in ks if 'mtm_kernel<' in n]
-    for n, v in sorted(ks.items()):
-        print('%s: vgpr %d agpr %d sgpr %d scratch %d static lds %d' % (n.split('oth::')[-1], v['vgpr'], v['agpr'], v['sgpr'],
-                                                                         v['scratch'], v['lds']))
-    bad = {n: (v['scratch'], v['spill_vgpr'], v['spill_sgpr']) for n, v in ks.items()
-           if v['scratch'] or v['spill_vgpr'] or v['spill_sgpr']}
-    assert not bad, bad
-    threads = {n: int(n.split('mtmcsd_kernel<')[1].split(',')[1]) for n in ks}
-    big = {n: ks[n]['vgpr'] + ks[n]['agpr'] for n in ks if threads[n] == 1024}      # 1024 threads: four waves per SIMD
-    assert any('mtmcsd_kernel<16384' in n for n in big) and all(v <= 128 for v in big.values()), big
-    for n in ks:
-        size, two = int(n.split('mtmcsd_kernel<')[1].split(',')[0]), n.split('mtmcsd_kernel<')[1].split(',')[3].strip().startswith('true')
-        assert two == (size <= 8192), n
-        assert (2 if two else 1) * size * 8 + 64 * 8 <= 160 * 1024, n
+    for (size, _, _, two, _), _ in check_builds('mtmcsd_kernel', POWERS, {1024: 128}):      # 1024 threads: four waves per SIMD
+        assert two == (size <= 8192), size
+        assert (2 if two else 1) * size * 8 + 64 * 8 <= 160 * 1024, size

@@ -1,16 +1,11 @@
 """CPU checks of the harmonic F-test addition (no GPU): the threshold (the F quantile without SciPy) against SciPy, the
 float64 oracle (tests/mtm_ftest_oracle.py) against itself and on the case the feature exists for, and the resource
 figures of every mtm_ftest_kernel build read from the code objects of the built library."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
 import mtm_ftest_oracle as FO
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from stat_support import POWERS, check_builds
 
 
 @pytest.mark.parametrize('nseg,K,p', [(1, 7, 1e-3), (1, 2, 1e-2), (1, 3, 1e-5), (4, 7, 1e-6), (20, 3, 1e-4), (2047, 4, 1e-9)])
@@ -82,17 +77,4 @@ def test_every_mtm_ftest_kernel_build_has_no_scratch():
     """Five floats of state per owned bin next to the butterflies: read from the code objects inside the built library,
     one build per power of two 64 ... 16384, each with a private segment of 0 bytes and no spilled register; the
     1024-thread build at 16384 points inside its 128 registers."""
-    import kernel_resources
-    from ofdm_tools import _hip
-    if not os.path.exists(_hip.LIB_PATH):
-        pytest.skip('library not built yet')
-    ks = {n: v for n, v in kernel_resources.kernels(_hip.LIB_PATH).items() if 'mtm_ftest_kernel<' in n}
-    sizes = sorted(int(n.split('mtm_ftest_kernel<')[1].split(',')[0]) for n in ks)
-    assert sizes == [64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384], sorted(ks)
-    for n, v in sorted(ks.items()):
-        print('%s: vgpr %d agpr %d sgpr %d scratch %d' % (n.split('oth::')[-1], v['vgpr'], v['agpr'], v['sgpr'], v['scratch']))
-    bad = {n: (v['scratch'], v['spill_vgpr'], v['spill_sgpr']) for n, v in ks.items()
-           if v['scratch'] or v['spill_vgpr'] or v['spill_sgpr']}
-    assert not bad, bad
-    big = [v for n, v in ks.items() if 'mtm_ftest_kernel<16384' in n][0]
-    assert big['vgpr'] + big['agpr'] <= 128, big
+    check_builds('mtm_ftest_kernel', POWERS, {1024: 128})

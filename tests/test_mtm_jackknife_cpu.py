@@ -3,16 +3,12 @@ SciPy, the float64 oracle (tests/mtm_jackknife_oracle.py) against the literal de
 for - the share of bins whose interval holds the truth - and the resource figures of every mtm_jack_kernel and
 mtmcsd_jack_kernel build read from the code objects of the built library."""
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
 import mtm_jackknife_oracle as JO
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from stat_support import POWERS, check_builds
 
 
 def white(n, seed):
@@ -110,20 +106,5 @@ def test_every_jackknife_kernel_build_has_no_scratch():
     """Two (one channel) or six (two channels) floats of state per owned bin next to the butterflies and a log1p / atanh per
     bin: read from the code objects inside the built library, one build per power of two 64 ... 16384 of each kernel, each
     with a private segment of 0 bytes and no spilled register; the 1024-thread builds inside their 128 registers."""
-    import kernel_resources
-    from ofdm_tools import _hip
-    if not os.path.exists(_hip.LIB_PATH):
-        pytest.skip('library not built yet')
-    allk = kernel_resources.kernels(_hip.LIB_PATH)
-    for kernel, big in (('mtm_jack_kernel<', (16384,)), ('mtmcsd_jack_kernel<', (8192, 16384))):
-        ks = {n: v for n, v in allk.items() if kernel in n}
-        sizes = sorted(int(n.split(kernel)[1].split(',')[0]) for n in ks)
-        assert sizes == [64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384], sorted(ks)
-        for n, v in sorted(ks.items()):
-            print('%s: vgpr %d agpr %d sgpr %d scratch %d' % (n[n.index(kernel):].split('(')[0], v['vgpr'], v['agpr'], v['sgpr'], v['scratch']))
-        bad = {n: (v['scratch'], v['spill_vgpr'], v['spill_sgpr']) for n, v in ks.items()
-               if v['scratch'] or v['spill_vgpr'] or v['spill_sgpr']}
-        assert not bad, bad
-        for size in big:      # the builds of 1024 threads
-            v = [v for n, v in ks.items() if '%s%d,' % (kernel, size) in n][0]
-            assert v['vgpr'] + v['agpr'] <= 128, (kernel, size, v)
+    check_builds('mtm_jack_kernel', POWERS, {1024: 128})
+    check_builds('mtmcsd_jack_kernel', POWERS, {1024: 128})

@@ -2,17 +2,12 @@
 (tests/welch_caf_oracle.py) on its identities and on a CP-OFDM signal, the decision of ofdm_blind_parameters on the oracle's
 rows, the Python helpers' refusals, the declared surface, and the resource figures of every welch_lag_kernel build read from
 the code objects of the built library."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
 import welch_caf_oracle as LO
+from stat_support import POWERS, check_builds, check_surface
 from test_welch_cyclic_cpu import cp_ofdm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
 SYMBOLS = ('oth_welch_set_lags', 'oth_welch_caf_dev', 'oth_welch_caf')
 BLIND_NFFT, BLIND_M, BLIND_LENS = 4096, 32, (32, 64, 128, 256)
@@ -151,35 +146,11 @@ def test_blind_parameters_refuses_candidates_the_row_cannot_separate():
 # ---- 5. surface, 6. resources --------------------------------------------------------------------------------------------------
 
 def test_surface_is_declared_and_exported():
-    from ofdm_tools import _hip
-    header = open(os.path.join(ROOT, 'include', 'ofdm_tools_hip.h')).read()
-    for name in SYMBOLS:
-        assert 'int %s(' % name in header and name in _hip.SIGNATURES
-    for name in ('set_lags', 'caf', 'caf_dev'):
-        assert hasattr(_hip.WelchPlan, name)
-    if not os.path.exists(_hip.LIB_PATH):
-        pytest.skip('library not built yet')
-    lib = _hip.load()
-    for name in SYMBOLS:
-        assert getattr(lib, name) is not None
+    check_surface(SYMBOLS, 'WelchPlan', ('set_lags', 'caf', 'caf_dev'))
 
 
 def test_every_welch_lag_kernel_build_has_no_scratch():
     """one running row per lag of the group next to the butterflies (or the partial rows where they do not fit): read from
     the code objects inside the built library, two builds (GL = 1, 2) per power of two 64 ... 16384, each with a private
     segment of 0 bytes and no spilled register; the 1024-thread builds inside their 128 registers."""
-    import kernel_resources
-    from ofdm_tools import _hip
-    if not os.path.exists(_hip.LIB_PATH):
-        pytest.skip('library not built yet')
-    ks = {n: v for n, v in kernel_resources.kernels(_hip.LIB_PATH).items() if 'welch_lag_kernel<' in n}
-    builds = sorted(tuple(int(t) for t in n.split('welch_lag_kernel<')[1].split(',')[:3:2]) for n in ks)
-    assert builds == [(n, gl) for n in (64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384) for gl in (1, 2)], sorted(ks)
-    for n, v in sorted(ks.items()):
-        print('%s: vgpr %d agpr %d sgpr %d scratch %d' % (n[n.index('welch_lag_kernel<'):].split('>')[0] + '>', v['vgpr'], v['agpr'], v['sgpr'], v['scratch']))
-    bad = {n: (v['scratch'], v['spill_vgpr'], v['spill_sgpr']) for n, v in ks.items()
-           if v['scratch'] or v['spill_vgpr'] or v['spill_sgpr']}
-    assert not bad, bad
-    for n, v in ks.items():
-        if ', 1024, ' in n.split('welch_lag_kernel<')[1]:
-            assert v['vgpr'] + v['agpr'] <= 128, (n, v)
+    check_builds('welch_lag_kernel', [(n, gl) for n in POWERS for gl in (1, 2)], {1024: 128})

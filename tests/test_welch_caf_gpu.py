@@ -12,57 +12,36 @@ segments of 4096 2.9e-6, 4.5e-8 and 100 x 5 of 16384 with W < nseg 8.3e-6, 4.4e-
 bit-identical on both builds at every size tried.  Against the torch product + exec_dev: 1.5e-6.  ofdm_blind_parameters on
 CP-OFDM at 0 dB: statistic 23.2 for (64, 16) and for (256, 64) against a threshold of 1.57, 1.24 on noise alone - the
 oracle's figures to seven digits."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
 import median_oracle as MO
 import welch_caf_oracle as LO
 import welch_cyclic_oracle as CO
+from stat_support import FS, forced_env, recipe_field, welch_plan
 from test_hip_parity import RTOL, ctx, hip  # noqa: F401 - ctx / hip are fixtures
-from test_median_gpu import SCALINGS, noise_tones, window
+from test_median_gpu import noise_tones
 from test_welch_caf_cpu import BLIND_LENS, BLIND_M, BLIND_NFFT, blind_capture, blind_oracle
 from test_welch_cyclic_cpu import check_detection
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED, INVALID = -3, -1
-FS = 2.5
 LAGS = (0, 1, 37, 64, 5000)      # L = 5: full groups and a partial one of the grouped build
 GROUPS = (1, 2)                  # the shipped builds of welchlag.hip
 
 
-@contextlib.contextmanager
 def forced_group(g):
     """plans created inside run the build of welchlag.hip with g lags per workgroup (None: the library's choice)"""
-    old = os.environ.get('OTH_LAG_GROUP')
-    if g is not None:
-        os.environ['OTH_LAG_GROUP'] = str(g)
-    try:
-        yield
-    finally:
-        if old is None:
-            os.environ.pop('OTH_LAG_GROUP', None)
-        else:
-            os.environ['OTH_LAG_GROUP'] = old
+    return forced_env('OTH_LAG_GROUP', g)
 
 
-def make_plan(ctx, hip, nfft, nperseg=None, noverlap=0, detrend=True, scaling='density', fftshift=False, trim=0, db=False,
-              lags=LAGS, group=None, **kw):
-    nperseg = nfft if nperseg is None else nperseg
+def make_plan(ctx, hip, nfft, *args, lags=LAGS, group=None, **kw):
     with forced_group(group):
-        plan = ctx.welch_plan(nfft, nperseg=nperseg, noverlap=noverlap, window=window('hann', nperseg),
-                              detrend=hip.DETREND_CONSTANT if detrend else hip.DETREND_NONE, scaling=SCALINGS[scaling], fs=FS,
-                              fftshift=fftshift, trim_bins=trim, db=db, **kw)
+        plan = welch_plan(ctx, hip, nfft, *args, **kw)
     if lags is not None:
         plan.set_lags(lags)
     return plan
-
-
-def recipe_field(recipe, name):
-    return int(recipe.split(' %s=' % name)[1].split()[0])
 
 
 def check_rows(caf, r, ref, fftshift=False, trim=0, db=False, one_segment=False, what=''):

@@ -1,16 +1,11 @@
 """CPU checks of the cyclic spectrum / cyclic coherence addition (no GPU): the float64 oracle by the definition
 (tests/welch_cyclic_oracle.py) on its identities and on a CP-OFDM signal, the Python helpers, the declared surface, and the
 resource figures of every welch_cyc_kernel build read from the code objects of the built library."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
 import welch_cyclic_oracle as CO
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from stat_support import POWERS, check_builds, check_surface
 
 SYMBOLS = ('oth_welch_set_cycles', 'oth_welch_cyclic_dev', 'oth_welch_cyclic')
 TU, TCP, NFFT, M = 64, 16, 256, 60
@@ -102,35 +97,11 @@ def test_cyclic_scan_refuses_in_python():
 
 
 def test_surface_is_declared_and_exported():
-    from ofdm_tools import _hip
-    header = open(os.path.join(ROOT, 'include', 'ofdm_tools_hip.h')).read()
-    for name in SYMBOLS:
-        assert 'int %s(' % name in header and name in _hip.SIGNATURES
-    for name in ('set_cycles', 'cyclic', 'cyclic_dev'):
-        assert hasattr(_hip.WelchPlan, name)
-    if not os.path.exists(_hip.LIB_PATH):
-        pytest.skip('library not built yet')
-    lib = _hip.load()
-    for name in SYMBOLS:
-        assert getattr(lib, name) is not None
+    check_surface(SYMBOLS, 'WelchPlan', ('set_cycles', 'cyclic', 'cyclic_dev'))
 
 
 def test_every_welch_cyc_kernel_build_has_no_scratch():
     """1 + 3 GA running sums per owned bin next to the butterflies (or the partial rows where they do not fit): read from the
     code objects inside the built library, three builds (GA = 1, 2, 4) per power of two 64 ... 16384, each with a private segment
     of 0 bytes and no spilled register; the 1024-thread builds inside their 128 registers."""
-    import kernel_resources
-    from ofdm_tools import _hip
-    if not os.path.exists(_hip.LIB_PATH):
-        pytest.skip('library not built yet')
-    ks = {n: v for n, v in kernel_resources.kernels(_hip.LIB_PATH).items() if 'welch_cyc_kernel<' in n}
-    builds = sorted(tuple(int(t) for t in n.split('welch_cyc_kernel<')[1].split(',')[:3:2]) for n in ks)
-    assert builds == [(n, ga) for n in (64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384) for ga in (1, 2, 4)], sorted(ks)
-    for n, v in sorted(ks.items()):
-        print('%s: vgpr %d agpr %d sgpr %d scratch %d' % (n[n.index('welch_cyc_kernel<'):].split('>')[0] + '>', v['vgpr'], v['agpr'], v['sgpr'], v['scratch']))
-    bad = {n: (v['scratch'], v['spill_vgpr'], v['spill_sgpr']) for n, v in ks.items()
-           if v['scratch'] or v['spill_vgpr'] or v['spill_sgpr']}
-    assert not bad, bad
-    for n, v in ks.items():
-        if ', 1024, ' in n.split('welch_cyc_kernel<')[1]:
-            assert v['vgpr'] + v['agpr'] <= 128, (n, v)
+    check_builds('welch_cyc_kernel', [(n, ga) for n in POWERS for ga in (1, 2, 4)], {1024: 128})

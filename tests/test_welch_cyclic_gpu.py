@@ -9,55 +9,34 @@ points, 1200 of 4096) 1.0e-5, 6.6e-6, 3.7e-7; 64 streams x 8 segments of 4096 an
 1.3e-5.  Rows of the A = 5 call against A = 1 calls: bit-identical on each of the three builds at every size tried.  cyclic_scan on the
 CP-OFDM case: profile 0.150 at +-1/80 against 0.015 / 0.018 off the cycle frequency and 0.016 ... 0.018 on noise alone
 (null 1 / M = 0.0167), the oracle's figures to four digits."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
 import median_oracle as MO
 import welch_cyclic_oracle as CO
+from stat_support import FS, forced_env, recipe_field, welch_plan
 from test_hip_parity import RTOL, ctx, hip  # noqa: F401 - ctx / hip are fixtures
-from test_median_gpu import SCALINGS, noise_tones, window
+from test_median_gpu import noise_tones
 from test_welch_cyclic_cpu import M as OFDM_M, NFFT as OFDM_NFFT, OFF, ON, check_detection, cp_ofdm
 from test_welch_sk_gpu import amp_for, tones_for
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED, INVALID = -3, -1
-FS = 2.5
 ALPHAS = (0.0, 0.0123456789, -0.37, 1.0 / 80.0, 0.5)      # A = 5: a full and a partial group of the grouped build
 
 
-@contextlib.contextmanager
 def forced_group(g):
     """plans created inside run the build of welchcyc.hip with g cycle frequencies per workgroup (None: the library's choice)"""
-    old = os.environ.get('OTH_CYC_GROUP')
-    if g is not None:
-        os.environ['OTH_CYC_GROUP'] = str(g)
-    try:
-        yield
-    finally:
-        if old is None:
-            os.environ.pop('OTH_CYC_GROUP', None)
-        else:
-            os.environ['OTH_CYC_GROUP'] = old
+    return forced_env('OTH_CYC_GROUP', g)
 
 
-def make_plan(ctx, hip, nfft, nperseg=None, noverlap=0, detrend=True, scaling='density', fftshift=False, trim=0, db=False,
-              alphas=ALPHAS, group=None, **kw):
-    nperseg = nfft if nperseg is None else nperseg
+def make_plan(ctx, hip, nfft, *args, alphas=ALPHAS, group=None, **kw):
     with forced_group(group):
-        plan = ctx.welch_plan(nfft, nperseg=nperseg, noverlap=noverlap, window=window('hann', nperseg),
-                              detrend=hip.DETREND_CONSTANT if detrend else hip.DETREND_NONE, scaling=SCALINGS[scaling], fs=FS,
-                              fftshift=fftshift, trim_bins=trim, db=db, **kw)
+        plan = welch_plan(ctx, hip, nfft, *args, **kw)
     if alphas is not None:
         plan.set_cycles(alphas)
     return plan
-
-
-def recipe_field(recipe, name):
-    return int(recipe.split(' %s=' % name)[1].split()[0])
 
 
 def check_rows(scf, coh, psd, ref, fftshift=False, trim=0, db=False, what=''):

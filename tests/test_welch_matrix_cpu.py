@@ -1,16 +1,11 @@
 """CPU checks of the spectral-matrix addition (no GPU): the float64 oracle by the definition (tests/welch_matrix_oracle.py)
 against SciPy, on two identities and on the detection case, the Python helper's refusals, the declared surface, and the
 resource figures of every welch_mat_kernel build and its finalize kernels read from the code objects of the built library."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
 import welch_matrix_oracle as XO
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from stat_support import POWERS, check_builds, check_surface
 
 SYMBOLS = ('oth_welch_matrix_dev', 'oth_welch_matrix')
 DET_C, DET_NFFT, DET_M = 4, 256, 32
@@ -173,18 +168,7 @@ def test_unpack_matrix_is_hermitian():
 # ---- 5. surface, 6. resources --------------------------------------------------------------------------------------------------
 
 def test_surface_is_declared_and_exported():
-    from ofdm_tools import _hip
-    header = open(os.path.join(ROOT, 'include', 'ofdm_tools_hip.h')).read()
-    for name in SYMBOLS:
-        assert 'int %s(' % name in header and name in _hip.SIGNATURES
-    assert 'float *s_out_dev, float *gcoh_out_dev, uint64_t *nseg_out);' in header
-    for name in ('matrix', 'matrix_dev'):
-        assert hasattr(_hip.WelchPlan, name)
-    if not os.path.exists(_hip.LIB_PATH):
-        pytest.skip('library not built yet')
-    lib = _hip.load()
-    for name in SYMBOLS:
-        assert getattr(lib, name) is not None
+    check_surface(SYMBOLS, 'WelchPlan', ('matrix', 'matrix_dev'), ['float *s_out_dev, float *gcoh_out_dev, uint64_t *nseg_out);'])
 
 
 def test_every_welch_mat_kernel_build_has_no_scratch():
@@ -192,24 +176,5 @@ def test_every_welch_mat_kernel_build_has_no_scratch():
     not fit: read from the code objects inside the built library, three builds (channel capacity 2, 4, 8) per power of two
     64 ... 16384 and the two finalize kernels, each with a private segment of 0 bytes and no spilled register; the
     1024-thread builds inside their 128 registers, the 512-thread builds inside 256."""
-    import kernel_resources
-    from ofdm_tools import _hip
-    if not os.path.exists(_hip.LIB_PATH):
-        pytest.skip('library not built yet')
-    every = kernel_resources.kernels(_hip.LIB_PATH)
-    ks = {n: v for n, v in every.items() if 'welch_mat_kernel<' in n}
-    fin = {n: v for n, v in every.items() if 'mat_finalize_kernel' in n or 'mat_det_kernel' in n}
-    builds = sorted(tuple(int(t) for t in n.split('welch_mat_kernel<')[1].split(',')[:3:2]) for n in ks)
-    assert builds == [(n, cc) for n in (64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384) for cc in (2, 4, 8)], sorted(ks)
-    assert len(fin) == 2, sorted(fin)
-    for n, v in sorted(ks.items()) + sorted(fin.items()):
-        name = n[n.index('welch_mat_kernel<'):].split('>')[0] + '>' if 'welch_mat_kernel<' in n else n.split('(')[0].split()[-1]
-        print('%s: vgpr %d agpr %d sgpr %d scratch %d lds %d' % (name, v['vgpr'], v['agpr'], v['sgpr'], v['scratch'], v.get('lds', 0)))
-    both = dict(ks)
-    both.update(fin)
-    bad = {n: (v['scratch'], v['spill_vgpr'], v['spill_sgpr']) for n, v in both.items()
-           if v['scratch'] or v['spill_vgpr'] or v['spill_sgpr']}
-    assert not bad, bad
-    for n, v in ks.items():
-        threads = int(n.split('welch_mat_kernel<')[1].split(',')[1])
-        assert v['vgpr'] + v['agpr'] <= {64: 512, 256: 512, 512: 256, 1024: 128}[threads], (n, v)
+    check_builds('welch_mat_kernel', [(n, cc) for n in POWERS for cc in (2, 4, 8)], {64: 512, 256: 512, 512: 256, 1024: 128},
+                 extra_kernels=('mat_finalize_kernel', 'mat_det_kernel'))

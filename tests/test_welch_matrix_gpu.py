@@ -13,24 +13,16 @@ import numpy as np
 import pytest
 
 import welch_matrix_oracle as XO
+from stat_support import FS, recipe_field, welch_plan as make_plan
 from test_hip_parity import RTOL, ctx, hip  # noqa: F401 - ctx / hip are fixtures
-from test_median_gpu import SCALINGS, window
 from test_welch_matrix_cpu import DET_C, DET_M, DET_NFFT, check_detection, detection_capture
 from test_welch_sk_gpu import amp_for, tones_for
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED, INVALID = -3, -1
-FS = 2.5
 SIZES = (64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384)
 CHANNELS = (2, 3, 4, 5, 8)      # capacity 2 full; 4 partial and full; 8 partial and full
-
-
-def make_plan(ctx, hip, nfft, nperseg=None, noverlap=0, detrend=True, scaling='density', fftshift=False, trim=0, db=False, **kw):
-    nperseg = nfft if nperseg is None else nperseg
-    return ctx.welch_plan(nfft, nperseg=nperseg, noverlap=noverlap, window=window('hann', nperseg),
-                          detrend=hip.DETREND_CONSTANT if detrend else hip.DETREND_NONE, scaling=SCALINGS[scaling], fs=FS,
-                          fftshift=fftshift, trim_bins=trim, db=db, **kw)
 
 
 def capture(nchan, n, seed, nfft, M, offset=0.0):
@@ -48,10 +40,6 @@ def capture(nchan, n, seed, nfft, M, offset=0.0):
         s = s + a * np.exp(2j * np.pi * f * t)
     x = x + s[None, :] * np.exp(2j * np.pi * rng.random(nchan))[:, None]
     return (x + offset).astype(np.complex64)
-
-
-def recipe_field(recipe, name):
-    return int(recipe.split(' %s=' % name)[1].split()[0])
 
 
 def check_matrix(S, gcoh, ref, fftshift=False, trim=0, what=''):

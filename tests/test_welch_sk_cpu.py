@@ -3,15 +3,14 @@ against the estimator's exact null moments, sk_limits (a Pearson type IV fit of 
 Monte Carlo of the null, the refusals that happen in Python, and the resource figures of every welch_sk_kernel build read
 from the code objects of the built library."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
 import welch_sk_oracle as SO
+from stat_support import POWERS, check_builds
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
 
 def test_oracle_on_noise_has_the_null_moments():
@@ -115,17 +114,4 @@ def test_every_welch_sk_kernel_build_has_no_scratch():
     """Two running sums per owned bin next to the butterflies: read from the code objects inside the built library, one
     build per power of two 64 ... 16384, each with a private segment of 0 bytes and no spilled register; the 1024-thread
     build at 16384 points inside its 128 registers."""
-    import kernel_resources
-    from ofdm_tools import _hip
-    if not os.path.exists(_hip.LIB_PATH):
-        pytest.skip('library not built yet')
-    ks = {n: v for n, v in kernel_resources.kernels(_hip.LIB_PATH).items() if 'welch_sk_kernel<' in n}
-    sizes = sorted(int(n.split('welch_sk_kernel<')[1].split(',')[0]) for n in ks)
-    assert sizes == [64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384], sorted(ks)
-    for n, v in sorted(ks.items()):
-        print('%s: vgpr %d agpr %d sgpr %d scratch %d' % (n[n.index('welch_sk_kernel<'):].split('>')[0] + '>', v['vgpr'], v['agpr'], v['sgpr'], v['scratch']))
-    bad = {n: (v['scratch'], v['spill_vgpr'], v['spill_sgpr']) for n, v in ks.items()
-           if v['scratch'] or v['spill_vgpr'] or v['spill_sgpr']}
-    assert not bad, bad
-    big = [v for n, v in ks.items() if 'welch_sk_kernel<16384' in n][0]
-    assert big['vgpr'] + big['agpr'] <= 128, big
+    check_builds('welch_sk_kernel', POWERS, {1024: 128})

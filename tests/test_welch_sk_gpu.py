@@ -15,13 +15,13 @@ import pytest
 import median_oracle as MO
 import welch_sk_oracle as SO
 from test_hip_parity import RTOL, ctx, hip  # noqa: F401 - ctx / hip are fixtures
-from test_median_gpu import SCALINGS, noise_tones, window
+from stat_support import FS, welch_plan as make_plan
+from test_median_gpu import noise_tones
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED, INVALID = -3, -1
 RTOL_R = 3e-4
-FS = 2.5
 
 
 def tones_for(nfft, amp=100.0):
@@ -41,13 +41,6 @@ def amp_for(M, bins):
     import math
     f = (math.factorial(M) / float(bins)) ** (1.0 / M) / M if M < 64 else 1.0
     return min(100.0, RTOL / 4.0 / 3e-6 * math.sqrt(M * f))
-
-
-def make_plan(ctx, hip, nfft, nperseg=None, noverlap=0, detrend=True, scaling='density', fftshift=False, trim=0, db=False, **kw):
-    nperseg = nfft if nperseg is None else nperseg
-    return ctx.welch_plan(nfft, nperseg=nperseg, noverlap=noverlap, window=window('hann', nperseg),
-                          detrend=hip.DETREND_CONSTANT if detrend else hip.DETREND_NONE, scaling=SCALINGS[scaling], fs=FS,
-                          fftshift=fftshift, trim_bins=trim, db=db, **kw)
 
 
 def check_rows(sk, psd, ref, ref_psd, fftshift=False, trim=0, db=False, what=''):

@@ -12,10 +12,12 @@ runs the same cases in a fresh child process per library (OFDM_TOOLS_HIP_LIB), o
 their paths, or by the labels given.  --twice runs OLD a second time first and leaves out, by name, every row that differs
 between its two runs.
 
-Cases: the six families (F-test, spectral kurtosis, jackknife, two-channel jackknife, adaptive, cyclic with 1, 3 and 5
-cycle frequencies), host and _dev forms, 64 / 4096 / 16384 points, 2 / 11 / 19 segments (11 and 19: the finalize slice
+Cases: the eight families (F-test, spectral kurtosis, jackknife, two-channel jackknife, adaptive, cyclic with 1, 3 and 5
+cycle frequencies, cyclic autocorrelation with 1 and 5 lags on both builds through OTH_LAG_GROUP, spectral matrix of 2, 3
+and 8 channels), host and _dev forms, 64 / 4096 / 16384 points, 2 / 11 / 19 segments (11 and 19: the finalize slice
 loop runs more than once, W not a multiple of 8), fftshift, trim 0 / 3 and dB on and off, 1 and 3 streams, each optional
-row present and NULL; the spectral kurtosis of silence and of a constant under detrend; the F-test of a pure tone.
+row present and NULL (the matrix takes channels, not streams, one capture per call, and one of its two rows at least); the
+spectral kurtosis of silence and of a constant under detrend; the F-test of a pure tone.
 
 --cases plain: the Welch / CSD / chain calls behind launch_finalize, launch_scale, launch_csd_scale and launch_chain_tail
 instead (PLAIN below: every row layout and every route of launch_finalize), each under all eight output stages, the Welch
@@ -32,12 +34,20 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES, SEGMENTS, K = (64, 4096, 16384), (2, 11, 19), 3
 OUT_STAGES = list(itertools.product((0, 1), (0, 3), (0, 1)))      # fftshift, trim, db
-# family -> (plan, entry point, rows in ABI order as multiples of out_len, index of the row every call needs)
+LAGS = [5, 0, 64, 1, 17]
+# family -> (plan, entry point, rows in ABI order as multiples of out_len (negative: that many floats), index of the row every
+# call needs (None: any one row will do))
 FAMILIES = {
     'ftest': ('mtm', 'oth_mtm_ftest', (1, 1, 1), 0), 'sk': ('welch', 'oth_welch_sk', (1, 1), 0),
     'jack': ('mtm', 'oth_mtm_jackknife', (1, 1), 0), 'csdjack': ('mtmcsd', 'oth_mtm_csd_jackknife', (1, 1, 1, 1), 1),
     'adapt': ('mtm', 'oth_mtm_adaptive', (1, 1), 0), 'cyc1': ('welch', 'oth_welch_cyclic', (2, 1, 1), 1),
     'cyc3': ('welch', 'oth_welch_cyclic', (6, 3, 1), 1), 'cyc5': ('welch', 'oth_welch_cyclic', (10, 5, 1), 1),
+    # cafLgG: L lags on the build OTH_LAG_GROUP=G, rows caf [L][out_len] and r [L] pairs
+    'caf1g1': ('welch', 'oth_welch_caf', (1, -2), 0), 'caf1g2': ('welch', 'oth_welch_caf', (1, -2), 0),
+    'caf5g1': ('welch', 'oth_welch_caf', (5, -10), 0), 'caf5g2': ('welch', 'oth_welch_caf', (5, -10), 0),
+    # matC: C channels, rows S (C (C + 1) / 2 complex rows) and gcoh
+    'mat2': ('welch', 'oth_welch_matrix', (6, 1), None), 'mat3': ('welch', 'oth_welch_matrix', (12, 1), None),
+    'mat8': ('welch', 'oth_welch_matrix', (72, 1), None),
 }
 
 
@@ -52,9 +62,16 @@ def make_plan(ctx, fam, n, stage, tapers):
     kind = FAMILIES[fam][0]
     kw = dict(fftshift=bool(stage[0]), trim_bins=stage[1], db=bool(stage[2]))
     if kind == 'welch':
-        p = ctx.welch_plan(n, noverlap=0, window=windows.get_window('hann', n), **kw)
+        if fam.startswith('caf'):
+            os.environ['OTH_LAG_GROUP'] = fam[-1]      # read when the plan is created
+        try:
+            p = ctx.welch_plan(n, noverlap=0, window=windows.get_window('hann', n), **kw)
+        finally:
+            os.environ.pop('OTH_LAG_GROUP', None)
         if fam.startswith('cyc'):
             p.set_cycles([0.25, -0.0625, 0.001, 0.5, -0.3][:int(fam[3:])])
+        if fam.startswith('caf'):
+            p.set_lags(LAGS[:int(fam[3])])
         return p
     p = (ctx.mtm_csd_plan if kind == 'mtmcsd' else ctx.mtm_plan)(n, tapers=tapers[n][0], **kw)
     p.set_ratios(np.clip(tapers[n][1], np.finfo(np.float64).tiny, 1.0))
@@ -62,28 +79,30 @@ def make_plan(ctx, fam, n, stage, tapers):
 
 
 def run(ctx, plan, fam, dev, x, y, ns, keep):
-    """One call, host form or (dev) device form on ns streams; keep: the optional rows wanted.  -> the rows' bytes (b'' for
-    a row left out) + the recipe"""
+    """One call, host form or (dev) device form on ns streams (the matrix: the ns channels of one capture); keep: the
+    optional rows wanted.  -> the rows' bytes (b'' for a row left out) + the recipe"""
     _, entry, units, need = FAMILIES[fam]
+    mat = fam.startswith('mat')
     nsamp = len(x) // ns
-    lens = [u * plan.out_len for u in units]
+    lens = [u * plan.out_len if u > 0 else -u for u in units]
     want = [r == need or r in keep for r in range(len(units))]
     nseg = C.c_uint64()
     if dev:
         src = [ctx.alloc(v.nbytes) for v in ((x, y) if y is not None else (x,))]
         for d, v in zip(src, (x, y)):
             ctx.h2d(d, v)
-        out = [ctx.alloc(4 * ns * n) if w else None for n, w in zip(lens, want)]
+        nrows = 1 if mat else ns
+        out = [ctx.alloc(4 * nrows * n) if w else None for n, w in zip(lens, want)]
         args = [C.c_void_p(d) for d in src] + [nsamp] + ([ns, nsamp] if y is None else []) + ([4] if fam == 'adapt' else [])
         args += [C.c_void_p(o) if o else None for o in out]
         ctx.check(getattr(ctx.lib, entry + '_dev')(plan.h, *args, C.byref(nseg)), entry + '_dev')
         ctx.sync()
-        rows = [ctx.d2h(o, (ns, n), np.float32).tobytes() if o else b'' for o, n in zip(out, lens)]
+        rows = [ctx.d2h(o, (nrows, n), np.float32).tobytes() if o else b'' for o, n in zip(out, lens)]
         for d in src + [o for o in out if o]:
             ctx.free(d)
     else:
         host = [np.full(n, np.nan, np.float32) if w else None for n, w in zip(lens, want)]
-        args = [v.ctypes.data_as(C.c_void_p) for v in ((x, y) if y is not None else (x,))] + [nsamp, 0] + ([4] if fam == 'adapt' else [])
+        args = [v.ctypes.data_as(C.c_void_p) for v in ((x, y) if y is not None else (x,))] + [nsamp] + [ns] * mat + [0] + ([4] if fam == 'adapt' else [])
         args += [h.ctypes.data_as(C.POINTER(C.c_float)) if h is not None else None for h in host]
         ctx.check(getattr(ctx.lib, entry)(plan.h, *args, C.byref(nseg)), entry)
         rows = [h.tobytes() if h is not None else b'' for h in host]
@@ -189,14 +208,25 @@ def stat_cases(ctx, record):
     tapers = {n: (np.ascontiguousarray(t, np.float32), r) for n, (t, r) in tapers.items()}
     for f, fam in enumerate(FAMILIES):
         two = FAMILIES[fam][0] == 'mtmcsd'
+        chans = int(fam[3:]) if fam.startswith('mat') else 0
         optional = [r for r in range(len(FAMILIES[fam][2])) if r != FAMILIES[fam][3]]
         for (i, n), (j, nseg) in itertools.product(enumerate(SIZES), enumerate(SEGMENTS)):
-            x3, y3 = noise(3 * n * nseg, 100 * i + j), noise(3 * n * nseg, 100 * i + j + 50)
+            # a stream holds nseg segments: the caf counts them on what the largest lag leaves
+            per = n * nseg + (max(LAGS[:int(fam[3])]) if fam.startswith('caf') else 0)
+            xs, y3 = noise(max(3, chans) * per, 100 * i + j), noise(3 * n * nseg, 100 * i + j + 50)
+            x3 = xs[:3 * per]
             for k in range(2):
                 stage = OUT_STAGES[(f + 3 * i + 2 * j + k) % 8]
                 plan = make_plan(ctx, fam, n, stage, tapers)
                 key = '%s/n%d/seg%d/shift%d-trim%d-db%d' % ((fam, n, nseg) + stage)
-                x1, y1 = x3[:n * nseg], (y3[:n * nseg] if two else None)
+                if chans:      # channels, not streams: one capture per call, and one of the two rows at least
+                    for form, dev in (('host', False), ('dev', True)):
+                        record('%s/%s/all' % (key, form), run(ctx, plan, fam, dev, xs[:chans * per], None, chans, optional))
+                        for r in optional:
+                            record('%s/%s/only%d' % (key, form, r), run(ctx, plan, fam, dev, xs[:chans * per], None, chans, (r,)))
+                    plan.close()
+                    continue
+                x1, y1 = x3[:per], (y3[:per] if two else None)
                 record(key + '/host/all', run(ctx, plan, fam, False, x1, y1, 1, optional))
                 record(key + '/host/none', run(ctx, plan, fam, False, x1, y1, 1, ()))
                 record(key + '/dev1/all', run(ctx, plan, fam, True, x1, y1, 1, optional))
