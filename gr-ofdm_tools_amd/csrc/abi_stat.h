@@ -1,4 +1,4 @@
-// What the host files of the per-bin statistics (abi_ftest, abi_sk, abi_jack, abi_adapt, abi_cyc, abi_lag, abi_mat; mtm_run for the work split
+// What the host files of the per-bin statistics (abi_ftest, abi_sk, abi_jack, abi_adapt, abi_cyc, abi_lag, abi_mat, abi_pfb; mtm_run for the work split
 // and the recipe) share: the size rule, the plan and stream-shape refusals, the kernel arguments a Welch statistic takes from
 // its plan, the work split over resident workgroups, the recipe text, the timed launch, the host and device forms around a
 // device run, and the replacement of a plan's tables.
@@ -24,7 +24,8 @@ inline int welch_stat_plan(oth_plan *p, const std::string &what, const char *seg
 }
 
 // The refusals of a statistic's stream shape in their common order - "bad argument" (args_ok: the caller's pointers), the
-// stride, the input's length (a segment reaches `reach` samples past its nperseg - the caf's largest lag -, and too_short is
+// stride, the input's length (a segment reaches `reach` samples past its nperseg - the caf's largest lag, the filter bank's
+// ntaps - 1 transform lengths -, and too_short is
 // the refusal's text where that is not 0), the stream limit (too_many: its text; nullptr where the caller has tested it in
 // front) - and the segment count.  A family's check calls it where that keeps the family's precedence.
 inline int stream_shape(oth_plan *p, bool args_ok, size_t nsamples, int nstreams, size_t stride, const char *too_many, long long *nseg,
@@ -39,9 +40,10 @@ inline int stream_shape(oth_plan *p, bool args_ok, size_t nsamples, int nstreams
 }
 constexpr const char *kMtmTooMany = "multitaper plans take at most 65535 streams per launch";
 
-// The fields the kernel arguments of the Welch statistics share (Args: WelchSkArgs, WelchCycArgs, WelchLagArgs), from the plan
+// The fields the kernel arguments of the Welch statistics share (Args: WelchSkArgs, WelchCycArgs, WelchLagArgs, WelchPfbArgs), from the plan
 // and the launch's shape, as mtm_args does for the taper loop; the rest of Args stays zero for the caller.  WelchMatArgs
-// names three of them after its channels (chan_stride, wg_count, nchan) and fills its own.
+// names three of them after its channels (chan_stride, wg_count, nchan) and fills its own; WelchPfbArgs.win is the prototype,
+// which its caller puts in the window's place.
 template <typename Args> Args welch_stat_args(const oth_plan *p, const float2 *x, long long nseg, int nstreams, size_t stride, int W) {
     Args a{};
     a.x = x;

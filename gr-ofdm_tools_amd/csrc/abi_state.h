@@ -161,6 +161,12 @@ struct oth_plan {
     DevBuf<double> d_lag_means;        // welchlag.hip's per-workgroup sums of the products' means (WelchLagArgs.means)
     int tune_lag_group = 0;            // OTH_LAG_GROUP, read when the plan is created: 1 or 2 forces that build of welchlag.hip
                                        // (A/B tools and the parity suite); 0 = the library's choice
+    // polyphase filter-bank PSD (oth_welch_set_prototype, oth_welch_pfb*: abi_pfb.hip / welchpfb.hip): Welch plans only
+    int pfb_taps = 0;                  // taps per branch P; 0 until oth_welch_set_prototype
+    DevBuf<float> d_pfb_h;             // [pfb_taps][nfft] the prototype h
+    DevBuf<float> d_pfb_fold;          // [nfft] hfold[n] = sum_p h[n + p nfft], formed in double
+    double pfb_sum = 0.0, pfb_sum2 = 0.0;      // sum h and sum h^2, in double
+    double pfb_scale = 1.0;            // the plan's scaling with h in the window's place; applies to the MEAN over frames
     // spectral matrix of C channels (oth_welch_matrix*: abi_mat.hip / welchmat.hip): Welch plans only
     DevBuf<float2> d_mat_ws;           // welchmat.hip's per-workgroup spectrum rows (WelchMatArgs.ws; the builds that keep them in memory)
     DevBuf<double> d_mat_totals;       // [nchan][nchan][nfft]: the summed rows between its two finalize launches

@@ -1,6 +1,6 @@
 // What the taper-loop kernels (mtm.hip: one channel, mtmcsd.hip: two, mtmftest.hip: the F-test, welchsk.hip: spectral
 // kurtosis with the plan's window as the one taper, mtmjack.hip: the jackknife's second pass, mtmadapt.hip: the adaptive
-// weighting) share: the fixed-order sums
+// weighting, welchpfb.hip: the filter bank's fold, which takes the pilot and the block sum) share: the fixed-order sums
 // behind a segment's pilot and residual mean, the segment entry built on them, the taper product, the rule for keeping a
 // segment's samples in registers, the list of sizes with its dispatch over (size, build), and the launchers' thread and LDS rules.
 #pragma once

@@ -571,6 +571,27 @@ int welch_lag_blocks_per_cu(int nfft, int gl);      // gl: 1 or kLagGroup
 hipError_t launch_welch_lag(int nfft, int gl, int groups, const WelchLagArgs &a, hipStream_t s);
 hipError_t launch_lag_finalize(const LagFinalizeArgs &a, int nstreams, hipStream_t s);
 
+// ---- welchpfb.hip: polyphase filter-bank (WOLA) PSD of a Welch plan - sum_s |FFT(y_s)|^2 of the folded frame
+// y_s[n] = sum_p h[n + p nfft] (x[s step + n + p nfft] - m_s); the finalize launch is launch_lag_finalize on one row -----------
+constexpr int kPfbTapsMin = 2, kPfbTapsMax = 16;      // taps per branch P
+struct WelchPfbArgs {
+    const float2 *x;        // device IQ, stream 0
+    const float *win;       // the prototype h, [ntaps][nfft] floats (the plan's window takes no part)
+    const float *hfold;     // [nfft] sum_p h[n + p nfft], formed in double
+    const float2 *tw;       // W_nfft^k, nfft entries
+    float *partial;         // [nstreams][wg_per_stream][nfft] sum |X|^2 of each workgroup's run, natural bin order
+    long long nseg;         // frames per stream, counted on nsamples - (ntaps - 1) nfft: no read of a frame leaves the stream
+    size_t stream_stride;   // samples between streams
+    int nperseg;            // = nfft
+    int step;
+    int detrend;            // != 0: each frame's own mean over its ntaps nfft samples comes off (pilot + residual)
+    int wg_per_stream;      // workgroups of a stream: each walks a contiguous run of the nseg frames
+    int nstreams;
+    int ntaps;              // P
+};
+int welch_pfb_blocks_per_cu(int nfft);
+hipError_t launch_welch_pfb(int nfft, const WelchPfbArgs &a, hipStream_t s);
+
 // ---- welchmat.hip: spectral matrix of C coherent channels on a Welch plan - sum_s conj(X_s,a) X_s,b for a <= b, then
 // S = scale T / M and the generalized coherence 1 - det G, G_ab = T_ab / sqrt(T_aa T_bb) ---------------------------------------
 constexpr int kMatChanMax = 8;      // channels at most; the kernels are built for a capacity of 2, 4 and 8

@@ -86,6 +86,9 @@ SIGNATURES = {
     'oth_welch_set_lags': (C.c_int, [_p, C.c_int, C.POINTER(C.c_int)]),
     'oth_welch_caf_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
     'oth_welch_caf': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
+    'oth_welch_set_prototype': (C.c_int, [_p, C.c_int, _f]),
+    'oth_welch_pfb_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _u64p]),
+    'oth_welch_pfb': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _u64p]),
     'oth_welch_matrix_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
     'oth_welch_matrix': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_int, _f, _f, _u64p]),
     'oth_mtm_jackknife_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
@@ -667,6 +670,47 @@ class WelchPlan(object):
         n = C.c_uint64()
         self.ctx.check(self.ctx.lib.oth_welch_caf_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
                                                       C.c_void_p(caf_dev), _optp(r_dev), C.byref(n)), 'oth_welch_caf_dev')
+        self.last_nseg = n.value
+        return n.value
+
+    ntaps = 0      # (class default: no prototype until set_prototype)
+
+    def set_prototype(self, h, ntaps=None):
+        """The prototype of pfb / pfb_dev (oth_welch_set_prototype): ntaps * nfft real taps, 2 <= ntaps <= 16 taps per
+        branch (ntaps from len(h) / nfft when it is left out; windows.pfb_prototype gives a Kaiser-windowed sinc).  Replaces
+        an earlier prototype; no other call of the plan is affected.  A multitaper plan, a median-averaging plan, a length
+        that is not a power of two 64 ... 16384 and a plan with nperseg != nfft raise HipError (OTH_ERR_UNSUPPORTED)."""
+        a = np.ascontiguousarray(np.asarray(h, np.float64).ravel(), np.float32)
+        if ntaps is None:
+            if len(a) == 0 or len(a) % self.nfft:
+                raise ValueError('the prototype holds ntaps * nfft taps: %d is no multiple of %d' % (len(a), self.nfft))
+            ntaps = len(a) // self.nfft
+        elif 1 <= int(ntaps) and len(a) != int(ntaps) * self.nfft:
+            raise ValueError('the prototype holds ntaps * nfft = %d taps, not %d' % (int(ntaps) * self.nfft, len(a)))
+        self.ctx.check(self.ctx.lib.oth_welch_set_prototype(self.h, int(ntaps), _fptr(a)), 'oth_welch_set_prototype')
+        self.ntaps = int(ntaps)
+
+    def pfb(self, x, nsamples=None):
+        """Polyphase filter-bank (WOLA) PSD (oth_welch_pfb) of one capture under the prototype of set_prototype: every
+        frame of ntaps * nfft samples, one every nfft - noverlap samples, is weighted by the prototype, folded onto nfft
+        points and transformed; the row is the mean of |X|^2 over the M = (n - ntaps nfft) / step + 1 frames - every
+        ntaps-th bin of a Welch PSD of ntaps * nfft points with the prototype as its window, so a bin has a flat top and a
+        stop band one bin away.  x: host complex64 array, or a device pointer when nsamples is given.
+        -> float32 [out_len] with the plan's scaling (the prototype in the window's place), fftshift, trim and dB.  Sets
+        last_nseg (M)."""
+        out = np.empty(self.out_len, np.float32)
+        n = C.c_uint64()
+        src, count, dev = _src(x, nsamples)
+        self.ctx.check(self.ctx.lib.oth_welch_pfb(self.h, src, count, dev, _fptr(out), C.byref(n)), 'oth_welch_pfb')
+        self.last_nseg = n.value
+        return out
+
+    def pfb_dev(self, iq_dev, nsamples, nstreams, stride, out_dev):
+        """Asynchronous: device in, device out - [nstreams][out_len] float32 at out_dev.  -> frames per stream (also
+        last_nseg)."""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_welch_pfb_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
+                                                      C.c_void_p(out_dev), C.byref(n)), 'oth_welch_pfb_dev')
         self.last_nseg = n.value
         return n.value
 

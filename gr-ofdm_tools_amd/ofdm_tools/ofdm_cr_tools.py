@@ -255,6 +255,48 @@ def mtm_power_estimate(vector, nFFT, Sf, NW=4.0, K=None, ctx=None):
     return float(np.sum(_mtm_plan(ctx, nFFT, Sf, len(vector), NW, K).exec(vector), dtype=np.float64))
 
 
+def _pfb_plan(ctx, nfft, ntaps, Sf, npts):
+    """The filter-bank estimate of one capture: windows.pfb_prototype(nfft, ntaps) folded onto nfft points, critically
+    sampled (hop nfft), constant detrend per frame, density scaling, fftshift.  Refuses in Python what the library would
+    refuse: a size outside the powers of two 64 ... 16384, ntaps outside 2 ... 16, a capture shorter than one frame."""
+    if not _is_int(nfft) or nfft < 64 or nfft > 16384 or nfft & (nfft - 1):
+        raise ValueError('the filter-bank PSD needs nFFT a power of two from 64 to 16384, not %r' % (nfft,))
+    if not _is_int(ntaps) or not 2 <= ntaps <= 16:
+        raise ValueError('the filter-bank PSD needs ntaps in 2 ... 16, not %r' % (ntaps,))
+    if npts < ntaps * nfft:
+        raise ValueError('the filter-bank PSD needs at least ntaps * nFFT = %d samples, not %d' % (ntaps * nfft, npts))
+    nfft, ntaps = int(nfft), int(ntaps)
+    ctx = ctx or _hip.default_context()
+
+    def make():
+        plan = ctx.welch_plan(nfft, nperseg=nfft, noverlap=0, window=None, fs=float(Sf), fftshift=True)
+        plan.set_prototype(windows.pfb_prototype(nfft, ntaps), ntaps)
+        return plan
+    return ctx.cached_plan(('pfb', nfft, ntaps, float(Sf)), make)
+
+
+def src_power_pfb(vector, npts, nFFT, Fr, Sf, bb_freqs, srch_bins, ntaps=8, ctx=None):
+    """src_power_welch with the polyphase filter-bank estimate (a Kaiser-windowed sinc of ntaps * nFFT taps folded in front
+    of the transform) in place of the flat-top Welch PSD: a strong neighbour does not leak into an empty channel's sum.
+    Blocking.  -> (psd, axis, channel sums)."""
+    plan = _pfb_plan(ctx, nFFT, ntaps, Sf, len(vector))
+    psd = plan.pfb(vector)
+    axis = np.fft.fftshift(np.fft.fftfreq(nFFT, 1.0 / Sf))
+    return psd, axis, _plain_channel_sums(psd, Fr, Sf, bb_freqs, srch_bins, plan.ctx)
+
+
+def pfb_plot_dB(data, Sf, fc, nfft, ntaps=8, ctx=None):
+    """welch_plot_dB with the polyphase filter-bank estimate (ntaps taps per branch)."""
+    psd = _pfb_plan(ctx, nfft, ntaps, Sf, len(data)).pfb(data)
+    axis = np.fft.fftshift(np.fft.fftfreq(nfft, 1.0 / Sf))
+    return [item + fc for item in axis], [10 * math.log10(item + 1e-20) for item in psd]
+
+
+def pfb_power_estimate(vector, nFFT, Sf, ntaps=8, ctx=None):
+    """welch_power_estimate with the polyphase filter-bank estimate: the sum over bins of the density."""
+    return float(np.sum(_pfb_plan(ctx, nFFT, ntaps, Sf, len(vector)).pfb(vector), dtype=np.float64))
+
+
 def _ftest_log_sf(f, a, b, logc):
     """log P(F > f) for F(2 a, 2 b), a and b integers: with x = a f / (a f + b) the survival function is the binomial sum
     sum_{i < a} C(a + b - 1, i) x^i (1 - x)^(a + b - 1 - i); logc[i] = log C(a + b - 1, i)."""

@@ -561,6 +561,66 @@ int oth_welch_matrix_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, in
 int oth_welch_matrix(oth_plan *plan, const void *iq, size_t nsamples, int nchan, int src_is_device,
                      float *s_out, float *gcoh_out, uint64_t *nseg_out);      /* iq: [nchan][nsamples], blocking */
 
+/* oth_welch_set_prototype, oth_welch_pfb_dev / oth_welch_pfb (additions inside ABI 6; probe by the symbols): the PSD of a
+ * polyphase filter bank (weighted overlap-add, WOLA) on a plan of oth_welch_plan with nperseg == nfft = N.  Every other PSD
+ * of the library uses a window no longer than the transform, and such a bin has a skirt: a strong neighbour leaks into an
+ * empty channel and sets the floor of a detector that sums bins over it.  Here a real prototype h of P N taps (P taps per
+ * branch, 2 <= P <= 16; ofdm_tools.windows.pfb_prototype gives a Kaiser-windowed sinc) is folded onto one transform length
+ * in front of the FFT: a bin has a flat top and a stop band that starts one bin away.  The hop is the plan's
+ * step = N - noverlap: noverlap = 0 is the critically sampled bank, N / 2 the 2x oversampled one, any value the plan accepts
+ * is allowed.  Per stream, frame s covers the P N samples from s step:
+ *   M       = (nsamples - P N) / step + 1                              integer division; nsamples >= P N
+ *   m_s     = (1 / (P N)) sum_{i < P N} x[s step + i]                  on a detrending plan, 0 otherwise
+ *   y_s[n]  = sum_{p < P} h[n + p N] (x[s step + n + p N] - m_s)       n < N
+ *   X_s     = FFT_N(y_s)
+ *   pfb[k]  = scale (1 / M) sum_s |X_s[k]|^2                           then the plan's fftshift, trim and dB
+ *   scale   = 1 / (fs sum h^2) (OTH_SCALE_DENSITY), 1 / (sum h)^2 (OTH_SCALE_SPECTRUM), 1 / N^2 (OTH_SCALE_OVER_N2), 1 otherwise
+ * The sums of h are formed in double when the prototype is set.  The plan's own window takes no part.  In real arithmetic the
+ * row equals every P-th bin of scipy.signal.welch(x, fs, window=h, nperseg=P N, noverlap=P N - step, nfft=P N,
+ * detrend='constant' | False, return_onesided=False, scaling=...) - a plan of P N points with h as its window runs P times
+ * the transforms at P times the length, and only while P N is a supported length; the fold runs one N-point transform per
+ * frame.  The mean comes off as in the multitaper kernels: a pilot (the mean of the frame's first 64 samples) comes off
+ * every sample as it is loaded, the residual mean of the frame then comes off by linearity,
+ * y[n] -= m hfold[n] with hfold[n] = sum_p h[n + p N] (formed in double), so a frame is read once.
+ * Output: pfb [nstreams][out_len] float32.  All-zero input gives a row of exact zeros; a constant input on a detrending plan
+ * gives exact zeros (-inf under dB).  A sample with a NaN or +-inf part inside a stream's frames: that stream's row reads NaN
+ * in every bin, linear or dB, never inf; other streams of the launch are untouched bit for bit.
+ * One averaging launch per call (csrc/welchpfb.hip: a workgroup takes whole frames of one stream in a contiguous run), then
+ * a small finalize launch that adds the workgroups' rows in double in a fixed order: bit-identical run to run.
+ * oth_welch_set_prototype: ntaps = P, h = ntaps * nfft host floats.  It replaces any earlier prototype, waits for the plan's
+ * queued work, and has no effect on any other call of the plan.
+ * _dev: device in, device out, asynchronous, nstreams as oth_welch_exec_dev (at most 65535).  oth_welch_pfb: one stream,
+ * host or device source, host output, blocking.
+ * Refused, the reason in oth_last_error(), before anything is staged, and the plan goes on working.  OTH_ERR_UNSUPPORTED:
+ *   a multitaper plan          "the filter-bank PSD is not available on a multitaper plan: its segments' transforms are
+ *                              Welch's (oth_welch_plan)"
+ *   OTH_AVERAGE_MEDIAN         "the filter-bank PSD is not available with OTH_AVERAGE_MEDIAN: its rows are means over segments
+ *                              (oth_plan_set_average(OTH_AVERAGE_MEAN) first)"
+ *   the transform length       "the filter-bank PSD takes a transform length that is a power of two from 64 to 16384, not <nfft>"
+ *   nperseg != nfft            "the filter-bank PSD folds whole transform lengths: it takes a plan with nperseg == nfft, not
+ *                              <nperseg> and <nfft>"
+ *   no prototype set           "the filter-bank PSD needs its prototype: call oth_welch_set_prototype on this plan"
+ *   more than 65535 streams    "the filter-bank PSD takes at most 65535 streams per launch"
+ * OTH_ERR_INVALID:
+ *   ntaps outside 2 ... 16     "ntaps must lie in 2 ... 16"
+ *   a NULL h                   "h is NULL"
+ *   a non-finite tap           "every tap of the prototype must be finite"
+ *   sum h^2 == 0               "the prototype is all zero"
+ *   sum h == 0, SPECTRUM       "OTH_SCALE_SPECTRUM needs a prototype with a non-zero sum"
+ *   a NULL input or output, nstreams < 1     "bad argument"
+ *   stream_stride < nsamples   "stream_stride < nsamples"
+ *   nsamples < P N             "input shorter than ntaps * nfft (<P> * <nfft> samples)"
+ * in this order: the plan's kind (both setter and run), then the setter's arguments, or the missing prototype and the run's
+ * arguments with the stream limit last.
+ * Not provided: complex prototypes, the channeliser's time-domain outputs, the circular-shift form that keeps phase
+ * continuity between hops (power does not need it), a sliding window that carries P - 1 blocks across frames (consecutive
+ * frames re-read their shared samples from L2), time-sharded partial sums, multitaper plans, the median average,
+ * any-length transforms, a ticketed asynchronous form. */
+int oth_welch_set_prototype(oth_plan *plan, int ntaps, const float *h);
+int oth_welch_pfb_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride,
+                      float *pfb_out_dev, uint64_t *nseg_out);
+int oth_welch_pfb(oth_plan *plan, const void *iq, size_t nsamples, int src_is_device, float *pfb_out, uint64_t *nseg_out);
+
 /* Degenerate inputs of the one-channel average - oth_welch_exec, _exec_async, _exec_dev, _scale_dev and _finalize, plans
  * of oth_welch_plan and oth_mtm_plan, every kernel route and detrend mode (tests/test_degenerate_gpu.py): the rule is the
  * two-channel path's, and SciPy's result is the specification.  A sample with a NaN or +-inf part makes every bin of that
