@@ -3,21 +3,11 @@
 // finalize launches into the packed matrix rows and the gcoh row.
 #include "abi_stat.h"
 
-namespace {
-// Every refusal of the two entry points, in the header's order, before anything is allocated, staged or launched.
-int mat_check(oth_plan *p, const void *x, size_t nsamples, int nchan, size_t stride, const float *s_out, const float *gcoh_out,
-              long long *nseg_out) {
-    oth_ctx *c = p->ctx;
-    if (int rc = welch_stat_plan(p, "the spectral matrix")) return rc;
-    if (nchan < 2 || nchan > kMatChanMax) return fail(c, OTH_ERR_INVALID, "nchan must lie in 2 ... " + std::to_string(kMatChanMax));
-    if (!x) return fail(c, OTH_ERR_INVALID, "the input is NULL");
-    if (!s_out && !gcoh_out) return fail(c, OTH_ERR_INVALID, "s_out and gcoh_out are both NULL");
-    if (stride < nsamples) return fail(c, OTH_ERR_INVALID, "chan_stride < nsamples");
-    return stream_shape(p, true, nsamples, nchan, stride, nullptr, nseg_out);
-}
-
-// after mat_check: device in, device out
-int mat_run(oth_plan *p, const float2 *x, long long nseg, int nchan, size_t stride, float *s_out, float *gcoh_out) {
+namespace oth {
+// The averaging launch of the matrix family after its check (oth_welch_matrix*, oth_welch_matrix_eig*): the workspaces, the
+// segment-per-workgroup launch of welchmat.hip at the channel capacity that takes nchan, the arguments of the finalize
+// launches (rows left NULL for the caller) and the recipe text.
+int welch_mat_sums(oth_plan *p, const float2 *x, long long nseg, int nchan, size_t stride, MatFinalizeArgs &f, std::string &recipe) {
     oth_ctx *c = p->ctx;
     if (use_device(c)) return OTH_ERR_HIP;
     const int N = p->nfft, C = nchan, cc = welch_mat_capacity(C);
@@ -42,20 +32,44 @@ int mat_run(oth_plan *p, const float2 *x, long long nseg, int nchan, size_t stri
     a.detrend = p->detrend != OTH_DETREND_NONE;
     a.wg_count = W;
     a.nchan = C;
-    MatFinalizeArgs f{};
+    f = MatFinalizeArgs{};
     f.partial = p->d_partial.get();
     f.totals = p->d_mat_totals.get();
-    f.s_out = s_out;
-    f.gcoh_out = gcoh_out;
     f.s_scale = p->scale / (double)nseg;
     f.W = W;
     f.nchan = C;
     f.nfft = N;
     f.out = out_stage(p);
     TIMED_LAUNCH(c, launch_welch_mat(N, cc, a, c->stream));
+    recipe = stat_recipe("welchmat", p, "", W, nseg, 1,
+                         " nchan=" + std::to_string(C) + " cap=" + std::to_string(cc) + (pts ? " state=rows" : " state=regs"), bpc);
+    return OTH_OK;
+}
+}  // namespace oth
+
+namespace {
+// Every refusal of the two entry points, in the header's order, before anything is allocated, staged or launched.
+int mat_check(oth_plan *p, const void *x, size_t nsamples, int nchan, size_t stride, const float *s_out, const float *gcoh_out,
+              long long *nseg_out) {
+    oth_ctx *c = p->ctx;
+    if (int rc = welch_stat_plan(p, "the spectral matrix")) return rc;
+    if (nchan < 2 || nchan > kMatChanMax) return fail(c, OTH_ERR_INVALID, "nchan must lie in 2 ... " + std::to_string(kMatChanMax));
+    if (!x) return fail(c, OTH_ERR_INVALID, "the input is NULL");
+    if (!s_out && !gcoh_out) return fail(c, OTH_ERR_INVALID, "s_out and gcoh_out are both NULL");
+    if (stride < nsamples) return fail(c, OTH_ERR_INVALID, "chan_stride < nsamples");
+    return stream_shape(p, true, nsamples, nchan, stride, nullptr, nseg_out);
+}
+
+// after mat_check: device in, device out
+int mat_run(oth_plan *p, const float2 *x, long long nseg, int nchan, size_t stride, float *s_out, float *gcoh_out) {
+    oth_ctx *c = p->ctx;
+    MatFinalizeArgs f{};
+    std::string recipe;
+    if (int rc = welch_mat_sums(p, x, nseg, nchan, stride, f, recipe)) return rc;
+    f.s_out = s_out;
+    f.gcoh_out = gcoh_out;
     TIMED_LAUNCH(c, launch_mat_finalize(f, c->stream));
-    p->last_recipe = stat_recipe("welchmat", p, "", W, nseg, 1,
-                                 " nchan=" + std::to_string(C) + " cap=" + std::to_string(cc) + (pts ? " state=rows" : " state=regs"), bpc);
+    p->last_recipe = recipe;
     return OTH_OK;
 }
 }  // namespace

@@ -622,6 +622,20 @@ int welch_mat_capacity(int nchan);                   // the build that takes nch
 size_t welch_mat_ws_points(int nfft, int cc);        // 0: the build keeps the spectra in registers
 int welch_mat_blocks_per_cu(int nfft, int cc);
 hipError_t launch_welch_mat(int nfft, int cc, const WelchMatArgs &a, hipStream_t s);
+hipError_t launch_mat_totals(const MatFinalizeArgs &a, hipStream_t s);        // the first of the two: the workgroups' rows into a.totals
 hipError_t launch_mat_finalize(const MatFinalizeArgs &a, hipStream_t s);      // two launches: the totals, then S and gcoh
+
+// ---- mateig.hip: eigenvalues and the principal eigenvector of the spectral matrix S or of the coherence matrix G per bin,
+// from the totals row of launch_mat_totals, by a cyclic Hermitian Jacobi in double ------------------------------------------------
+struct MatEigArgs {
+    const double *totals;   // [nchan][nchan][nfft] as MatFinalizeArgs.totals
+    float *eig_out;         // [nchan][nout], row k the k-th largest eigenvalue; or nullptr
+    float *vec_out;         // [nchan][nout] re, im interleaved: the eigenvector of the largest eigenvalue; or nullptr
+    double s_scale;         // scale / M (of S)
+    int of;                 // 0: S, 1: G
+    int nchan, nfft;
+    OutStage out;           // fftshift and trim; the rows are always linear
+};
+hipError_t launch_mat_eig(int cc, const MatEigArgs &a, hipStream_t s);        // cc: welch_mat_capacity(a.nchan)
 
 }  // namespace oth

@@ -33,7 +33,7 @@
 // exactly 0 on identical channels and exactly negated when the two channels change places.
 //
 // Not here: partial sums for time-sharded runs, multitaper plans, transform lengths that are not a power of two, more than 8
-// channels, eigenvalues.
+// channels.  The eigenvalues of S and G are mateig.hip's, from the totals row of launch_mat_totals.
 #include "mtm_common.hip.h"
 #include "out_stage.hip.h"
 #include "launch.h"
@@ -277,9 +277,13 @@ hipError_t launch_welch_mat(int nfft, int cc, const WelchMatArgs &a, hipStream_t
     });
 }
 
-hipError_t launch_mat_finalize(const MatFinalizeArgs &a, hipStream_t s) {
+hipError_t launch_mat_totals(const MatFinalizeArgs &a, hipStream_t s) {
     if (a.nchan < 2 || a.nchan > kMatChanMax) return hipErrorInvalidValue;
-    const hipError_t e = launch_stat_finalize<mat_finalize_kernel>(a, 1, a.nchan * a.nchan, s);
+    return launch_stat_finalize<mat_finalize_kernel>(a, 1, a.nchan * a.nchan, s);
+}
+
+hipError_t launch_mat_finalize(const MatFinalizeArgs &a, hipStream_t s) {
+    const hipError_t e = launch_mat_totals(a, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(mat_det_kernel, dim3((a.nfft + kMatDetThreads - 1) / kMatDetThreads), dim3(kMatDetThreads), 0, s, a);
     return hipGetLastError();

@@ -18,6 +18,7 @@ KERNEL_AUTO, KERNEL_GENERIC, KERNEL_TUNED = 0, 1, 2
 SCHED_CONTIGUOUS, SCHED_INTERLEAVED, SCHED_DYNAMIC = 0, 1, 2
 HOSTWAIT_POLL, HOSTWAIT_SYNC = 0, 1
 AVERAGE_MEAN, AVERAGE_MEDIAN = 0, 1      # oth_plan_set_average: scipy.signal.welch average='mean' / 'median'
+EIG_OF_S, EIG_OF_G = 0, 1      # oth_welch_matrix_eig: the spectral matrix S, the coherence matrix G
 OUT_RING = 4      # oth_plan::kOutRing: launch (ticket) t of a plan delivers into output slot t % OUT_RING
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -91,6 +92,8 @@ SIGNATURES = {
     'oth_welch_pfb': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _u64p]),
     'oth_welch_matrix_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
     'oth_welch_matrix': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_int, _f, _f, _u64p]),
+    'oth_welch_matrix_eig_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, C.c_int, _p, _p, _u64p]),
+    'oth_welch_matrix_eig': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, _f, _f, _u64p]),
     'oth_mtm_jackknife_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
     'oth_mtm_jackknife': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
     'oth_mtm_csd_jackknife_dev': (C.c_int, [_p, _p, _p, C.c_size_t, _p, _p, _p, _p, _u64p]),
@@ -220,6 +223,11 @@ def _src2(x, y, nsamples):
 def _optp(v):
     """a device pointer, or NULL for a row the caller leaves out"""
     return C.c_void_p(v) if v else None
+
+
+def _eig_of(of):
+    """'S' / 'G' -> EIG_OF_S / EIG_OF_G; an integer passes as it is (the library refuses what it does not know)"""
+    return {'S': EIG_OF_S, 'G': EIG_OF_G}[of] if isinstance(of, str) else int(of)
 
 
 def unpack_matrix(packed, nchan):
@@ -752,6 +760,47 @@ class WelchPlan(object):
         n = C.c_uint64()
         self.ctx.check(self.ctx.lib.oth_welch_matrix_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nchan), int(stride),
                                                          _optp(s_dev), _optp(gcoh_dev), C.byref(n)), 'oth_welch_matrix_dev')
+        self.last_nseg = n.value
+        return n.value
+
+    def matrix_eig(self, x, of='S', return_vector=True, nsamples=None):
+        """Eigenvalues and principal eigenvector per bin (oth_welch_matrix_eig) of the spectral matrix S of matrix()
+        (of='S' or EIG_OF_S) or of its coherence matrix G_ab = S_ab / sqrt(S_aa S_bb) (of='G' or EIG_OF_G: unit diagonal,
+        unchanged by a gain per channel).  x as in matrix(): host complex64 array (C, n), or a device pointer to
+        [C][nsamples] when nsamples is given as (C, nsamples).  -> (eig float32 [C, out_len], row k the k-th largest
+        eigenvalue, always linear, with the plan's fftshift and trim, vec complex64 [C, out_len], the unit eigenvector of
+        the largest eigenvalue with component 0 real and >= 0), or eig alone with return_vector=False.  A bin with a silent
+        channel reads an exact 0 eigenvalue of S and all ones of G; a non-finite sample reads NaN everywhere.  Sets
+        last_nseg (M); with M < C the trailing C - M eigenvalues read 0 up to rounding."""
+        if nsamples is None:
+            x = np.asarray(x)
+            if x.ndim != 2:
+                raise ValueError('x must be a (C, n) array of C channels')
+            x = np.ascontiguousarray(x, np.complex64)
+            nchan, count, src, dev = x.shape[0], x.shape[1], x.ctypes.data_as(_p), 0
+        else:
+            nchan, count = (int(v) for v in nsamples)
+            src, dev = C.c_void_p(x), 1
+        if not 2 <= nchan <= 8:
+            raise ValueError('the spectral matrix takes 2 ... 8 channels, not %d' % nchan)
+        m = self.out_len
+        eig = np.empty((nchan, m), np.float32)
+        vec = np.empty((nchan, m), np.complex64) if return_vector else None
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_welch_matrix_eig(self.h, src, count, nchan, dev, _eig_of(of), _fptr(eig),
+                                                         vec.ctypes.data_as(_f) if return_vector else None, C.byref(n)),
+                       'oth_welch_matrix_eig')
+        self.last_nseg = n.value
+        return (eig, vec) if return_vector else eig
+
+    def matrix_eig_dev(self, iq_dev, nsamples, nchan, stride, of, eig_dev=None, vec_dev=None):
+        """Asynchronous: device in, device out - [C][out_len] float32 at eig_dev (the rows descend) and [C][out_len] re, im
+        pairs at vec_dev; either may be left out, not both.  of: 'S' / 'G' or EIG_OF_S / EIG_OF_G.  stride: samples between
+        channels.  -> segments per channel (also last_nseg)."""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_welch_matrix_eig_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nchan), int(stride),
+                                                             _eig_of(of), _optp(eig_dev), _optp(vec_dev), C.byref(n)),
+                       'oth_welch_matrix_eig_dev')
         self.last_nseg = n.value
         return n.value
 

@@ -757,6 +757,72 @@ def multiantenna_scan(vectors, nFFT, Sf, fc=0.0, ctx=None):
     return axis, psd, gcoh, multiantenna_null_mean(x.shape[0], M)
 
 
+def eigenvalue_stats(eig, M):
+    """The blind multi-antenna detection statistics of the eigenvalues of a spectral (or coherence) matrix of C channels
+    averaged over M segments, in float64.  eig: [C, m], the rows descending (WelchPlan.matrix_eig).  -> dict of rows [m]:
+    'mme'   l_1 / l_C, the maximum-minimum eigenvalue ratio; inf where l_C == 0 < l_1, NaN where l_1 is 0 or NaN.
+    'agm'   the arithmetic over the geometric mean of all C eigenvalues (the sphericity test); inf where the geometric mean
+            is 0 (an eigenvalue is 0), NaN where an eigenvalue is NaN.
+    'nsrc'  int: the Wax-Kailath MDL source count, the k in 0 ... C - 1 that minimises
+            MDL(k) = -M (C - k) ln(g_k / a_k) + k (2 C - k) ln(M) / 2, a_k and g_k the arithmetic and the geometric mean of
+            l_{k+1} ... l_C (the lowest k on ties); -1 where M < C or an eigenvalue is <= 0 or not finite."""
+    l = np.asarray(eig, np.float64)
+    if l.ndim != 2:
+        raise ValueError('eigenvalue_stats takes the eigenvalue rows [C, m]')
+    C, m = l.shape
+    M = int(M)
+    with np.errstate(all='ignore'):
+        top, low = l[0], l[C - 1]
+        mme = np.where(top > 0, np.where(low == 0, np.inf, top / low), np.nan)
+        mme = np.where(np.isnan(l).any(axis=0), np.nan, mme)
+        am = l.mean(axis=0)
+        gm = np.exp(np.log(l).mean(axis=0))
+        gm = np.where((l == 0).any(axis=0), 0.0, gm)
+        agm = np.where(gm == 0, np.inf, am / gm)
+        agm = np.where(np.isnan(l).any(axis=0), np.nan, agm)
+        usable = np.all(np.isfinite(l) & (l > 0), axis=0) & (M >= C)
+        nsrc = np.full(m, -1, np.int64)
+        if usable.any():
+            lu = l[:, usable]
+            mdl = np.empty((C, lu.shape[1]))
+            for k in range(C):
+                tail = lu[k:]
+                a_k, lng_k = tail.mean(axis=0), np.log(tail).mean(axis=0)
+                mdl[k] = -M * (C - k) * (lng_k - np.log(a_k)) + 0.5 * k * (2 * C - k) * np.log(M)
+            nsrc[usable] = np.argmin(mdl, axis=0)
+    return {'mme': mme, 'agm': agm, 'nsrc': nsrc}
+
+
+def eigen_scan(vectors, nFFT, Sf, fc=0.0, of='S', ctx=None):
+    """Eigenvalues and the principal eigenvector per bin of the spectral matrix (of='S') or of the coherence matrix (of='G')
+    of C coherent channels, 2 <= C <= 8, on the plan multiantenna_scan makes (WelchPlan.matrix_eig; Hann window,
+    nperseg = nFFT, no overlap, density scaling), and the detection statistics that follow from the eigenvalues.
+    vectors: (C, n) complex array.
+    -> (frequency axis [Hz] fftshifted, eig [C, nFFT] float32 descending rows, fftshifted, vec [C, nFFT] complex64: the unit
+    eigenvector of the largest eigenvalue, the array response of the strongest emitter in the bin, stats: eigenvalue_stats(eig,
+    M) with M = n // nFFT).  Needs nFFT a power of two from 64 to 16384, 2 ... 8 channels and at least one segment (ValueError
+    otherwise, before anything runs)."""
+    if nFFT not in SK_SIZES:
+        raise ValueError('eigen_scan needs nFFT a power of two from 64 to 16384, not %r' % (nFFT,))
+    if not Sf > 0:
+        raise ValueError('eigen_scan needs a sample rate Sf > 0')
+    x = np.asarray(vectors)
+    if x.ndim != 2 or not 2 <= x.shape[0] <= 8:
+        raise ValueError('eigen_scan needs a (C, n) array of 2 ... 8 channels, not shape %r' % (x.shape,))
+    M = x.shape[1] // int(nFFT)
+    if M < 1:
+        raise ValueError('eigen_scan needs at least nFFT = %d samples per channel' % nFFT)
+    ctx = ctx or _hip.default_context()
+    key = ('matrix', nFFT, float(Sf))      # multiantenna_scan's plan
+
+    def make():
+        return ctx.welch_plan(nFFT, nperseg=nFFT, noverlap=0, window=windows.get_window('hann', nFFT), fs=float(Sf), fftshift=True)
+
+    eig, vec = ctx.cached_plan(key, make).matrix_eig(x, of=of)
+    axis = np.fft.fftshift(np.fft.fftfreq(nFFT, 1.0 / Sf)) + fc
+    return axis, eig, vec, eigenvalue_stats(eig, M)
+
+
 def ofdm_blind_hypotheses(fft_lens, cp_fractions, nFFT):
     """The (Tu, cp = Tu // f, bin) triples ofdm_blind_parameters tests, bin = round(nFFT / (Tu + cp)): where the symbol
     rate of the hypothesis falls in a caf row of nFFT points.  ValueError when two of them fall on the same bin or one on a

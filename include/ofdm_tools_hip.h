@@ -554,12 +554,50 @@ int oth_welch_caf(oth_plan *plan, const void *iq, size_t nsamples, int src_is_de
  * multitaper plan, a plan set to OTH_AVERAGE_MEDIAN, a transform length that is not a power of two from 64 to 16384;
  * OTH_ERR_INVALID for nchan outside 2 ... 8, a NULL input, both outputs NULL, chan_stride < nsamples, input shorter than
  * nperseg.
- * Not provided: partial sums for time-sharded multi-GPU runs, multitaper plans, any-length transforms, more than 8 channels,
- * eigenvalues. */
+ * Not provided: partial sums for time-sharded multi-GPU runs, multitaper plans, any-length transforms, more than 8 channels.
+ * (Eigenvalues: oth_welch_matrix_eig below.) */
 int oth_welch_matrix_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nchan, size_t chan_stride,
                          float *s_out_dev, float *gcoh_out_dev, uint64_t *nseg_out);
 int oth_welch_matrix(oth_plan *plan, const void *iq, size_t nsamples, int nchan, int src_is_device,
                      float *s_out, float *gcoh_out, uint64_t *nseg_out);      /* iq: [nchan][nsamples], blocking */
+
+/* oth_welch_matrix_eig_dev / oth_welch_matrix_eig (additions inside ABI 6; probe by the symbols): per bin, the eigenvalues
+ * and the principal eigenvector of the spectral matrix S of oth_welch_matrix (of = OTH_EIG_OF_S) or of its coherence matrix G
+ * (of = OTH_EIG_OF_G: unit diagonal, unchanged by a complex gain per channel).  The blind multi-antenna detectors are
+ * functions of these eigenvalues - the largest over the smallest (MME), the arithmetic over the geometric mean (sphericity),
+ * the MDL / AIC source count -, and the eigenvector of the largest one is the array response of the strongest emitter in the
+ * bin.  Same plan, segmentation, window, detrend, scaling, M, fftshift and trim as oth_welch_matrix, and the same sums T;
+ * always linear: a plan set to dB gives its linear twin's rows bit for bit.
+ * Outputs: eig_out [C][out_len] float32, row k the k-th largest eigenvalue of the bin (the rows descend); a value below 0
+ * from rounding reads 0.  vec_out [C][out_len] interleaved re, im: row a is component a of the eigenvector of the largest
+ * eigenvalue, of unit 2-norm, rotated so that component 0 is real and >= 0 with its imaginary part stored as exactly 0 (a
+ * vector whose component 0 is exactly 0 is left as computed); among equal largest eigenvalues it belongs to the lowest
+ * Jacobi column index.  Either pointer may be NULL, not both; the eigenvalue rows are the same bits with and without vec_out.
+ * Degenerate input (the matrix family's rules): finite input never gives NaN or inf.  A channel whose T_aa is not finite (a
+ * NaN or +-inf sample) makes every eig and vec entry NaN in every bin, never inf.  OTH_EIG_OF_S, a channel with T_aa <= 0 in
+ * a bin (silence, a constant under detrend): its row and column of S are 0, as s_out reads, the decomposition is of that
+ * matrix and one eigenvalue reads exactly 0; all channels silent: every eigenvalue is 0 and vec = e_0.  OTH_EIG_OF_G, any
+ * silent channel: G is taken as the identity, which is what gcoh = 0 says - every eigenvalue reads 1 and vec = e_0.  M = 1
+ * and M < C are not refused: the matrix is singular and the trailing eigenvalues read 0 up to rounding.
+ * Three launches per call: the averaging launch and the totals launch of oth_welch_matrix, then one thread per bin
+ * (csrc/mateig.hip): the matrix in double from the totals, a cyclic Hermitian Jacobi (row-cyclic, Rutishauser's rotation, a
+ * rotation with |a_pq| exactly 0 skipped, sweeps until the off-diagonal norm squared is at most 2^-104 of the diagonal's, a
+ * fixed cap on sweeps), the diagonal sorted, clamped at 0 and cast to float.  The result is a function of the double totals
+ * only.  Bit-identical run to run.
+ * _dev: device in, device out, asynchronous.  oth_welch_matrix_eig: iq is [nchan][nsamples] contiguous, host or device
+ * source, host outputs, blocking.
+ * Refused, the reason in oth_last_error(), before anything is allocated, staged or launched, and the plan goes on working, in
+ * this order: OTH_ERR_UNSUPPORTED on a multitaper plan, a plan set to OTH_AVERAGE_MEDIAN, a transform length that is not a
+ * power of two from 64 to 16384; OTH_ERR_INVALID for nchan outside 2 ... 8, of not OTH_EIG_OF_S or OTH_EIG_OF_G, a NULL input,
+ * both outputs NULL, chan_stride < nsamples, input shorter than nperseg.
+ * Not provided: all C eigenvectors, multitaper plans, any-length transforms, more than 8 channels, partial sums for
+ * time-sharded runs, MUSIC / Capon spectra. */
+#define OTH_EIG_OF_S 0   /* the spectral matrix S = scale T / M        */
+#define OTH_EIG_OF_G 1   /* the coherence matrix G_ab = T_ab / sqrt(T_aa T_bb): unit diagonal, gain-invariant */
+int oth_welch_matrix_eig_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nchan, size_t chan_stride,
+                             int of, float *eig_out_dev, float *vec_out_dev, uint64_t *nseg_out);
+int oth_welch_matrix_eig(oth_plan *plan, const void *iq, size_t nsamples, int nchan, int src_is_device,
+                         int of, float *eig_out, float *vec_out, uint64_t *nseg_out);   /* iq: [nchan][nsamples], blocking */
 
 /* oth_welch_set_prototype, oth_welch_pfb_dev / oth_welch_pfb (additions inside ABI 6; probe by the symbols): the PSD of a
  * polyphase filter bank (weighted overlap-add, WOLA) on a plan of oth_welch_plan with nperseg == nfft = N.  Every other PSD
