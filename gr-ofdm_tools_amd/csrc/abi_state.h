@@ -170,6 +170,10 @@ struct oth_plan {
     // spectral matrix of C channels (oth_welch_matrix*: abi_mat.hip / welchmat.hip): Welch plans only
     DevBuf<float2> d_mat_ws;           // welchmat.hip's per-workgroup spectrum rows (WelchMatArgs.ws; the builds that keep them in memory)
     DevBuf<double> d_mat_totals;       // [nchan][nchan][nfft]: the summed rows between its two finalize launches
+    // direction spectra (oth_welch_set_steering, oth_welch_matrix_doa*: abi_doa.hip / matdoa.hip): Welch plans only
+    int doa_ndir = 0, doa_nchan = 0;   // 0 until oth_welch_set_steering
+    DevBuf<double> d_doa_steer;        // [2][doa_ndir][doa_nchan]: the delays tau in samples, then frac(fc tau) reduced on the host
+    DevBuf<double> d_doa_basis;        // mateig.hip's basis build: [mat_eig_basis_entries(cc)][nfft] eigenvalues and vectors
 };
 
 struct oth_chain {

@@ -637,5 +637,28 @@ struct MatEigArgs {
     OutStage out;           // fftshift and trim; the rows are always linear
 };
 hipError_t launch_mat_eig(int cc, const MatEigArgs &a, hipStream_t s);        // cc: welch_mat_capacity(a.nchan)
+// the basis build: the ranked eigenvalues (clamped at 0) and the whole ranked V in double to basis
+// [mat_eig_basis_entries(cc)][nfft] - entry i < cc the i-th largest eigenvalue, entry cc + 2 (i cc + c) and the one behind it
+// re and im of component c of its vector; a.eig_out and a.vec_out are not read
+constexpr int mat_basis_at(int cc, int i, int c) { return cc + 2 * (i * cc + c); }      // re of component c of vector i
+size_t mat_eig_basis_entries(int cc);
+hipError_t launch_mat_eig_basis(int cc, const MatEigArgs &a, double *basis, hipStream_t s);
+
+// ---- matdoa.hip: Bartlett, Capon and MUSIC direction spectra per bin and direction from the basis of launch_mat_eig_basis
+// and a steering table of delays ----------------------------------------------------------------------------------------------
+constexpr int kDoaDirsMax = 1024;      // OTH_DOA_DIRS_MAX
+struct MatDoaArgs {
+    const double *basis;    // [mat_eig_basis_entries(cc)][nfft]
+    const double *tau;      // [ndir][nchan] delays in samples
+    const double *frac;     // [ndir][nchan] frac(fc tau), reduced on the host
+    float *bartlett_out;    // [ndir][nout] each, always linear; or nullptr
+    float *capon_out;
+    float *music_out;
+    double loading;         // delta = loading trace / nchan
+    int nsrc;               // MUSIC: the signal subspace's dimension, 1 ... nchan - 1 (read with music_out only)
+    int ndir, nchan, nfft;
+    OutStage out;           // fftshift and trim
+};
+hipError_t launch_mat_doa(int cc, const MatDoaArgs &a, hipStream_t s);        // cc: welch_mat_capacity(a.nchan)
 
 }  // namespace oth

@@ -94,6 +94,9 @@ SIGNATURES = {
     'oth_welch_matrix': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_int, _f, _f, _u64p]),
     'oth_welch_matrix_eig_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, C.c_int, _p, _p, _u64p]),
     'oth_welch_matrix_eig': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, _f, _f, _u64p]),
+    'oth_welch_set_steering': (C.c_int, [_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double]),
+    'oth_welch_matrix_doa_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_double, _p, _p, _p, _u64p]),
+    'oth_welch_matrix_doa': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _f, _f, _f, _u64p]),
     'oth_mtm_jackknife_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
     'oth_mtm_jackknife': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
     'oth_mtm_csd_jackknife_dev': (C.c_int, [_p, _p, _p, C.c_size_t, _p, _p, _p, _p, _u64p]),
@@ -801,6 +804,72 @@ class WelchPlan(object):
         self.ctx.check(self.ctx.lib.oth_welch_matrix_eig_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nchan), int(stride),
                                                              _eig_of(of), _optp(eig_dev), _optp(vec_dev), C.byref(n)),
                        'oth_welch_matrix_eig_dev')
+        self.last_nseg = n.value
+        return n.value
+
+    ndir = 0      # (class default: no steering table until set_steering)
+    DOA_METHODS = ('bartlett', 'capon', 'music')
+
+    def set_steering(self, delays, fc):
+        """The steering table of matrix_doa / matrix_doa_dev (oth_welch_set_steering): delays [D, C] in samples, fractional
+        or negative as they come, 1 <= D <= 1024 directions of 2 <= C <= 8 channels - channel c of direction d carries
+        s(t - delays[d, c]) -, and fc the carrier in cycles per sample (0 for a baseband array).  Replaces an earlier
+        table; an empty array clears it."""
+        a = np.ascontiguousarray(delays, np.float64)
+        if a.size == 0:
+            self.ctx.check(self.ctx.lib.oth_welch_set_steering(self.h, 0, 0, None, float(fc)), 'oth_welch_set_steering')
+            self.ndir = 0
+            return
+        if a.ndim != 2:
+            raise ValueError('delays must be a (D, C) array: a row of C channel delays per direction')
+        self.ctx.check(self.ctx.lib.oth_welch_set_steering(self.h, a.shape[0], a.shape[1], a.ctypes.data_as(C.POINTER(C.c_double)),
+                                                           float(fc)), 'oth_welch_set_steering')
+        self.ndir = a.shape[0]
+
+    def matrix_doa(self, x, of='S', nsrc=None, loading=0.0, methods=('bartlett', 'capon', 'music'), nsamples=None):
+        """Direction spectra per bin (oth_welch_matrix_doa) over the D directions of set_steering, of the spectral matrix S
+        of matrix() (of='S') or of its coherence matrix G (of='G': a gain per channel drops out).  With w the steering
+        vector of a direction at a bin, l_i and v_i the eigenvalues (descending) and eigenvectors of the bin's matrix A,
+        p_i = |v_i^H w|^2 and delta = loading trace(A) / C:
+          'bartlett'  w^H A w / C^2                        the conventional beamformer
+          'capon'     1 / w^H (A + delta I)^-1 w           MVDR; 0 in a bin where A + delta I is singular
+          'music'     C / sum_{i > nsrc} p_i               nsrc: the dimension of the signal subspace, 1 ... C - 1
+        x as in matrix(): host complex64 array (C, n), or a device pointer to [C][nsamples] when nsamples is given as
+        (C, nsamples).  -> dict method -> float32 [D, out_len] for the methods asked for, always linear, with the plan's
+        fftshift and trim.  A non-finite sample reads NaN everywhere.  Sets last_nseg (M)."""
+        methods = (methods,) if isinstance(methods, str) else tuple(methods)
+        if not methods or any(m not in self.DOA_METHODS for m in methods):
+            raise ValueError("methods must name at least one of 'bartlett', 'capon', 'music'")
+        if 'music' in methods and nsrc is None:
+            raise ValueError('the MUSIC spectrum needs nsrc, the number of sources')
+        if nsamples is None:
+            x = np.asarray(x)
+            if x.ndim != 2:
+                raise ValueError('x must be a (C, n) array of C channels')
+            x = np.ascontiguousarray(x, np.complex64)
+            nchan, count, src, dev = x.shape[0], x.shape[1], x.ctypes.data_as(_p), 0
+        else:
+            nchan, count = (int(v) for v in nsamples)
+            src, dev = C.c_void_p(x), 1
+        if not 2 <= nchan <= 8:
+            raise ValueError('the spectral matrix takes 2 ... 8 channels, not %d' % nchan)
+        rows = {m: np.empty((self.ndir, self.out_len), np.float32) for m in methods}
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_welch_matrix_doa(self.h, src, count, nchan, dev, _eig_of(of), int(nsrc or 0), float(loading),
+                                                         *[_fptr(rows[m]) if m in rows else None for m in self.DOA_METHODS],
+                                                         C.byref(n)), 'oth_welch_matrix_doa')
+        self.last_nseg = n.value
+        return rows
+
+    def matrix_doa_dev(self, iq_dev, nsamples, nchan, stride, of, nsrc, loading, bartlett_dev=None, capon_dev=None, music_dev=None):
+        """Asynchronous: device in, device out - [D][out_len] float32 at each of bartlett_dev, capon_dev and music_dev; any may
+        be left out, not all three (nsrc is read only with music_dev).  of: 'S' / 'G' or EIG_OF_S / EIG_OF_G.  stride: samples
+        between channels.  -> segments per channel (also last_nseg)."""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_welch_matrix_doa_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nchan), int(stride),
+                                                             _eig_of(of), int(nsrc or 0), float(loading), _optp(bartlett_dev),
+                                                             _optp(capon_dev), _optp(music_dev), C.byref(n)),
+                       'oth_welch_matrix_doa_dev')
         self.last_nseg = n.value
         return n.value
 

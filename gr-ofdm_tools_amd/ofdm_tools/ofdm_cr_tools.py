@@ -823,6 +823,80 @@ def eigen_scan(vectors, nFFT, Sf, fc=0.0, of='S', ctx=None):
     return axis, eig, vec, eigenvalue_stats(eig, M)
 
 
+def ula_delays(nchan, angles_deg, spacing_wavelengths, fc_cycles):
+    """The steering table of a uniform line array for WelchPlan.set_steering / doa_scan: element c of nchan sits c spacings
+    along the line, a spacing is spacing_wavelengths wavelengths of the carrier, the carrier is fc_cycles cycles per sample,
+    and a plane wave from angle theta off broadside reaches element c later by c spacing sin(theta) carrier periods.
+    -> float64 [len(angles_deg), nchan] delays in samples, tau[d, c] = c spacing_wavelengths sin(theta_d) / fc_cycles."""
+    if not _is_int(nchan) or not 2 <= nchan <= 8:
+        raise ValueError('ula_delays needs 2 ... 8 channels, not %r' % (nchan,))
+    if not (np.isfinite(fc_cycles) and fc_cycles > 0):
+        raise ValueError('ula_delays needs a carrier fc_cycles > 0 in cycles per sample')
+    if not (np.isfinite(spacing_wavelengths) and spacing_wavelengths > 0):
+        raise ValueError('ula_delays needs a spacing > 0 in wavelengths')
+    theta = np.atleast_1d(np.asarray(angles_deg, np.float64))
+    if theta.ndim != 1 or theta.size < 1 or not np.all(np.abs(theta) <= 90.0):
+        raise ValueError('ula_delays needs a list of angles from -90 to 90 degrees')
+    return np.arange(int(nchan))[None, :] * (float(spacing_wavelengths) * np.sin(np.deg2rad(theta)) / float(fc_cycles))[:, None]
+
+
+def doa_band_combine(rows, band=None):
+    """The band-combined spectrum of doa_scan, in float64, over the bins band = (lo, hi) of the rows' last axis (hi excluded;
+    None: every bin): rows: dict method -> [D, m].  -> dict method -> [D]: the mean over the band for 'bartlett',
+    1 / mean(1 / P) - the bins' null spectra added - for 'capon' and 'music'."""
+    out = {}
+    for name, r in rows.items():
+        r = np.asarray(r, np.float64)
+        r = r if band is None else r[:, band[0]:band[1]]
+        with np.errstate(all='ignore'):
+            out[name] = r.mean(axis=1) if name == 'bartlett' else 1.0 / (1.0 / r).mean(axis=1)
+    return out
+
+
+def doa_scan(vectors, nFFT, Sf, delays, fc, nsrc, loading=1e-2, band=None, ctx=None):
+    """Where is the emitter?  The Bartlett, Capon (MVDR) and MUSIC spectra per bin and per direction of the spectral matrix
+    of C coherent channels, 2 <= C <= 8, on the plan multiantenna_scan makes (WelchPlan.matrix_doa; Hann window,
+    nperseg = nFFT, no overlap, density scaling), and their combination over a band.  vectors: (C, n) complex array.
+    delays: [D, C] in samples, channel c of direction d carries s(t - delays[d, c]) (ula_delays gives a uniform line array's),
+    1 <= D <= 1024.  fc: the carrier in cycles per sample.  nsrc: the number of sources MUSIC takes, 1 ... C - 1.  loading:
+    Capon's diagonal loading as a fraction of the mean eigenvalue.  band: (lo, hi) bins of the fftshifted axis, hi excluded;
+    None for all of them.
+    -> (frequency axis [Hz] fftshifted around fc Sf, bartlett, capon, music: float32 [D, nFFT] each, fftshifted, combined:
+    doa_band_combine of the three over band, float64 [D] each).  Needs nFFT a power of two from 64 to 16384, 2 ... 8 channels
+    and at least one segment (ValueError otherwise, before anything runs)."""
+    if nFFT not in SK_SIZES:
+        raise ValueError('doa_scan needs nFFT a power of two from 64 to 16384, not %r' % (nFFT,))
+    if not Sf > 0:
+        raise ValueError('doa_scan needs a sample rate Sf > 0')
+    x = np.asarray(vectors)
+    if x.ndim != 2 or not 2 <= x.shape[0] <= 8:
+        raise ValueError('doa_scan needs a (C, n) array of 2 ... 8 channels, not shape %r' % (x.shape,))
+    if x.shape[1] // int(nFFT) < 1:
+        raise ValueError('doa_scan needs at least nFFT = %d samples per channel' % nFFT)
+    tab = np.asarray(delays, np.float64)
+    if tab.ndim != 2 or tab.shape[1] != x.shape[0] or not 1 <= tab.shape[0] <= 1024 or not np.all(np.isfinite(tab)):
+        raise ValueError('doa_scan needs finite delays of shape (D, %d), 1 <= D <= 1024, not shape %r' % (x.shape[0], tab.shape))
+    if not np.isfinite(fc):
+        raise ValueError('doa_scan needs a finite carrier fc in cycles per sample')
+    if not _is_int(nsrc) or not 1 <= nsrc <= x.shape[0] - 1:
+        raise ValueError('doa_scan needs nsrc in 1 ... %d, not %r' % (x.shape[0] - 1, nsrc))
+    if not (np.isfinite(loading) and loading >= 0):
+        raise ValueError('doa_scan needs a finite loading >= 0')
+    if band is not None and not (len(band) == 2 and _is_int(band[0]) and _is_int(band[1]) and 0 <= band[0] < band[1] <= nFFT):
+        raise ValueError('doa_scan needs band = (lo, hi) with 0 <= lo < hi <= nFFT = %d' % nFFT)
+    ctx = ctx or _hip.default_context()
+    key = ('matrix', nFFT, float(Sf))      # multiantenna_scan's plan
+
+    def make():
+        return ctx.welch_plan(nFFT, nperseg=nFFT, noverlap=0, window=windows.get_window('hann', nFFT), fs=float(Sf), fftshift=True)
+
+    plan = ctx.cached_plan(key, make)
+    plan.set_steering(tab, fc)
+    rows = plan.matrix_doa(x, of='S', nsrc=int(nsrc), loading=float(loading))
+    axis = np.fft.fftshift(np.fft.fftfreq(nFFT, 1.0 / Sf)) + fc * Sf
+    return axis, rows['bartlett'], rows['capon'], rows['music'], doa_band_combine(rows, band)
+
+
 def ofdm_blind_hypotheses(fft_lens, cp_fractions, nFFT):
     """The (Tu, cp = Tu // f, bin) triples ofdm_blind_parameters tests, bin = round(nFFT / (Tu + cp)): where the symbol
     rate of the hypothesis falls in a caf row of nFFT points.  ValueError when two of them fall on the same bin or one on a

@@ -591,13 +591,58 @@ int oth_welch_matrix(oth_plan *plan, const void *iq, size_t nsamples, int nchan,
  * power of two from 64 to 16384; OTH_ERR_INVALID for nchan outside 2 ... 8, of not OTH_EIG_OF_S or OTH_EIG_OF_G, a NULL input,
  * both outputs NULL, chan_stride < nsamples, input shorter than nperseg.
  * Not provided: all C eigenvectors, multitaper plans, any-length transforms, more than 8 channels, partial sums for
- * time-sharded runs, MUSIC / Capon spectra. */
+ * time-sharded runs.  (Bartlett, Capon and MUSIC spectra: oth_welch_matrix_doa below.) */
 #define OTH_EIG_OF_S 0   /* the spectral matrix S = scale T / M        */
 #define OTH_EIG_OF_G 1   /* the coherence matrix G_ab = T_ab / sqrt(T_aa T_bb): unit diagonal, gain-invariant */
 int oth_welch_matrix_eig_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nchan, size_t chan_stride,
                              int of, float *eig_out_dev, float *vec_out_dev, uint64_t *nseg_out);
 int oth_welch_matrix_eig(oth_plan *plan, const void *iq, size_t nsamples, int nchan, int src_is_device,
                          int of, float *eig_out, float *vec_out, uint64_t *nseg_out);   /* iq: [nchan][nsamples], blocking */
+
+/* oth_welch_set_steering, oth_welch_matrix_doa_dev / oth_welch_matrix_doa (additions inside ABI 6; probe by the symbols):
+ * where is the emitter?  Per bin and per direction of a steering table, the Bartlett (conventional beamformer), Capon (MVDR)
+ * and MUSIC spectra of the matrix oth_welch_matrix_eig decomposes - S (of = OTH_EIG_OF_S) or G (of = OTH_EIG_OF_G, on which a
+ * gain per channel drops out) -, with the same plan, segmentation, window, detrend, scaling, M, fftshift and trim, the same
+ * sums T and the same `empty` / `bad` rules.
+ * oth_welch_set_steering: delays[ndir][nchan] host doubles in samples, fractional or negative as they come; fc the carrier
+ * in cycles per sample.  1 <= ndir <= OTH_DOA_DIRS_MAX, 2 <= nchan <= 8.  Channel c carries s(t - tau_c), so at bin k its
+ * transform obeys X_c = X_s exp(-j 2 pi (fc + f_k) tau_dc), f_k the signed bin frequency k / nfft for k < nfft / 2 and
+ * (k - nfft) / nfft from there on (it does not depend on the plan's fs).  With S_ab = E[conj(X_a) X_b] the vector of every
+ * quadratic form below is w_c(d, k) = exp(+j 2 pi (fc + f_k) tau_dc).  The library keeps tau and frac(fc tau) in double - the
+ * carrier's whole cycles come off on the host, exactly - and the kernel forms frac(fc tau) + f_k tau in double per bin and
+ * takes sincospi of twice that: no recurrence over bins.  A second call replaces the first table, after the plan's queued
+ * launches have drained; ndir = 0 clears it.  Refused: a plan that is refused below, ndir or nchan out of range, delays
+ * NULL, fc or a delay (or their product) not finite.
+ * With A the matrix, l_1 >= ... >= l_C its eigenvalues clamped at 0 and ranked as oth_welch_matrix_eig ranks them, v_i its
+ * eigenvectors, y_i = v_i^H w, p_i = |y_i|^2 and delta = loading trace(A) / C:
+ *   bartlett = sum_i l_i p_i / C^2                   = w^H A w / C^2
+ *   capon    = 1 / sum_i p_i / (l_i + delta)         = 1 / w^H (A + delta I)^-1 w;  exactly 0 in a bin where l_C + delta <= 0
+ *   music    = C / sum_{i > nsrc} p_i                +inf where the sum is exactly 0
+ * Outputs: float32 [ndir][out_len] each, row d the table's direction d, always linear (a plan set to dB gives its linear
+ * twin's rows bit for bit), with the plan's fftshift and trim.  Any pointer may be NULL, not all three; a row is the same
+ * bits alone or with the others, and a direction's row does not depend on the other directions of the table.  nsrc, the
+ * dimension of the signal subspace, is read only with music_out.  A bin with a non-finite channel reads NaN in every row.
+ * Among equal eigenvalues the subspaces are taken as computed (the lower Jacobi index first).
+ * Four launches per call: the averaging launch and the totals launch of oth_welch_matrix, the basis build of csrc/mateig.hip
+ * (the Jacobi of oth_welch_matrix_eig; the ranked eigenvalues and all C vectors stay on the device in double), then
+ * csrc/matdoa.hip over bins x directions: one projection onto the eigenbasis serves the three spectra.  Bit-identical run
+ * to run.
+ * _dev: device in, device out, asynchronous.  oth_welch_matrix_doa: iq is [nchan][nsamples] contiguous, host or device
+ * source, host outputs, blocking.
+ * Refused, the reason in oth_last_error(), before anything is allocated, staged or launched, and the plan goes on working, in
+ * this order: OTH_ERR_UNSUPPORTED on a multitaper plan, a plan set to OTH_AVERAGE_MEDIAN, a transform length that is not a
+ * power of two from 64 to 16384; OTH_ERR_INVALID for nchan outside 2 ... 8, of not OTH_EIG_OF_S or OTH_EIG_OF_G, a NULL input,
+ * all three outputs NULL; OTH_ERR_UNSUPPORTED without a steering table; OTH_ERR_INVALID for nchan other than the table's,
+ * nsrc outside 1 ... nchan - 1 when music_out is given, loading not finite or below 0, chan_stride < nsamples, input shorter
+ * than nperseg.
+ * Not provided: a wideband combination over bins on the device, tabulated (calibrated) array manifolds, more than 8 channels,
+ * multitaper plans. */
+#define OTH_DOA_DIRS_MAX 1024
+int oth_welch_set_steering(oth_plan *plan, int ndir, int nchan, const double *delays, double fc);
+int oth_welch_matrix_doa_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nchan, size_t chan_stride, int of, int nsrc,
+                             double loading, float *bartlett_out_dev, float *capon_out_dev, float *music_out_dev, uint64_t *nseg_out);
+int oth_welch_matrix_doa(oth_plan *plan, const void *iq, size_t nsamples, int nchan, int src_is_device, int of, int nsrc,
+                         double loading, float *bartlett_out, float *capon_out, float *music_out, uint64_t *nseg_out);
 
 /* oth_welch_set_prototype, oth_welch_pfb_dev / oth_welch_pfb (additions inside ABI 6; probe by the symbols): the PSD of a
  * polyphase filter bank (weighted overlap-add, WOLA) on a plan of oth_welch_plan with nperseg == nfft = N.  Every other PSD
