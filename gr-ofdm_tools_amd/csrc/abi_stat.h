@@ -1,4 +1,4 @@
-// What the host files of the per-bin statistics (abi_ftest, abi_sk, abi_jack, abi_adapt, abi_cyc, abi_lag, abi_mat, abi_eig, abi_doa, abi_pfb; mtm_run for the work split
+// What the host files of the per-bin statistics (abi_ftest, abi_sk, abi_jack, abi_adapt, abi_cyc, abi_lag, abi_mat, abi_eig, abi_doa, abi_gcc, abi_pfb; mtm_run for the work split
 // and the recipe) share: the size rule, the plan and stream-shape refusals, the kernel arguments a Welch statistic takes from
 // its plan, the work split over resident workgroups, the recipe text, the timed launch, the host and device forms around a
 // device run, and the replacement of a plan's tables.
@@ -136,7 +136,7 @@ template <typename Check, typename Run> int dev_form(oth_plan *p, uint64_t *nseg
 }
 
 // abi_mat.hip: the matrix family's averaging launch after its check, shared by oth_welch_matrix*, oth_welch_matrix_eig*
-// (abi_eig.hip) and oth_welch_matrix_doa* (abi_doa.hip) - workspaces, launch_welch_mat, the finalize arguments with their rows left NULL, the recipe text
+// (abi_eig.hip), oth_welch_matrix_doa* (abi_doa.hip) and oth_welch_matrix_gcc* (abi_gcc.hip) - workspaces, launch_welch_mat, the finalize arguments with their rows left NULL, the recipe text
 int welch_mat_sums(oth_plan *p, const float2 *x, long long nseg, int nchan, size_t stride, MatFinalizeArgs &f, std::string &recipe);
 
 // Fresh device tables take the place of a plan's earlier ones only when they are complete: launches queued on the old ones

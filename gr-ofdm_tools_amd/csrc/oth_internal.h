@@ -661,4 +661,20 @@ struct MatDoaArgs {
 };
 hipError_t launch_mat_doa(int cc, const MatDoaArgs &a, hipStream_t s);        // cc: welch_mat_capacity(a.nchan)
 
+// ---- matgcc.hip: generalized cross-correlation (PHAT, SCOT, plain) and the delay of every channel pair a < b, from the totals
+// row of launch_mat_totals over all nfft bins (its OutStage without shift and trim) -------------------------------------------
+constexpr int kGccUpsampleMax = 8;     // OTH_GCC_UPSAMPLE_MAX
+constexpr int kGccPointsMax = 16384;   // NI = upsample nfft at most: one LDS tile
+struct MatGccArgs {
+    const double *totals;   // [nchan][nchan][nfft] as MatFinalizeArgs.totals, every bin live
+    const float2 *tw;       // W_NI^k, NI entries (get_twiddles(NI): the plan's own table only where NI == nfft)
+    float *gcc_out;         // [nchan (nchan - 1) / 2][2 maxlag + 1] re, im interleaved, lags -maxlag ... maxlag; or nullptr
+    float *peak_out;        // [nchan (nchan - 1) / 2][3] delay in samples, |R| and arg R at the peak; or nullptr
+    int weighting;          // 0 plain, 1 PHAT, 2 SCOT
+    int band_lo, band_hi;   // signed bins of the nfft-point transform, both inclusive, in [-nfft / 2, nfft / 2 - 1]
+    int maxlag;             // 0 ... NI / 2 - 1, in units of 1 / upsample sample
+    int nchan, nfft;
+};
+hipError_t launch_mat_gcc(int ni, const MatGccArgs &a, hipStream_t s);        // ni: upsample a.nfft, a power of two 64 ... 16384
+
 }  // namespace oth

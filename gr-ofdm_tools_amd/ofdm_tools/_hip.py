@@ -19,6 +19,8 @@ SCHED_CONTIGUOUS, SCHED_INTERLEAVED, SCHED_DYNAMIC = 0, 1, 2
 HOSTWAIT_POLL, HOSTWAIT_SYNC = 0, 1
 AVERAGE_MEAN, AVERAGE_MEDIAN = 0, 1      # oth_plan_set_average: scipy.signal.welch average='mean' / 'median'
 EIG_OF_S, EIG_OF_G = 0, 1      # oth_welch_matrix_eig: the spectral matrix S, the coherence matrix G
+GCC_PLAIN, GCC_PHAT, GCC_SCOT = 0, 1, 2      # oth_welch_matrix_gcc: the weighting of the generalized cross-correlation
+GCC_POINTS_MAX = 16384      # upsample * nfft at most
 OUT_RING = 4      # oth_plan::kOutRing: launch (ticket) t of a plan delivers into output slot t % OUT_RING
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -97,6 +99,8 @@ SIGNATURES = {
     'oth_welch_set_steering': (C.c_int, [_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double]),
     'oth_welch_matrix_doa_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_double, _p, _p, _p, _u64p]),
     'oth_welch_matrix_doa': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _f, _f, _f, _u64p]),
+    'oth_welch_matrix_gcc_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _u64p]),
+    'oth_welch_matrix_gcc': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f, _f, _u64p]),
     'oth_mtm_jackknife_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, _p, _p, _u64p]),
     'oth_mtm_jackknife': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f, _f, _u64p]),
     'oth_mtm_csd_jackknife_dev': (C.c_int, [_p, _p, _p, C.c_size_t, _p, _p, _p, _p, _u64p]),
@@ -231,6 +235,17 @@ def _optp(v):
 def _eig_of(of):
     """'S' / 'G' -> EIG_OF_S / EIG_OF_G; an integer passes as it is (the library refuses what it does not know)"""
     return {'S': EIG_OF_S, 'G': EIG_OF_G}[of] if isinstance(of, str) else int(of)
+
+
+def _gcc_weighting(weighting):
+    """'plain' / 'phat' / 'scot' -> GCC_PLAIN / GCC_PHAT / GCC_SCOT; an integer passes as it is (the library refuses what it
+    does not know)"""
+    return {'plain': GCC_PLAIN, 'phat': GCC_PHAT, 'scot': GCC_SCOT}[weighting] if isinstance(weighting, str) else int(weighting)
+
+
+def gcc_pairs(nchan):
+    """the pair of each row of matrix_gcc, in the rows' order: (0,1), (0,2), ..., (C-2,C-1)"""
+    return [(a, b) for a in range(nchan) for b in range(a + 1, nchan)]
 
 
 def unpack_matrix(packed, nchan):
@@ -870,6 +885,67 @@ class WelchPlan(object):
                                                              _eig_of(of), int(nsrc or 0), float(loading), _optp(bartlett_dev),
                                                              _optp(capon_dev), _optp(music_dev), C.byref(n)),
                        'oth_welch_matrix_doa_dev')
+        self.last_nseg = n.value
+        return n.value
+
+    def _gcc_args(self, band, upsample, maxlag):
+        """band=None: every bin; maxlag=None: NI / 2 - 1 (NI = upsample nfft) -> (lo, hi, upsample, maxlag) as integers"""
+        lo, hi = (-(self.nfft // 2), self.nfft // 2 - 1) if band is None else (int(band[0]), int(band[1]))
+        upsample = int(upsample)
+        return lo, hi, upsample, (max(upsample, 1) * self.nfft // 2 - 1 if maxlag is None else int(maxlag))
+
+    def matrix_gcc(self, x, weighting='phat', band=None, upsample=1, maxlag=None, return_rows=True, nsamples=None):
+        """Generalized cross-correlation and the delay of every pair of C coherent channels (oth_welch_matrix_gcc),
+        2 <= C <= 8: the inverse transform of the weighted sums T_ab of matrix() over a band, R_ab[l] = (1 / Z) sum_k w_k
+        T_ab[k] / |T_ab[k]| e^(+j 2 pi k l / NI) with w = 1 ('phat'), |T_ab| / sqrt(T_aa T_bb) ('scot') or |T_ab| ('plain':
+        the band's correlation coefficient) and |R| <= 1.  band: (lo, hi) signed bins of the natural transform, both
+        inclusive, in -nfft / 2 ... nfft / 2 - 1 (None: all of them); upsample U: 1, 2, 4 or 8 with NI = U nfft <= 16384 -
+        lags count 1 / U sample (band-limited interpolation: it removes the parabola's bias at U = 1); maxlag: the rows hold
+        the lags -maxlag ... maxlag, 0 <= maxlag <= NI / 2 - 1 (None: the largest).  Channel c carries s(t - tau_c), the
+        convention of set_steering: |R_ab| peaks at tau_b - tau_a.  x as in matrix(): host complex64 array (C, n), or a
+        device pointer to [C][nsamples] when nsamples is given as (C, nsamples).
+        -> (delays float32 [C, C] in samples, delays[a][b] = tau_b - tau_a at the peak of |R_ab| with a parabola through its
+        neighbours, antisymmetric; peaks float32 [C, C], |R_ab| at the peak, symmetric, the diagonal 1; phases float32
+        [C, C], arg R_ab at the peak in radians, antisymmetric; rows complex64 [C (C - 1) / 2, 2 maxlag + 1], pairs in the
+        order of gcc_pairs(C)), or the first three with return_rows=False.  The plan's scaling, fftshift, trim and dB take
+        no part.  A pair with a silent channel reads 0 everywhere; a non-finite sample reads NaN in its channel's pairs.
+        Sets last_nseg (M)."""
+        if nsamples is None:
+            x = np.asarray(x)
+            if x.ndim != 2:
+                raise ValueError('x must be a (C, n) array of C channels')
+            x = np.ascontiguousarray(x, np.complex64)
+            nchan, count, src, dev = x.shape[0], x.shape[1], x.ctypes.data_as(_p), 0
+        else:
+            nchan, count = (int(v) for v in nsamples)
+            src, dev = C.c_void_p(x), 1
+        if not 2 <= nchan <= 8:
+            raise ValueError('the spectral matrix takes 2 ... 8 channels, not %d' % nchan)
+        lo, hi, upsample, maxlag = self._gcc_args(band, upsample, maxlag)
+        npairs = nchan * (nchan - 1) // 2
+        rows = np.empty((npairs, 2 * max(maxlag, 0) + 1), np.complex64) if return_rows else None
+        peak = np.empty((npairs, 3), np.float32)
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_welch_matrix_gcc(self.h, src, count, nchan, dev, _gcc_weighting(weighting), lo, hi, upsample, maxlag,
+                                                         rows.ctypes.data_as(_f) if return_rows else None, _fptr(peak), C.byref(n)),
+                       'oth_welch_matrix_gcc')
+        self.last_nseg = n.value
+        delays, peaks, phases = np.zeros((nchan, nchan), np.float32), np.eye(nchan, dtype=np.float32), np.zeros((nchan, nchan), np.float32)
+        for (a, b), (tau, top, arg) in zip(gcc_pairs(nchan), peak):
+            delays[a, b], delays[b, a] = tau, -tau
+            peaks[a, b] = peaks[b, a] = top
+            phases[a, b], phases[b, a] = arg, -arg
+        return (delays, peaks, phases, rows) if return_rows else (delays, peaks, phases)
+
+    def matrix_gcc_dev(self, iq_dev, nsamples, nchan, stride, weighting='phat', band=None, upsample=1, maxlag=None, gcc_dev=None, peak_dev=None):
+        """Asynchronous: device in, device out - [C (C - 1) / 2][2 maxlag + 1] re, im pairs at gcc_dev and [C (C - 1) / 2][3]
+        float32 (delay in samples, |R|, arg R at the peak) at peak_dev; either may be left out, not both.  weighting, band,
+        upsample and maxlag as in matrix_gcc.  stride: samples between channels.  -> segments per channel (also last_nseg)."""
+        lo, hi, upsample, maxlag = self._gcc_args(band, upsample, maxlag)
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_welch_matrix_gcc_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nchan), int(stride),
+                                                             _gcc_weighting(weighting), lo, hi, upsample, maxlag, _optp(gcc_dev),
+                                                             _optp(peak_dev), C.byref(n)), 'oth_welch_matrix_gcc_dev')
         self.last_nseg = n.value
         return n.value
 

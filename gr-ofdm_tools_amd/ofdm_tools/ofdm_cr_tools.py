@@ -897,6 +897,87 @@ def doa_scan(vectors, nFFT, Sf, delays, fc, nsrc, loading=1e-2, band=None, ctx=N
     return axis, rows['bartlett'], rows['capon'], rows['music'], doa_band_combine(rows, band)
 
 
+GCC_WEIGHTINGS = ('plain', 'phat', 'scot')
+
+
+def tdoa_scan(vectors, nFFT, Sf, weighting='phat', band=None, upsample=1, maxlag=None, ctx=None):
+    """What are the delays between these C coherent channels, 2 <= C <= 8?  The generalized cross-correlation of every pair
+    (WelchPlan.matrix_gcc: 'phat', 'scot' or 'plain') on the plan multiantenna_scan makes (Hann window, nperseg = nFFT, no
+    overlap) and the delay at its peak - what a steering table has to be calibrated with, and the TDOA of separated
+    receivers.  vectors: (C, n) complex array.  band: (f_lo, f_hi) in Hz of the baseband axis, -Sf / 2 <= f_lo <= f_hi
+    < Sf / 2, both inclusive: the bins ceil(f_lo nFFT / Sf) ... floor(f_hi nFFT / Sf), of which there must be one; None for
+    every bin.  upsample U: 1, 2, 4 or 8 with U nFFT <= 16384; the lags count 1 / (U Sf) seconds.  maxlag: the largest lag
+    in seconds, floor(maxlag U Sf) lags to either side, at most U nFFT / 2 - 1; None for that most.
+    -> (delays float64 [C, C] in seconds, delays[a][b] = tau_b - tau_a where channel c carries s(t - tau_c), antisymmetric;
+    peaks float32 [C, C], |R_ab| at the peak; phases float32 [C, C], arg R_ab at the peak in radians; the lag axis in
+    seconds, float64 [2 L + 1]; rows complex64 [C (C - 1) / 2, 2 L + 1], R_ab over the axis, pairs (0,1), (0,2), ...,
+    (C-2,C-1)).  channel_delays turns the pair matrix into per-channel delays.  Needs nFFT a power of two from 64 to 16384,
+    2 ... 8 channels and at least one segment (ValueError otherwise, before anything runs)."""
+    if nFFT not in SK_SIZES:
+        raise ValueError('tdoa_scan needs nFFT a power of two from 64 to 16384, not %r' % (nFFT,))
+    if not Sf > 0:
+        raise ValueError('tdoa_scan needs a sample rate Sf > 0')
+    x = np.asarray(vectors)
+    if x.ndim != 2 or not 2 <= x.shape[0] <= 8:
+        raise ValueError('tdoa_scan needs a (C, n) array of 2 ... 8 channels, not shape %r' % (x.shape,))
+    if x.shape[1] // int(nFFT) < 1:
+        raise ValueError('tdoa_scan needs at least nFFT = %d samples per channel' % nFFT)
+    if weighting not in GCC_WEIGHTINGS:
+        raise ValueError("tdoa_scan needs weighting 'plain', 'phat' or 'scot', not %r" % (weighting,))
+    if not _is_int(upsample) or upsample not in (1, 2, 4, 8) or upsample * nFFT > _hip.GCC_POINTS_MAX:
+        raise ValueError('tdoa_scan needs upsample 1, 2, 4 or 8 with upsample * nFFT <= %d, not %r' % (_hip.GCC_POINTS_MAX, upsample))
+    half, ni = nFFT // 2, int(upsample) * nFFT
+    bins = None
+    if band is not None:
+        if not (len(band) == 2 and np.all(np.isfinite(band)) and -0.5 * Sf <= band[0] <= band[1] < 0.5 * Sf):
+            raise ValueError('tdoa_scan needs band = (f_lo, f_hi) in Hz with -Sf / 2 <= f_lo <= f_hi < Sf / 2')
+        bins = (max(int(math.ceil(band[0] * nFFT / float(Sf))), -half), min(int(math.floor(band[1] * nFFT / float(Sf))), half - 1))
+        if bins[0] > bins[1]:
+            raise ValueError('tdoa_scan: the band %r Hz holds no bin of width %g Hz' % (tuple(band), Sf / float(nFFT)))
+    lags = ni // 2 - 1
+    if maxlag is not None:
+        if not (np.isfinite(maxlag) and maxlag >= 0):
+            raise ValueError('tdoa_scan needs maxlag >= 0 in seconds')
+        lags = int(math.floor(maxlag * upsample * float(Sf)))
+        if lags > ni // 2 - 1:
+            raise ValueError('tdoa_scan: maxlag is %d lags of 1 / (upsample Sf); upsample * nFFT / 2 - 1 = %d at most' % (lags, ni // 2 - 1))
+    ctx = ctx or _hip.default_context()
+    key = ('matrix', nFFT, float(Sf))      # multiantenna_scan's plan
+
+    def make():
+        return ctx.welch_plan(nFFT, nperseg=nFFT, noverlap=0, window=windows.get_window('hann', nFFT), fs=float(Sf), fftshift=True)
+
+    delays, peaks, phases, rows = ctx.cached_plan(key, make).matrix_gcc(x, weighting=weighting, band=bins, upsample=int(upsample), maxlag=lags)
+    axis = np.arange(-lags, lags + 1) / (float(upsample) * float(Sf))
+    return delays.astype(np.float64) / float(Sf), peaks, phases, axis, rows
+
+
+def channel_delays(pair_delays, weights=None):
+    """Per-channel delays from the antisymmetric pair matrix of tdoa_scan / WelchPlan.matrix_gcc, pair_delays[a][b] =
+    tau_b - tau_a: the tau with tau_0 = 0 that minimises sum_{a < b} weights[a][b] (tau_b - tau_a - pair_delays[a][b])^2, in
+    float64.  weights: [C, C] >= 0, read above the diagonal (the pairs' peaks, say: a pair without a common signal counts
+    less); None for equal weights.  Every channel must hang on channel 0 through pairs of weight > 0 (ValueError otherwise).
+    -> float64 [C], in the unit of pair_delays.  Cable and front-end delays measured this way, added to a geometry's
+    (ula_delays), are the rows WelchPlan.set_steering takes."""
+    d = np.asarray(pair_delays, np.float64)
+    if d.ndim != 2 or d.shape[0] != d.shape[1] or d.shape[0] < 2 or not np.all(np.isfinite(d)):
+        raise ValueError('channel_delays needs a finite (C, C) matrix of pair delays, C >= 2')
+    nchan = d.shape[0]
+    w = np.ones((nchan, nchan)) if weights is None else np.asarray(weights, np.float64)
+    if w.shape != d.shape or not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError('channel_delays needs finite weights >= 0 of the shape of pair_delays')
+    pairs = [(a, b) for a in range(nchan) for b in range(a + 1, nchan) if w[a, b] > 0]
+    A = np.zeros((len(pairs), nchan))
+    for r, (a, b) in enumerate(pairs):
+        A[r, a], A[r, b] = -1.0, 1.0
+    root = np.sqrt(np.array([w[a, b] for a, b in pairs]))
+    A = A[:, 1:] * root[:, None]      # tau_0 = 0
+    if not pairs or np.linalg.matrix_rank(A) < nchan - 1:
+        raise ValueError('channel_delays: a channel is not tied to channel 0 by pairs of weight > 0')
+    rhs = np.array([d[a, b] for a, b in pairs]) * root
+    return np.concatenate(([0.0], np.linalg.lstsq(A, rhs, rcond=None)[0]))
+
+
 def ofdm_blind_hypotheses(fft_lens, cp_fractions, nFFT):
     """The (Tu, cp = Tu // f, bin) triples ofdm_blind_parameters tests, bin = round(nFFT / (Tu + cp)): where the symbol
     rate of the hypothesis falls in a caf row of nFFT points.  ValueError when two of them fall on the same bin or one on a

@@ -644,6 +644,58 @@ int oth_welch_matrix_doa_dev(oth_plan *plan, const void *iq_dev, size_t nsamples
 int oth_welch_matrix_doa(oth_plan *plan, const void *iq, size_t nsamples, int nchan, int src_is_device, int of, int nsrc,
                          double loading, float *bartlett_out, float *capon_out, float *music_out, uint64_t *nseg_out);
 
+/* oth_welch_matrix_gcc_dev / oth_welch_matrix_gcc (additions inside ABI 6; probe by the symbols): what are the delays between
+ * the channels?  The generalized cross-correlation of Knapp and Carter for every pair a < b of the C channels, and the delay
+ * at its peak - the figure a steering table of oth_welch_set_steering has to be calibrated with (cable and front-end delays),
+ * and the TDOA of separated receivers.  Same plan, segmentation, window, detrend and M as oth_welch_matrix, and the same sums
+ * T; the plan's fftshift, trim, dB switch and scaling take no part: the outputs are rows over lags, and every weighting
+ * cancels the scale.
+ * Band: band_lo <= band_hi, signed bins of the natural transform (bin k at frequency k / nfft cycles per sample), both
+ * inclusive, each in -nfft / 2 ... nfft / 2 - 1.  Upsampling: upsample = U is 1, 2, 4 or 8 with NI = U nfft <= 16384; signed
+ * bin k goes to index k mod NI of an NI-point inverse transform (band-limited interpolation), so lags count 1 / U sample.
+ * Per pair, with Z and the weights in double and the weighted phasors handed to a float32 transform:
+ *   u_k = T_ab[k] / |T_ab[k]|       0 where |T_ab[k]| = 0, or where T_aa[k] <= 0, or where T_bb[k] <= 0
+ *   w_k = 1 (OTH_GCC_PHAT), |T_ab| / sqrt(T_aa T_bb) (OTH_GCC_SCOT), |T_ab| (OTH_GCC_PLAIN)
+ *   Z   = the number of in-band bins with u_k != 0 (PHAT, SCOT);  sqrt(sum_k T_aa[k] sum_k T_bb[k]) over the band (PLAIN)
+ *   R_ab[l] = (1 / Z) sum_{k in band} w_k u_k e^(+j 2 pi k l / NI),    l = -maxlag ... maxlag,   0 <= maxlag <= NI / 2 - 1
+ * |R| <= 1 under all three; PLAIN is the correlation coefficient of the band, and the SCOT peak is the mean coherence
+ * magnitude along the delay.  Channel c carries s(t - tau_c), the convention of oth_welch_set_steering: |R_ab| peaks at
+ * l / U = tau_b - tau_a.
+ * Outputs, P = C (C - 1) / 2 pairs in the order (0,1), (0,2), ..., (C-2,C-1); either pointer may be NULL, not both, and each is
+ * the same bytes with and without the other:
+ *   gcc_out  [P][2 maxlag + 1] interleaved re, im, float32: R_ab at the lags -maxlag ... maxlag
+ *   peak_out [P][3] float32, with i the lag of the largest |R| of the window (the lowest lag among equals): the delay in
+ *            samples (i + d) / U, d = 0.5 (y- - y+) / (y- - 2 y0 + y+) on |R| at i - 1, i, i + 1, and d = 0 where i is a
+ *            window edge or the denominator is not negative; |R[i]|; arg R[i] in radians (at a carrier fc cycles per sample:
+ *            -2 pi fc (tau_b - tau_a) modulo 2 pi).
+ * The parabola on |R| at U = 1 is biased towards the nearest whole lag; upsample is what removes the bias.
+ * Degenerate input (the matrix family's rules): finite input never gives NaN or inf.  Z = 0 (a silent channel, or a constant
+ * under detrend, across the band) gives an all-zero row and a peak of (0, 0, 0).  A channel with a non-finite sum inside the
+ * band (a NaN or +-inf sample) makes every output of every pair that involves it NaN, never inf; every other pair stays bit
+ * for bit what it is without the bad sample.  M = 1 is allowed.  Bit-identical run to run.
+ * Three launches per call: the averaging launch and the totals launch of oth_welch_matrix (over every bin, whatever the plan
+ * trims), then one workgroup per pair (csrc/matgcc.hip): w_k u_k / Z in double into an NI-point tile of LDS, the inverse
+ * transform, the window and a fixed-order argmax.
+ * _dev: device in, device out, asynchronous.  oth_welch_matrix_gcc: iq is [nchan][nsamples] contiguous, host or device
+ * source, host outputs, blocking.
+ * Refused, the reason in oth_last_error(), before anything is allocated, staged or launched, and the plan goes on working, in
+ * this order: OTH_ERR_UNSUPPORTED on a multitaper plan, a plan set to OTH_AVERAGE_MEDIAN, a transform length that is not a
+ * power of two from 64 to 16384; OTH_ERR_INVALID for nchan outside 2 ... 8, a NULL input, chan_stride < nsamples, input shorter
+ * than nperseg, a weighting that is not one of the three, a band outside the range or band_lo > band_hi, upsample not 1, 2, 4
+ * or 8; OTH_ERR_UNSUPPORTED for upsample nfft > 16384; OTH_ERR_INVALID for maxlag outside 0 ... NI / 2 - 1, both outputs NULL.
+ * Not provided: the ML / Hannan-Thomson weighting, coherence-gated weights, more than 8 channels, multitaper plans, partial
+ * sums for time-sharded runs. */
+#define OTH_GCC_PLAIN 0   /* w = |T_ab|: the band's correlation coefficient             */
+#define OTH_GCC_PHAT  1   /* w = 1: the phase transform                                 */
+#define OTH_GCC_SCOT  2   /* w = |T_ab| / sqrt(T_aa T_bb): the smoothed coherence transform */
+#define OTH_GCC_UPSAMPLE_MAX 8
+int oth_welch_matrix_gcc_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nchan, size_t chan_stride,
+                             int weighting, int band_lo, int band_hi, int upsample, int maxlag,
+                             float *gcc_out_dev, float *peak_out_dev, uint64_t *nseg_out);
+int oth_welch_matrix_gcc(oth_plan *plan, const void *iq, size_t nsamples, int nchan, int src_is_device,
+                         int weighting, int band_lo, int band_hi, int upsample, int maxlag,
+                         float *gcc_out, float *peak_out, uint64_t *nseg_out);   /* iq: [nchan][nsamples], blocking */
+
 /* oth_welch_set_prototype, oth_welch_pfb_dev / oth_welch_pfb (additions inside ABI 6; probe by the symbols): the PSD of a
  * polyphase filter bank (weighted overlap-add, WOLA) on a plan of oth_welch_plan with nperseg == nfft = N.  Every other PSD
  * of the library uses a window no longer than the transform, and such a bin has a skirt: a strong neighbour leaks into an
