@@ -591,6 +591,8 @@ int oth_welch_segments_dev(oth_plan *p, const void *iq_dev, size_t nsamples, flo
     if (use_device(c)) return OTH_ERR_HIP;
     const char *route = "";
     if (int rc = median_rows(p, (const float2 *)iq_dev, 1, nsamples, nseg, &route)) return rc;
+    // (a launch of its own: without this line oth__debug_last_recipe went on naming the call before this one)
+    p->last_recipe = std::string("kernel=segments rows=") + route + " nfft=" + std::to_string(p->nfft) + " nseg=" + std::to_string(nseg);
     // the plan's scaling, fftshift, trim and dB per row: finalize_kernel with one "stream" per segment (grid.y <= 65535)
     FinalizeArgs f = finalize_args(p, 1, ROW_NATURAL, 1, out_stage(p));
     f.scratch = nullptr;

@@ -952,7 +952,8 @@ int oth_fac(oth_ctx *ctx, const void *data, size_t n, int L, float *out);
  * oth__debug_recipe needs NO device: window_class 0 = all ones, 1 = confined spectrum (periodic cosine-sum windows),
  * 2 = wide (no detrend table), 3 = confined to 256 nfft / 4096 bins only; runtime_occupancy 0 = resident workgroups per CU
  * from the built-in MI355X table, 1 = from the occupancy calculator (needs a GPU).  oth__debug_last_recipe: the recipe of
- * the plan's last averaging launch.
+ * the plan's last averaging launch; every call that launches one writes it (the statistics, the median average and
+ * oth_welch_segments_dev name their own kernels), so it never names an earlier call.
  * oth__debug_live_resources needs no context and no device: how many device buffers, pinned host buffers and events the
  * library's contexts, plans and chains hold in this process right now (memory from oth_dev_alloc is the caller's and is
  * not counted).  Any pointer may be NULL.  After every context has been destroyed all three are zero. */

@@ -48,6 +48,23 @@ def one_round(c, hip):
     assert relerr(p.finalize(), ref) < RTOL and p.last_nseg == 16
     pxx, pyy, _, _ = p.csd(x, Y)                                    # the two-channel run
     assert np.all(pxx > 0) and np.all(pyy > 0)
+    # one call of each statistic family: their tables (d_cyc_tap, d_lags, d_pfb_h, d_doa_steer) and workspaces (d_cyc_ws,
+    # d_lag_means, d_mat_ws, d_mat_totals, d_doa_basis) are counted too
+    sk, psd = p.sk(x, return_psd=True)
+    assert np.all(psd > 0) and np.all(np.isfinite(sk)) and p.last_nseg == 16
+    p.set_cycles([0.0, 0.0125])
+    assert np.all(p.cyclic(x)[1] >= 0)
+    p.set_lags([0, 64])
+    assert np.all(p.caf(x) > 0)
+    p.set_prototype(np.ones(2 * 4096, np.float32))
+    assert np.all(p.pfb(x) > 0)
+    xc = X[:3 * len(x)].reshape(3, len(x))
+    S, gcoh = p.matrix(xc)
+    assert np.all(S[0, 0].real > 0) and np.all(gcoh >= 0)
+    assert np.all(p.matrix_eig(xc, of='G')[0][0] > 0)
+    p.set_steering(np.arange(6.0).reshape(2, 3), 0.0)
+    assert all(np.all(r > 0) for r in p.matrix_doa(xc, nsrc=1, loading=1e-2).values())
+    assert np.all(p.matrix_gcc(xc, maxlag=8)[1] > 0) and p.last_nseg == 16
     p.set_average('median')                                         # d_rows, d_med, d_msel
     assert np.all(p.exec(x) > 0)
     p.close()
@@ -60,6 +77,14 @@ def one_round(c, hip):
         p.close()
     p = c.mtm_plan(256, nw=4.0, ntapers=7)
     assert np.all(p.exec(X[:2048]) > 0)
+    assert np.all(p.adaptive(X[:2048]) > 0)                         # d_mtm_lam; d_adapt_ws and d_ftest_ws from 1024 points on
+    assert np.all(p.ftest(X[:2048]) >= 0)
+    assert np.all(p.jackknife(X[:2048]) > 0)                        # d_jack_tot
+    p.close()
+    p = c.mtm_csd_plan(1024, nw=3.0, ntapers=5)                     # d_mtm_ws's smaller builds; the two-channel jackknife
+    assert np.all(p.adaptive(X[:4096]) > 0) and np.all(p.ftest(X[:4096]) >= 0)
+    assert np.all(p.csd(X[:4096], Y[:4096])[0] > 0)
+    assert np.all(p.csd_jackknife(X[:4096], Y[:4096])[1] > 0)
     p.close()
     ch = c.chain(1024, None, True, hip.EPI_MAG2, 1)                 # h_tail, h_in, h_row, the events
     ch.set_iir_log(0.3, -90.0)
