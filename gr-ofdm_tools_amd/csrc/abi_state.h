@@ -220,6 +220,26 @@ struct oth_chain {
     bool tail_ev_live = false;         // ... which a dropped push waits for before it rewrites h_tail
 };
 
+// Polyphase channelizer (oth_channelizer_*, abi_chan.hip / chanpfb.hip): one wideband stream in, nchan baseband rows out
+struct oth_channelizer {
+    oth_ctx *ctx = nullptr;
+    int nchan = 0, decim = 0, ntaps = 0;
+    size_t taps = 0;                   // L = ntaps nchan: the samples a frame covers
+    DevBuf<float> d_h;                 // [ntaps][nchan] the prototype
+    const float2 *d_tw = nullptr;      // borrowed: the context's twiddle cache owns it
+    // streaming state: the samples a later frame still needs (fewer than L) sit in d_tail[cur]; a push that yields frames
+    // saves its tail into the other buffer behind its launch (a push shorter than L would otherwise copy onto its own source)
+    DevBuf<float2> d_tail[2];          // L samples each
+    int cur = 0;
+    size_t pending = 0;                // samples in d_tail[cur]
+    uint64_t frames_total = 0;         // frames since creation or the last reset: the circular shift's absolute frame index
+    DevBuf<float2> d_stage;            // host input lands here (H2D), then feeds the kernel
+    DevBuf<float2> d_out;              // [nchan][frames] of the host-output form
+    int tune_wg = 0;                   // OTH_CHAN_WG, read when the handle is created: at most that many workgroups per launch
+                                       // (A/B tools and the parity suite); 0 = the library's choice
+    std::string last_recipe;           // of the last push that launched (oth__debug_channelizer_recipe)
+};
+
 namespace oth {
 // host chunks up to this size go through the pinned staging rings (work()-sized buffers: the copy is trivial and the
 // call returns at once); larger ones use the runtime's staged copy from pageable memory directly

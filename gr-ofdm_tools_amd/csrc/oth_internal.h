@@ -592,6 +592,28 @@ struct WelchPfbArgs {
 int welch_pfb_blocks_per_cu(int nfft);
 hipError_t launch_welch_pfb(int nfft, const WelchPfbArgs &a, hipStream_t s);
 
+// ---- chanpfb.hip: polyphase channelizer (oth_channelizer) - the fold of welchpfb.hip without detrend, the circular shift
+// by (m decim) mod nchan, the transform, and the frames' bins out channel-major: out[k][m] = FFT(v_m)[k] -------------------------
+constexpr int kChanTapsMin = 1, kChanTapsMax = 16;      // taps per branch P
+constexpr int kChanMin = 64, kChanMax = 4096;           // channels M, a power of two
+constexpr int kChanTile = 8;                            // F: frames of a tile, 8 F bytes of a channel row leave at once
+struct ChanPfbArgs {
+    const float2 *tail;     // the `pending` samples in front of x that earlier pushes left (frame m starts at sample m decim of tail ++ x)
+    const float2 *x;        // the new samples
+    const float *h;         // the prototype, [ntaps][nchan] floats
+    const float2 *tw;       // W_nchan^k, nchan entries
+    float2 *out;            // [nchan][out_stride]: frame m of this push in column m
+    size_t out_stride;      // complex samples between channel rows, >= nframes
+    long long nframes;      // frames of this push: (nframes - 1) decim + ntaps nchan <= pending + the new samples
+    long long pending;      // samples in tail, < ntaps nchan
+    int decim;              // hop D: nchan, nchan / 2 or nchan / 4
+    int ntaps;              // P
+    int rot0;               // (frames before this push) mod (nchan / decim): frame m is shifted by ((rot0 + m) mod (nchan / decim)) decim
+    int wg_count;           // workgroups: each walks a contiguous run of whole tiles of kChanTile frames
+};
+int chan_pfb_blocks_per_cu(int nchan);
+hipError_t launch_chan_pfb(int nchan, const ChanPfbArgs &a, hipStream_t s);
+
 // ---- welchmat.hip: spectral matrix of C coherent channels on a Welch plan - sum_s conj(X_s,a) X_s,b for a <= b, then
 // S = scale T / M and the generalized coherence 1 - det G, G_ab = T_ab / sqrt(T_aa T_bb) ---------------------------------------
 constexpr int kMatChanMax = 8;      // channels at most; the kernels are built for a capacity of 2, 4 and 8

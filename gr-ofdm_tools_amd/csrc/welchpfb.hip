@@ -41,8 +41,8 @@
 // With step = N consecutive frames of a run share (P - 1) N samples; the re-reads go to L2 (one frame of 16384 x 16 points
 // is 2 MiB against 4 MiB per XCD).
 //
-// Not here: a sliding register window that carries P - 1 blocks across a run, complex prototypes, the channeliser's
-// time-domain outputs, the circular-shift form that keeps phase continuity between hops (power does not need it),
+// Not here: a sliding register window that carries P - 1 blocks across a run, complex prototypes, the bank's time-domain
+// outputs in the circular-shift form that keeps phase continuity between hops (chanpfb.hip; power does not need it),
 // time-sharded partials, multitaper plans, the median average, transform lengths that are not a power of two.
 #include "mtm_common.hip.h"
 #include "out_stage.hip.h"

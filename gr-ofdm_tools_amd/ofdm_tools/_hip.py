@@ -139,6 +139,13 @@ SIGNATURES = {
     'oth_chain_last_push_ops': (C.c_int, [_p, _u64p]),
     'oth_chain_get_peak': (C.c_int, [_p, _f]),
     'oth_chain_get_iir': (C.c_int, [_p, _f]),
+    'oth_channelizer_create': (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _f, _pp]),
+    'oth_channelizer_destroy': (C.c_int, [_p]),
+    'oth_channelizer_reset': (C.c_int, [_p]),
+    'oth_channelizer_frames': (C.c_int, [_p, C.c_size_t, _u64p]),
+    'oth_channelizer_pending': (C.c_int, [_p, C.POINTER(C.c_size_t)]),
+    'oth_channelizer_push_dev': (C.c_int, [_p, _p, C.c_size_t, _p, C.c_size_t, _u64p]),
+    'oth_channelizer_push': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _p, C.c_size_t, _u64p]),
     'oth_rows_group_mean': (C.c_int, [_p, _f, C.c_size_t, C.c_int, C.c_int, _f]),
     'oth_channel_power': (C.c_int, [_p, _f, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     _f, _f]),
@@ -152,6 +159,7 @@ SIGNATURES = {
     'oth__debug_recipe': (C.c_int, [C.c_int] * 7 + [C.c_char_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_char_p,
                                                     C.c_size_t]),
     'oth__debug_last_recipe': (C.c_int, [_p, C.c_char_p, C.c_size_t]),
+    'oth__debug_channelizer_recipe': (C.c_int, [_p, C.c_char_p, C.c_size_t]),
     'oth__debug_live_resources': (C.c_int, [C.POINTER(C.c_int)] * 3),
 }
 
@@ -410,6 +418,12 @@ class Context(object):
 
     def chain(self, nfft, window=None, fftshift=True, epilogue=EPI_MAG2, keep_one_in_n=1):
         return Chain(self, nfft, window, fftshift, epilogue, keep_one_in_n)
+
+    def channelizer(self, nchan, decim=None, taps=8, prototype=None):
+        """Polyphase channelizer (oth_channelizer): nchan channels (a power of two 64 ... 4096), a new output sample of
+        every channel per decim input samples (nchan, nchan / 2 or nchan / 4; nchan // 2 by default), a real prototype of
+        taps * nchan taps (1 <= taps <= 16; windows.pfb_prototype(nchan, taps) by default).  -> Channelizer."""
+        return Channelizer(self, nchan, decim, taps, prototype)
 
     # -- small ops --------------------------------------------------------------
     def rows_group_mean(self, rows, group):
@@ -1416,6 +1430,111 @@ class Chain(object):
         out = np.empty(self.nfft, np.float32)
         self.ctx.check(self.ctx.lib.oth_chain_get_iir(self.h, _fptr(out)), 'oth_chain_get_iir')
         return out
+
+
+CHAN_SIZES = (64, 128, 256, 512, 1024, 2048, 4096)      # the channel counts chanpfb.hip is built for
+CHAN_TAPS_MAX = 16
+
+
+def channelizer_args(nchan, decim=None, taps=8, prototype=None):
+    """The arguments of Context.channelizer checked and completed without a context -> (nchan, decim, taps, prototype as
+    float32 [taps * nchan]); ValueError for what the library would refuse."""
+    nchan, taps = int(nchan), int(taps)
+    if nchan not in CHAN_SIZES:
+        raise ValueError('the channelizer takes a channel count that is a power of two from 64 to 4096, not %d' % nchan)
+    decim = nchan // 2 if decim is None else int(decim)
+    if decim not in (nchan, nchan // 2, nchan // 4):
+        raise ValueError('decim must be nchan, nchan / 2 or nchan / 4 (got %d for %d channels)' % (decim, nchan))
+    if not 1 <= taps <= CHAN_TAPS_MAX:
+        raise ValueError('taps must lie in 1 ... %d (got %d)' % (CHAN_TAPS_MAX, taps))
+    if prototype is None:
+        from . import windows
+        prototype = windows.pfb_prototype(nchan, taps)
+    h = np.ascontiguousarray(np.asarray(prototype, np.float64).ravel(), np.float32)
+    if len(h) != taps * nchan:
+        raise ValueError('the prototype holds taps * nchan = %d taps, not %d' % (taps * nchan, len(h)))
+    if not np.all(np.isfinite(h)):
+        raise ValueError('every tap of the prototype must be finite')
+    if not np.any(h):
+        raise ValueError('the prototype is all zero')
+    return nchan, decim, taps, h
+
+
+class Channelizer(object):
+    """Polyphase channelizer with its streaming state on the device (oth_channelizer): one wideband stream in, nchan
+    baseband rows out - y_k[m] = sum_n h[n] x[m D + n] exp(-2j pi k (m D + n) / nchan), k in natural (fftfreq) order, the
+    phase that of the absolute sample index since creation or reset().  Any split of a stream into pushes gives the same
+    bytes as one push."""
+
+    def __init__(self, ctx, nchan, decim=None, taps=8, prototype=None):
+        self.nchan, self.decim, self.taps, self.prototype = channelizer_args(nchan, decim, taps, prototype)
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx.check(ctx.lib.oth_channelizer_create(ctx.h, self.nchan, self.decim, self.taps, _fptr(self.prototype), C.byref(h)),
+                  'oth_channelizer_create')
+        self.h = h
+
+    def close(self):
+        if getattr(self, 'h', None) and getattr(self.ctx, 'h', None):
+            self.ctx.lib.oth_channelizer_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        """the sample count back to 0, the pending tail emptied: the next push gives what a new channelizer gives"""
+        self.ctx.check(self.ctx.lib.oth_channelizer_reset(self.h), 'oth_channelizer_reset')
+
+    def frames_for(self, nsamples):
+        """frames the NEXT push of nsamples will yield (host arithmetic)"""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_channelizer_frames(self.h, int(nsamples), C.byref(n)), 'oth_channelizer_frames')
+        return int(n.value)
+
+    @property
+    def pending(self):
+        """samples a later frame still needs, kept on the device: at most taps * nchan - 1"""
+        n = C.c_size_t()
+        self.ctx.check(self.ctx.lib.oth_channelizer_pending(self.h, C.byref(n)), 'oth_channelizer_pending')
+        return int(n.value)
+
+    def push(self, x, nsamples=None):
+        """Feed samples (a host complex64 array, or a device pointer when nsamples is given); blocking.
+        -> complex64 [nchan, frames] of this push, frames possibly 0."""
+        src, count, dev = _src(x, nsamples)
+        frames = self.frames_for(count)
+        out = np.empty((self.nchan, frames), np.complex64)
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_channelizer_push(self.h, src, count, dev, out.ctypes.data_as(_p) if frames else None, frames,
+                                                         C.byref(n)), 'oth_channelizer_push')
+        assert int(n.value) == frames
+        return out
+
+    def push_dev(self, dptr, nsamples, out_dptr, out_stride):
+        """Asynchronous: device-resident samples in, this push's frames to the columns 0 ... frames - 1 of the device
+        buffer [nchan][out_stride] complex64 at out_dptr (0 / None where the push yields no frame).  -> frames."""
+        n = C.c_uint64()
+        self.ctx.check(self.ctx.lib.oth_channelizer_push_dev(self.h, _optp(dptr), int(nsamples), _optp(out_dptr), int(out_stride),
+                                                             C.byref(n)), 'oth_channelizer_push_dev')
+        return int(n.value)
+
+    def last_recipe(self):
+        """the launch of the last push that yielded frames (oth__debug_channelizer_recipe); '' before the first"""
+        buf = C.create_string_buffer(512)
+        self.ctx.check(self.ctx.lib.oth__debug_channelizer_recipe(self.h, buf, 512), 'oth__debug_channelizer_recipe')
+        return buf.value.decode()
+
+    def channel_freqs(self, fs, fc=0.0):
+        """the channels' centres in Hz in the rows' (natural) order: fftfreq(nchan, 1 / fs) + fc"""
+        return np.fft.fftfreq(self.nchan, 1.0 / float(fs)) + float(fc)
+
+    def channel_rate(self, fs):
+        """the sample rate of every output row: fs / decim"""
+        return float(fs) / self.decim
 
 
 _default_ctx = None

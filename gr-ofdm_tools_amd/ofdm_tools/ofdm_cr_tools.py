@@ -632,6 +632,58 @@ def sk_scan(vector, nFFT, Sf, fc=0.0, p_false=None, ctx=None):
     return sk, axis, sk < lower, sk > upper
 
 
+def channelized_scan(vector, nchan, nFFT, Sf, fc=0.0, decim=None, taps=8, p_false=None, ctx=None):
+    """sk_scan per channel of a wide band: the capture goes through a polyphase channelizer (Context.channelizer: nchan
+    channels, hop decim = nchan // 2 by default, a prototype of taps * nchan taps), and the nchan baseband rows - rate
+    Sf / decim each - go as they lie on the device into WelchPlan.sk_dev (Hann window, nperseg = nFFT, no overlap): a fine
+    PSD and the spectral kurtosis of every channel from one upload and two launches; nothing but the two result arrays
+    comes back.  p_false = 1e-3 per side by default.
+    -> (channel centres [nchan] in Hz, fftshifted; offsets [nFFT] in Hz from a channel's centre at rate Sf / decim,
+    fftshifted; psd [nchan, nFFT]; sk [nchan, nFFT]; steady mask; intermittent mask; M), rows in the order of the centres,
+    M the fine segments per channel.
+    Needs nFFT a power of two from 64 to 16384 and M = frames // nFFT >= 32 with frames = (len(vector) - taps nchan) //
+    decim + 1 (ValueError otherwise, before anything runs); the limits are sk_limits(M, p_false)."""
+    nchan, decim, taps, h = _hip.channelizer_args(nchan, decim, taps)
+    if nFFT not in SK_SIZES:
+        raise ValueError('channelized_scan needs nFFT a power of two from 64 to 16384, not %r' % (nFFT,))
+    nFFT = int(nFFT)
+    x = _hip._c64(vector)
+    L = taps * nchan
+    frames = (len(x) - L) // decim + 1 if len(x) >= L else 0
+    M = frames // nFFT
+    if M < 32:
+        raise ValueError('channelized_scan needs at least 32 fine segments per channel: %d samples give %d frames of %d channels, '
+                         '%d segments of %d points' % (len(x), frames, nchan, M, nFFT))
+    p_false = 1e-3 if p_false is None else p_false
+    lower, upper = sk_limits(M, p_false)
+    ctx = ctx or _hip.default_context()
+    rate = float(Sf) / decim
+    chan = ctx.cached_plan(('chan', nchan, decim, taps), lambda: ctx.channelizer(nchan, decim, taps, h))
+    plan = ctx.cached_plan(('sk', nFFT, rate), lambda: ctx.welch_plan(nFFT, nperseg=nFFT, noverlap=0, window=windows.get_window('hann', nFFT),
+                                                                     fs=rate, fftshift=True))
+    bufs = []
+    try:
+        for nbytes in (8 * len(x), 8 * nchan * frames, 4 * nchan * nFFT, 4 * nchan * nFFT):
+            bufs.append(ctx.alloc(nbytes))
+        d_x, d_rows, d_sk, d_psd = bufs
+        ctx.h2d(d_x, x)
+        chan.reset()
+        got = chan.push_dev(d_x, len(x), d_rows, frames)
+        assert got == frames
+        segs = plan.sk_dev(d_rows, frames, nchan, frames, d_sk, d_psd)
+        assert segs == M
+        sk = ctx.d2h(d_sk, (nchan, nFFT), np.float32)
+        psd = ctx.d2h(d_psd, (nchan, nFFT), np.float32)
+    finally:
+        ctx.sync()
+        for b in bufs:
+            ctx.free(b)
+    sk, psd = np.fft.fftshift(sk, axes=0), np.fft.fftshift(psd, axes=0)
+    centres = np.fft.fftshift(chan.channel_freqs(Sf, fc))
+    offsets = np.fft.fftshift(np.fft.fftfreq(nFFT, 1.0 / rate))
+    return centres, offsets, psd, sk, sk < lower, sk > upper, M
+
+
 def ofdm_cycle_frequencies(fft_len, cp_len, Sf, harmonics=2):
     """The cycle frequencies of a cyclic-prefix OFDM signal of fft_len useful and cp_len prefix samples per symbol at
     sample rate Sf: +-k Sf / (fft_len + cp_len) in Hz for k = 1 ... harmonics, ordered +1, -1, +2, -2, ...  The prefix

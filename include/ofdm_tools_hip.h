@@ -143,6 +143,7 @@ extern "C" {
 typedef struct oth_ctx oth_ctx;
 typedef struct oth_plan oth_plan;
 typedef struct oth_chain oth_chain;
+typedef struct oth_channelizer oth_channelizer;
 
 /* ---- library / context ------------------------------------------------- */
 int         oth_abi_version(void);
@@ -747,10 +748,10 @@ int oth_welch_matrix_gcc(oth_plan *plan, const void *iq, size_t nsamples, int nc
  *   nsamples < P N             "input shorter than ntaps * nfft (<P> * <nfft> samples)"
  * in this order: the plan's kind (both setter and run), then the setter's arguments, or the missing prototype and the run's
  * arguments with the stream limit last.
- * Not provided: complex prototypes, the channeliser's time-domain outputs, the circular-shift form that keeps phase
- * continuity between hops (power does not need it), a sliding window that carries P - 1 blocks across frames (consecutive
+ * Not provided: complex prototypes, a sliding window that carries P - 1 blocks across frames (consecutive
  * frames re-read their shared samples from L2), time-sharded partial sums, multitaper plans, the median average,
- * any-length transforms, a ticketed asynchronous form. */
+ * any-length transforms, a ticketed asynchronous form.  The bank's time-domain outputs, in the circular-shift form that keeps
+ * the phase continuous between hops, are oth_channelizer_* below. */
 int oth_welch_set_prototype(oth_plan *plan, int ntaps, const float *h);
 int oth_welch_pfb_dev(oth_plan *plan, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride,
                       float *pfb_out_dev, uint64_t *nseg_out);
@@ -902,6 +903,61 @@ int oth_chain_get_iir(oth_chain *chain, float *lin_out);      /* float[nfft], li
 int oth_rows_group_mean(oth_ctx *ctx, const float *rows_host, size_t nrows, int nfft, int group,
                         float *out_host);
 
+/* ---- polyphase channelizer (additions inside ABI 6; probe by the symbols) ------------------------------------------------
+ * oth_channelizer_*: one wideband stream in, nchan baseband IQ rows out, on the device - the rows are the `nstreams` streams
+ * every `stream_stride` samples that the _dev statistics take (oth_welch_exec_dev, _sk_dev, _cyclic_dev, _caf_dev, _pfb_dev,
+ * the multitaper _dev forms).  A handle of its own, as oth_chain: M = nchan channels, hop D = decim (a new output sample of
+ * every channel per D input samples), a real prototype h of L = ntaps * nchan taps (ntaps = P taps per branch;
+ * ofdm_tools.windows.pfb_prototype gives a Kaiser-windowed sinc).  With t counting the input samples since creation or the
+ * last reset, frame m = 0, 1, ... covers the samples m D ... m D + L - 1 and
+ *   y_k[m] = sum_{n < L} h[n] x[m D + n] e^{-j 2 pi k (m D + n) / M}       k = 0 ... M - 1, natural order (k >= M / 2: the
+ *                                                                          negative frequencies)
+ * - channel k / M cycles per sample mixed to DC by the phase of the absolute sample index, filtered by h, every D-th output
+ * kept: each row is a proper baseband stream at rate fs / D, and a tone delta bins off a channel's centre advances
+ * delta D / M cycles per output.  Computed as the fold of the filter-bank PSD, a circular shift and one transform per frame,
+ *   u_m[r] = sum_{p < P} h[r + p M] x[m D + r + p M]  (r < M),   v_m[(r + m D) mod M] = u_m[r],   y_.[m] = FFT_M(v_m)
+ * with m D mod M taken from the absolute frame index in integer arithmetic: it survives any number of pushes.  ntaps = 1 is
+ * the short-time Fourier transform under h in the phase-continuous convention.  No detrend, no scale, no fftshift.
+ * oth_channelizer_create: h = ntaps * nchan host floats; the prototype goes to the device once.
+ * oth_channelizer_reset: the sample count back to 0, the pending tail emptied; waits for the context's queued work.
+ * oth_channelizer_frames: host arithmetic - the frames the NEXT push of nsamples will yield: with q samples pending,
+ *   q + nsamples >= L ? (q + nsamples - L) / D + 1 : 0.      oth_channelizer_pending: q, always at most L - 1.
+ * oth_channelizer_push_dev: device in, device out, asynchronous on the context's stream.  out_dev is [nchan][out_stride]
+ * complex64: channel k starts at out_dev + k * out_stride and this push's frames go to its columns 0 ... nframes - 1;
+ * nothing else of the buffer is written.  out_dev may be NULL when the push yields no frame.  The input may be reused once
+ * the stream has passed the call: the samples a later frame still needs (fewer than L) are kept in a device tail of the
+ * handle.  One launch per push (csrc/chanpfb.hip) and at most two small device copies for the tail.
+ * oth_channelizer_push: blocking, host or device source, host output in the same layout.
+ * Any split of a stream into pushes gives the same bytes as one push: a result depends on the absolute frame index alone.
+ * All-zero input gives exact zeros; a NaN or +-inf sample makes exactly the frames that cover it non-finite, in every
+ * channel, and leaves every other frame as it is bit for bit; a gain that is a power of two scales the output bit for bit.
+ * Refused, the reason in oth_last_error(), before anything is allocated, staged or launched; the handle goes on working.
+ * At creation, in this order:
+ *   OTH_ERR_UNSUPPORTED  nchan no power of two 64 ... 4096   "the channelizer takes a channel count that is a power of two
+ *                                                            from 64 to 4096, not <nchan>"
+ *   OTH_ERR_INVALID      decim                               "decim must be nchan, nchan / 2 or nchan / 4"
+ *                        ntaps outside 1 ... 16              "ntaps must lie in 1 ... 16"
+ *                        a NULL h                            "h is NULL"
+ *                        a non-finite tap                    "every tap of the prototype must be finite"
+ *                        sum h^2 == 0                        "the prototype is all zero"
+ * On a push, OTH_ERR_INVALID, in this order:
+ *   a NULL input with nsamples > 0, a NULL nframes_out       "bad argument"
+ *   frames to deliver and a NULL output                      "the output is NULL"
+ *   out_stride below the push's frame count                  "out_stride < frames of this push"
+ * nsamples == 0 is no error: 0 frames.
+ * Not provided: complex prototypes, hops other than nchan, nchan / 2 and nchan / 4, fewer than 64 or more than 4096
+ * channels, a channel subset, a synthesis bank, a ticketed asynchronous form, a sliding register window across frames
+ * (consecutive frames re-read their shared samples from L2, as in csrc/welchpfb.hip). */
+int oth_channelizer_create(oth_ctx *ctx, int nchan, int decim, int ntaps, const float *h, oth_channelizer **out);
+int oth_channelizer_destroy(oth_channelizer *ch);
+int oth_channelizer_reset(oth_channelizer *ch);
+int oth_channelizer_frames(oth_channelizer *ch, size_t nsamples, uint64_t *nframes_out);
+int oth_channelizer_pending(oth_channelizer *ch, size_t *nsamples_out);
+int oth_channelizer_push_dev(oth_channelizer *ch, const void *iq_dev, size_t nsamples, void *out_dev, size_t out_stride,
+                             uint64_t *nframes_out);
+int oth_channelizer_push(oth_channelizer *ch, const void *iq, size_t nsamples, int src_is_device, void *out_host,
+                         size_t out_stride, uint64_t *nframes_out);
+
 /* ---- channel power -------------------------------------------------------
  * src_power (ofdm_cr_tools.py:232-249): |convolve(psd, ones(int(sb))/sb, 'same')|
  * then per-channel slice sums.  lo/hi are the slice bounds the host computed with
@@ -956,11 +1012,15 @@ int oth_fac(oth_ctx *ctx, const void *data, size_t n, int L, float *out);
  * oth_welch_segments_dev name their own kernels), so it never names an earlier call.
  * oth__debug_live_resources needs no context and no device: how many device buffers, pinned host buffers and events the
  * library's contexts, plans and chains hold in this process right now (memory from oth_dev_alloc is the caller's and is
- * not counted).  Any pointer may be NULL.  After every context has been destroyed all three are zero. */
+ * not counted).  Any pointer may be NULL.  After every context has been destroyed all three are zero.
+ * oth__debug_channelizer_recipe: the launch of the handle's last push that yielded frames,
+ *   "kernel=chanpfb nchan=64 decim=32 ntaps=8 tile=8 W=5 frames=37 tiles=5 pending=0 bpc=16"
+ * (tile: frames of a tile, W: workgroups, each walking tiles / W whole tiles). */
 int oth__debug_recipe(int nfft, int nperseg, int noverlap, int window_class, int detrend_mode, int two_channel, int kernel_pref,
                       const char *variant, int sched_pref, long long nseg, int nstreams, int cu_count, int runtime_occupancy,
                       char *buf, size_t buflen);
 int oth__debug_last_recipe(oth_plan *plan, char *buf, size_t buflen);
+int oth__debug_channelizer_recipe(oth_channelizer *ch, char *buf, size_t buflen);
 int oth__debug_live_resources(int *device_buffers, int *pinned_buffers, int *events);
 
 #ifdef __cplusplus
