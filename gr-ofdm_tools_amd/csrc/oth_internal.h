@@ -614,6 +614,40 @@ struct ChanPfbArgs {
 int chan_pfb_blocks_per_cu(int nchan);
 hipError_t launch_chan_pfb(int nchan, const ChanPfbArgs &a, hipStream_t s);
 
+// ---- cpsync.hip: cyclic-prefix symbol timing and carrier offset (oth_cp_sync) - the lag products z[n] = x[n + Tu] conj(x[n])
+// and the energies e[n] folded over the symbols by residue n mod Ts, the circular cp-window, the maximum of Lambda ---------------
+constexpr int kCpsHypMax = 16;                          // hypotheses (Tu, cp) of a call at most
+constexpr int kCpsTuMin = 8, kCpsTuMax = 16384;         // Tu; 1 <= cp <= Tu, so Ts = Tu + cp <= 32768
+constexpr int kCpsSymBlock = 64;                        // symbols a float32 sum runs over before it is added in double
+constexpr int kCpsBlock = 64;                           // residues of a block of the window's block sums
+constexpr int kCpsGroupRows = 32, kCpsGroupMax = 32;    // the totals launch: about kCpsGroupRows runs to a group, kCpsGroupMax groups at most
+struct CpsArgs {
+    const float2 *x;        // device IQ, stream 0
+    double *rows;           // per hypothesis h from part_off[h]: [nstreams][w[h]][3][Ts_h] F re, F im, G of each run of symbols;
+                            // from grp_off[h]: [nstreams][ng[h]][3][Ts_h] the rows of each group of runs added up;
+                            // from tot_off[h]: [nstreams] x ([3][Ts_h] totals, [3][nb_h] their block sums)
+    float2 *gamma;          // [nstreams][nhyp][row_stride], or nullptr
+    float *phi;             // [nstreams][nhyp][row_stride], or nullptr
+    float *est;             // [nstreams][nhyp][4] theta, eps, rho_hat, Lambda[theta]
+    size_t stream_stride;   // samples between streams
+    size_t row_stride;      // entries between the rows of gamma and phi, >= every Ts_h
+    double rho;
+    int nstreams, nhyp;
+    int tiles_max;          // residue tiles of the fold launch: the largest ceil(Ts_h / (4 threads))
+    int w_max;              // the largest w[h]
+    int nb_max;             // the largest nb_h = ceil(Ts_h / kCpsBlock)
+    int ng_max;             // the largest ng[h]
+    int tu[kCpsHypMax], cp[kCpsHypMax];
+    int w[kCpsHypMax];      // runs of symbols per stream: each workgroup walks a contiguous run of the nsym[h] symbols
+    int ng[kCpsHypMax];     // groups of contiguous runs the totals launch adds up on their own, 1 ... kCpsGroupMax
+    long long nsym[kCpsHypMax];      // S_h: (S_h - 1) Ts_h + Ts_h - 1 + Tu_h < nsamples, the bound of every load
+    size_t part_off[kCpsHypMax], grp_off[kCpsHypMax], tot_off[kCpsHypMax];      // in doubles from `rows`
+};
+int cps_fold_threads(int ts_max);                 // 64, 128 or 256 by the launch's largest Ts
+int cps_fold_blocks_per_cu(int threads);
+hipError_t launch_cps_fold(int threads, const CpsArgs &a, hipStream_t s);
+hipError_t launch_cps_finalize(const CpsArgs &a, hipStream_t s);      // two launches: the groups' rows, then the totals, the window and est
+
 // ---- welchmat.hip: spectral matrix of C coherent channels on a Welch plan - sum_s conj(X_s,a) X_s,b for a <= b, then
 // S = scale T / M and the generalized coherence 1 - det G, G_ab = T_ab / sqrt(T_aa T_bb) ---------------------------------------
 constexpr int kMatChanMax = 8;      // channels at most; the kernels are built for a capacity of 2, 4 and 8

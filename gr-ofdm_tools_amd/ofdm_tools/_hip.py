@@ -146,6 +146,10 @@ SIGNATURES = {
     'oth_channelizer_pending': (C.c_int, [_p, C.POINTER(C.c_size_t)]),
     'oth_channelizer_push_dev': (C.c_int, [_p, _p, C.c_size_t, _p, C.c_size_t, _u64p]),
     'oth_channelizer_push': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _p, C.c_size_t, _u64p]),
+    'oth_cp_sync_dev': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_float,
+                                  C.c_size_t, _p, _p, _p, _u64p]),
+    'oth_cp_sync': (C.c_int, [_p, _p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_float, C.c_size_t,
+                              _p, _f, _f, _u64p]),
     'oth_rows_group_mean': (C.c_int, [_p, _f, C.c_size_t, C.c_int, C.c_int, _f]),
     'oth_channel_power': (C.c_int, [_p, _f, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     _f, _f]),
@@ -424,6 +428,42 @@ class Context(object):
         every channel per decim input samples (nchan, nchan / 2 or nchan / 4; nchan // 2 by default), a real prototype of
         taps * nchan taps (1 <= taps <= 16; windows.pfb_prototype(nchan, taps) by default).  -> Channelizer."""
         return Channelizer(self, nchan, decim, taps, prototype)
+
+    # -- cyclic-prefix synchronisation ----------------------------------------------
+    def cp_sync(self, x, hyps, rho=1.0, nsamples=None, want_rows=True):
+        """Cyclic-prefix symbol timing and carrier offset (oth_cp_sync) of one capture - a host complex64 array, or a device
+        pointer with nsamples - at the hypotheses hyps = [(Tu, cp), ...] (1 ... 16 of them; 8 <= Tu <= 16384, 1 <= cp <= Tu).
+        -> (gamma, phi, est, nsym): gamma[h] complex64 [Tu + cp] and phi[h] float32 [Tu + cp], the folded correlation and energy
+        under the circular cp-window (None, None with want_rows=False); est float32 [nhyp, 4] = theta, eps, rho_hat,
+        Lambda[theta] with Lambda = |gamma| - rho phi; nsym uint64 [nhyp] the symbols folded."""
+        tu, cp, nhyp, row = cp_sync_args(hyps)
+        src, count, dev = _src(x, nsamples)
+        gamma = np.zeros((nhyp, row), np.complex64) if want_rows else None
+        phi = np.zeros((nhyp, row), np.float32) if want_rows else None
+        est = np.empty((nhyp, 4), np.float32)
+        nsym = np.zeros(max(nhyp, 1), np.uint64)
+        ip = C.POINTER(C.c_int)
+        self.check(self.lib.oth_cp_sync(self.h, src, count, dev, nhyp, tu.ctypes.data_as(ip), cp.ctypes.data_as(ip), float(rho), row,
+                                        gamma.ctypes.data_as(_p) if want_rows else None, _fptr(phi) if want_rows else None,
+                                        _fptr(est), nsym.ctypes.data_as(_u64p)), 'oth_cp_sync')
+        if not want_rows:
+            return None, None, est, nsym
+        ts = tu + cp
+        return [gamma[h, :ts[h]] for h in range(nhyp)], [phi[h, :ts[h]] for h in range(nhyp)], est, nsym
+
+    def cp_sync_dev(self, iq_dev, nsamples, hyps, est_dev, gamma_dev=0, phi_dev=0, row_stride=None, rho=1.0, nstreams=1, stride=None):
+        """The same on device-resident streams with device outputs (oth_cp_sync_dev), asynchronous on the context's stream:
+        nstreams streams every `stride` samples (the rows of Channelizer.push_dev as they are), est_dev float32
+        [nstreams][nhyp][4], gamma_dev complex64 and phi_dev float32 [nstreams][nhyp][row_stride] (0: left out; row_stride
+        defaults to the largest Tu + cp; the columns behind a hypothesis' Tu + cp are not written).  -> nsym uint64 [nhyp]."""
+        tu, cp, nhyp, row = cp_sync_args(hyps)
+        nsym = np.zeros(max(nhyp, 1), np.uint64)
+        ip = C.POINTER(C.c_int)
+        self.check(self.lib.oth_cp_sync_dev(self.h, _optp(iq_dev), int(nsamples), int(nstreams), int(nsamples if stride is None else stride),
+                                            nhyp, tu.ctypes.data_as(ip), cp.ctypes.data_as(ip), float(rho),
+                                            int(row if row_stride is None else row_stride), _optp(gamma_dev), _optp(phi_dev),
+                                            _optp(est_dev), nsym.ctypes.data_as(_u64p)), 'oth_cp_sync_dev')
+        return nsym
 
     # -- small ops --------------------------------------------------------------
     def rows_group_mean(self, rows, group):
@@ -1434,6 +1474,15 @@ class Chain(object):
 
 CHAN_SIZES = (64, 128, 256, 512, 1024, 2048, 4096)      # the channel counts chanpfb.hip is built for
 CHAN_TAPS_MAX = 16
+
+
+def cp_sync_args(hyps):
+    """The hypotheses [(Tu, cp), ...] of Context.cp_sync as the library takes them -> (tu int32 [nhyp], cp int32 [nhyp], nhyp,
+    the rows' width: the largest Tu + cp, held inside 1 ... 32768 - the library refuses the lengths behind that)."""
+    h = np.asarray(hyps, np.int64).reshape(-1, 2)
+    tu, cp = np.ascontiguousarray(h[:, 0], np.int32), np.ascontiguousarray(h[:, 1], np.int32)
+    row = int(min(max(int((h[:, 0] + h[:, 1]).max()) if len(h) else 1, 1), 32768))
+    return tu, cp, len(h), row
 
 
 def channelizer_args(nchan, decim=None, taps=8, prototype=None):

@@ -1098,6 +1098,42 @@ def ofdm_blind_parameters(vector, Sf, fft_lens=(64, 128, 256, 512), cp_fractions
     return ofdm_blind_decision(np.fft.ifftshift(caf, axes=-1), r, nseg, Sf, fft_lens, cp_fractions, p_false)
 
 
+def ofdm_sync_scan(vector, fft_len, cp_len, Sf, rho=1.0, ctx=None):
+    """Where a symbol of a CP-OFDM signal of known lengths starts and how far its carrier is off, by the cyclic-prefix
+    correlator folded over all symbols of the capture (Context.cp_sync, one hypothesis): Lambda[t] = |gamma[t]| - rho phi[t]
+    over t < fft_len + cp_len, `rho` the weight of the energy term (1: the likelihood at high SNR, 0: the correlation alone).
+    -> dict: timing = theta, the samples from the capture's first to the first sample of a cyclic prefix modulo
+    fft_len + cp_len; eps, the carrier offset in subcarrier spacings (|eps| <= 1/2: the fractional part only);
+    cfo_hz = eps * Sf / fft_len; rho = rho_hat = |gamma[theta]| / phi[theta], about SNR / (SNR + 1);
+    snr_db = 10 log10(rho / (1 - rho)), inf at rho >= 1 and -inf at rho <= 0; nsym, the symbols folded; gamma complex64 and phi
+    float32 [fft_len + cp_len].  A capture with a NaN or inf sample gives NaN timing, eps, rho and snr_db."""
+    ctx = ctx or _hip.default_context()
+    gamma, phi, est, nsym = ctx.cp_sync(vector, [(int(fft_len), int(cp_len))], rho=rho)
+    theta, eps, rho_hat = float(est[0, 0]), float(est[0, 1]), float(est[0, 2])
+    if not rho_hat == rho_hat:
+        snr_db = float('nan')
+    elif rho_hat >= 1.0:
+        snr_db = float('inf')
+    elif rho_hat <= 0.0:
+        snr_db = float('-inf')
+    else:
+        snr_db = 10.0 * math.log10(rho_hat / (1.0 - rho_hat))
+    return {'timing': int(theta) if theta == theta else theta, 'eps': eps, 'cfo_hz': eps * float(Sf) / float(fft_len), 'rho': rho_hat,
+            'snr_db': snr_db, 'nsym': int(nsym[0]), 'gamma': gamma[0], 'phi': phi[0]}
+
+
+def ofdm_blind_sync(vector, Sf, rho=1.0, ctx=None, **kw):
+    """ofdm_blind_parameters(vector, Sf, **kw), and on a detected signal ofdm_sync_scan at the lengths it found.  -> the two
+    dicts merged; both name a `rho`, so the correlation coefficient at lag Tu of ofdm_blind_parameters is `caf_rho` here and
+    `rho` the synchroniser's rho_hat.  Not detected: the dict of ofdm_blind_parameters as it is."""
+    found = ofdm_blind_parameters(vector, Sf, ctx=ctx, **kw)
+    if not found['detected']:
+        return found
+    out = dict(found, caf_rho=found['rho'])
+    out.update(ofdm_sync_scan(vector, found['fft_len'], found['cp_len'], Sf, rho=rho, ctx=ctx))
+    return out
+
+
 class SpectrumScan(object):
     """The legacy sensor's scan (reference: ofdm_cr_tools.py:471-537; its matplotlib branch is not carried over), split
     where the GPU works: the constructor enqueues the PSD of the chosen method ('welch': flat-top Welch, 'fft': one

@@ -958,6 +958,62 @@ int oth_channelizer_push_dev(oth_channelizer *ch, const void *iq_dev, size_t nsa
 int oth_channelizer_push(oth_channelizer *ch, const void *iq, size_t nsamples, int src_is_device, void *out_host,
                          size_t out_stride, uint64_t *nframes_out);
 
+/* ---- cyclic-prefix symbol timing and carrier offset (additions inside ABI 6; probe by the symbols) -------------------------
+ * oth_cp_sync_dev / oth_cp_sync: where a symbol of a CP-OFDM signal starts and how far its carrier is off, by the
+ * cyclic-prefix correlator (van de Beek, Sandell, Boerjesson 1997) folded over all symbols of a capture - the step behind
+ * oth_welch_caf (which finds Tu and cp) and oth_welch_cyclic (which confirms the signal).  They hang off the context, not a
+ * plan: no transform, window or scaling is involved.  Per stream x of nsamples complex64 samples and per hypothesis
+ * h = (Tu, cp), with 8 <= Tu <= 16384, 1 <= cp <= Tu and Ts = Tu + cp <= 32768:
+ *   S        = floor((nsamples - Tu) / Ts)                     symbols folded; S >= 1 or the call is refused
+ *   z[n]     = x[n + Tu] conj(x[n])                            the lag product of oth_welch_caf: re = fma(ar, br, ai bi), im = ai br - ar bi
+ *   e[n]     = (|x[n]|^2 + |x[n + Tu]|^2) / 2
+ *   F[r]     = sum_{s < S} z[r + s Ts]        G[r] = sum_{s < S} e[r + s Ts]           r < Ts
+ *   Gamma[t] = sum_{j < cp} F[(t + j) mod Ts] Phi[t] = sum_{j < cp} G[(t + j) mod Ts]  t < Ts   (circular window)
+ *   Lambda[t]= |Gamma[t]| - rho Phi[t]                         rho a caller's float, 0 <= rho <= 1
+ *   theta    = the lowest t that maximises Lambda
+ *   eps      = arg(Gamma[theta]) / (2 pi)                      carrier offset in subcarrier spacings, |eps| <= 1/2; in cycles per sample: eps / Tu
+ *   rho_hat  = |Gamma[theta]| / Phi[theta]   (0 where Phi == 0)    -> SNR = rho_hat / (1 - rho_hat)
+ * The last sample read is S Ts - 1 + Tu <= nsamples - 1: nothing behind a stream's own nsamples is touched.  theta counts
+ * from sample 0 of the stream to the first sample of a cyclic prefix, modulo Ts.
+ * Outputs: gamma [nstreams][nhyp][row_stride] complex64 and phi [nstreams][nhyp][row_stride] float32, of which the columns
+ * Ts_h ... row_stride - 1 are not written; est [nstreams][nhyp][4] float32 = theta, eps, rho_hat, Lambda[theta] (theta is
+ * exact as a float: Ts <= 32768); nsym_out host uint64[nhyp] = S per hypothesis, by host arithmetic.  gamma and phi may be
+ * NULL, est may not.
+ * oth_cp_sync_dev: device in, device out, asynchronous on the context's stream; nstreams streams every stream_stride samples
+ * as oth_welch_exec_dev (at most 65535) - the rows of oth_channelizer_push_dev as they are.  oth_cp_sync: one stream from a
+ * host or device source, host outputs, blocking.  Three launches (csrc/cpsync.hip): the fold into one row of F re, F im, G per
+ * run of symbols (float32 over blocks of at most 64 symbols, the blocks in double), the rows' totals, and the window with
+ * the maximum - all sums behind the first in double, Gamma and Phi rounded to float32 once, Lambda formed from the unrounded
+ * sums.  No atomics: the same call on the same device gives the same bytes.  The runs of symbols (W per hypothesis: what the
+ * device holds at once over streams x hypotheses, at most S; the environment variable OTH_CPS_WG, read per call, caps it)
+ * decide the order of the sums, so a hypothesis gives the same bytes alone and next to others whenever its W is the same
+ * (always when S is below the device's share, or under OTH_CPS_WG).  The rows live in scratch the context owns; it grows when
+ * needed and a call that finds it large enough allocates nothing.
+ * All-zero input: Gamma, Phi and Lambda are exact zeros and est is (0, 0, 0, 0).  A sample with a NaN or +-inf part poisons
+ * the residues it enters (n mod Ts and (n - Tu) mod Ts): every Gamma / Phi entry whose window covers a poisoned residue reads
+ * NaN (never inf), every other entry of the row keeps the clean run's bits, est of a row with a non-finite entry is four
+ * NaNs, and the other streams and hypotheses of the call are untouched bit for bit.
+ * Refused, the reason in oth_last_error(), before anything is allocated, staged or launched; the context goes on working.
+ * In this order:
+ *   OTH_ERR_INVALID      a NULL input, tu, cp, est or nsym_out; nstreams < 1     "bad argument"
+ *                        nhyp outside 1 ... 16                                    "nhyp must lie in 1 ... 16"
+ *                        Tu outside 8 ... 16384                                   "Tu must lie in 8 ... 16384, not <Tu>"
+ *                        cp outside 1 ... Tu                                      "cp must lie in 1 ... Tu, not <cp>"
+ *                        rho outside [0, 1] or not finite                         "rho must be a finite value in 0 ... 1"
+ *                        stream_stride < nsamples                                 "stream_stride < nsamples"
+ *   OTH_ERR_UNSUPPORTED  more than 65535 streams                                  "cp_sync takes at most 65535 streams per launch"
+ *   OTH_ERR_INVALID      row_stride below the largest Ts                          "row_stride below the largest Tu + cp (<Ts>)"
+ *                        a hypothesis with S == 0                                 "input shorter than one symbol and its lag
+ *                                                                                 (2 Tu + cp = <n> samples)"
+ * Not provided: a streaming form that carries F / G across calls, fractional-sample timing, the integer part of the carrier
+ * offset, pilot- or preamble-based synchronisation, Ts above 32768. */
+int oth_cp_sync_dev(oth_ctx *ctx, const void *iq_dev, size_t nsamples, int nstreams, size_t stream_stride,
+                    int nhyp, const int *tu, const int *cp, float rho, size_t row_stride,
+                    float *gamma_out_dev, float *phi_out_dev, float *est_out_dev, uint64_t *nsym_out);
+int oth_cp_sync(oth_ctx *ctx, const void *iq, size_t nsamples, int src_is_device,
+                int nhyp, const int *tu, const int *cp, float rho, size_t row_stride,
+                float *gamma_out, float *phi_out, float *est_out, uint64_t *nsym_out);
+
 /* ---- channel power -------------------------------------------------------
  * src_power (ofdm_cr_tools.py:232-249): |convolve(psd, ones(int(sb))/sb, 'same')|
  * then per-channel slice sums.  lo/hi are the slice bounds the host computed with
