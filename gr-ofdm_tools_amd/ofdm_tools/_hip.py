@@ -42,6 +42,9 @@ _p = C.c_void_p
 _pp = C.POINTER(C.c_void_p)
 _f = C.POINTER(C.c_float)
 _u64p = C.POINTER(C.c_uint64)
+_ip = C.POINTER(C.c_int)
+_dp = C.POINTER(C.c_double)
+_ubp = C.POINTER(C.c_ubyte)
 
 # name -> (restype, argtypes); must list every symbol include/ofdm_tools_hip.h declares
 SIGNATURES = {
@@ -228,7 +231,7 @@ def _src(x, nsamples):
     if nsamples is None:
         x = _c64(x)
         return x.ctypes.data_as(_p), len(x), 0
-    return C.c_void_p(x), int(nsamples), 1
+    return x, int(nsamples), 1
 
 
 def _src2(x, y, nsamples):
@@ -239,9 +242,22 @@ def _src2(x, y, nsamples):
     return sx, sy, count, dev
 
 
-def _optp(v):
-    """a device pointer, or NULL for a row the caller leaves out"""
-    return C.c_void_p(v) if v else None
+def _channels(x, nsamples):
+    """The input of the matrix family -> (pointer, samples per channel, channels, src_is_device): a host complex64 array
+    (C, n), or a device pointer to [C][nsamples] when nsamples is given as (C, nsamples).  (The pointer holds on to the
+    array it was taken from.)"""
+    if nsamples is None:
+        x = np.asarray(x)
+        if x.ndim != 2:
+            raise ValueError('x must be a (C, n) array of C channels')
+        x = np.ascontiguousarray(x, np.complex64)
+        nchan, count, src, dev = x.shape[0], x.shape[1], x.ctypes.data_as(_p), 0
+    else:
+        nchan, count = (int(v) for v in nsamples)
+        src, dev = x, 1
+    if not 2 <= nchan <= 8:
+        raise ValueError('the spectral matrix takes 2 ... 8 channels, not %d' % nchan)
+    return src, count, nchan, dev
 
 
 def _eig_of(of):
@@ -273,7 +289,25 @@ def unpack_matrix(packed, nchan):
     return S
 
 
-class Context(object):
+class _Handle(object):
+    """What Context, WelchPlan, Chain and Channelizer share: a handle self.h of the library under a context self.ctx (a
+    Context has none: it is its own), and the one way their methods call it.  The prototypes of load() convert the arguments: a device pointer goes in as the
+    integer it is, 0 or None for a row the caller leaves out is NULL."""
+
+    def _call(self, name, *args):
+        """lib.<name>(self.h, *args); anything but OTH_OK raises HipError under the same name"""
+        ctx = getattr(self, 'ctx', self)
+        ctx.check(getattr(ctx.lib, name)(self.h, *args), name)
+
+    def _count(self, name, *args):
+        """The same with a uint64_t * behind the arguments -> what the library wrote there: segments, rows, frames.  (Spelled
+        out, not on top of _call: a second Python frame per call showed in the host cost, profiles/binding_fold_ab.txt.)"""
+        n, ctx = C.c_uint64(), getattr(self, 'ctx', self)
+        ctx.check(getattr(ctx.lib, name)(self.h, *args, C.byref(n)), name)
+        return n.value
+
+
+class Context(_Handle):
     """One device + one HIP stream (oth_ctx).  The library serialises calls per context, so blocks
     running on different scheduler threads may share one."""
 
@@ -283,7 +317,7 @@ class Context(object):
         if stream is None:
             rc = self.lib.oth_ctx_create(int(device), C.byref(h))
         else:
-            rc = self.lib.oth_ctx_create_on_stream(int(device), C.c_void_p(int(stream)), C.byref(h))
+            rc = self.lib.oth_ctx_create_on_stream(int(device), int(stream), C.byref(h))
         if rc != OK:
             raise HipError(rc, 'oth_ctx_create', self.lib.oth_last_error(None).decode())
         self.h = h
@@ -338,58 +372,52 @@ class Context(object):
 
     # -- plumbing -------------------------------------------------------------
     def sync(self):
-        self.check(self.lib.oth_ctx_sync(self.h), 'oth_ctx_sync')
+        self._call('oth_ctx_sync')
 
     def device_name(self):
         buf = C.create_string_buffer(256)
-        self.check(self.lib.oth_ctx_device_name(self.h, buf, 256), 'oth_ctx_device_name')
+        self._call('oth_ctx_device_name', buf, 256)
         return buf.value.decode()
 
     def set_timing(self, on):
-        self.check(self.lib.oth_ctx_set_timing(self.h, 1 if on else 0), 'oth_ctx_set_timing')
+        self._call('oth_ctx_set_timing', 1 if on else 0)
 
     def get_timing(self, reset=True):
         ms, n = C.c_double(), C.c_uint64()
-        self.check(self.lib.oth_ctx_get_timing(self.h, C.byref(ms), C.byref(n), 1 if reset else 0),
-                   'oth_ctx_get_timing')
+        self._call('oth_ctx_get_timing', C.byref(ms), C.byref(n), 1 if reset else 0)
         return ms.value, n.value
 
     def alloc(self, nbytes):
         p = C.c_void_p()
-        self.check(self.lib.oth_dev_alloc(self.h, nbytes, C.byref(p)), 'oth_dev_alloc')
+        self._call('oth_dev_alloc', nbytes, C.byref(p))
         return p.value
 
     def free(self, ptr):
-        self.check(self.lib.oth_dev_free(self.h, C.c_void_p(ptr)), 'oth_dev_free')
+        self._call('oth_dev_free', ptr)
 
     def h2d(self, dptr, arr):
         arr = np.ascontiguousarray(arr)
-        self.check(self.lib.oth_memcpy_h2d(self.h, C.c_void_p(dptr), arr.ctypes.data_as(_p), arr.nbytes),
-                   'oth_memcpy_h2d')
+        self._call('oth_memcpy_h2d', dptr, arr.ctypes.data_as(_p), arr.nbytes)
 
     def d2h(self, dptr, shape, dtype):
         out = np.empty(shape, dtype)
-        self.check(self.lib.oth_memcpy_d2h(self.h, out.ctypes.data_as(_p), C.c_void_p(dptr), out.nbytes),
-                   'oth_memcpy_d2h')
+        self._call('oth_memcpy_d2h', out.ctypes.data_as(_p), dptr, out.nbytes)
         return out
 
     def synth_iq(self, dptr, nsamples, seed, tones=(), dc=0j):
         amp = np.array([t[0] for t in tones], np.float32)
         frq = np.array([t[1] for t in tones], np.float32)
-        self.check(self.lib.oth_synth_iq(self.h, C.c_void_p(dptr), nsamples, seed, len(tones),
-                                         _fptr(amp) if len(tones) else None, _fptr(frq) if len(tones) else None,
-                                         float(np.real(dc)), float(np.imag(dc))), 'oth_synth_iq')
+        self._call('oth_synth_iq', dptr, nsamples, seed, len(tones), _fptr(amp) if len(tones) else None,
+                   _fptr(frq) if len(tones) else None, float(np.real(dc)), float(np.imag(dc)))
 
     def stream_read_probe(self, dptr, nbytes, repeats=5):
         ms = C.c_double()
-        self.check(self.lib.oth_stream_read_probe(self.h, C.c_void_p(dptr), nbytes, repeats, C.byref(ms)),
-                   'oth_stream_read_probe')
+        self._call('oth_stream_read_probe', dptr, nbytes, repeats, C.byref(ms))
         return ms.value
 
     def iq_power(self, dptr, nsamples):
         mr, mi, var = C.c_double(), C.c_double(), C.c_double()
-        self.check(self.lib.oth_iq_power(self.h, C.c_void_p(dptr), nsamples, C.byref(mr), C.byref(mi),
-                                         C.byref(var)), 'oth_iq_power')
+        self._call('oth_iq_power', dptr, nsamples, C.byref(mr), C.byref(mi), C.byref(var))
         return complex(mr.value, mi.value), var.value
 
     # -- factories ------------------------------------------------------------
@@ -442,10 +470,9 @@ class Context(object):
         phi = np.zeros((nhyp, row), np.float32) if want_rows else None
         est = np.empty((nhyp, 4), np.float32)
         nsym = np.zeros(max(nhyp, 1), np.uint64)
-        ip = C.POINTER(C.c_int)
-        self.check(self.lib.oth_cp_sync(self.h, src, count, dev, nhyp, tu.ctypes.data_as(ip), cp.ctypes.data_as(ip), float(rho), row,
-                                        gamma.ctypes.data_as(_p) if want_rows else None, _fptr(phi) if want_rows else None,
-                                        _fptr(est), nsym.ctypes.data_as(_u64p)), 'oth_cp_sync')
+        self._call('oth_cp_sync', src, count, dev, nhyp, tu.ctypes.data_as(_ip), cp.ctypes.data_as(_ip), float(rho), row,
+                   gamma.ctypes.data_as(_p) if want_rows else None, _fptr(phi) if want_rows else None, _fptr(est),
+                   nsym.ctypes.data_as(_u64p))
         if not want_rows:
             return None, None, est, nsym
         ts = tu + cp
@@ -458,11 +485,9 @@ class Context(object):
         defaults to the largest Tu + cp; the columns behind a hypothesis' Tu + cp are not written).  -> nsym uint64 [nhyp]."""
         tu, cp, nhyp, row = cp_sync_args(hyps)
         nsym = np.zeros(max(nhyp, 1), np.uint64)
-        ip = C.POINTER(C.c_int)
-        self.check(self.lib.oth_cp_sync_dev(self.h, _optp(iq_dev), int(nsamples), int(nstreams), int(nsamples if stride is None else stride),
-                                            nhyp, tu.ctypes.data_as(ip), cp.ctypes.data_as(ip), float(rho),
-                                            int(row if row_stride is None else row_stride), _optp(gamma_dev), _optp(phi_dev),
-                                            _optp(est_dev), nsym.ctypes.data_as(_u64p)), 'oth_cp_sync_dev')
+        self._call('oth_cp_sync_dev', iq_dev, int(nsamples), int(nstreams), int(nsamples if stride is None else stride), nhyp,
+                   tu.ctypes.data_as(_ip), cp.ctypes.data_as(_ip), float(rho), int(row if row_stride is None else row_stride),
+                   gamma_dev, phi_dev, est_dev, nsym.ctypes.data_as(_u64p))
         return nsym
 
     # -- small ops --------------------------------------------------------------
@@ -470,8 +495,7 @@ class Context(object):
         rows = np.ascontiguousarray(rows, np.float32)
         nrows, nfft = rows.shape
         out = np.empty((nrows // group, nfft), np.float32)
-        self.check(self.lib.oth_rows_group_mean(self.h, _fptr(rows), nrows, nfft, group, _fptr(out)),
-                   'oth_rows_group_mean')
+        self._call('oth_rows_group_mean', _fptr(rows), nrows, nfft, group, _fptr(out))
         return out
 
     def channel_power(self, psd, srch_bins, lo, hi, want_movavg=False):
@@ -480,10 +504,8 @@ class Context(object):
         hi = np.ascontiguousarray(hi, np.int32)
         out = np.empty(len(lo), np.float32)
         ma = np.empty(len(psd), np.float32) if want_movavg else None
-        self.check(self.lib.oth_channel_power(self.h, _fptr(psd), len(psd), float(srch_bins), len(lo),
-                                              lo.ctypes.data_as(C.POINTER(C.c_int)),
-                                              hi.ctypes.data_as(C.POINTER(C.c_int)), _fptr(out),
-                                              _fptr(ma) if want_movavg else None), 'oth_channel_power')
+        self._call('oth_channel_power', _fptr(psd), len(psd), float(srch_bins), len(lo), lo.ctypes.data_as(_ip),
+                   hi.ctypes.data_as(_ip), _fptr(out), _fptr(ma) if want_movavg else None)
         return (out, ma) if want_movavg else out
 
     def bin_threshold(self, psd_rows, srch_bins, thr_leveler):
@@ -492,9 +514,8 @@ class Context(object):
         nrows, nfft = rows.shape
         mask = np.empty((nrows, nfft), np.uint8)
         noise = np.empty(nrows, np.float32)
-        self.check(self.lib.oth_bin_threshold(self.h, _fptr(rows), nrows, nfft, float(srch_bins), float(thr_leveler),
-                                              mask.ctypes.data_as(C.POINTER(C.c_ubyte)), _fptr(noise)),
-                   'oth_bin_threshold')
+        self._call('oth_bin_threshold', _fptr(rows), nrows, nfft, float(srch_bins), float(thr_leveler),
+                   mask.ctypes.data_as(_ubp), _fptr(noise))
         return mask, noise
 
     def scan_decide_dev(self, rows_dptr, nrows, nfft, srch_bins, thr_leveler, lo=(), hi=(), want_mask=True):
@@ -506,12 +527,9 @@ class Context(object):
         mask = np.empty((nrows, nfft), np.uint8) if want_mask else None
         noise = np.empty(nrows, np.float32)
         power = np.empty((nrows, nch), np.float32)
-        ip = C.POINTER(C.c_int)
-        self.check(self.lib.oth_scan_decide_dev(self.h, C.c_void_p(rows_dptr), int(nrows), int(nfft), float(srch_bins),
-                                                float(thr_leveler), nch, lo.ctypes.data_as(ip) if nch else None,
-                                                hi.ctypes.data_as(ip) if nch else None,
-                                                mask.ctypes.data_as(C.POINTER(C.c_ubyte)) if want_mask else None,
-                                                _fptr(noise), _fptr(power) if nch else None), 'oth_scan_decide_dev')
+        self._call('oth_scan_decide_dev', rows_dptr, int(nrows), int(nfft), float(srch_bins), float(thr_leveler), nch,
+                   lo.ctypes.data_as(_ip) if nch else None, hi.ctypes.data_as(_ip) if nch else None,
+                   mask.ctypes.data_as(_ubp) if want_mask else None, _fptr(noise), _fptr(power) if nch else None)
         return mask, noise, power
 
     def scan_decide_dev_out(self, rows_dptr, nrows, nfft, srch_bins, thr_leveler, lo, hi, noise_dptr, power_dptr,
@@ -520,24 +538,20 @@ class Context(object):
         lo = np.ascontiguousarray(lo, np.int32)
         hi = np.ascontiguousarray(hi, np.int32)
         nch = len(lo)
-        ip = C.POINTER(C.c_int)
-        self.check(self.lib.oth_scan_decide_dev_out(self.h, C.c_void_p(rows_dptr), int(nrows), int(nfft), float(srch_bins),
-                                                    float(thr_leveler), nch, lo.ctypes.data_as(ip) if nch else None,
-                                                    hi.ctypes.data_as(ip) if nch else None,
-                                                    C.c_void_p(mask_dptr) if mask_dptr else None, C.c_void_p(noise_dptr),
-                                                    C.c_void_p(power_dptr) if nch else None), 'oth_scan_decide_dev_out')
+        self._call('oth_scan_decide_dev_out', rows_dptr, int(nrows), int(nfft), float(srch_bins), float(thr_leveler), nch,
+                   lo.ctypes.data_as(_ip) if nch else None, hi.ctypes.data_as(_ip) if nch else None, mask_dptr, noise_dptr,
+                   power_dptr if nch else None)
 
     def xcorr(self, a, b, length):
         a, b = _c64(a)[:length], _c64(b)[:length]
         out = np.empty(length - length // 2, np.float32)
-        self.check(self.lib.oth_xcorr(self.h, a.ctypes.data_as(_p), len(a), b.ctypes.data_as(_p), len(b),
-                                      int(length), _fptr(out)), 'oth_xcorr')
+        self._call('oth_xcorr', a.ctypes.data_as(_p), len(a), b.ctypes.data_as(_p), len(b), int(length), _fptr(out))
         return out
 
     def fac(self, data, length):
         a = _c64(data)[:length]
         out = np.empty(length - length // 2, np.float32)
-        self.check(self.lib.oth_fac(self.h, a.ctypes.data_as(_p), len(a), int(length), _fptr(out)), 'oth_fac')
+        self._call('oth_fac', a.ctypes.data_as(_p), len(a), int(length), _fptr(out))
         return out
 
 
@@ -553,7 +567,7 @@ def average_code(average):
     return int(average)
 
 
-class WelchPlan(object):
+class WelchPlan(_Handle):
     def __init__(self, ctx, nfft, nperseg, noverlap, window, detrend, scaling, fs, fftshift, trim_bins, db, kernel):
         self.ctx = ctx
         # exec_async() tickets not collected yet, and the last one issued; poll() / wait() may run on other threads
@@ -568,17 +582,20 @@ class WelchPlan(object):
             if w.shape != (nperseg,):
                 raise ValueError('window must have nperseg=%d entries' % nperseg)
         h = C.c_void_p()
-        ctx.check(ctx.lib.oth_welch_plan(ctx.h, int(nfft), nperseg, noverlap, _fptr(w) if w is not None else None,
-                                         int(detrend), int(scaling), float(fs), 1 if fftshift else 0,
-                                         int(trim_bins), C.byref(h)), 'oth_welch_plan')
+        ctx._call('oth_welch_plan', int(nfft), nperseg, noverlap, _fptr(w) if w is not None else None, int(detrend),
+                  int(scaling), float(fs), 1 if fftshift else 0, int(trim_bins), C.byref(h))
+        self._created(h, db)
+        if kernel != KERNEL_AUTO:
+            self._call('oth_plan_set_kernel', int(kernel))
+
+    def _created(self, h, db):
+        """the tail of a plan's constructor: the new handle, its output length, dB output where asked for"""
         self.h = h
         n = C.c_int()
-        ctx.check(ctx.lib.oth_plan_out_len(h, C.byref(n)), 'oth_plan_out_len')
+        self._call('oth_plan_out_len', C.byref(n))
         self.out_len = n.value
         if db:
-            ctx.check(ctx.lib.oth_plan_set_output_db(h, 1), 'oth_plan_set_output_db')
-        if kernel != KERNEL_AUTO:
-            ctx.check(ctx.lib.oth_plan_set_kernel(h, int(kernel)), 'oth_plan_set_kernel')
+            self._call('oth_plan_set_output_db', 1)
 
     def close(self):
         if getattr(self, 'h', None) and getattr(self.ctx, 'h', None):
@@ -591,22 +608,27 @@ class WelchPlan(object):
         except Exception:
             pass
 
+    def _rows(self, k, j):
+        """The output rows of a statistic's host form that takes k of them, the first j asked for -> (j float32 rows of
+        out_len, k pointers: those rows, then NULL for the rows left out)"""
+        rows = [np.empty(self.out_len, np.float32) for _ in range(j)]
+        return rows, [_fptr(r) for r in rows] + [None] * (k - j)
+
     def set_kernel(self, which):
-        self.ctx.check(self.ctx.lib.oth_plan_set_kernel(self.h, int(which)), 'oth_plan_set_kernel')
+        self._call('oth_plan_set_kernel', int(which))
 
     def set_tuning(self, variant=None, sched=-1, chunk=0, tail=0):
         """A/B tools and the parity suite: pick a build of the 4096-point kernel ('dpp', 'pipe', 'ws'), override the
         schedule, set the segments per chunk / tail chunk.  Defaults restore the library's choices."""
         v = variant.encode() if variant else None
-        self.ctx.check(self.ctx.lib.oth_plan_set_tuning(self.h, v, int(sched), int(chunk), int(tail)),
-                       'oth_plan_set_tuning')
+        self._call('oth_plan_set_tuning', v, int(sched), int(chunk), int(tail))
 
     def set_schedule(self, which):
-        self.ctx.check(self.ctx.lib.oth_plan_set_schedule(self.h, int(which)), 'oth_plan_set_schedule')
+        self._call('oth_plan_set_schedule', int(which))
 
     def set_hostwait(self, sync):
         """True: exec() / wait() sleep in hipStreamSynchronize instead of polling the completion word (low CPU)."""
-        self.ctx.check(self.ctx.lib.oth_plan_set_hostwait(self.h, HOSTWAIT_SYNC if sync else HOSTWAIT_POLL), 'oth_plan_set_hostwait')
+        self._call('oth_plan_set_hostwait', HOSTWAIT_SYNC if sync else HOSTWAIT_POLL)
 
     def nseg(self, nsamples):
         return (nsamples - self.noverlap) // self.step if nsamples >= self.nperseg else 0
@@ -617,7 +639,7 @@ class WelchPlan(object):
         """'mean' / 'median' (or AVERAGE_*): how exec / exec_async / exec_dev average the segments' periodograms.  The
         median refuses the partial / scale / accumulate / csd calls (HipError OTH_ERR_UNSUPPORTED)."""
         code = average_code(average)
-        self.ctx.check(self.ctx.lib.oth_plan_set_average(self.h, code), 'oth_plan_set_average')
+        self._call('oth_plan_set_average', code)
         self.average = code
 
     def segments(self, x):
@@ -641,10 +663,7 @@ class WelchPlan(object):
 
     def segments_dev(self, dptr, nsamples, rows_dptr, capacity):
         """Asynchronous: device in, device out [nseg][out_len] float32 (capacity >= nseg rows).  -> nseg"""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_segments_dev(self.h, C.c_void_p(dptr), int(nsamples), C.c_void_p(rows_dptr),
-                                                           int(capacity), C.byref(n)), 'oth_welch_segments_dev')
-        return n.value
+        return self._count('oth_welch_segments_dev', dptr, int(nsamples), rows_dptr, int(capacity))
 
     def sk(self, x, return_psd=False, nsamples=None):
         """Spectral kurtosis (oth_welch_sk) of one capture: per bin SK = (M + 1) / (M - 1) (M S2 / S1^2 - 1) over the M
@@ -653,23 +672,16 @@ class WelchPlan(object):
         -> SK (float32, out_len bins, the plan's fftshift and trim; never dB), or with return_psd (SK, PSD): the row exec()
         gives for the same input.  Sets last_nseg (M).  Needs at least two segments and a mean-averaging Welch plan of a
         power-of-two length 64 ... 16384 (HipError otherwise)."""
-        rows = [np.empty(self.out_len, np.float32) for _ in range(2 if return_psd else 1)]
-        n = C.c_uint64()
+        rows, ptrs = self._rows(2, 2 if return_psd else 1)
         src, count, dev = _src(x, nsamples)
-        self.ctx.check(self.ctx.lib.oth_welch_sk(self.h, src, count, dev, _fptr(rows[0]), _fptr(rows[1]) if return_psd else None,
-                                                 C.byref(n)), 'oth_welch_sk')
-        self.last_nseg = n.value
+        self.last_nseg = self._count('oth_welch_sk', src, count, dev, *ptrs)
         return tuple(rows) if return_psd else rows[0]
 
     def sk_dev(self, iq_dev, nsamples, nstreams, stride, sk_dev, psd_dev=None):
         """Asynchronous: device in, device out - [nstreams][out_len] float32 at sk_dev and, where given, psd_dev.
         -> segments per stream (also last_nseg)."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_sk_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
-                                                     C.c_void_p(sk_dev), _optp(psd_dev), C.byref(n)),
-                       'oth_welch_sk_dev')
-        self.last_nseg = n.value
-        return n.value
+        self.last_nseg = self._count('oth_welch_sk_dev', iq_dev, int(nsamples), int(nstreams), int(stride), sk_dev, psd_dev)
+        return self.last_nseg
 
     ncycles = 0      # (class default: no cycle frequencies until set_cycles)
 
@@ -681,7 +693,7 @@ class WelchPlan(object):
         a = np.ascontiguousarray(np.atleast_1d(alphas), np.float64)
         if a.ndim != 1:
             raise ValueError('alphas must be a sequence of cycle frequencies')
-        self.ctx.check(self.ctx.lib.oth_welch_set_cycles(self.h, len(a), a.ctypes.data_as(C.POINTER(C.c_double))), 'oth_welch_set_cycles')
+        self._call('oth_welch_set_cycles', len(a), a.ctypes.data_as(_dp))
         self.ncycles = len(a)
 
     def cyclic(self, x, return_psd=False, nsamples=None):
@@ -695,23 +707,18 @@ class WelchPlan(object):
         A, m = int(self.ncycles), self.out_len
         scf, coh = np.empty((max(A, 1), m), np.complex64), np.empty((max(A, 1), m), np.float32)
         psd = np.empty(m, np.float32) if return_psd else None
-        n = C.c_uint64()
         src, count, dev = _src(x, nsamples)
-        self.ctx.check(self.ctx.lib.oth_welch_cyclic(self.h, src, count, dev, scf.ctypes.data_as(_f), _fptr(coh),
-                                                     _fptr(psd) if return_psd else None, C.byref(n)), 'oth_welch_cyclic')
-        self.last_nseg = n.value
+        self.last_nseg = self._count('oth_welch_cyclic', src, count, dev, scf.ctypes.data_as(_f), _fptr(coh),
+                                     _fptr(psd) if return_psd else None)
         return (scf, coh, psd) if return_psd else (scf, coh)
 
     def cyclic_dev(self, iq_dev, nsamples, nstreams, stride, coh_dev, scf_dev=None, psd_dev=None):
         """Asynchronous: device in, device out - [nstreams][A][out_len] float32 at coh_dev and, where given,
         [nstreams][A][out_len] re, im pairs at scf_dev and [nstreams][out_len] at psd_dev.
         -> segments per stream (also last_nseg)."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_cyclic_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
-                                                         _optp(scf_dev), C.c_void_p(coh_dev),
-                                                         _optp(psd_dev), C.byref(n)), 'oth_welch_cyclic_dev')
-        self.last_nseg = n.value
-        return n.value
+        self.last_nseg = self._count('oth_welch_cyclic_dev', iq_dev, int(nsamples), int(nstreams), int(stride), scf_dev, coh_dev,
+                                     psd_dev)
+        return self.last_nseg
 
     nlags = 0      # (class default: no lags until set_lags)
 
@@ -723,7 +730,7 @@ class WelchPlan(object):
         if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
             raise ValueError('lags must be a sequence of integer lags in samples')
         a = np.ascontiguousarray(np.clip(a.astype(np.int64), -1, 1 << 30), np.intc)      # (out of range stays out of range)
-        self.ctx.check(self.ctx.lib.oth_welch_set_lags(self.h, len(a), a.ctypes.data_as(C.POINTER(C.c_int))), 'oth_welch_set_lags')
+        self._call('oth_welch_set_lags', len(a), a.ctypes.data_as(_ip))
         self.nlags = len(a)
 
     def caf(self, x, return_r=False, nsamples=None):
@@ -737,21 +744,15 @@ class WelchPlan(object):
         L, m = int(self.nlags), self.out_len
         caf = np.empty((max(L, 1), m), np.float32)
         r = np.empty(max(L, 1), np.complex64) if return_r else None
-        n = C.c_uint64()
         src, count, dev = _src(x, nsamples)
-        self.ctx.check(self.ctx.lib.oth_welch_caf(self.h, src, count, dev, _fptr(caf), r.ctypes.data_as(_f) if return_r else None,
-                                                  C.byref(n)), 'oth_welch_caf')
-        self.last_nseg = n.value
+        self.last_nseg = self._count('oth_welch_caf', src, count, dev, _fptr(caf), r.ctypes.data_as(_f) if return_r else None)
         return (caf, r) if return_r else caf
 
     def caf_dev(self, iq_dev, nsamples, nstreams, stride, caf_dev, r_dev=None):
         """Asynchronous: device in, device out - [nstreams][L][out_len] float32 at caf_dev and, where given, [nstreams][L]
         re, im pairs at r_dev.  -> segments per stream (also last_nseg)."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_caf_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
-                                                      C.c_void_p(caf_dev), _optp(r_dev), C.byref(n)), 'oth_welch_caf_dev')
-        self.last_nseg = n.value
-        return n.value
+        self.last_nseg = self._count('oth_welch_caf_dev', iq_dev, int(nsamples), int(nstreams), int(stride), caf_dev, r_dev)
+        return self.last_nseg
 
     ntaps = 0      # (class default: no prototype until set_prototype)
 
@@ -767,7 +768,7 @@ class WelchPlan(object):
             ntaps = len(a) // self.nfft
         elif 1 <= int(ntaps) and len(a) != int(ntaps) * self.nfft:
             raise ValueError('the prototype holds ntaps * nfft = %d taps, not %d' % (int(ntaps) * self.nfft, len(a)))
-        self.ctx.check(self.ctx.lib.oth_welch_set_prototype(self.h, int(ntaps), _fptr(a)), 'oth_welch_set_prototype')
+        self._call('oth_welch_set_prototype', int(ntaps), _fptr(a))
         self.ntaps = int(ntaps)
 
     def pfb(self, x, nsamples=None):
@@ -779,20 +780,15 @@ class WelchPlan(object):
         -> float32 [out_len] with the plan's scaling (the prototype in the window's place), fftshift, trim and dB.  Sets
         last_nseg (M)."""
         out = np.empty(self.out_len, np.float32)
-        n = C.c_uint64()
         src, count, dev = _src(x, nsamples)
-        self.ctx.check(self.ctx.lib.oth_welch_pfb(self.h, src, count, dev, _fptr(out), C.byref(n)), 'oth_welch_pfb')
-        self.last_nseg = n.value
+        self.last_nseg = self._count('oth_welch_pfb', src, count, dev, _fptr(out))
         return out
 
     def pfb_dev(self, iq_dev, nsamples, nstreams, stride, out_dev):
         """Asynchronous: device in, device out - [nstreams][out_len] float32 at out_dev.  -> frames per stream (also
         last_nseg)."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_pfb_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
-                                                      C.c_void_p(out_dev), C.byref(n)), 'oth_welch_pfb_dev')
-        self.last_nseg = n.value
-        return n.value
+        self.last_nseg = self._count('oth_welch_pfb_dev', iq_dev, int(nsamples), int(nstreams), int(stride), out_dev)
+        return self.last_nseg
 
     def matrix(self, x, return_gcoh=True, nsamples=None):
         """Spectral matrix and generalized coherence (oth_welch_matrix) of C coherent channels, 2 <= C <= 8: with X_s,a the
@@ -804,24 +800,12 @@ class WelchPlan(object):
         S[b][a] = conj(S[a][b]) and the plan's fftshift and trim, gcoh float32 [out_len]), or S alone with
         return_gcoh=False.  A bin where a channel holds no power reads 0 in that channel's rows and in gcoh.  Sets
         last_nseg (M); with M < C the matrix is singular and gcoh reads 1."""
-        if nsamples is None:
-            x = np.asarray(x)
-            if x.ndim != 2:
-                raise ValueError('x must be a (C, n) array of C channels')
-            x = np.ascontiguousarray(x, np.complex64)
-            nchan, count, src, dev = x.shape[0], x.shape[1], x.ctypes.data_as(_p), 0
-        else:
-            nchan, count = (int(v) for v in nsamples)
-            src, dev = C.c_void_p(x), 1
-        if not 2 <= nchan <= 8:
-            raise ValueError('the spectral matrix takes 2 ... 8 channels, not %d' % nchan)
+        src, count, nchan, dev = _channels(x, nsamples)
         m, pairs = self.out_len, nchan * (nchan + 1) // 2
         packed = np.empty((pairs, m), np.complex64)
         gcoh = np.empty(m, np.float32) if return_gcoh else None
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_matrix(self.h, src, count, nchan, dev, packed.ctypes.data_as(_f),
-                                                     _fptr(gcoh) if return_gcoh else None, C.byref(n)), 'oth_welch_matrix')
-        self.last_nseg = n.value
+        self.last_nseg = self._count('oth_welch_matrix', src, count, nchan, dev, packed.ctypes.data_as(_f),
+                                     _fptr(gcoh) if return_gcoh else None)
         S = unpack_matrix(packed, nchan)
         return (S, gcoh) if return_gcoh else S
 
@@ -829,11 +813,8 @@ class WelchPlan(object):
         """Asynchronous: device in, device out - the packed upper triangle [C (C + 1) / 2][out_len] re, im pairs at s_dev
         (pairs (0,0), (0,1), ..., (0,C-1), (1,1), ...: unpack_matrix) and [out_len] float32 at gcoh_dev; either may be left
         out, not both.  stride: samples between channels.  -> segments per channel (also last_nseg)."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_matrix_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nchan), int(stride),
-                                                         _optp(s_dev), _optp(gcoh_dev), C.byref(n)), 'oth_welch_matrix_dev')
-        self.last_nseg = n.value
-        return n.value
+        self.last_nseg = self._count('oth_welch_matrix_dev', iq_dev, int(nsamples), int(nchan), int(stride), s_dev, gcoh_dev)
+        return self.last_nseg
 
     def matrix_eig(self, x, of='S', return_vector=True, nsamples=None):
         """Eigenvalues and principal eigenvector per bin (oth_welch_matrix_eig) of the spectral matrix S of matrix()
@@ -844,37 +825,21 @@ class WelchPlan(object):
         the largest eigenvalue with component 0 real and >= 0), or eig alone with return_vector=False.  A bin with a silent
         channel reads an exact 0 eigenvalue of S and all ones of G; a non-finite sample reads NaN everywhere.  Sets
         last_nseg (M); with M < C the trailing C - M eigenvalues read 0 up to rounding."""
-        if nsamples is None:
-            x = np.asarray(x)
-            if x.ndim != 2:
-                raise ValueError('x must be a (C, n) array of C channels')
-            x = np.ascontiguousarray(x, np.complex64)
-            nchan, count, src, dev = x.shape[0], x.shape[1], x.ctypes.data_as(_p), 0
-        else:
-            nchan, count = (int(v) for v in nsamples)
-            src, dev = C.c_void_p(x), 1
-        if not 2 <= nchan <= 8:
-            raise ValueError('the spectral matrix takes 2 ... 8 channels, not %d' % nchan)
+        src, count, nchan, dev = _channels(x, nsamples)
         m = self.out_len
         eig = np.empty((nchan, m), np.float32)
         vec = np.empty((nchan, m), np.complex64) if return_vector else None
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_matrix_eig(self.h, src, count, nchan, dev, _eig_of(of), _fptr(eig),
-                                                         vec.ctypes.data_as(_f) if return_vector else None, C.byref(n)),
-                       'oth_welch_matrix_eig')
-        self.last_nseg = n.value
+        self.last_nseg = self._count('oth_welch_matrix_eig', src, count, nchan, dev, _eig_of(of), _fptr(eig),
+                                     vec.ctypes.data_as(_f) if return_vector else None)
         return (eig, vec) if return_vector else eig
 
     def matrix_eig_dev(self, iq_dev, nsamples, nchan, stride, of, eig_dev=None, vec_dev=None):
         """Asynchronous: device in, device out - [C][out_len] float32 at eig_dev (the rows descend) and [C][out_len] re, im
         pairs at vec_dev; either may be left out, not both.  of: 'S' / 'G' or EIG_OF_S / EIG_OF_G.  stride: samples between
         channels.  -> segments per channel (also last_nseg)."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_matrix_eig_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nchan), int(stride),
-                                                             _eig_of(of), _optp(eig_dev), _optp(vec_dev), C.byref(n)),
-                       'oth_welch_matrix_eig_dev')
-        self.last_nseg = n.value
-        return n.value
+        self.last_nseg = self._count('oth_welch_matrix_eig_dev', iq_dev, int(nsamples), int(nchan), int(stride), _eig_of(of),
+                                     eig_dev, vec_dev)
+        return self.last_nseg
 
     ndir = 0      # (class default: no steering table until set_steering)
     DOA_METHODS = ('bartlett', 'capon', 'music')
@@ -886,13 +851,12 @@ class WelchPlan(object):
         table; an empty array clears it."""
         a = np.ascontiguousarray(delays, np.float64)
         if a.size == 0:
-            self.ctx.check(self.ctx.lib.oth_welch_set_steering(self.h, 0, 0, None, float(fc)), 'oth_welch_set_steering')
+            self._call('oth_welch_set_steering', 0, 0, None, float(fc))
             self.ndir = 0
             return
         if a.ndim != 2:
             raise ValueError('delays must be a (D, C) array: a row of C channel delays per direction')
-        self.ctx.check(self.ctx.lib.oth_welch_set_steering(self.h, a.shape[0], a.shape[1], a.ctypes.data_as(C.POINTER(C.c_double)),
-                                                           float(fc)), 'oth_welch_set_steering')
+        self._call('oth_welch_set_steering', a.shape[0], a.shape[1], a.ctypes.data_as(_dp), float(fc))
         self.ndir = a.shape[0]
 
     def matrix_doa(self, x, of='S', nsrc=None, loading=0.0, methods=('bartlett', 'capon', 'music'), nsamples=None):
@@ -911,36 +875,19 @@ class WelchPlan(object):
             raise ValueError("methods must name at least one of 'bartlett', 'capon', 'music'")
         if 'music' in methods and nsrc is None:
             raise ValueError('the MUSIC spectrum needs nsrc, the number of sources')
-        if nsamples is None:
-            x = np.asarray(x)
-            if x.ndim != 2:
-                raise ValueError('x must be a (C, n) array of C channels')
-            x = np.ascontiguousarray(x, np.complex64)
-            nchan, count, src, dev = x.shape[0], x.shape[1], x.ctypes.data_as(_p), 0
-        else:
-            nchan, count = (int(v) for v in nsamples)
-            src, dev = C.c_void_p(x), 1
-        if not 2 <= nchan <= 8:
-            raise ValueError('the spectral matrix takes 2 ... 8 channels, not %d' % nchan)
+        src, count, nchan, dev = _channels(x, nsamples)
         rows = {m: np.empty((self.ndir, self.out_len), np.float32) for m in methods}
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_matrix_doa(self.h, src, count, nchan, dev, _eig_of(of), int(nsrc or 0), float(loading),
-                                                         *[_fptr(rows[m]) if m in rows else None for m in self.DOA_METHODS],
-                                                         C.byref(n)), 'oth_welch_matrix_doa')
-        self.last_nseg = n.value
+        self.last_nseg = self._count('oth_welch_matrix_doa', src, count, nchan, dev, _eig_of(of), int(nsrc or 0), float(loading),
+                                     *[_fptr(rows[m]) if m in rows else None for m in self.DOA_METHODS])
         return rows
 
     def matrix_doa_dev(self, iq_dev, nsamples, nchan, stride, of, nsrc, loading, bartlett_dev=None, capon_dev=None, music_dev=None):
         """Asynchronous: device in, device out - [D][out_len] float32 at each of bartlett_dev, capon_dev and music_dev; any may
         be left out, not all three (nsrc is read only with music_dev).  of: 'S' / 'G' or EIG_OF_S / EIG_OF_G.  stride: samples
         between channels.  -> segments per channel (also last_nseg)."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_matrix_doa_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nchan), int(stride),
-                                                             _eig_of(of), int(nsrc or 0), float(loading), _optp(bartlett_dev),
-                                                             _optp(capon_dev), _optp(music_dev), C.byref(n)),
-                       'oth_welch_matrix_doa_dev')
-        self.last_nseg = n.value
-        return n.value
+        self.last_nseg = self._count('oth_welch_matrix_doa_dev', iq_dev, int(nsamples), int(nchan), int(stride), _eig_of(of),
+                                     int(nsrc or 0), float(loading), bartlett_dev, capon_dev, music_dev)
+        return self.last_nseg
 
     def _gcc_args(self, band, upsample, maxlag):
         """band=None: every bin; maxlag=None: NI / 2 - 1 (NI = upsample nfft) -> (lo, hi, upsample, maxlag) as integers"""
@@ -964,26 +911,13 @@ class WelchPlan(object):
         order of gcc_pairs(C)), or the first three with return_rows=False.  The plan's scaling, fftshift, trim and dB take
         no part.  A pair with a silent channel reads 0 everywhere; a non-finite sample reads NaN in its channel's pairs.
         Sets last_nseg (M)."""
-        if nsamples is None:
-            x = np.asarray(x)
-            if x.ndim != 2:
-                raise ValueError('x must be a (C, n) array of C channels')
-            x = np.ascontiguousarray(x, np.complex64)
-            nchan, count, src, dev = x.shape[0], x.shape[1], x.ctypes.data_as(_p), 0
-        else:
-            nchan, count = (int(v) for v in nsamples)
-            src, dev = C.c_void_p(x), 1
-        if not 2 <= nchan <= 8:
-            raise ValueError('the spectral matrix takes 2 ... 8 channels, not %d' % nchan)
+        src, count, nchan, dev = _channels(x, nsamples)
         lo, hi, upsample, maxlag = self._gcc_args(band, upsample, maxlag)
         npairs = nchan * (nchan - 1) // 2
         rows = np.empty((npairs, 2 * max(maxlag, 0) + 1), np.complex64) if return_rows else None
         peak = np.empty((npairs, 3), np.float32)
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_matrix_gcc(self.h, src, count, nchan, dev, _gcc_weighting(weighting), lo, hi, upsample, maxlag,
-                                                         rows.ctypes.data_as(_f) if return_rows else None, _fptr(peak), C.byref(n)),
-                       'oth_welch_matrix_gcc')
-        self.last_nseg = n.value
+        self.last_nseg = self._count('oth_welch_matrix_gcc', src, count, nchan, dev, _gcc_weighting(weighting), lo, hi, upsample,
+                                     maxlag, rows.ctypes.data_as(_f) if return_rows else None, _fptr(peak))
         delays, peaks, phases = np.zeros((nchan, nchan), np.float32), np.eye(nchan, dtype=np.float32), np.zeros((nchan, nchan), np.float32)
         for (a, b), (tau, top, arg) in zip(gcc_pairs(nchan), peak):
             delays[a, b], delays[b, a] = tau, -tau
@@ -996,47 +930,37 @@ class WelchPlan(object):
         float32 (delay in samples, |R|, arg R at the peak) at peak_dev; either may be left out, not both.  weighting, band,
         upsample and maxlag as in matrix_gcc.  stride: samples between channels.  -> segments per channel (also last_nseg)."""
         lo, hi, upsample, maxlag = self._gcc_args(band, upsample, maxlag)
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_matrix_gcc_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nchan), int(stride),
-                                                             _gcc_weighting(weighting), lo, hi, upsample, maxlag, _optp(gcc_dev),
-                                                             _optp(peak_dev), C.byref(n)), 'oth_welch_matrix_gcc_dev')
-        self.last_nseg = n.value
-        return n.value
+        self.last_nseg = self._count('oth_welch_matrix_gcc_dev', iq_dev, int(nsamples), int(nchan), int(stride),
+                                     _gcc_weighting(weighting), lo, hi, upsample, maxlag, gcc_dev, peak_dev)
+        return self.last_nseg
 
     def last_recipe(self):
         """Diagnostics: 'kernel=... form=... pilot=... sched=... chunk=... W=...' of the last averaging launch."""
         buf = C.create_string_buffer(512)
-        self.ctx.check(self.ctx.lib.oth__debug_last_recipe(self.h, buf, 512), 'oth__debug_last_recipe')
+        self._call('oth__debug_last_recipe', buf, 512)
         return buf.value.decode()
+
+    def _exec(self, x, nsamples):
+        """exec (nsamples=None) and exec_device_src"""
+        out = np.empty(self.out_len, np.float32)
+        src, count, dev = _src(x, nsamples)
+        self.last_nseg = self._count('oth_welch_exec', src, count, dev, _fptr(out))
+        return out
 
     def exec(self, x):
         """x: host complex64 array -> float32 PSD of out_len bins."""
-        x = _c64(x)
-        out = np.empty(self.out_len, np.float32)
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_exec(self.h, x.ctypes.data_as(_p), len(x), 0, _fptr(out),
-                                                   C.byref(n)), 'oth_welch_exec')
-        self.last_nseg = n.value
-        return out
+        return self._exec(x, None)
 
     def exec_device_src(self, dptr, nsamples):
-        out = np.empty(self.out_len, np.float32)
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_exec(self.h, C.c_void_p(dptr), nsamples, 1, _fptr(out), C.byref(n)),
-                       'oth_welch_exec')
-        self.last_nseg = n.value
-        return out
+        return self._exec(dptr, nsamples)
 
     def exec_async(self, x, nsamples=None):
         """work() form: enqueue one Welch scan and return a ticket at once.  x: host complex64 array (may be reused as
         soon as the call returns), or a device pointer when nsamples is given."""
+        src, count, dev = _src(x, nsamples)
         t = C.c_uint64()
-        if nsamples is None:
-            x = _c64(x)
-            rc = self.ctx.lib.oth_welch_exec_async(self.h, x.ctypes.data_as(_p), len(x), 0, C.byref(t))
-        else:
-            rc = self.ctx.lib.oth_welch_exec_async(self.h, C.c_void_p(x), int(nsamples), 1, C.byref(t))
-        self.ctx.check(rc, 'oth_welch_exec_async')
+        # direct, not the helper: on the work() path its extra Python call showed (profiles/binding_fold_ab.txt)
+        self.ctx.check(self.ctx.lib.oth_welch_exec_async(self.h, src, count, dev, C.byref(t)), 'oth_welch_exec_async')
         with self._tickets_lock:
             self._tickets.add(int(t.value))
             self._last_ticket = int(t.value)
@@ -1062,8 +986,8 @@ class WelchPlan(object):
         """-> None while the GPU is still working, else the float32 PSD (last_nseg is set)."""
         out = np.empty(self.out_len, np.float32)
         n, ready = C.c_uint64(), C.c_int()
-        self.ctx.check(self.ctx.lib.oth_welch_poll(self.h, int(ticket), _fptr(out), C.byref(n), C.byref(ready)),
-                       'oth_welch_poll')
+        # direct, not the helper: on the work() path its extra Python call showed (profiles/binding_fold_ab.txt)
+        self.ctx.check(self.ctx.lib.oth_welch_poll(self.h, int(ticket), _fptr(out), C.byref(n), C.byref(ready)), 'oth_welch_poll')
         if not ready.value:
             return None
         self._collected(ticket)
@@ -1074,6 +998,7 @@ class WelchPlan(object):
         out = np.empty(self.out_len, np.float32)
         n = C.c_uint64()
         try:
+            # direct, not the helper: on the work() path its extra Python call showed (profiles/binding_fold_ab.txt)
             self.ctx.check(self.ctx.lib.oth_welch_wait(self.h, int(ticket), _fptr(out), C.byref(n)), 'oth_welch_wait')
         finally:
             self._collected(ticket)
@@ -1082,92 +1007,54 @@ class WelchPlan(object):
 
     def exec_dev(self, dptr, nsamples, out_dptr, nstreams=1, stream_stride=None):
         """Asynchronous: device in, device out ([nstreams][out_len] float32)."""
-        n = C.c_uint64()
         stride = nsamples if stream_stride is None else stream_stride
-        self.ctx.check(self.ctx.lib.oth_welch_exec_dev(self.h, C.c_void_p(dptr), nsamples, nstreams, stride,
-                                                       C.c_void_p(out_dptr), C.byref(n)), 'oth_welch_exec_dev')
-        return n.value
+        return self._count('oth_welch_exec_dev', dptr, nsamples, nstreams, stride, out_dptr)
 
     def partial_dev(self, dptr, nsamples, sum_dptr):
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_partial_dev(self.h, C.c_void_p(dptr), nsamples, C.c_void_p(sum_dptr),
-                                                          C.byref(n)), 'oth_welch_partial_dev')
-        return n.value
+        return self._count('oth_welch_partial_dev', dptr, nsamples, sum_dptr)
 
     def scale_dev(self, sum_dptr, nseg_total, out_dptr):
-        self.ctx.check(self.ctx.lib.oth_welch_scale_dev(self.h, C.c_void_p(sum_dptr), nseg_total,
-                                                        C.c_void_p(out_dptr)), 'oth_welch_scale_dev')
+        self._call('oth_welch_scale_dev', sum_dptr, nseg_total, out_dptr)
 
     def accumulate(self, x):
         x = _c64(x)
-        self.ctx.check(self.ctx.lib.oth_welch_accumulate(self.h, x.ctypes.data_as(_p), len(x)),
-                       'oth_welch_accumulate')
+        self._call('oth_welch_accumulate', x.ctypes.data_as(_p), len(x))
 
     def finalize(self):
         out = np.empty(self.out_len, np.float32)
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_welch_finalize(self.h, _fptr(out), C.byref(n)), 'oth_welch_finalize')
-        self.last_nseg = n.value
+        self.last_nseg = self._count('oth_welch_finalize', _fptr(out))
         return out
 
     def reset(self):
-        self.ctx.check(self.ctx.lib.oth_welch_reset(self.h), 'oth_welch_reset')
+        self._call('oth_welch_reset')
 
-    def csd(self, x, y):
-        """-> pxx, pyy, pxy (complex64), cxy for host inputs."""
-        x, y = _c64(x), _c64(y)
-        if len(x) != len(y):
-            raise ValueError('x and y must have the same length')
+    def _csd(self, x, y, nsamples):
+        """csd (nsamples=None) and csd_device_src"""
         m = self.out_len
         pxx, pyy, cxy = (np.empty(m, np.float32) for _ in range(3))
         pxy = np.empty(2 * m, np.float32)
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_csd_exec(self.h, x.ctypes.data_as(_p), y.ctypes.data_as(_p), len(x), 0,
-                                                 _fptr(pxx), _fptr(pyy), _fptr(pxy), _fptr(cxy), C.byref(n)),
-                       'oth_csd_exec')
-        self.last_nseg = n.value
+        sx, sy, count, dev = _src2(x, y, nsamples)
+        self.last_nseg = self._count('oth_csd_exec', sx, sy, count, dev, _fptr(pxx), _fptr(pyy), _fptr(pxy), _fptr(cxy))
         return pxx, pyy, pxy.view(np.complex64), cxy
 
+    def csd(self, x, y):
+        """-> pxx, pyy, pxy (complex64), cxy for host inputs."""
+        return self._csd(x, y, None)
 
-def _csd_device_src(self, dx, dy, nsamples):
-    """-> pxx, pyy, pxy (complex64), cxy for device inputs."""
-    m = self.out_len
-    pxx, pyy, cxy = (np.empty(m, np.float32) for _ in range(3))
-    pxy = np.empty(2 * m, np.float32)
-    n = C.c_uint64()
-    self.ctx.check(self.ctx.lib.oth_csd_exec(self.h, C.c_void_p(dx), C.c_void_p(dy), nsamples, 1, _fptr(pxx),
-                                             _fptr(pyy), _fptr(pxy), _fptr(cxy), C.byref(n)), 'oth_csd_exec')
-    self.last_nseg = n.value
-    return pxx, pyy, pxy.view(np.complex64), cxy
+    def csd_device_src(self, dx, dy, nsamples):
+        """-> pxx, pyy, pxy (complex64), cxy for device inputs."""
+        return self._csd(dx, dy, nsamples)
 
+    def csd_exec_dev(self, dx, dy, nsamples, pxx=0, pyy=0, pxy=0, cxy=0):
+        """Asynchronous: device in, device out (any output pointer may be 0)."""
+        return self._count('oth_csd_exec_dev', dx, dy, nsamples, pxx, pyy, pxy, cxy)
 
-WelchPlan.csd_device_src = _csd_device_src
+    def csd_partial_dev(self, dx, dy, nsamples, sums_dptr):
+        """Raw sums [sum|X|^2 | sum|Y|^2 | sum conj(X)Y re,im] (4 * nfft floats, natural order) of this time chunk."""
+        return self._count('oth_csd_partial_dev', dx, dy, nsamples, sums_dptr)
 
-
-def _csd_exec_dev(self, dx, dy, nsamples, pxx=0, pyy=0, pxy=0, cxy=0):
-    """Asynchronous: device in, device out (any output pointer may be 0)."""
-    n = C.c_uint64()
-    self.ctx.check(self.ctx.lib.oth_csd_exec_dev(self.h, C.c_void_p(dx), C.c_void_p(dy), nsamples, _optp(pxx), _optp(pyy),
-                                                 _optp(pxy), _optp(cxy), C.byref(n)), 'oth_csd_exec_dev')
-    return n.value
-
-
-def _csd_partial_dev(self, dx, dy, nsamples, sums_dptr):
-    """Raw sums [sum|X|^2 | sum|Y|^2 | sum conj(X)Y re,im] (4 * nfft floats, natural order) of this time chunk."""
-    n = C.c_uint64()
-    self.ctx.check(self.ctx.lib.oth_csd_partial_dev(self.h, C.c_void_p(dx), C.c_void_p(dy), nsamples,
-                                                    C.c_void_p(sums_dptr), C.byref(n)), 'oth_csd_partial_dev')
-    return n.value
-
-
-def _csd_scale_dev(self, sums_dptr, nseg_total, pxx=0, pyy=0, pxy=0, cxy=0):
-    self.ctx.check(self.ctx.lib.oth_csd_scale_dev(self.h, C.c_void_p(sums_dptr), int(nseg_total), _optp(pxx), _optp(pyy),
-                                                  _optp(pxy), _optp(cxy)), 'oth_csd_scale_dev')
-
-
-WelchPlan.csd_exec_dev = _csd_exec_dev
-WelchPlan.csd_partial_dev = _csd_partial_dev
-WelchPlan.csd_scale_dev = _csd_scale_dev
+    def csd_scale_dev(self, sums_dptr, nseg_total, pxx=0, pyy=0, pxy=0, cxy=0):
+        self._call('oth_csd_scale_dev', sums_dptr, int(nseg_total), pxx, pyy, pxy, cxy)
 
 
 def mtm_weights(weights, ntapers, slepian=True):
@@ -1227,16 +1114,9 @@ class MtmPlan(WelchPlan):
         self.ntapers = ntapers
         self.tapers, self.ratios = t, ratios
         h = C.c_void_p()
-        ctx.check(getattr(ctx.lib, self._CONSTRUCTOR)(ctx.h, int(nfft), nperseg, noverlap, self.ntapers, _fptr(t),
-                                                      _fptr(w) if w is not None else None, int(detrend), int(scaling),
-                                                      float(fs), 1 if fftshift else 0, int(trim_bins), C.byref(h)),
-                  self._CONSTRUCTOR)
-        self.h = h
-        n = C.c_int()
-        ctx.check(ctx.lib.oth_plan_out_len(h, C.byref(n)), 'oth_plan_out_len')
-        self.out_len = n.value
-        if db:
-            ctx.check(ctx.lib.oth_plan_set_output_db(h, 1), 'oth_plan_set_output_db')
+        ctx._call(self._CONSTRUCTOR, int(nfft), nperseg, noverlap, self.ntapers, _fptr(t), _fptr(w) if w is not None else None,
+                  int(detrend), int(scaling), float(fs), 1 if fftshift else 0, int(trim_bins), C.byref(h))
+        self._created(h, db)
         if slepian:      # (the computed ratio of a taper can come out an ulp past 1, or not above 0 far beyond 2 nw tapers)
             self.set_ratios(np.clip(ratios, np.finfo(np.float64).tiny, 1.0))
             self.ratios = ratios
@@ -1247,7 +1127,7 @@ class MtmPlan(WelchPlan):
         r = np.ascontiguousarray(ratios, np.float64)
         if r.shape != (self.ntapers,):
             raise ValueError('ratios must have ntapers=%d entries' % self.ntapers)
-        self.ctx.check(self.ctx.lib.oth_mtm_set_ratios(self.h, r.ctypes.data_as(C.POINTER(C.c_double))), 'oth_mtm_set_ratios')
+        self._call('oth_mtm_set_ratios', r.ctypes.data_as(_dp))
         self.ratios = r
 
     def adaptive(self, x, iters=4, return_dof=False, nsamples=None):
@@ -1258,46 +1138,34 @@ class MtmPlan(WelchPlan):
         -> PSD (float32, out_len bins, the plan's scaling, fftshift, trim and dB), or with return_dof (PSD, dof): the per-bin
         equivalent degrees of freedom 2 (sum w)^2 / sum w^2, mean over the segments, between 2 and 2 K, always linear.
         Sets last_nseg.  The plan's weights take no part."""
-        rows = [np.empty(self.out_len, np.float32) for _ in range(2 if return_dof else 1)]
-        n = C.c_uint64()
+        rows, ptrs = self._rows(2, 2 if return_dof else 1)
         src, count, dev = _src(x, nsamples)
-        self.ctx.check(self.ctx.lib.oth_mtm_adaptive(self.h, src, count, dev, int(iters), _fptr(rows[0]),
-                                                     _fptr(rows[1]) if return_dof else None, C.byref(n)), 'oth_mtm_adaptive')
-        self.last_nseg = n.value
+        self.last_nseg = self._count('oth_mtm_adaptive', src, count, dev, int(iters), *ptrs)
         return tuple(rows) if return_dof else rows[0]
 
     def adaptive_dev(self, iq_dev, nsamples, nstreams, stride, psd_dev, dof_dev=None, iters=4):
         """Asynchronous: device in, device out - [nstreams][out_len] float32 at psd_dev and, where given, dof_dev.
         -> segments per stream (also last_nseg)."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_mtm_adaptive_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
-                                                         int(iters), C.c_void_p(psd_dev), _optp(dof_dev),
-                                                         C.byref(n)), 'oth_mtm_adaptive_dev')
-        self.last_nseg = n.value
-        return n.value
+        self.last_nseg = self._count('oth_mtm_adaptive_dev', iq_dev, int(nsamples), int(nstreams), int(stride), int(iters), psd_dev,
+                                     dof_dev)
+        return self.last_nseg
 
     def ftest(self, x, return_rows=False, nsamples=None):
         """Thomson's harmonic F-test (oth_mtm_ftest) of one capture: per bin F = (K - 1) sum_s num_s / sum_s den_s, large
         where a coherent line sits at the bin whatever the background.  x: host complex64 array, or a device pointer when
         nsamples is given.  -> F (float32, out_len bins, the plan's fftshift and trim; always linear), or with return_rows
         (F, line, resid): the line's power and the background with the line removed.  Sets last_nseg (see dof)."""
-        rows = [np.empty(self.out_len, np.float32) for _ in range(3 if return_rows else 1)]
-        ptrs = [_fptr(r) for r in rows] + [None] * (3 - len(rows))
-        n = C.c_uint64()
+        rows, ptrs = self._rows(3, 3 if return_rows else 1)
         src, count, dev = _src(x, nsamples)
-        self.ctx.check(self.ctx.lib.oth_mtm_ftest(self.h, src, count, dev, ptrs[0], ptrs[1], ptrs[2], C.byref(n)), 'oth_mtm_ftest')
-        self.last_nseg = n.value
+        self.last_nseg = self._count('oth_mtm_ftest', src, count, dev, *ptrs)
         return tuple(rows) if return_rows else rows[0]
 
     def ftest_dev(self, iq_dev, nsamples, nstreams, stride, f_dev, line_dev=None, resid_dev=None):
         """Asynchronous: device in, device out - [nstreams][out_len] float32 at f_dev and, where given, line_dev and
         resid_dev.  -> segments per stream (also last_nseg)."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_mtm_ftest_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
-                                                      C.c_void_p(f_dev), _optp(line_dev), _optp(resid_dev), C.byref(n)),
-                       'oth_mtm_ftest_dev')
-        self.last_nseg = n.value
-        return n.value
+        self.last_nseg = self._count('oth_mtm_ftest_dev', iq_dev, int(nsamples), int(nstreams), int(stride), f_dev, line_dev,
+                                     resid_dev)
+        return self.last_nseg
 
     def jackknife(self, x, return_psd=False, nsamples=None):
         """Jackknife (oth_mtm_jackknife) of one capture over its M = ntapers * nseg (segment, taper) items: per bin the
@@ -1305,23 +1173,16 @@ class MtmPlan(WelchPlan):
         is psd * exp(-+ q * lnsd).  x: host complex64 array, or a device pointer when nsamples is given.  -> lnsd (float32,
         out_len bins, the plan's fftshift and trim; never dB, never scaled), or with return_psd (lnsd, PSD): the row exec()
         gives for the same input.  Sets last_nseg.  Needs equal weights and M >= 2 (HipError otherwise)."""
-        rows = [np.empty(self.out_len, np.float32) for _ in range(2 if return_psd else 1)]
-        n = C.c_uint64()
+        rows, ptrs = self._rows(2, 2 if return_psd else 1)
         src, count, dev = _src(x, nsamples)
-        self.ctx.check(self.ctx.lib.oth_mtm_jackknife(self.h, src, count, dev, _fptr(rows[0]), _fptr(rows[1]) if return_psd else None,
-                                                      C.byref(n)), 'oth_mtm_jackknife')
-        self.last_nseg = n.value
+        self.last_nseg = self._count('oth_mtm_jackknife', src, count, dev, *ptrs)
         return tuple(rows) if return_psd else rows[0]
 
     def jackknife_dev(self, iq_dev, nsamples, nstreams, stride, lnsd_dev, psd_dev=None):
         """Asynchronous: device in, device out - [nstreams][out_len] float32 at lnsd_dev and, where given, psd_dev.
         -> segments per stream (also last_nseg)."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_mtm_jackknife_dev(self.h, C.c_void_p(iq_dev), int(nsamples), int(nstreams), int(stride),
-                                                          C.c_void_p(lnsd_dev), _optp(psd_dev),
-                                                          C.byref(n)), 'oth_mtm_jackknife_dev')
-        self.last_nseg = n.value
-        return n.value
+        self.last_nseg = self._count('oth_mtm_jackknife_dev', iq_dev, int(nsamples), int(nstreams), int(stride), lnsd_dev, psd_dev)
+        return self.last_nseg
 
     @property
     def dof(self):
@@ -1342,26 +1203,19 @@ class MtmCsdPlan(MtmPlan):
         deviation of z = atanh(sqrt(cxy)) - the interval at Student-t quantile q (M - 1 degrees of freedom) is
         tanh(max(0, z -+ q * zsd)) ** 2 - and of each channel's ln PSD.  x, y: host complex64 arrays, or device pointers
         when nsamples is given.  Sets last_nseg.  Needs equal weights and M >= 3 (HipError otherwise)."""
-        rows = [np.empty(self.out_len, np.float32) for _ in range(4)]
-        n = C.c_uint64()
+        rows, ptrs = self._rows(4, 4)
         sx, sy, count, dev = _src2(x, y, nsamples)
-        self.ctx.check(self.ctx.lib.oth_mtm_csd_jackknife(self.h, sx, sy, count, dev, *([_fptr(r) for r in rows] + [C.byref(n)])),
-                       'oth_mtm_csd_jackknife')
-        self.last_nseg = n.value
+        self.last_nseg = self._count('oth_mtm_csd_jackknife', sx, sy, count, dev, *ptrs)
         return tuple(rows)
 
     def csd_jackknife_dev(self, dx, dy, nsamples, zsd_dev, cxy_dev=None, lnsdx_dev=None, lnsdy_dev=None):
         """Asynchronous: device in, device out - out_len float32 at zsd_dev and, where given, cxy_dev, lnsdx_dev and
         lnsdy_dev.  -> segments (also last_nseg)."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_mtm_csd_jackknife_dev(self.h, C.c_void_p(dx), C.c_void_p(dy), int(nsamples), _optp(cxy_dev),
-                                                              C.c_void_p(zsd_dev), _optp(lnsdx_dev), _optp(lnsdy_dev), C.byref(n)),
-                       'oth_mtm_csd_jackknife_dev')
-        self.last_nseg = n.value
-        return n.value
+        self.last_nseg = self._count('oth_mtm_csd_jackknife_dev', dx, dy, int(nsamples), cxy_dev, zsd_dev, lnsdx_dev, lnsdy_dev)
+        return self.last_nseg
 
 
-class Chain(object):
+class Chain(_Handle):
     """stream_to_vector -> keep_one_in_n -> fft_vcc -> |.|/|.|^2 [-> IIR -> log] with GNU Radio's
     streaming state kept on the device (oth_chain)."""
 
@@ -1374,9 +1228,8 @@ class Chain(object):
             if w.shape != (self.nfft,):
                 raise ValueError('window must have nfft entries')
         h = C.c_void_p()
-        ctx.check(ctx.lib.oth_chain_create(ctx.h, self.nfft, _fptr(w) if w is not None else None,
-                                           1 if fftshift else 0, int(epilogue), int(keep_one_in_n), C.byref(h)),
-                  'oth_chain_create')
+        ctx._call('oth_chain_create', self.nfft, _fptr(w) if w is not None else None, 1 if fftshift else 0, int(epilogue),
+                  int(keep_one_in_n), C.byref(h))
         self.h = h
 
     def close(self):
@@ -1391,84 +1244,76 @@ class Chain(object):
             pass
 
     def set_keep_one_in_n(self, n):
-        self.ctx.check(self.ctx.lib.oth_chain_set_keep_one_in_n(self.h, int(n)), 'oth_chain_set_keep_one_in_n')
+        self._call('oth_chain_set_keep_one_in_n', int(n))
 
     def set_iir_log(self, alpha, k_db):
-        self.ctx.check(self.ctx.lib.oth_chain_set_iir_log(self.h, float(alpha), float(k_db)),
-                       'oth_chain_set_iir_log')
+        self._call('oth_chain_set_iir_log', float(alpha), float(k_db))
 
     def set_kernel(self, which):
-        self.ctx.check(self.ctx.lib.oth_chain_set_kernel(self.h, int(which)), 'oth_chain_set_kernel')
+        self._call('oth_chain_set_kernel', int(which))
 
     def set_peak_hold(self, on):
-        self.ctx.check(self.ctx.lib.oth_chain_set_peak_hold(self.h, 1 if on else 0), 'oth_chain_set_peak_hold')
+        self._call('oth_chain_set_peak_hold', 1 if on else 0)
 
     def reset(self):
-        self.ctx.check(self.ctx.lib.oth_chain_reset(self.h), 'oth_chain_reset')
+        self._call('oth_chain_reset')
 
     def push(self, x, max_rows=None):
         """Feed samples; returns (rows, nrows_produced).  rows holds the LAST min(nrows, max_rows) rows."""
         x = _c64(x)
         cap = (len(x) // self.nfft + 2) if max_rows is None else int(max_rows)
         rows = np.empty((max(cap, 1), self.nfft), np.float32)
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_chain_push(self.h, x.ctypes.data_as(_p), len(x), 0, _fptr(rows), cap,
-                                                   C.byref(n)), 'oth_chain_push')
-        got = min(int(n.value), cap)
-        return rows[:got], int(n.value)
+        n = self._count('oth_chain_push', x.ctypes.data_as(_p), len(x), 0, _fptr(rows), cap)
+        return rows[:min(n, cap)], n
 
     def push_dev(self, dptr, nsamples, rows_dptr=0, capacity=0):
         """Asynchronous: device-resident samples in, the last `capacity` rows to rows_dptr (device).  -> rows produced."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_chain_push_dev(self.h, C.c_void_p(dptr), nsamples,
-                                                       C.c_void_p(rows_dptr) if rows_dptr else None, int(capacity),
-                                                       C.byref(n)), 'oth_chain_push_dev')
-        return int(n.value)
+        return self._count('oth_chain_push_dev', dptr, nsamples, rows_dptr, int(capacity))
 
     def push_async(self, x):
         """work() form: enqueue and return a ticket; the latest row is collected with poll() / wait()."""
         x = _c64(x)
         t = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_chain_push_async(self.h, x.ctypes.data_as(_p), len(x), C.byref(t)),
-                       'oth_chain_push_async')
-        return int(t.value)
+        # direct, not the helper: on the work() path its extra Python call showed (profiles/binding_fold_ab.txt)
+        self.ctx.check(self.ctx.lib.oth_chain_push_async(self.h, x.ctypes.data_as(_p), len(x), C.byref(t)), 'oth_chain_push_async')
+        return t.value
 
     def last_push_ops(self):
         """Stream operations (asynchronous copies + kernel launches) the last push enqueued."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_chain_last_push_ops(self.h, C.byref(n)), 'oth_chain_last_push_ops')
-        return int(n.value)
+        return self._count('oth_chain_last_push_ops')
 
     def ticket_rows(self, ticket):
         """Rows the push behind `ticket` produces (known at enqueue time; never waits)."""
         n = C.c_uint64()
+        # direct, not the helper: on the work() path its extra Python call showed (profiles/binding_fold_ab.txt)
         self.ctx.check(self.ctx.lib.oth_chain_ticket_rows(self.h, int(ticket), C.byref(n)), 'oth_chain_ticket_rows')
-        return int(n.value)
+        return n.value
 
     def poll(self, ticket):
         """-> None while the GPU is still working, else (row or None, rows produced by that push)."""
         row = np.empty(self.nfft, np.float32)
         n, ready = C.c_uint64(), C.c_int()
-        self.ctx.check(self.ctx.lib.oth_chain_poll(self.h, int(ticket), _fptr(row), C.byref(n), C.byref(ready)),
-                       'oth_chain_poll')
+        # direct, not the helper: on the work() path its extra Python call showed (profiles/binding_fold_ab.txt)
+        self.ctx.check(self.ctx.lib.oth_chain_poll(self.h, int(ticket), _fptr(row), C.byref(n), C.byref(ready)), 'oth_chain_poll')
         if not ready.value:
             return None
-        return (row if n.value else None), int(n.value)
+        return (row if n.value else None), n.value
 
     def wait(self, ticket):
         row = np.empty(self.nfft, np.float32)
         n = C.c_uint64()
+        # direct, not the helper: on the work() path its extra Python call showed (profiles/binding_fold_ab.txt)
         self.ctx.check(self.ctx.lib.oth_chain_wait(self.h, int(ticket), _fptr(row), C.byref(n)), 'oth_chain_wait')
-        return (row if n.value else None), int(n.value)
+        return (row if n.value else None), n.value
 
     def peak(self):
         out = np.empty(self.nfft, np.float32)
-        self.ctx.check(self.ctx.lib.oth_chain_get_peak(self.h, _fptr(out)), 'oth_chain_get_peak')
+        self._call('oth_chain_get_peak', _fptr(out))
         return out
 
     def iir(self):
         out = np.empty(self.nfft, np.float32)
-        self.ctx.check(self.ctx.lib.oth_chain_get_iir(self.h, _fptr(out)), 'oth_chain_get_iir')
+        self._call('oth_chain_get_iir', _fptr(out))
         return out
 
 
@@ -1509,7 +1354,7 @@ def channelizer_args(nchan, decim=None, taps=8, prototype=None):
     return nchan, decim, taps, h
 
 
-class Channelizer(object):
+class Channelizer(_Handle):
     """Polyphase channelizer with its streaming state on the device (oth_channelizer): one wideband stream in, nchan
     baseband rows out - y_k[m] = sum_n h[n] x[m D + n] exp(-2j pi k (m D + n) / nchan), k in natural (fftfreq) order, the
     phase that of the absolute sample index since creation or reset().  Any split of a stream into pushes gives the same
@@ -1519,8 +1364,7 @@ class Channelizer(object):
         self.nchan, self.decim, self.taps, self.prototype = channelizer_args(nchan, decim, taps, prototype)
         self.ctx = ctx
         h = C.c_void_p()
-        ctx.check(ctx.lib.oth_channelizer_create(ctx.h, self.nchan, self.decim, self.taps, _fptr(self.prototype), C.byref(h)),
-                  'oth_channelizer_create')
+        ctx._call('oth_channelizer_create', self.nchan, self.decim, self.taps, _fptr(self.prototype), C.byref(h))
         self.h = h
 
     def close(self):
@@ -1536,19 +1380,17 @@ class Channelizer(object):
 
     def reset(self):
         """the sample count back to 0, the pending tail emptied: the next push gives what a new channelizer gives"""
-        self.ctx.check(self.ctx.lib.oth_channelizer_reset(self.h), 'oth_channelizer_reset')
+        self._call('oth_channelizer_reset')
 
     def frames_for(self, nsamples):
         """frames the NEXT push of nsamples will yield (host arithmetic)"""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_channelizer_frames(self.h, int(nsamples), C.byref(n)), 'oth_channelizer_frames')
-        return int(n.value)
+        return self._count('oth_channelizer_frames', int(nsamples))
 
     @property
     def pending(self):
         """samples a later frame still needs, kept on the device: at most taps * nchan - 1"""
         n = C.c_size_t()
-        self.ctx.check(self.ctx.lib.oth_channelizer_pending(self.h, C.byref(n)), 'oth_channelizer_pending')
+        self._call('oth_channelizer_pending', C.byref(n))
         return int(n.value)
 
     def push(self, x, nsamples=None):
@@ -1557,24 +1399,19 @@ class Channelizer(object):
         src, count, dev = _src(x, nsamples)
         frames = self.frames_for(count)
         out = np.empty((self.nchan, frames), np.complex64)
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_channelizer_push(self.h, src, count, dev, out.ctypes.data_as(_p) if frames else None, frames,
-                                                         C.byref(n)), 'oth_channelizer_push')
-        assert int(n.value) == frames
+        n = self._count('oth_channelizer_push', src, count, dev, out.ctypes.data_as(_p) if frames else None, frames)
+        assert n == frames
         return out
 
     def push_dev(self, dptr, nsamples, out_dptr, out_stride):
         """Asynchronous: device-resident samples in, this push's frames to the columns 0 ... frames - 1 of the device
         buffer [nchan][out_stride] complex64 at out_dptr (0 / None where the push yields no frame).  -> frames."""
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.lib.oth_channelizer_push_dev(self.h, _optp(dptr), int(nsamples), _optp(out_dptr), int(out_stride),
-                                                             C.byref(n)), 'oth_channelizer_push_dev')
-        return int(n.value)
+        return self._count('oth_channelizer_push_dev', dptr, int(nsamples), out_dptr, int(out_stride))
 
     def last_recipe(self):
         """the launch of the last push that yielded frames (oth__debug_channelizer_recipe); '' before the first"""
         buf = C.create_string_buffer(512)
-        self.ctx.check(self.ctx.lib.oth__debug_channelizer_recipe(self.h, buf, 512), 'oth__debug_channelizer_recipe')
+        self._call('oth__debug_channelizer_recipe', buf, 512)
         return buf.value.decode()
 
     def channel_freqs(self, fs, fc=0.0):
