@@ -69,6 +69,17 @@ int get_twiddles(oth_ctx *c, int nfft, const float2 **out) {
     c->twiddles[nfft] = std::move(d);
     return OTH_OK;
 }
+
+// The three-shear form of the same twiddles (twiddle16.hip.h, rot3): entry kSymTwOrigin + e holds tan(theta / 2) and sin(theta),
+// theta = 2 pi e / 4096, for |e| <= kSymTwOrigin - inside (-0.54 pi, 0.54 pi), where the tangent stays below 1.14.
+std::vector<float2> symtw_table() {
+    std::vector<float2> h(2 * kSymTwOrigin + 1);
+    for (int e = -kSymTwOrigin; e <= kSymTwOrigin; ++e) {
+        const double a = 2.0 * M_PI * (double)e / 4096.0;
+        h[kSymTwOrigin + e] = make_float2((float)std::tan(0.5 * a), (float)std::sin(a));
+    }
+    return h;
+}
 }  // namespace oth
 
 extern "C" {

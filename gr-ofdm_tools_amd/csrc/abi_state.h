@@ -80,6 +80,9 @@ struct oth_plan {
     bool fast_detrend = false;         // OTH_DETREND_CONSTANT_FAST: the builds without the pilot (WelchArgs.pilot)
     bool rect_window = false;          // every window value is 1 (window == NULL or boxcar): builds without the multiply
     bool compl_window = false;         // w[n] + w[n + nfft / 2] = 1 to one float32 ulp (window_is_complementary, abi_welch.hip)
+                                       // and, in a detrending plan, a spectrum inside [-136, 120) (d_fd_sym)
+    DevBuf<float2> d_symtw;            // compl_window: WelchArgs.symtw
+    DevBuf<float2> d_fd_sym;           // compl_window, detrending: WelchArgs.fd_sym
     DevBuf<float> d_partial;
     DevBuf<float> d_reduce;            // stage-1 output of the two-stage partial-sum reduction
     DevBuf<float> d_out;               // [4][nfft] + pxy extra
@@ -283,6 +286,7 @@ int use_device(oth_ctx *c);
 int copy_in_and_wait(oth_ctx *c, void *dst, const void *src, size_t bytes);
 
 int get_twiddles(oth_ctx *c, int nfft, const float2 **out);
+std::vector<float2> symtw_table();      // WelchArgs.symtw (host)
 
 struct Timed {
     oth_ctx *c;

@@ -9,7 +9,9 @@
 namespace {
 // The transform of the n-point window (host_fft_pow2) into re / im -> true when it is negligible outside the bins
 // [0, band) and [n - band, n) that a frequency-domain detrend corrects: |W[k]|^2 <= 1e-10 sum(w^2) (see below).
-bool window_spectrum(const std::vector<float> &w, int n, int band, std::vector<double> &re, std::vector<double> &im) {
+// (band_neg: the bins [n - band_neg, n) instead, for a correction that reaches further down than up)
+bool window_spectrum(const std::vector<float> &w, int n, int band, std::vector<double> &re, std::vector<double> &im, int band_neg = 0) {
+    if (!band_neg) band_neg = band;
     re.assign(n, 0.0);
     im.assign(n, 0.0);
     double s2 = 0.0;
@@ -18,7 +20,7 @@ bool window_spectrum(const std::vector<float> &w, int n, int band, std::vector<d
         s2 += (double)w[i] * (double)w[i];
     }
     host_fft_pow2(re, im);
-    for (int k = band; k < n - band; ++k)
+    for (int k = band; k < n - band_neg; ++k)
         if (re[k] * re[k] + im[k] * im[k] > 1e-10 * s2) return false;
     return true;
 }
@@ -37,6 +39,27 @@ bool window_spectrum_table(const std::vector<float> &w, std::vector<float> &fd) 
         fd[4 * t + 1] = (float)im[k];
         fd[4 * t + 2] = (float)re[k + 3840];
         fd[4 * t + 3] = (float)im[k + 3840];
+    }
+    return true;
+}
+
+// The table of welch4096ws's complementary-window build (WelchArgs.fd_sym).  That build runs its three passes on signed digits
+// around the time origin n' = n - 136: register mu of consumer thread t = 16 k0 + k1 holds
+//     (-1)^(lambda + mu) e^(+2 pi i 136 k / 4096) X[k],   k = kappa + 16 lambda + 256 mu,  kappa = sym16(k0), lambda = sym16(k1),
+// so the registers mu = 0 are exactly the bins [-136, 120) and each thread corrects that one bin with FFT(w)[k] carrying the
+// same phase and sign, formed here in double.  The table exists when FFT(w) is negligible outside those bins, by the
+// criterion of window_spectrum_table (every periodic cosine-sum window: Hann reaches +-1, flattop +-4).
+bool window_spectrum_table_sym(const std::vector<float> &w, std::vector<float2> &fd) {
+    std::vector<double> re, im;
+    if (!window_spectrum(w, 4096, 120, re, im, kSymShift)) return false;
+    fd.resize(256);
+    for (int t = 0; t < 256; ++t) {
+        const int k0 = t >> 4, k1 = t & 15;
+        const int lambda = k1 < 8 ? k1 : k1 - 16;
+        const int k = (k0 < 8 ? k0 : k0 - 16) + 16 * lambda;
+        const double a = 2.0 * M_PI * (double)((kSymShift * k) % 4096) / 4096.0, sg = (lambda & 1) ? -1.0 : 1.0;
+        const double fr = re[(k + 4096) & 4095], fi = im[(k + 4096) & 4095];
+        fd[t] = make_float2((float)(sg * (fr * std::cos(a) - fi * std::sin(a))), (float)(sg * (fr * std::sin(a) + fi * std::cos(a))));
     }
     return true;
 }
@@ -239,6 +262,8 @@ Averaged run_average(oth_plan *p, const float2 *x, const float2 *y, size_t nsamp
         a.pilot_inline = r.pilot == 2 ? 1 : 0;
         // (read by launch_welch_tuned4096_ws only; the tuning word "wsgen" keeps the general build: the A/B and the parity tests)
         a.compl_win = p->compl_window && p->tune_variant != "wsgen" ? 1 : 0;
+        a.symtw = p->d_symtw.get();
+        a.fd_sym = p->d_fd_sym.get();
         Timed tm(c);
         switch (r.kern) {
             case RK_W4096: HIPCHK(c, r.variant->launch(a, c->stream)); break;
@@ -440,7 +465,10 @@ int oth_welch_plan(oth_ctx *c, int nfft, int nperseg, int noverlap, const float 
     p->win_host.assign(w.begin(), w.begin() + nperseg);                   // oth_welch_set_cycles' complex tapers
     if (const char *e = getenv("OTH_CYC_GROUP")) p->tune_cyc_group = atoi(e);
     if (const char *e = getenv("OTH_LAG_GROUP")) p->tune_lag_group = atoi(e);
-    p->compl_window = nfft == 4096 && nperseg == 4096 && window_is_complementary(w, nfft);      // the welch4096ws route's shape
+    // the welch4096ws route's shape; its complementary-window build detrends one bin per thread and needs its own table
+    std::vector<float2> fd_sym, symtw;
+    p->compl_window = nfft == 4096 && nperseg == 4096 && window_is_complementary(w, nfft) && (!det || window_spectrum_table_sym(w, fd_sym));
+    if (p->compl_window) symtw = symtw_table();
     // the host tables first, then the uploads: nothing between the first asynchronous copy and the synchronise can throw
     std::vector<float> fd, fd1x, wpm;
     const bool have_fd = det && ((nfft == 4096 && nperseg == 4096 && window_spectrum_table(w, fd)) ||
@@ -459,6 +487,8 @@ int oth_welch_plan(oth_ctx *c, int nfft, int nperseg, int noverlap, const float 
     if (e == hipSuccess) e = p->d_sum.alloc(sizeof(float) * nfft);
     if (e == hipSuccess) e = hipMemsetAsync(p->d_sum.get(), 0, sizeof(float) * nfft, c->stream);
     if (e == hipSuccess && have_fd) e = p->d_fd.upload(c, fd.data(), sizeof(float) * fd.size());
+    if (e == hipSuccess && !symtw.empty()) e = p->d_symtw.upload(c, symtw.data(), sizeof(float2) * symtw.size());
+    if (e == hipSuccess && !fd_sym.empty()) e = p->d_fd_sym.upload(c, fd_sym.data(), sizeof(float2) * fd_sym.size());
     if (e == hipSuccess && have_fd1x) e = p->d_fd1x.upload(c, fd1x.data(), sizeof(float) * fd1x.size());
     if (e == hipSuccess && !wpm.empty()) e = p->d_wpm.upload(c, wpm.data(), sizeof(float) * wpm.size());
     const hipError_t es = hipStreamSynchronize(c->stream);      // also after a failure: the host tables die here

@@ -252,36 +252,6 @@ __device__ __forceinline__ void prio_compute() { __builtin_amdgcn_s_setprio(0); 
 // global loads stay in flight across the barrier (the compiler still waits for them at first use).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// scatter_pow16_six (twiddle16.hip.h) with 6 + NM stored powers: pm = W^5, W^6, W^7, W^9, W^10, W^11, ... in that order
-// (NM = 3: nine stored, six products; NM = 4: ten, five).  Each remaining product is formed at the store that uses it (formed
-// ahead of the stores they cost 14-18 spilled registers).  Not a twiddle16() call site: which factors are opaque depends on
-// NM (below), and welch4096ws.hip's code object is not to move.
-__host__ __device__ constexpr int pow16_slot(int k) { return k - 5 - (k >> 2) + 1; }      // k = 5, 6, 7, 9, 10, 11, 13, ... -> 0, 1, 2, ...
-template <int STRIDE, int NM>
-__device__ __forceinline__ void scatter_pow16_stored(const float2 (&v)[16], float2 *out, float2 p1, float2 p2, float2 p3, float2 p4,
-                                                     float2 p8, float2 p12, const float2 (&pm)[NM]) {
-    float2 wj[4], wi[4];
-    wj[1] = p1, wj[2] = p2, wj[3] = p3;
-    wi[1] = p4, wi[2] = p8, wi[3] = p12;
-    // Opaque is only what the remaining products are formed from, one factor each: W^(4i) for every row i that still has a
-    // product.  An opaque copy of a loop-invariant register is a v_mov per call; with W^1, W^2, W^3 made opaque whatever
-    // NM, the thirteen-power producer paid six per segment for its two products (W^14, W^15), now two.
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-        if (pow16_slot(4 * i + 3) >= NM) asm volatile("" : "+v"(wi[i].x), "+v"(wi[i].y));
-    out[0] = v[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) {
-        const int i = k >> 2, j = k & 3;
-        float2 w;
-        if (i == 0) w = wj[j];
-        else if (j == 0) w = wi[i];
-        else if (pow16_slot(k) < NM) w = pm[pow16_slot(k) < NM ? pow16_slot(k) : 0];
-        else w = cmul(wi[i], wj[j]);
-        out[STRIDE * k] = cmul(v[r16(k)], w);
-    }
-}
-
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();

@@ -52,7 +52,16 @@ struct WelchArgs {
     // Hann; checked in double at plan time), so the producer forms r w[n + nfft / 2] as fma(-r, w[n], r) and holds no
     // window value in a register.  0: the general build, any window.
     int compl_win;
+    // compl_win only.  symtw: the plan's (tan(theta / 2), sin(theta)) pairs, theta = 2 pi e / 4096, entry kSymTwOrigin + e for
+    // |e| <= kSymTwOrigin (symtw_table(), abi_ctx.hip) - the three-shear twiddles of the build's signed-digit passes.
+    // fd_sym (detrending plans): per consumer thread t = 16 k0 + k1 the window spectrum at the bin of its register 0,
+    // k = sym16(k0) + 16 sym16(k1) in [-136, 120), times the phase and sign the build leaves on that register
+    // (window_spectrum_table_sym(), abi_welch.hip); the plan has checked that the window's spectrum is negligible elsewhere.
+    const float2 *symtw;
+    const float2 *fd_sym;
 };
+constexpr int kSymShift = 136;          // welch4096ws, compl_win: time origin of the transform (n' = n - 136 = 256 a + 16 (b - 8) + (c - 8))
+constexpr int kSymTwOrigin = 1100;      // exponents read: |kappa (t - 136)| <= 8 * 136 = 1088, |16 lambda (c - 8)| <= 1024
 
 // Launch description of segfft.hip: segment transforms of 1024 / 2048 / 4096 points by teams of nfft / 16
 // threads, Welch average or periodogram chain (see the file header).

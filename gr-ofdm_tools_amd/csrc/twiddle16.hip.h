@@ -80,6 +80,31 @@ template <bool IMM = false, class F> __device__ __forceinline__ void twiddle16(c
     }
 }
 
+// The SYMMETRIC flavour (welch4096ws.hip's complementary-window build): the output digit k is read as a signed digit
+// d = k or k - 16 in [-8, 8) and the caller measures its own index from the middle of its range, so every angle
+// theta = d * (caller's step) stays inside (-0.55 pi, 0.55 pi).  There the rotation v e^(-i theta) is three shears,
+//     x1 = x + t y,  y1 = y - s x1,  x2 = x1 + t y1,   t = tan(theta / 2), s = sin(theta)   (|t| < 1.2),
+// three v_fma_f32 instead of cmul's four instructions, exact in real arithmetic, no scale left behind.  t and s are odd in
+// theta: the eight stored pairs of |d| = 1..8 serve all fifteen rotations, the conjugate is the operand negation of
+// v_fma_f32 (free).  Nothing is formed from the stored pairs, so there is nothing for the compiler to hoist and no opaque
+// copy.  ts[m - 1] = (tan, sin) of m * (caller's step), signed as the step is (symtw_table(), abi_ctx.hip).
+__host__ __device__ constexpr int sym16(int k) { return k < 8 ? k : k - 16; }
+template <bool CONJ> __device__ __forceinline__ float2 rot3(float2 v, float2 ts) {
+    const float t = CONJ ? -ts.x : ts.x, s = CONJ ? -ts.y : ts.y;
+    const float x1 = fmaf(t, v.y, v.x);
+    const float y1 = fmaf(-s, x1, v.y);
+    return make_float2(fmaf(t, y1, x1), y1);
+}
+// put(k, v[r16(k)] * e^(-i sym16(k) theta)) for k = 0..15, theta the angle of ts[0]
+template <class F> __device__ __forceinline__ void twiddle16_sym(const float2 (&v)[16], const float2 (&ts)[8], F put) {
+    put(0, v[0]);
+#pragma unroll
+    for (int k = 1; k < 16; ++k) put(k, k < 8 ? rot3<false>(v[r16(k)], ts[k - 1]) : rot3<true>(v[r16(k)], ts[15 - k]));
+}
+template <int STRIDE> __device__ __forceinline__ void scatter_sym16(const float2 (&v)[16], float2 *out, const float2 (&ts)[8]) {
+    twiddle16_sym(v, ts, [&](int k, float2 val) { out[STRIDE * k] = val; });
+}
+
 // out[STRIDE * k] = v[r16(k)] * W^k from two seeds / from six stored powers
 template <int STRIDE>
 __device__ __forceinline__ void scatter_pow16(const float2 (&v)[16], float2 *out, float2 p1, float2 p4) {

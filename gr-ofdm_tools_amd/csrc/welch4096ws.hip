@@ -32,8 +32,8 @@
 // needed, rows 0..7 take their place in the LDS table and no window value stays in a register.  The kept half stays
 // UNWINDOWED: its product with w[n] contracts into the two additions of the first butterfly layer (windowed ahead, the
 // pair cost sixteen instructions more than the general form), so the window costs what it did and the eight freed
-// registers plus what the form leaves over hold thirteen pass-1 twiddle powers (two products per segment; fourteen and
-// fifteen spill in the PILOT flavour).  Producer hot loop 311 -> 281 VALU per segment at 128 VGPRs, no scratch
+// registers plus what the form leaves over held thirteen pass-1 twiddle powers (two products per segment; fourteen and
+// fifteen spilled in the PILOT flavour; now eight (tan, sin) pairs, below).  Producer hot loop 311 -> 281 VALU per segment
 // (same-box A/B against the parent library with the change below, alternating runs of bench.py: kernel 0.5993-0.6013
 // against 0.6132-0.6147 ms = -2.3 %, step 0.613-0.616 against 0.627-0.630 ms, profiles/ab_headline_compl.txt)
 // The consumer waits ONCE for its table loads, in front of its loop: fifteen s_waitcnt vmcnt(n) per segment, one in front
@@ -47,6 +47,23 @@
 // twiddle powers instead of six).  Same-box A/B against the parent library, six alternating runs of bench.py each: step
 // 0.5766-0.5804 against 0.5835-0.5862 ms, kernel 0.5636-0.5658 against 0.5710-0.5722 ms = -1.2 %; SQ_INSTS_VALU 3.737e8 ->
 // 3.616e8, SQ_WAIT_INST_LDS -6.8 % per launch; outputs bit for bit the parent's (profiles/ab_headline_consumer_path.txt)
+// Signed digits and three-shear twiddles (the complementary-window build; DESIGN 4.1, model: tests/test_symtw_model_cpu.py).
+// With n = 256 a + 16 b + c measured from sample 136 - n' = 256 a + tau, tau = 16 (b - 8) + (c - 8) = t - 136 - and the output
+// digits of passes 1 and 2 read as kappa = sym16(k0), lambda = sym16(k1) in [-8, 8), k = kappa + 16 lambda + 256 mu, the
+// pass-1 twiddle is W4096^(kappa tau) and the pass-2 twiddle W256^(lambda (c - 8)): |theta| <= 0.54 pi.  The butterflies keep
+// the plain digits b, c; that leaves (-1)^lambda on all sixteen inputs of a pass-3 transform, (-1)^mu on its output and the
+// origin's unit phase on X[k], none of which survives |X|^2.  No thread holds other samples, no load or LDS address moves;
+// register mu of consumer thread (k0, k1) holds another bin, and the final store puts it where finalize layout 1 wants it.
+// Inside that range a rotation is three shears - three v_fma_f32 against cmul's four instructions, no scale left behind
+// (rot3, twiddle16.hip.h) - from eight stored (tan(theta / 2), sin(theta)) pairs per role (WelchArgs.symtw), the conjugate by
+// operand negation: sixteen twiddle registers in the producer (26 before: thirteen powers, two products per segment) and in
+// the consumer (30).  The registers mu = 0 are the bins [-136, 120): the plan checks that the window's spectrum stays inside
+// them, and each consumer thread detrends that one register (WelchArgs.fd_sym carries the phase and the sign).
+// Producer 277 -> 252, consumer 406 -> 385 VALU per segment, 124 / 105 / 108 VGPRs, no scratch; the general build's code is
+// unchanged instruction for instruction.  Same-box A/B against the parent library, six alternating runs of bench.py each:
+// step 0.5778-0.5808 against 0.5915-0.5954 ms, kernel 0.5647-0.5676 against 0.5776-0.5807 ms = -2.2 %; SQ_INSTS_VALU
+// 3.616e8 -> 3.375e8 per launch, SQ_WAIT_INST_LDS +58 % (a rotation is a chain of three dependent operations in front of its
+// exchange write); one-segment rows 0.86 against 0.80 ulp of the row's peak amplitude (profiles/ab_headline_symtw.txt)
 // tried: the eight loads of a step spread over 2 / 3 places instead of one burst, no gain (NOTES 8,
 // profiles/r05_ab_headline_spread_loads.txt)
 // not tried: the two components of the segment sum reduced in one interleaved DPP sequence (ten s_nop per segment in the
@@ -71,12 +88,6 @@ constexpr int WS_PAL = 2, WS_PAC = 0, WS_PAS = WS_PAL, WS_PBL = 2;
 constexpr int WS_PBC = 1;                  // the consumer is the critical path: its butterflies go ahead of the producer's (-4.5 %)
 
 enum { ITEM_STOP = 0, ITEM_DATA = 1, ITEM_BUBBLE = 2 };
-
-#ifndef OTH_WS_COMPL_POWERS
-#define OTH_WS_COMPL_POWERS 13
-#endif
-constexpr int WS_COMPL_POWERS = OTH_WS_COMPL_POWERS;      // pass-1 twiddle powers the complementary-window producer stores
-                                                          // (6 ... 15; thirteen is the most that fits without scratch)
 
 // COMPL: the complementary-window producer (w[n] + w[n + 2048] = 1, see the file header); everything else is shared
 template <bool DETREND, bool PILOT, bool COMPL>
@@ -113,12 +124,13 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
         wl[0] = make_float4(p.win[256 * WROW + t], p.win[256 * (WROW + 1) + t], p.win[256 * (WROW + 2) + t], p.win[256 * (WROW + 3) + t]);
         wl[256] = make_float4(p.win[256 * (WROW + 4) + t], p.win[256 * (WROW + 5) + t], p.win[256 * (WROW + 6) + t],
                               p.win[256 * (WROW + 7) + t]);
-        const float2 b1 = p.tw[t], b2 = p.tw[2 * t], b3 = p.tw[3 * t], b4 = p.tw[4 * t], b8 = p.tw[8 * t],
-                     b12 = p.tw[(12 * t) & 4095];
-        float2 bm[WS_COMPL_POWERS - 6 > 0 && COMPL ? WS_COMPL_POWERS - 6 : 1];      // COMPL: W^5, W^6, W^7, W^9, ... (pow16_slot)
+        Pow6 b6;                       // general build: W^1, 2, 3, 4, 8, 12 of this thread
+        float2 ts1[COMPL ? 8 : 1];     // COMPL: (tan, sin) pairs of |kappa| (t - 136), |kappa| = 1..8 (file header)
         if constexpr (COMPL) {
 #pragma unroll
-            for (int k = 0; k < WS_COMPL_POWERS - 6; ++k) bm[k] = p.tw[((5 + k + k / 3) * t) & 4095];
+            for (int m = 1; m <= 8; ++m) ts1[m - 1] = p.symtw[kSymTwOrigin + m * (t - kSymShift)];
+        } else {
+            b6 = Pow6{p.tw[t], p.tw[2 * t], p.tw[3 * t], p.tw[4 * t], p.tw[8 * t], p.tw[(12 * t) & 4095]};
         }
         float2 kw[8], nxt[8];
         float2 prev_new = make_float2(0.f, 0.f);     // this wave's sum of the previous segment's new half
@@ -232,8 +244,8 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
             __builtin_amdgcn_s_setprio(WS_PAC);
             dft16(v);
             __builtin_amdgcn_s_setprio(WS_PAS);
-            if constexpr (COMPL) scatter_pow16_stored<RS>(v, lx + w1, b1, b2, b3, b4, b8, b12, bm);
-            else scatter_pow16_six<RS>(v, lx + w1, Pow6{b1, b2, b3, b4, b8, b12});
+            if constexpr (COMPL) scatter_sym16<RS>(v, lx + w1, ts1);
+            else scatter_pow16_six<RS>(v, lx + w1, b6);
             step_end(ITEM_DATA);
         };
 
@@ -314,11 +326,21 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
         step_end(ITEM_STOP);
     } else {
         // ------------------------------------------------------------------ consumer
-        float2 tw2[16];
-#pragma unroll
-        for (int k = 1; k < 16; ++k) tw2[k] = p.tw[16 * lo * k];      // W256^(k1 c), c = lo
+        float2 tw2[COMPL ? 1 : 16];      // general build: W256^(k1 c), c = lo
+        float2 ts2[COMPL ? 8 : 1];       // COMPL: (tan, sin) pairs of W256^(|lambda| (c - 8)), |lambda| = 1..8
         float4 fw = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (DETREND) fw = p.fd[t];      // FFT(w) at this thread's k2 = 0 and k2 = 15 bins
+        if constexpr (COMPL) {
+#pragma unroll
+            for (int m = 1; m <= 8; ++m) ts2[m - 1] = p.symtw[kSymTwOrigin + 16 * m * (lo - 8)];
+            if (DETREND) {      // the re-phased FFT(w) at this thread's mu = 0 bin, the only one the window reaches
+                const float2 f = p.fd_sym[t];
+                fw.x = f.x, fw.y = f.y;
+            }
+        } else {
+#pragma unroll
+            for (int k = 1; k < 16; ++k) tw2[k] = p.tw[16 * lo * k];
+            if (DETREND) fw = p.fd[t];      // FFT(w) at this thread's k2 = 0 and k2 = 15 bins
+        }
         float acc[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) acc[k] = 0.f;
@@ -327,6 +349,12 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
         // The table loads above are this role's only vector-memory operations.  One wait here, with the values made opaque:
         // the compiler otherwise carries their wait-count state into the loop and re-emits an s_waitcnt vmcnt(n) in front
         // of every pass-2 twiddle product of every step (fifteen issue turns of the critical path per segment).
+        if constexpr (COMPL) {
+            asm volatile("s_waitcnt vmcnt(0)"
+                         : "+v"(ts2[0].x), "+v"(ts2[0].y), "+v"(ts2[1].x), "+v"(ts2[1].y), "+v"(ts2[2].x), "+v"(ts2[2].y), "+v"(ts2[3].x),
+                           "+v"(ts2[3].y), "+v"(ts2[4].x), "+v"(ts2[4].y), "+v"(ts2[5].x), "+v"(ts2[5].y), "+v"(ts2[6].x), "+v"(ts2[6].y));
+            asm volatile("" : "+v"(ts2[7].x), "+v"(ts2[7].y), "+v"(fw.x), "+v"(fw.y));
+        } else {
         asm volatile("s_waitcnt vmcnt(0)"
                      : "+v"(tw2[1].x), "+v"(tw2[1].y), "+v"(tw2[2].x), "+v"(tw2[2].y), "+v"(tw2[3].x), "+v"(tw2[3].y), "+v"(tw2[4].x),
                        "+v"(tw2[4].y), "+v"(tw2[5].x), "+v"(tw2[5].y), "+v"(tw2[6].x), "+v"(tw2[6].y), "+v"(tw2[7].x), "+v"(tw2[7].y));
@@ -334,6 +362,7 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
                           "+v"(tw2[11].x), "+v"(tw2[11].y), "+v"(tw2[12].x), "+v"(tw2[12].y), "+v"(tw2[13].x), "+v"(tw2[13].y));
         asm volatile("" : "+v"(tw2[14].x), "+v"(tw2[14].y), "+v"(tw2[15].x), "+v"(tw2[15].y), "+v"(fw.x), "+v"(fw.y), "+v"(fw.z),
                           "+v"(fw.w));
+        }
         int it = 0;
         // What the producer left in image q: the item kind and, in the same batch of LDS reads (harmless when it is not a
         // segment), the per-wave sums and pass 2's sixteen exchange-1 reads as full-rate ds_read_b64 on counted waits.
@@ -385,9 +414,14 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
         while (item != ITEM_STOP) {       // (the producer left after the barrier of the step that published it)
             float2 *lx = img + ((it & 1) ^ 1) * LDS_X;      // v holds pass 2 of image (it - 1) & 1
             __builtin_amdgcn_s_setprio(WS_PBL);
-            lx[w2] = v[r16(0)];           // in place: each thread rewrites exactly the sixteen elements it read
+            // in place: each thread rewrites exactly the sixteen elements it read
+            if constexpr (COMPL) {
+                scatter_sym16<17>(v, lx + w2, ts2);
+            } else {
+                lx[w2] = v[r16(0)];
 #pragma unroll
-            for (int k1 = 1; k1 < 16; ++k1) lx[w2 + k1 * 17] = cmul(v[r16(k1)], tw2[k1]);
+                for (int k1 = 1; k1 < 16; ++k1) lx[w2 + k1 * 17] = cmul(v[r16(k1)], tw2[k1]);
+            }
             wave_lds_sync();              // exchange 2 stays inside the wave: program order is enough
             // exchange-2 reads as ordered ds_read_b64, the first butterfly layer on counted waits (-1.7 % kernel
             // time against the sixteen plain reads, which hipcc pairs into ds_read2_b64 behind one lgkmcnt(0);
@@ -397,8 +431,9 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
             if (DETREND) {                // X[k] -= mean * FFT(w)[k] where FFT(w) is not negligible
                 v[r16(0)] = make_float2(v[r16(0)].x - (mean.x * fw.x - mean.y * fw.y),
                                         v[r16(0)].y - (mean.x * fw.y + mean.y * fw.x));
-                v[r16(15)] = make_float2(v[r16(15)].x - (mean.x * fw.z - mean.y * fw.w),
-                                         v[r16(15)].y - (mean.x * fw.w + mean.y * fw.z));
+                if constexpr (!COMPL)      // (COMPL: the window's spectrum lies in [-136, 120), all of it in register 0)
+                    v[r16(15)] = make_float2(v[r16(15)].x - (mean.x * fw.z - mean.y * fw.w),
+                                             v[r16(15)].y - (mean.x * fw.w + mean.y * fw.z));
             }
 #pragma unroll
             for (int k2 = 0; k2 < 16; ++k2) {
@@ -419,8 +454,18 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
         }
         // bin k0 + 16 k1 + 256 k2 of this workgroup sits at t + 256 k2 (finalize_kernel layout 1)
         float *dst = p.partial + ((size_t)stream * W + wg) * 4096;
+        if constexpr (COMPL) {
+            // register mu of thread (k0, k1) = (hi, lo) holds bin kappa + 16 lambda + 256 mu with kappa = sym16(k0),
+            // lambda = sym16(k1): in plain digits k0, k1 - [k0 >= 8] (mod 16) and mu less the borrows
+            const int g = hi >> 3;
+            const int down = (lo >> 3) + (lo == 0 ? g : 0);      // (never both)
+            const int at = 16 * hi + ((lo - g) & 15);
 #pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2) dst[256 * k2 + t] = acc[k2];
+            for (int mu = 0; mu < 16; ++mu) dst[((256 * mu - 256 * down) & 4095) + at] = acc[mu];
+        } else {
+#pragma unroll
+            for (int k2 = 0; k2 < 16; ++k2) dst[256 * k2 + t] = acc[k2];
+        }
     }
 }
 
