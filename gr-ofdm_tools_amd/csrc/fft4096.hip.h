@@ -45,6 +45,36 @@ __device__ __forceinline__ void dft4_tail(float2 t0, float2 t1, float2 p1, float
     a1 = make_float2(fmaf(S, r.y, t1.x), fmaf(-S, r.x, t1.y));       // t1 + (-i) S r
     a3 = make_float2(fmaf(-S, r.y, t1.x), fmaf(S, r.x, t1.y));
 }
+// group KL of the second layer: the 4-point butterfly that makes outputs k = KL, KL + 4, KL + 8, KL + 12 final, in
+// v[4 KL .. 4 KL + 3] (r16(k) = 4 (k & 3) + (k >> 2))
+template <int KL> __device__ __forceinline__ void dft16_layer2_group(float2 (&v)[16]) {
+    if constexpr (KL == 0) {
+        dft4<false>(v[0], v[1], v[2], v[3]);
+    } else if constexpr (KL == 1) {   // kl = 1: W^1, W^2, W^3 on v[5], v[6], v[7]
+        const float2 u1 = v[5], u2 = v[6], u3 = v[7];
+        const float2 p1 = make_float2(fmaf(T1, u1.y, u1.x), fmaf(-T1, u1.x, u1.y));       // W^1 u = C1 p1
+        const float2 p2 = make_float2(u2.x + u2.y, u2.y - u2.x);                           // W^2 u = RH p2
+        const float2 p3 = make_float2(fmaf(T1, u3.x, u3.y), fmaf(T1, u3.y, -u3.x));        // W^3 u = C1 p3
+        const float2 t0 = make_float2(fmaf(RH, p2.x, v[4].x), fmaf(RH, p2.y, v[4].y));
+        const float2 t1 = make_float2(fmaf(-RH, p2.x, v[4].x), fmaf(-RH, p2.y, v[4].y));
+        dft4_tail(t0, t1, p1, p3, C1, v[4], v[5], v[6], v[7]);
+    } else if constexpr (KL == 2) {   // kl = 2: W^2, W^4 = -i, W^6 on v[9], v[10], v[11]
+        const float2 u1 = v[9], u2 = v[10], u3 = v[11];
+        const float2 p1 = make_float2(u1.x + u1.y, u1.y - u1.x);                           // W^2 u = RH p1
+        const float2 p3 = make_float2(u3.y - u3.x, -u3.x - u3.y);                          // W^6 u = RH p3
+        const float2 t0 = make_float2(v[8].x + u2.y, v[8].y - u2.x);
+        const float2 t1 = make_float2(v[8].x - u2.y, v[8].y + u2.x);
+        dft4_tail(t0, t1, p1, p3, RH, v[8], v[9], v[10], v[11]);
+    } else if constexpr (KL == 3) {   // kl = 3: W^3, W^6, W^9 = -W^1 on v[13], v[14], v[15]
+        const float2 u1 = v[13], u2 = v[14], u3 = v[15];
+        const float2 p1 = make_float2(fmaf(T1, u1.x, u1.y), fmaf(T1, u1.y, -u1.x));        // W^3 u = C1 p1
+        const float2 p2 = make_float2(u2.y - u2.x, -u2.x - u2.y);                          // W^6 u = RH p2
+        const float2 p3 = make_float2(fmaf(-T1, u3.y, -u3.x), fmaf(T1, u3.x, -u3.y));      // W^9 u = C1 p3
+        const float2 t0 = make_float2(fmaf(RH, p2.x, v[12].x), fmaf(RH, p2.y, v[12].y));
+        const float2 t1 = make_float2(fmaf(-RH, p2.x, v[12].x), fmaf(-RH, p2.y, v[12].y));
+        dft4_tail(t0, t1, p1, p3, C1, v[12], v[13], v[14], v[15]);
+    }
+}
 // PLAIN: multiply-then-add (160 operations; every inner twiddle product rounded on its own) - the periodogram-chain
 // builds take it, their single rows are compared bin by bin and the chain is HBM-bound; the Welch averages take the
 // folded form
@@ -63,33 +93,10 @@ __device__ __forceinline__ void dft16_layer2(float2 (&v)[16]) {
 #pragma unroll
     for (int kl = 0; kl < 4; ++kl) dft4<false>(v[4 * kl], v[4 * kl + 1], v[4 * kl + 2], v[4 * kl + 3]);
   } else {
-    dft4<false>(v[0], v[1], v[2], v[3]);
-    {   // kl = 1: W^1, W^2, W^3 on v[5], v[6], v[7]
-        const float2 u1 = v[5], u2 = v[6], u3 = v[7];
-        const float2 p1 = make_float2(fmaf(T1, u1.y, u1.x), fmaf(-T1, u1.x, u1.y));       // W^1 u = C1 p1
-        const float2 p2 = make_float2(u2.x + u2.y, u2.y - u2.x);                           // W^2 u = RH p2
-        const float2 p3 = make_float2(fmaf(T1, u3.x, u3.y), fmaf(T1, u3.y, -u3.x));        // W^3 u = C1 p3
-        const float2 t0 = make_float2(fmaf(RH, p2.x, v[4].x), fmaf(RH, p2.y, v[4].y));
-        const float2 t1 = make_float2(fmaf(-RH, p2.x, v[4].x), fmaf(-RH, p2.y, v[4].y));
-        dft4_tail(t0, t1, p1, p3, C1, v[4], v[5], v[6], v[7]);
-    }
-    {   // kl = 2: W^2, W^4 = -i, W^6 on v[9], v[10], v[11]
-        const float2 u1 = v[9], u2 = v[10], u3 = v[11];
-        const float2 p1 = make_float2(u1.x + u1.y, u1.y - u1.x);                           // W^2 u = RH p1
-        const float2 p3 = make_float2(u3.y - u3.x, -u3.x - u3.y);                          // W^6 u = RH p3
-        const float2 t0 = make_float2(v[8].x + u2.y, v[8].y - u2.x);
-        const float2 t1 = make_float2(v[8].x - u2.y, v[8].y + u2.x);
-        dft4_tail(t0, t1, p1, p3, RH, v[8], v[9], v[10], v[11]);
-    }
-    {   // kl = 3: W^3, W^6, W^9 = -W^1 on v[13], v[14], v[15]
-        const float2 u1 = v[13], u2 = v[14], u3 = v[15];
-        const float2 p1 = make_float2(fmaf(T1, u1.x, u1.y), fmaf(T1, u1.y, -u1.x));        // W^3 u = C1 p1
-        const float2 p2 = make_float2(u2.y - u2.x, -u2.x - u2.y);                          // W^6 u = RH p2
-        const float2 p3 = make_float2(fmaf(-T1, u3.y, -u3.x), fmaf(T1, u3.x, -u3.y));      // W^9 u = C1 p3
-        const float2 t0 = make_float2(fmaf(RH, p2.x, v[12].x), fmaf(RH, p2.y, v[12].y));
-        const float2 t1 = make_float2(fmaf(-RH, p2.x, v[12].x), fmaf(-RH, p2.y, v[12].y));
-        dft4_tail(t0, t1, p1, p3, C1, v[12], v[13], v[14], v[15]);
-    }
+    dft16_layer2_group<0>(v);
+    dft16_layer2_group<1>(v);
+    dft16_layer2_group<2>(v);
+    dft16_layer2_group<3>(v);
   }
 }
 
@@ -160,10 +167,14 @@ template <bool WORD, bool SUMS> struct LdsCtl {
 struct LdsNoMid {
     __device__ __forceinline__ void operator()() const {}
 };
+// `last(v)` runs the second butterfly layer; a caller that has something to weave into it (dft16_layer2_scatter_sym) passes its own
+struct LdsLayer2 {
+    __device__ __forceinline__ void operator()(float2 (&v)[16]) const { dft16_layer2(v); }
+};
 
-template <int STRIDE, class F, class M = LdsNoMid, bool WORD = false, bool SUMS = false>
+template <int STRIDE, class F, class M = LdsNoMid, bool WORD = false, bool SUMS = false, class L = LdsLayer2>
 __device__ __forceinline__ void dft16_from_lds(float2 (&v)[16], const float2 *base, F issued, M mid = M(),
-                                               LdsCtl<WORD, SUMS> *ctl = nullptr) {
+                                               LdsCtl<WORD, SUMS> *ctl = nullptr, L last = L()) {
     const unsigned addr = (unsigned)(unsigned long long)base;      // LDS byte address = low half of the flat address
     double r[16];
     if constexpr (WORD) asm volatile("ds_read_b32 %0, %1" : "=v"(ctl->word) : "v"((unsigned)(unsigned long long)ctl->word_at));
@@ -198,7 +209,45 @@ __device__ __forceinline__ void dft16_from_lds(float2 (&v)[16], const float2 *ba
     // the word becomes visible here, tied to outputs of the last butterfly
     if constexpr (WORD) asm volatile("" : "+v"(ctl->word), "+v"(v[3].x), "+v"(v[15].y));
     mid();
-    dft16_layer2(v);
+    last(v);
+}
+
+// The second butterfly layer of dft16(), the symmetric inter-pass twiddle (twiddle16_sym) and the exchange stores
+// out[STRIDE * k] as ONE software pipeline: group g of the layer makes outputs k = g, g + 4, g + 8, g + 12 final, so the
+// order is  butterfly g | rotations and stores of group g - 1,  output 0 (no rotation) first, and only the last group's
+// twelve FMAs and four stores are left behind the arithmetic.  Written butterflies, then sixteen rotations, then sixteen
+// stores, every store of the exchange sits between the last FMA and the point the caller waits at - in welch4096ws's
+// consumer pass 3's first counted wait - and the four waves of the role, in lockstep from the barrier, fire their bursts
+// together: a ds_write_b64 is paced by moving its registers to the LDS, about six cycles of the CU's store path each,
+// during which those waves issue nothing.  Started early the stores hide behind arithmetic that runs anyway (welch4096ws
+// consumer: SQ_WAIT_INST_LDS -42 %, kernel -2.1 %; its producer, whose stores wait at the barrier, lost 0.4-0.9 % with it).
+// The stores are asm: single ds_write_b64 with immediate offsets (hipcc pairs its own into ds_write2_b64 at STRIDE 17, which
+// needs both halves ready and costs 13 cycles against 2 x 6) that keep their order among each other and against the asm
+// reads and waits of dft16_from_lds, wave_lds_sync() and lds_barrier().  hipcc does not count them: the caller's next
+// lgkmcnt wait covers them - LDS operations return in order, so a counted wait behind sixteen reads issued after them, or
+// lds_barrier()'s lgkmcnt(0), does.  Each group is a scheduling region of its own (sched_barrier): left free, hipcc moves
+// all the butterflies in front of all the rotations again.  v[] is consumed.
+template <int BYTE_OFFSET> __device__ __forceinline__ void lds_store_b64(unsigned addr, float2 val) {
+    typedef float lds_f2 __attribute__((ext_vector_type(2)));
+    const lds_f2 d = {val.x, val.y};
+    asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(d), "n"(BYTE_OFFSET) : "memory");
+}
+template <int STRIDE> __device__ __forceinline__ void dft16_layer2_scatter_sym(float2 (&v)[16], float2 *out, const float2 (&ts)[8]) {
+    static_assert(8 * STRIDE * 15 < 65536, "immediate offsets");
+    const unsigned addr = (unsigned)(unsigned long long)out;      // LDS byte address = low half of the flat address
+    static_for<0, 5>([&](auto gc) {
+        constexpr int G = decltype(gc)::value;
+        if constexpr (G < 4) dft16_layer2_group<G>(v);
+        if constexpr (G == 0) lds_store_b64<0>(addr, v[0]);      // output 0 needs no rotation (r16(0) == 0): out at once
+        if constexpr (G > 0) {
+            static_for<(G == 1), 4>([&](auto ic) {
+                constexpr int k = (G - 1) + 4 * decltype(ic)::value;
+                if constexpr (k < 8) lds_store_b64<8 * STRIDE * k>(addr, rot3<false>(v[r16(k)], ts[k - 1]));
+                else lds_store_b64<8 * STRIDE * k>(addr, rot3<true>(v[r16(k)], ts[15 - k]));
+            });
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    });
 }
 
 // Non-temporal load of a sample that is read once: it does not displace the tables and partial sums in L2.

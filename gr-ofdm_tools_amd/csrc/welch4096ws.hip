@@ -64,8 +64,19 @@
 // step 0.5778-0.5808 against 0.5915-0.5954 ms, kernel 0.5647-0.5676 against 0.5776-0.5807 ms = -2.2 %; SQ_INSTS_VALU
 // 3.616e8 -> 3.375e8 per launch, SQ_WAIT_INST_LDS +58 % (a rotation is a chain of three dependent operations in front of its
 // exchange write); one-segment rows 0.86 against 0.80 ulp of the row's peak amplitude (profiles/ab_headline_symtw.txt)
+// Exchange-2 stores inside pass 2's last butterfly layer (the complementary-window build's consumer): the +58 % above was
+// where the rotations left the stores - all sixteen behind the last FMA, in front of pass 3's first counted wait, the four
+// consumer waves at once.  dft16_layer2_scatter_sym (fft4096.hip.h) issues butterfly g, then the rotations and single
+// ds_write_b64 of group g - 1; pass2() writes exchange 2 itself, before the item word is looked at.  385 VALU per segment
+// still, 119 / 107 / 105 VGPRs; same-box A/B against the parent library, six alternating runs of bench.py each: step
+// 0.5637-0.5651 against 0.5749-0.5763 ms, kernel 0.5492-0.5500 against 0.5604-0.5616 ms = -2.1 % (a second, busy box: -0.7 % in
+// the mean, no separation); SQ_WAIT_INST_LDS 1.566e8 -> 0.913e8, SQ_INSTS_VALU unchanged, outputs bit for bit the parent's
+// (profiles/ab_headline_exchange_overlap.txt, profiles/exchange_overlap_device_diff.txt)
 // tried: the eight loads of a step spread over 2 / 3 places instead of one burst, no gain (NOTES 8,
 // profiles/r05_ab_headline_spread_loads.txt)
+// tried: the same pipeline for the producer's exchange-1 stores (the first layer, then dft16_layer2_scatter_sym<RS>), its
+// section at wave priority 2, at 0, and at 0 up to the last store group: +0.9 %, +0.4 %, +0.9 % against the parent, and with
+// the consumer's together -0.8 % instead of -2.1 % (profiles/ab_headline_exchange_overlap.txt, NOTES 4.1)
 // not tried: the two components of the segment sum reduced in one interleaved DPP sequence (ten s_nop per segment in the
 // producer, which is not the critical path)
 
@@ -373,7 +384,19 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
         auto pass2 = [&](int q) -> int {
             LdsCtl<true, DETREND> c;
             c.word_at = ctrl + q, c.sums_at = red + q * 8;
+            if constexpr (COMPL) {
+                // exchange 2 goes out with pass 2's last butterfly layer (dft16_layer2_scatter_sym), before the item word is
+                // looked at.  In place: each thread rewrites exactly the sixteen elements it read above, and those reads
+                // were complete at the last counted wait of the first layer.  In an idle step and in the last it rewrites
+                // junk with junk: image q is this role's until the next barrier, which waits for the stores.
+                int qs = q;      // (w2 == r1: the store address is formed on its own from an opaque image index, one
+                asm volatile("" : "+s"(qs));      // v_add as in the parent - the budget tests pin the count with ==)
+                float2 *ox = img + qs * LDS_X + w2;
+                dft16_from_lds<17>(v, img + q * LDS_X + r1, [] { __builtin_amdgcn_s_setprio(WS_PBC); }, LdsNoMid(), &c,
+                                   [&](float2 (&u)[16]) { dft16_layer2_scatter_sym<17>(u, ox, ts2); });
+            } else {
             dft16_from_lds<17>(v, img + q * LDS_X + r1, [] { __builtin_amdgcn_s_setprio(WS_PBC); }, LdsNoMid(), &c);
+            }
             if (DETREND) {
                 const float2 h0 = make_float2(c.s[0].x, c.s[0].y), h1 = make_float2(c.s[0].z, c.s[0].w);
                 const float2 h2 = make_float2(c.s[1].x, c.s[1].y), h3 = make_float2(c.s[1].z, c.s[1].w);
@@ -414,15 +437,14 @@ __device__ __forceinline__ void welch4096ws_body(const WelchArgs &p) {
         while (item != ITEM_STOP) {       // (the producer left after the barrier of the step that published it)
             float2 *lx = img + ((it & 1) ^ 1) * LDS_X;      // v holds pass 2 of image (it - 1) & 1
             __builtin_amdgcn_s_setprio(WS_PBL);
-            // in place: each thread rewrites exactly the sixteen elements it read
-            if constexpr (COMPL) {
-                scatter_sym16<17>(v, lx + w2, ts2);
-            } else {
+            // in place: each thread rewrites exactly the sixteen elements it read (COMPL: pass2() has written them)
+            if constexpr (!COMPL) {
                 lx[w2] = v[r16(0)];
 #pragma unroll
                 for (int k1 = 1; k1 < 16; ++k1) lx[w2 + k1 * 17] = cmul(v[r16(k1)], tw2[k1]);
             }
-            wave_lds_sync();              // exchange 2 stays inside the wave: program order is enough
+            wave_lds_sync();              // exchange 2 stays inside the wave: program order is enough (COMPL: this is the
+                                          // point between pass2()'s last store and the first read below)
             // exchange-2 reads as ordered ds_read_b64, the first butterfly layer on counted waits (-1.7 % kernel
             // time against the sixteen plain reads, which hipcc pairs into ds_read2_b64 behind one lgkmcnt(0);
             // the same treatment of the exchange-1 reads, which needs the butterfly before the item word is
