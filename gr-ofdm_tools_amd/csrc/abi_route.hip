@@ -331,9 +331,10 @@ extern "C" {
 //   window_class: 0 all ones, 1 spectrum confined (periodic cosine-sum windows: both detrend tables exist), 2 wide
 //   (e.g. a symmetric Hamming: no table), 3 confined to 256 F bins but not to |k| < 16 (16384 points only)
 //   detrend_mode: OTH_DETREND_*;  kernel_pref: OTH_KERNEL_*;  sched_pref: OTH_SCHED_*;  variant: as oth_plan_set_tuning
-int oth__debug_recipe(int nfft, int nperseg, int noverlap, int window_class, int detrend_mode, int two_channel, int kernel_pref,
-                      const char *variant, int sched_pref, long long nseg, int nstreams, int cu_count, int runtime_occupancy,
-                      char *buf, size_t buflen) {
+//   oth__debug_recipe_tuned: the same with the overrides of oth_plan_set_tuning (sched -1, chunk 0, tail_chunk 0: none)
+int oth__debug_recipe_tuned(int nfft, int nperseg, int noverlap, int window_class, int detrend_mode, int two_channel, int kernel_pref,
+                            const char *variant, int sched_pref, long long nseg, int nstreams, int cu_count, int runtime_occupancy,
+                            int tune_sched, int tune_chunk, int tune_tail, char *buf, size_t buflen) {
     OTH_TRY
     if (!buf || !buflen || nperseg < 1 || nperseg > nfft || noverlap < 0 || noverlap >= nperseg || nseg < 1 || nstreams < 1)
         return fail(nullptr, OTH_ERR_INVALID, "bad argument");
@@ -351,6 +352,9 @@ int oth__debug_recipe(int nfft, int nperseg, int noverlap, int window_class, int
     sh.kernel = kernel_pref;
     sh.sched = sched_pref;
     sh.tune_variant = variant ? variant : "";
+    sh.tune_sched = tune_sched;
+    sh.tune_chunk = tune_chunk;
+    sh.tune_tail = tune_tail;
     if (!generic_supported(nfft) && any_describe(nfft, &sh.any))
         return fail(nullptr, OTH_ERR_UNSUPPORTED, "transform length outside [1, 1048576] (Bluestein: n <= 524288)");
     LaunchRecipe r;
@@ -360,6 +364,15 @@ int oth__debug_recipe(int nfft, int nperseg, int noverlap, int window_class, int
         return fail(nullptr, rc, why);
     snprintf(buf, buflen, "%s", recipe_text(r, nfft).c_str());
     return OTH_OK;
+    OTH_CATCH(nullptr)
+}
+
+int oth__debug_recipe(int nfft, int nperseg, int noverlap, int window_class, int detrend_mode, int two_channel, int kernel_pref,
+                      const char *variant, int sched_pref, long long nseg, int nstreams, int cu_count, int runtime_occupancy,
+                      char *buf, size_t buflen) {
+    OTH_TRY
+    return oth__debug_recipe_tuned(nfft, nperseg, noverlap, window_class, detrend_mode, two_channel, kernel_pref, variant, sched_pref,
+                                   nseg, nstreams, cu_count, runtime_occupancy, -1, 0, 0, buf, buflen);
     OTH_CATCH(nullptr)
 }
 }  // extern "C"

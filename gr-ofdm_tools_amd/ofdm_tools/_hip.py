@@ -165,6 +165,7 @@ SIGNATURES = {
     'oth_fac': (C.c_int, [_p, _p, C.c_size_t, C.c_int, _f]),
     'oth__debug_recipe': (C.c_int, [C.c_int] * 7 + [C.c_char_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_char_p,
                                                     C.c_size_t]),
+    'oth__debug_recipe_tuned': (C.c_int, [C.c_int] * 7 + [C.c_char_p, C.c_int, C.c_longlong] + [C.c_int] * 6 + [C.c_char_p, C.c_size_t]),
     'oth__debug_last_recipe': (C.c_int, [_p, C.c_char_p, C.c_size_t]),
     'oth__debug_channelizer_recipe': (C.c_int, [_p, C.c_char_p, C.c_size_t]),
     'oth__debug_live_resources': (C.c_int, [C.POINTER(C.c_int)] * 3),

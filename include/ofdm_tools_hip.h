@@ -1075,6 +1075,10 @@ int oth_fac(oth_ctx *ctx, const void *data, size_t n, int L, float *out);
 int oth__debug_recipe(int nfft, int nperseg, int noverlap, int window_class, int detrend_mode, int two_channel, int kernel_pref,
                       const char *variant, int sched_pref, long long nseg, int nstreams, int cu_count, int runtime_occupancy,
                       char *buf, size_t buflen);
+/* oth__debug_recipe with the overrides of oth_plan_set_tuning: sched (-1: none), chunk and tail_chunk (0: none) */
+int oth__debug_recipe_tuned(int nfft, int nperseg, int noverlap, int window_class, int detrend_mode, int two_channel, int kernel_pref,
+                            const char *variant, int sched_pref, long long nseg, int nstreams, int cu_count, int runtime_occupancy,
+                            int tune_sched, int tune_chunk, int tune_tail, char *buf, size_t buflen);
 int oth__debug_last_recipe(oth_plan *plan, char *buf, size_t buflen);
 int oth__debug_channelizer_recipe(oth_channelizer *ch, char *buf, size_t buflen);
 int oth__debug_live_resources(int *device_buffers, int *pinned_buffers, int *events);

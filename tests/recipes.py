@@ -23,10 +23,12 @@ def _lib():
 
 
 def recipe(lib, nfft, nperseg, noverlap, window=1, detrend=1, two_channel=0, kernel=0, variant=None, sched=2, nseg=600,
-           nstreams=1, cu=256, runtime=0):
+           nstreams=1, cu=256, runtime=0, tune_sched=-1, chunk=0, tail=0):
+    """tune_sched / chunk / tail: the overrides of WelchPlan.set_tuning (oth__debug_recipe_tuned)"""
     buf = ctypes.create_string_buffer(512)
-    rc = lib.oth__debug_recipe(nfft, nperseg, noverlap, window, detrend, two_channel, kernel,
-                               variant.encode() if variant else None, sched, nseg, nstreams, cu, runtime, buf, 512)
+    rc = lib.oth__debug_recipe_tuned(nfft, nperseg, noverlap, window, detrend, two_channel, kernel,
+                                     variant.encode() if variant else None, sched, nseg, nstreams, cu, runtime, tune_sched, chunk,
+                                     tail, buf, 512)
     if rc:
         return 'error %d: %s' % (rc, lib.oth_last_error(None).decode())
     return buf.value.decode()

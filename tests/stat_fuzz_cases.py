@@ -57,7 +57,9 @@ import zlib
 
 import numpy as np
 
+import fuzz_layout as FL
 import median_oracle as MO
+from fuzz_layout import BEHIND, NAN64, float32_transform  # noqa: F401 - the layout's names, as this module had them
 from stat_support import FS, POWERS
 
 SEED = 68                  # the suite's seed
@@ -287,10 +289,6 @@ def check_domain(c):
 
 # ---- the memory layout ----------------------------------------------------------------------------------------------------------
 
-NAN64 = np.complex64(complex(np.nan, np.nan))
-BEHIND = 64                # samples behind the last stream
-
-
 def lane_data(c):
     """the finite samples of every lane: [lanes][nsamples] complex64, or for a pair (x, y) each [1][nsamples]"""
     return _lane_data(c)
@@ -307,17 +305,12 @@ def _lane_data(c):
 
 def with_nan_tail(c, lane):
     """one lane as the layout holds it: the tail behind its last whole segment reads NaN"""
-    out = np.array(lane, np.complex64)
-    out[..., owned(c):] = NAN64
-    return out
+    return FL.nan_tail(lane, owned(c))
 
 
 def _buffer(c, lead, data):
-    L, n, st = lanes(c), nsamples(c), stride(c)
-    buf = np.full(lead + (L - 1) * st + n + BEHIND, NAN64, np.complex64)
-    for i in range(L):
-        buf[lead + i * st:lead + i * st + owned(c)] = data[i, :owned(c)]
-    return buf
+    assert len(data) == lanes(c)
+    return FL.nan_buffer(data, lead, stride(c), nsamples(c), owned(c))
 
 
 def layout(c):
@@ -342,27 +335,6 @@ def lane_input(c, i):
 def units(c):
     """independent results of a launch: its streams; one for the matrix and for a pair"""
     return 1 if FAMILY[c.family].single else c.nstreams
-
-
-# ---- float32 transform in the oracles' place ---------------------------------------------------------------------------------------
-
-def _fft32(a, n=None, axis=-1):
-    import scipy.fft
-    out = scipy.fft.fft(np.asarray(a).astype(np.complex64), n, axis)
-    assert out.dtype == np.complex64
-    return out.astype(np.complex128)
-
-
-@contextlib.contextmanager
-def float32_transform():
-    """np.fft.fft is pocketfft's single-precision transform inside: the input cast to complex64, the result back to
-    complex128; everything else of an oracle stays float64"""
-    old = np.fft.fft
-    np.fft.fft = _fft32
-    try:
-        yield
-    finally:
-        np.fft.fft = old
 
 
 # ---- the families ---------------------------------------------------------------------------------------------------------------
@@ -1096,7 +1068,7 @@ def run_case(ctx, hip, c, check=True, say=print):
         for name, present in zip(F.row_names, c.rows):
             outs[name] = None
             if present:      # (a row passed as NULL has no storage at all)
-                blocks[name] = put(np.full(2 * GUARD + (U + 1) * F.floats(c, name), SENTINEL, np.uint32))
+                blocks[name] = put(FL.row_block(U, F.floats(c, name)))
                 outs[name] = blocks[name] + 4 * GUARD
         nseg = F.call_dev(plan, c, ins, outs)
         recipe = plan.last_recipe()
@@ -1106,12 +1078,7 @@ def run_case(ctx, hip, c, check=True, say=print):
         rows = {}
         for name, base in blocks.items():
             w = F.floats(c, name)
-            words = ctx.d2h(base, (2 * GUARD + (U + 1) * w,), np.uint32)
-            assert np.all(words[:GUARD] == SENTINEL) and np.all(words[GUARD + U * w:] == SENTINEL), \
-                'row %s: a guard or the spare row was written [%s]' % (name, shape_text(c))
-            body = words[GUARD:GUARD + U * w]
-            assert not np.any(body == SENTINEL), 'row %s: %d words left unwritten [%s]' % (name, int(np.sum(body == SENTINEL)), shape_text(c))
-            rows[name] = body.view(np.float32).reshape(U, w)
+            rows[name] = FL.rows_of_block(ctx.d2h(base, (2 * GUARD + (U + 1) * w,), np.uint32), U, w, name, shape_text(c))
         for base, (buf, _) in zip(bases, bufs):
             assert ctx.d2h(base, buf.shape, np.complex64).tobytes() == buf.tobytes(), 'the input buffer changed [%s]' % shape_text(c)
         worst = {}

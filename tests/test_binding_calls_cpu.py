@@ -1072,7 +1072,7 @@ def test_value_errors_come_before_any_call(text, fn):
 
 # not bound to a handle: the tests of the ABI and of windows.dpss call them
 PROCESS_WIDE = {'oth_abi_version', 'oth_strerror', 'oth_device_count', 'oth_dpss', 'oth_last_error', 'oth__debug_recipe',
-                'oth__debug_live_resources'}
+                'oth__debug_recipe_tuned', 'oth__debug_live_resources'}
 UNBOUND = set()      # entry points no public method of the binding calls: adding one here is a decision
 
 

@@ -1147,6 +1147,13 @@ def test_beyond_4GiB_offsets(ctx, hip):
 
 # ------------------------------------------------- randomized plan sweep ----
 
+def plan_err(got, ref):
+    """The comparison of the randomized plan sweep (and of tests/core_fuzz_cases.py), on linear power over every bin: a
+    detrended rectangular-ish window can leave a bin near zero; judge against the spectrum's scale."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    return float(np.max(np.abs(got - ref) / np.maximum(ref, 1e-6 * ref.max())))
+
+
 def test_randomized_welch_plans_vs_oracle(ctx, hip):
     """60 random plans (sizes, segment lengths, overlaps, windows, detrend, scaling, shift/trim/dB,
     kernel choice) against the float64 oracle - catches dispatch mistakes between the kernels."""
@@ -1184,8 +1191,7 @@ def test_randomized_welch_plans_vs_oracle(ctx, hip):
         if db:
             got = 10 ** (got / 10)
         assert got.shape == ref.shape
-        # a detrended rectangular-ish window can leave a bin near zero; judge against the spectrum's scale
-        err = np.max(np.abs(got - ref) / np.maximum(ref, 1e-6 * ref.max()))
+        err = plan_err(got, ref)
         assert err < RTOL, (it, nfft, nperseg, noverlap, detrend, scaling, wkind, shift, trim, db, kern, err)
         plan.close()
 
